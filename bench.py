@@ -12,7 +12,7 @@ no data-path collective, one RCCL gather of the solutions to rank 0 inside the t
   --scaling weak   (default)  --batch problems PER GPU          (what the driver's N=1,2,4,8 sweep measures)
   --scaling strong            --batch problems in the WHOLE job (slice [r*B/G, (r+1)*B/G))
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scaling weak|strong] [--workload ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scaling weak|strong] [--workload ...] [--dump-outputs DIR]
     (N>1 without WORLD_SIZE in the environment: bench.py starts its own N ranks — `python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N` as a child process, before anything touches the GPU — and
      forwards rank 0's JSON line and the exit code; under torchrun it is a rank.)
@@ -161,6 +161,37 @@ def status_fractions(st):
             "T_out_of_box_frac": float(((st & 32) != 0).mean())}
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: at most 64 MB in all
+DUMP_SAMPLE_SEED = 20240002      # the fixed row sample taken when the outputs exceed DUMP_MAX_BYTES
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: write what the timed path returned in its last step as DIR/<name>.npy (float64; integer fields converted).
+    Every array is indexed by problem along axis 0; when together they exceed DUMP_MAX_BYTES, the same fixed, seeded sample of problems
+    is kept in every array and its indices are written as DIR/sample_rows.npy.  Returns the record of the dump for the JSON line."""
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    n = {v.shape[0] for v in arrays.values()}
+    assert len(n) == 1, {k: v.shape for k, v in arrays.items()}
+    n = n.pop()
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    rows = None
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)) // (row_bytes + 8)     # (room for the .npy headers; 8 bytes a row: the index array)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return {"dir": d, "files": sorted(k + ".npy" for k in arrays), "problems": n, "sampled": None if rows is None else int(len(rows)),
+            "bytes": int(sum(v.nbytes for v in arrays.values())), "dtype": "float64", "what": "outputs of the last timed step"}
+
+
+def info_arrays(inf):
+    """the per-problem mpcmp_info fields (include/mpcmp.h) as separate arrays, for dump_outputs"""
+    return {"info_" + f: inf[f] for f in inf.dtype.names}
+
+
 def committed_counters(workload):
     """FP64 VALU instruction counters of the dominant kernels from the newest committed rocprofv3 PMC pass (profiles/r0N_fp64_counters.json, written
     by tools/fp64_counters.py from `tools/profile_round.sh`): flops the ISA executed per ADMM iteration of one trajectory (factorisation included in
@@ -259,7 +290,7 @@ def rh_collect(rank, world, dist, device, total, x_final, sT, status, qp_iters, 
     return rec, int(cnt[0].item()), int(cnt[1].item()), float(tmax.item())
 
 
-def bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags=None, B=None):
+def bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags=None, B=None, dump=None):
     """BASELINE.json configs[4]: 512 parallel Panda instances x 200 warm-started re-solves, hipGraph-captured step, sharded over the ranks.
     (reference-as-shipped solver depth: 2 SQP iterations per re-solve, motionPlanner.cpp:15; N = 13; dt = 10 ms.)  flags: None = the driver's
     defaults (carried multipliers + warm QP duals + arrival, include/mpcmp.h mpcmp_rh_run), "cold" = both start flags off (-1)."""
@@ -303,6 +334,12 @@ def bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags=N
     if rank != 0:
         return None
     N = 3 * nseg + 1
+    dumped = None
+    if dump:
+        if world == 1:           # what mpcmp_rh_get hands its caller after the timed (graph) run
+            dumped = dump_outputs(dump, {"rh_x": xg, "sol_x": sx, "sol_u": su, "sol_T": sT, **info_arrays(info)})
+        else:                    # the gathered final-state records (state, T, status, QP iterations) of every instance
+            dumped = dump_outputs(dump, {"rh_records": rec})
     st_all = rec[:, 15].astype(np.int64)
     alive = (st_all & 64) == 0
     value = total * resolves / el_max                                  # instance-steps per second, arrived instances included (they cost nothing)
@@ -332,6 +369,8 @@ def bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags=N
                             T_mean_remaining_live=float(np.nanmean(rec[alive, 14])) if alive.any() else 0.0,
                             T_nan_frac=float(np.isnan(rec[:, 14]).mean()), state_nonfinite_frac=float((~np.isfinite(rec[:, :14]).all(axis=1)).mean()),
                             note="status of every instance's LAST executed re-solve (an arrived instance keeps the record of the solve it arrived with)")}
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
         # CPU baseline: the oracle's loop (same rule: re-guess, carried multipliers, advance + arrival) on a bounded sample of the instances
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -478,6 +517,9 @@ def main():
     ap.add_argument("--rh-cold", action="store_true", help="rh workload: both start flags off (-1): every re-solve from lambda = 0 with cold QPs; default = the driver's defaults (carried multipliers, warm QP duals)")
     ap.add_argument("--qp-warm-start", action="store_true", help="mpcmp_config.qp_warm_start = 1 (opt-in: QPs start from the NLP multipliers); the contract line keeps the default 0")
     ap.add_argument("--no-secondary", action="store_true", help="default workload only: skip the brief runs of the three other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (solutions, final times, info fields) "
+                         "as DIR/<name>.npy, float64, at most 64 MB (a fixed, seeded sample of problems beyond that)")
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)      # launcher self-test on a CPU-only box (gloo, no solve)
     args = ap.parse_args()
 
@@ -505,12 +547,13 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
 
     if args.workload == "rh":
-        line = bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags="cold" if args.rh_cold else None)
+        line = bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags="cold" if args.rh_cold else None, dump=args.dump_outputs)
     elif args.workload == "dual14":
         import bench_dual14
-        line = bench_dual14.run(args, rank, world, local, dist)
+        line = bench_dual14.run(args, rank, world, local, dist, dump=args.dump_outputs)
     else:
-        line = run_batch_workload(args, args.workload, args.steps, args.warmup, rank, world, local, dist, args.cpu_sample, args.batch or 1024)
+        line = run_batch_workload(args, args.workload, args.steps, args.warmup, rank, world, local, dist, args.cpu_sample, args.batch or 1024,
+                                  dump=args.dump_outputs)
     if line is not None and args.workload == "batch" and world == 1 and not args.no_secondary:
         # the other three workloads, briefly, inside the ONE contract line: value, ms_per_step, roofline fractions, CPU baseline
         import bench_dual14
@@ -540,7 +583,7 @@ def main():
         dist.destroy_process_group()
 
 
-def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, cpu_sample, batch, host_to_host=True, qp_warm_start=None):
+def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, cpu_sample, batch, host_to_host=True, qp_warm_start=None, dump=None):
     """one batch workload (`batch` = BASELINE.json configs[1], `shipped` = the reference-as-shipped depth) on this rank; rank 0 returns the line"""
     import torch
     import mpc_motion_planner_amd as M
@@ -599,6 +642,13 @@ def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, 
 
     if rank == 0:
         inf = np.frombuffer(info.cpu().numpy().tobytes(), dtype=M.INFO_DTYPE)
+        dumped = None
+        if dump:
+            if world == 1:       # what solve_device hands its caller
+                dumped = dump_outputs(dump, {"sol_x": sol_x.cpu().numpy(), "sol_u": sol_u.cpu().numpy(), "sol_T": sol_T.cpu().numpy(), **info_arrays(inf)})
+            else:                # what rank 0 holds after the gather: every rank's solutions, in problem order
+                g = sb.assemble().cpu().numpy()
+                dumped = dump_outputs(dump, {"sol_x": g[:, :14 * N].reshape(-1, N, 14), "sol_u": g[:, 14 * N:21 * N].reshape(-1, N, 7), "sol_T": g[:, 21 * N]})
         value = total * steps / elapsed
         admm_mean = float(inf["qp_iters_total"].mean())
         flops_traj = canonical_flops(N, sqp, admm_mean, narm)
@@ -664,6 +714,8 @@ def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, 
                         "feasible_def": "no hard failure, collocation defect and path violation <= eps_abs (1e-3), terminal error <= eps_target + eps_abs "
                                         "(1.1e-2), T inside its box: status bits 1, 2, 4, 16, 32 clear (include/mpcmp.h)"},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and host_to_host:
             # host -> host (inputs and outputs in host memory, PCIe inclusive): warm, median of 5 repeats
             ts = []

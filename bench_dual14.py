@@ -23,8 +23,9 @@ def dual_states(B, margins, offset=0):
     return np.ascontiguousarray(x0), np.ascontiguousarray(xf)
 
 
-def run(args, rank, world, local, dist, steps=None, warmup=None, batch=None):
-    """rank 0 returns the JSON line (a dict); steps / warmup / batch override the command line (bench.py's brief secondary run)"""
+def run(args, rank, world, local, dist, steps=None, warmup=None, batch=None, dump=None):
+    """rank 0 returns the JSON line (a dict); steps / warmup / batch override the command line (bench.py's brief secondary run);
+    dump: directory for the outputs of the last timed step (bench.py --dump-outputs)"""
     import torch
     import bench as Bn
     import mpc_motion_planner_amd as M
@@ -87,6 +88,14 @@ def run(args, rank, world, local, dist, steps=None, warmup=None, batch=None):
     if rank != 0:
         return None
     inf = np.frombuffer(info.cpu().numpy().tobytes(), dtype=M.INFO_DTYPE)
+    dumped = None
+    if dump:
+        if world == 1:           # what solve_device hands its caller
+            dumped = Bn.dump_outputs(dump, {"sol_x": sol_x.cpu().numpy(), "sol_u": sol_u.cpu().numpy(), "sol_T": sol_T.cpu().numpy(), **Bn.info_arrays(inf)})
+        else:                    # what rank 0 holds after the gather: every rank's solutions, in problem order
+            g = np.concatenate([gathered[r][:sharding.shard_bounds(r, world, total)[1] - sharding.shard_bounds(r, world, total)[0]].cpu().numpy()
+                                for r in range(world)])
+            dumped = Bn.dump_outputs(dump, {"sol_x": g[:, :28 * N].reshape(-1, N, 28), "sol_u": g[:, 28 * N:42 * N].reshape(-1, N, 14), "sol_T": g[:, 42 * N]})
     value = total * steps / elapsed
     admm_mean = float(inf["qp_iters_total"].mean())
     flops_traj = Bn.canonical_flops(N, sqp, admm_mean, narm)
@@ -131,6 +140,8 @@ def run(args, rank, world, local, dist, steps=None, warmup=None, batch=None):
                     "defect_inf_median": float(np.median(inf["defect_inf"])), "term_err_inf_median": float(np.median(inf["term_err_inf"])),
                     "path_viol_inf_max": float(inf["path_viol_inf"].max())},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py as o

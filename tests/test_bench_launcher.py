@@ -67,3 +67,25 @@ def test_receding_horizon_workload_is_sharded_over_the_ranks():
     assert rw.returncode == 0, rw.stderr[-2000:]
     dw = json.loads([l for l in rw.stdout.splitlines() if l.strip().startswith("{")][0])
     assert dw["config"]["instances_total"] == 4 and dw["scaling"] == "weak" and len(dw["records"]) == 4
+
+
+def test_dump_outputs_writes_float64_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 .npy per output; beyond the cap the same seeded sample of problems in every array"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    x, st = np.arange(6 * 4 * 2, dtype=np.float64).reshape(6, 4, 2), np.arange(6, dtype=np.int32)
+    rec = bench.dump_outputs(str(tmp_path / "full"), {"sol_x": x, "info_status": st})
+    assert rec["sampled"] is None and sorted(os.listdir(tmp_path / "full")) == ["info_status.npy", "sol_x.npy"]
+    got = np.load(tmp_path / "full" / "info_status.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, st) and np.array_equal(np.load(tmp_path / "full" / "sol_x.npy"), x)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 * 3 + 72 * 100)      # headers of 3 files + 100 rows of 56 + 8 bytes and their index
+    big = np.random.default_rng(0).random((1000, 7))
+    runs = []
+    for d in ("a", "b"):
+        rec = bench.dump_outputs(str(tmp_path / d), {"sol_x": big, "sol_T": big[:, 0]})
+        rows = np.load(tmp_path / d / "sample_rows.npy").astype(int)
+        assert rec["sampled"] == len(rows) == 100 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(np.load(tmp_path / d / "sol_x.npy"), big[rows]) and np.array_equal(np.load(tmp_path / d / "sol_T.npy"), big[rows, 0])
+        runs.append(rows)
+    assert np.array_equal(runs[0], runs[1])

@@ -63,10 +63,7 @@ def test_model_matches_oracle_and_urdf(M):
     a, b = M.default_model(), o.default_model()
     for f in ["R0", "p", "mass", "com", "I", "tool", "link8", "gravity"]:
         assert np.array_equal(np.array(getattr(a, f)), np.array(getattr(b, f))), f
-    urdf = "/root/reference/robot_utils/panda-model/panda_arm.urdf"
-    if not os.path.exists(urdf):
-        pytest.skip("reference URDF not present on this machine")
-    u = M.model_from_urdf(urdf)
+    u = M.model_from_urdf(os.path.join(ROOT, "tests", "golden", "panda_arm.urdf"))      # the Panda description the model was taken from
     for f in ["R0", "p", "mass", "com", "I", "tool", "link8", "gravity"]:
         assert np.array_equal(np.array(getattr(a, f)), np.array(getattr(u, f))), f
     assert abs(u.mass[6] - 1.735522) < 1e-12      # link7 + link8 (m=0) + tool (m=1) lumped
