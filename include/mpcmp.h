@@ -255,8 +255,9 @@ int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const double *xf);
  * start already lies in its terminal box degenerates (T -> lbT = 0).  After every solve the driver therefore RETIRES an instance
  *   - whose plan ends within the control period (T <= dt): it follows the plan to its last node first, or
  *   - whose advanced state lies inside the terminal box, |x - x_target|_inf <= eps_target (motionPlanner.hpp:44).
- * A retired instance keeps its state, last solution and record (status |= MPCMP_STATUS_ARRIVED) and is not re-solved: its workgroups return
- * at once.  An instance whose solve failed hard (NaN, lost positive definiteness, dead exchange) or left the box of T holds its state and
+ * A retired instance keeps its state, last solution and record (status |= MPCMP_STATUS_ARRIVED) and is not re-solved: at N = 13 and N = 19 the
+ * workgroups of every kernel return at once for it; at N = 25 its QP kernels (k_qp3f, k_qp3) still run on its last linearisation every SQP
+ * iteration and their results are discarded (the other kernels return at once).  An instance whose solve failed hard (NaN, lost positive definiteness, dead exchange) or left the box of T holds its state and
  * re-solves from the driver's start guess with zero multipliers.
  * Start guess of the driver (first solve of every instance, and such restarts): the jerk-limited time-synchronised trajectory from the current
  * state to the target — what the reference takes from Ruckig for solve_trajectory(true), motionPlanner.cpp:146-175 — with the velocity and

@@ -64,12 +64,18 @@ def library_path():
     return _SO
 
 
+def build_dependencies():
+    """every file the library is built from, taken from the directory itself: csrc/*.hip, csrc/*.hpp, csrc/Makefile and include/mpcmp.h"""
+    import glob
+    src = os.path.join(_HERE, "csrc")
+    deps = sorted(glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.hpp")))
+    return deps + [os.path.join(src, "Makefile"), os.path.join(os.path.dirname(_HERE), "include", "mpcmp.h")]
+
+
 def build_library(force=False):
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     src = os.path.join(_HERE, "csrc")
-    deps = [os.path.join(src, f) for f in ("mpcmp.hip", "solver_kernels.hpp", "qp_kernel_v2.hpp", "qp_kernel_v3.hpp", "qp_kernel_v5.hpp", "structure3.hpp", "rbd_device.hpp", "structure.hpp", "multi_kernels.hpp",
-                                           "kinematics_host.hpp", "jerk_device.hpp")]
-    deps.append(os.path.join(os.path.dirname(_HERE), "include", "mpcmp.h"))
+    deps = build_dependencies()
     if force or not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in deps):
         subprocess.check_call(["make", "-C", src, "-B"], stdout=subprocess.DEVNULL)
     return _SO

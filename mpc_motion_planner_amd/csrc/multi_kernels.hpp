@@ -147,6 +147,9 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
     const int tid = threadIdx.x, b = blockIdx.x;
     if (MPCMP_RETIRED(ws, b)) {      // arrived (k_advance): nothing is re-solved; only the launch-order bookkeeping of the slot
         if (tid == 0) { ws.perm[b] = b; ws.okey[b] = 0; if (b == 0) *ws.done = 0; }
+        // k_qp3 has no retirement exit at N = 25: the two arm workgroups of a retired instance still run their ADMM loop (results discarded), so
+        // they too start from empty exchange slots, as a live instance's do, instead of the values their previous launch left behind
+        if (NARM == 2) for (int i = tid; i < 2 * MPCMP_XCH_STRIDE; i += NT) xch.buf[(size_t)b * 2 * MPCMP_XCH_STRIDE + i] = MPCMP_XCH_EMPTY;
         return;
     }
     // (the slot's previous solve, as in k_init: a failed solve leaves neither a re-guess nor multipliers behind)
@@ -247,7 +250,12 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
     constexpr int N = D::N, na = D::na, n = D::n, meq = D::meq, ma = D::ma, NT = D::NT;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x, b = blockIdx.x;
-    if (MPCMP_RETIRED(ws, b)) { if (tid == 0) ws.qpit[b] = 0; step_tail(ws, lds, tid, NT); return; }
+    if (MPCMP_RETIRED(ws, b)) {
+        if (tid == 0) ws.qpit[b] = 0;
+        if (NARM == 2) for (int i = tid; i < 2 * MPCMP_XCH_STRIDE; i += NT) xch.buf[(size_t)b * 2 * MPCMP_XCH_STRIDE + i] = MPCMP_XCH_EMPTY;   // (see k_init_m)
+        step_tail(ws, lds, tid, NT);
+        return;
+    }
     double *zl = lds + D::oZ, *pl = lds + D::oP, *scr = lds + D::oScr, *sct = lds + D::oSct, *pv = lds + D::oPv, *xa = lds + D::oX0,
            *red = lds + D::oRed;
     const double *x0 = ws.x0 + (size_t)b * 14 * NARM, *xf = ws.xf + (size_t)b * 14 * NARM;

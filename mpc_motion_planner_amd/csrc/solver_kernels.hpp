@@ -42,7 +42,7 @@ struct WS {
     int *status;              // [B]
     double *alpha;            // [B]
     unsigned long long *dbg;  // [B][MPCMP_DBG_WORDS] phase cycle stamps (diagnostic builds with -DMPCMP_STAMPS only)
-    const int *retired;       // [B] or null: receding-horizon instances that have arrived (k_advance) are not re-solved: every solve kernel returns at once
+    const int *retired;       // [B] or null: receding-horizon instances that have arrived (k_advance) are not re-solved: every solve kernel returns at once (at N = 25 the QP kernels k_qp3f / k_qp3 still run, results discarded)
     const double *alt_x, *alt_u, *alt_T;   // or null: the receding-horizon driver's start guess (jerk-limited trajectory from the current state) for an instance
                                            // that cannot be re-guessed from its previous solve (k_init: reguess && prev_bad); null = the built-in initialiser
 };

@@ -164,6 +164,9 @@ void orc_mpc_point(const orc_model *m, int num_seg, const double *xs, const doub
 
 /* state advance + arrival rule of the receding-horizon driver (mpcmp_rh_run, include/mpcmp.h): x_io [14] in / out; returns 1 if the instance is retired */
 int orc_rh_advance(const orc_config *c, const double *xs, const double *us, double T, int status, double dt, const double *xf, double *x_io);
+/* the same for a robot of narm arms: x_io [14 narm] in the multi-arm layout [q(7 narm); qd(7 narm)], xs [N][14 narm]; arrival needs every component inside the box */
+int orc_rh_advance_multi(const orc_config *c, int narm, const double *xs, const double *us, double T, int status, double dt, const double *xf,
+                         double *x_io);
 
 /* examples/benchmark.cpp:58-160: out[74] = min(28) | max(28) | x(T)-target (14) | flags jerk, lin vel, ang vel, collision */
 void orc_traj_stats(const orc_model *m, int num_seg, const double *xs, const double *us, double T, const double *xf,

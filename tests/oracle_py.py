@@ -319,16 +319,67 @@ def mpc_point(num_seg, xs, us, T, time, model=None):
 def rh_start_guess(cfg, x, xf):
     """the receding-horizon driver's start guess (mpcmp_rh_run: first solve, and the restart of an instance whose previous solve is no guess): the
     jerk-limited time-synchronised trajectory from the current state, velocity / acceleration limits of the configuration, jerk margin 0.1
-    (examples/offline_trajectory.cpp:9)"""
-    return warm_start_jerk(cfg.num_seg, np.array(cfg.ubx[7:14]), np.array(cfg.ubu[:]), 0.1 * default_limits()["jmax"], x, xf)
+    (examples/offline_trajectory.cpp:9).  The arm count follows from the state length: two arms take warm_start_jerk_multi with the same
+    limits for every arm (the device's per-arm generator and merge: warm_start_jerk_device)"""
+    x, xf = f64(x), f64(xf)
+    vmax, amax, jmax = np.array(cfg.ubx[7:14]), np.array(cfg.ubu[:7]), 0.1 * default_limits()["jmax"]
+    if x.shape[0] == 14:
+        return warm_start_jerk(cfg.num_seg, vmax, amax, jmax, x, xf)
+    return warm_start_jerk_multi(cfg.num_seg, vmax, amax, jmax, x, xf)
 
 
 def rh_advance(cfg, xs, us, T, status, dt, xf, x_now):
-    """state advance + arrival rule of the receding-horizon driver (orc_rh_advance): returns (new state [14], retired)"""
+    """state advance + arrival rule of the receding-horizon driver (orc_rh_advance, orc_rh_advance_multi for more than one arm: the arm count
+    follows from the state length): returns (new state [14 narm], retired)"""
     xs, us, xf = f64(xs), f64(us), f64(xf); x = f64(x_now).copy()
-    lib().orc_rh_advance.restype = C.c_int
-    r = lib().orc_rh_advance(C.byref(cfg), _p(xs), _p(us), C.c_double(T), int(status), C.c_double(dt), _p(xf), _p(x))
+    narm = x.shape[0] // 14
+    assert x.shape == (14 * narm,) and xf.shape == x.shape and xs.shape == (3 * cfg.num_seg + 1, 14 * narm)
+    if narm == 1:
+        lib().orc_rh_advance.restype = C.c_int
+        r = lib().orc_rh_advance(C.byref(cfg), _p(xs), _p(us), C.c_double(T), int(status), C.c_double(dt), _p(xf), _p(x))
+    else:
+        lib().orc_rh_advance_multi.restype = C.c_int
+        r = lib().orc_rh_advance_multi(C.byref(cfg), int(narm), _p(xs), _p(us), C.c_double(T), int(status), C.c_double(dt), _p(xf), _p(x))
     return x, bool(r)
+
+
+def rh_chain(cfg, x0, xf, steps, dt, models=None):
+    """mpcmp_rh_run restated with the oracle (include/mpcmp.h): re-guess rule of motionPlanner.cpp:199-207, a re-solve per live instance (from the
+    multipliers of the one before when cfg.carry_multipliers), state advance + arrival rule (rh_advance).  A failed solve (status & (1|2|4|32)) is no
+    guess: the next one restarts from rh_start_guess; orc_solve_carry hands back zero multipliers after one.  models: None (the Panda) or the arm
+    models of a multi-arm robot (arm_models).
+
+    Returns a dict: after the last step x, T, its (ADMM iterations of the last solve executed), status (its status word), retired, n_solves;
+    and per step (lists of `steps` entries, each taken after that step) hist_x, hist_T, hist_its, hist_status, hist_retired, hist_n_solves;
+    retired_at [B] (the step, counted from 1, that retired the instance; 0 = never) and restarts [B] (solves started from rh_start_guess after
+    a failed one)."""
+    B = len(x0); xc = f64(x0).copy(); xf = f64(xf); prev = [None] * B; lam = [None] * B
+    retired = np.zeros(B, dtype=bool); its = np.zeros(B, dtype=int); status = np.zeros(B, dtype=int); T_last = np.zeros(B); n_solves = 0
+    retired_at = np.zeros(B, dtype=int); restarts = np.zeros(B, dtype=int)
+    h = {k: [] for k in ("hist_x", "hist_T", "hist_its", "hist_status", "hist_retired", "hist_n_solves")}
+    for step in range(1, steps + 1):
+        for b in range(B):
+            if retired[b]:
+                continue
+            n_solves += 1
+            if prev[b] is None or (prev[b][3] & (1 | 2 | 4 | 32)):
+                wx, wu, wT = rh_start_guess(cfg, xc[b], xf[b])
+                restarts[b] += prev[b] is not None
+            else:
+                wx, wu, wT = prev[b][0].copy(), prev[b][1], prev[b][2]
+                wx[0] = xc[b]; wx[-1] = xf[b]
+            if models is None:
+                xs, us, T, oi, lam[b] = solve_carry(cfg, xc[b], xf[b], wx, wu, wT, lam=lam[b])
+            else:
+                xs, us, T, oi, lam[b] = solve_carry_multi(models, cfg, xc[b], xf[b], wx, wu, wT, lam=lam[b])
+            prev[b] = (xs, us, T, oi.status); its[b] = oi.qp_iters_total; status[b] = oi.status; T_last[b] = T
+            xc[b], retired[b] = rh_advance(cfg, xs, us, T, oi.status, dt, xf[b], xc[b])
+            if retired[b]:
+                retired_at[b] = step
+        for k, v in (("hist_x", xc), ("hist_T", T_last), ("hist_its", its), ("hist_status", status), ("hist_retired", retired)):
+            h[k].append(v.copy())
+        h["hist_n_solves"].append(n_solves)
+    return dict(x=xc, T=T_last, its=its, status=status, retired=retired, n_solves=n_solves, retired_at=retired_at, restarts=restarts, **h)
 
 
 def traj_stats(num_seg, xs, us, T, xf, n_pts=200, model=None):

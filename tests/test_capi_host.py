@@ -196,3 +196,59 @@ def test_inverse_kinematic_reaches_reachable_poses(M):
     # an unreachable pose hits the iteration cap and says so
     q, conv, it = M.inverse_kinematic(mdl, np.eye(3), np.array([3.0, 0.0, 0.0]))
     assert not conv and it == 1000
+
+
+def _build_inputs(csrc):
+    """the files of csrc/ a build reads: everything but build products and hidden files"""
+    skip = (".o", ".so", ".a", ".bc", ".hipi")
+    return sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)) and not f.startswith(".") and not f.endswith(skip)
+                  and "-hip-amdgcn-" not in f and "-host-x86_64-" not in f)
+
+
+def test_every_source_file_is_a_build_dependency(M):
+    """build_library() rebuilds when any file the library is built from is newer than the library: every file of csrc/ (sources, headers of every
+    translation unit, the Makefile with its per-unit compiler options) and the public header"""
+    from mpc_motion_planner_amd import capi
+    csrc = os.path.join(ROOT, "mpc_motion_planner_amd", "csrc")
+    deps = {os.path.realpath(d) for d in capi.build_dependencies()}
+    files = _build_inputs(csrc)
+    assert {"qp3_n25.hip", "qp5_n19.hip", "Makefile", "mpcmp.hip"} <= set(files)
+    missing = [f for f in files if os.path.realpath(os.path.join(csrc, f)) not in deps]
+    assert not missing, missing
+    assert os.path.realpath(os.path.join(ROOT, "include", "mpcmp.h")) in deps
+    assert all(os.path.isfile(d) for d in deps)
+
+
+def test_build_library_rebuilds_after_an_edit_to_any_source(M, tmp_path, monkeypatch):
+    """a copy of the sources with a library newer than all of them: no rebuild; then each file in turn made newer than the library (an edit to
+    qp5_n19.hip among them): build_library() runs make in that source directory"""
+    import shutil
+    from mpc_motion_planner_amd import capi
+    csrc = os.path.join(ROOT, "mpc_motion_planner_amd", "csrc")
+    pkg = tmp_path / "mpc_motion_planner_amd"
+    (pkg / "csrc").mkdir(parents=True); (tmp_path / "include").mkdir()
+    files = _build_inputs(csrc)
+    for f in files:
+        shutil.copy(os.path.join(csrc, f), pkg / "csrc" / f)
+    shutil.copy(os.path.join(ROOT, "include", "mpcmp.h"), tmp_path / "include" / "mpcmp.h")
+    so = pkg / "libmpcmp.so"
+    so.write_bytes(b"")
+    t0 = 1.0e9
+    for p in [pkg / "csrc" / f for f in files] + [tmp_path / "include" / "mpcmp.h"]:
+        os.utime(p, (t0, t0))
+    os.utime(so, (t0 + 10, t0 + 10))
+    calls = []
+    monkeypatch.setattr(capi, "_HERE", str(pkg))
+    monkeypatch.setattr(capi, "_SO", str(so))
+    monkeypatch.setattr(capi.subprocess, "check_call", lambda cmd, **kw: calls.append(list(cmd)))
+    capi.build_library()
+    assert calls == []                                         # up to date
+    for i, p in enumerate([pkg / "csrc" / "qp5_n19.hip"] + [pkg / "csrc" / f for f in files] + [tmp_path / "include" / "mpcmp.h"]):
+        os.utime(p, (t0 + 20 + 2 * i, t0 + 20 + 2 * i))              # an edit after the last build
+        del calls[:]
+        capi.build_library()
+        assert len(calls) == 1 and calls[0][:3] == ["make", "-C", str(pkg / "csrc")], (p, calls)
+        os.utime(so, (t0 + 21 + 2 * i, t0 + 21 + 2 * i))             # (the rebuilt library)
+        del calls[:]
+        capi.build_library()
+        assert calls == [], p

@@ -279,25 +279,10 @@ def test_error_behaviour(M):
 
 
 def _oracle_rh_chain(ocfg, x0, xf, steps, dt):
-    """mpcmp_rh_run restated with the oracle (include/mpcmp.h): re-guess rule of motionPlanner.cpp:199-207, a re-solve per live instance (from the multipliers
-    of the one before when ocfg.carry_multipliers), state advance + arrival rule (orc_rh_advance).  A failed solve (status & (1|2|4|32)) is not a guess:
-    built-in initialiser (k_init); orc_solve_carry hands back zero multipliers after one."""
-    B = len(x0); xc = x0.copy(); prev = [None] * B; lam = [None] * B
-    retired = np.zeros(B, dtype=bool); its = np.zeros(B, dtype=int); status = np.zeros(B, dtype=int); T_last = np.zeros(B); n_solves = 0
-    for _ in range(steps):
-        for b in range(B):
-            if retired[b]:
-                continue
-            n_solves += 1
-            if prev[b] is None or (prev[b][3] & (1 | 2 | 4 | 32)):
-                wx, wu, wT = o.rh_start_guess(ocfg, xc[b], xf[b])
-            else:
-                wx, wu, wT = prev[b][0].copy(), prev[b][1], prev[b][2]
-                wx[0] = xc[b]; wx[-1] = xf[b]
-            xs, us, T, oi, lam[b] = o.solve_carry(ocfg, xc[b], xf[b], wx, wu, wT, lam=lam[b])
-            prev[b] = (xs, us, T, oi.status); its[b] = oi.qp_iters_total; status[b] = oi.status; T_last[b] = T
-            xc[b], retired[b] = o.rh_advance(ocfg, xs, us, T, oi.status, dt, xf[b], xc[b])
-    return xc, T_last, its, status, retired, n_solves
+    """mpcmp_rh_run restated with the oracle: the shared chain (oracle_py.rh_chain), its final state, final times, iteration counts and status words of
+    the last solve executed, retired instances and re-solve count"""
+    r = o.rh_chain(ocfg, x0, xf, steps, dt)
+    return r["x"], r["T"], r["its"], r["status"], r["retired"], r["n_solves"]
 
 
 def test_receding_horizon_vs_oracle(M):

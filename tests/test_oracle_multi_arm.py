@@ -62,3 +62,112 @@ def test_yawed_base_does_not_change_the_torques():
         assert np.abs(o.rnea(q, v, a, model=m0) - o.rnea(q, v, a, model=m1)).max() < 1e-11
         p0, p1 = o.fk(q, model=m0)[3], o.fk(q, model=m1)[3]
         assert abs(p0[2] - p1[2]) < 1e-12 and abs((1.0 - p1[0]) - p0[0]) < 1e-12 and abs(p1[1] + p0[1]) < 1e-12
+
+
+# ---- the receding-horizon driver's rule for a robot of narm arms (orc_rh_advance_multi; device: k_advance with nx = 14 narm) ----
+def _rh_advance_raw(cfg, narm, xs, T, status, dt, xf, x_now):
+    """orc_rh_advance_multi called directly (narm = 1 included, which oracle_py.rh_advance routes to orc_rh_advance)"""
+    import ctypes as C
+    xs, xf, x = o.f64(xs), o.f64(xf), o.f64(x_now).copy()
+    o.lib().orc_rh_advance_multi.restype = C.c_int
+    r = o.lib().orc_rh_advance_multi(C.byref(cfg), int(narm), o._p(xs), None, C.c_double(T), int(status), C.c_double(dt), o._p(xf), o._p(x))
+    return x, bool(r)
+
+
+def _rh_advance_numpy(num_seg, eps_target, xs, T, status, dt, xf, x_now):
+    """the arrival rule restated in numpy: cubic Lagrange interpolation on the segment's nodes at local time -1, -1/2, 1/2, 1"""
+    if status & (1 | 2 | 4 | 32):
+        return x_now.copy(), False
+    if T <= dt:
+        return xs[-1].copy(), True
+    t = dt / T
+    s = min(max(int(np.floor(t * num_seg)), 0), num_seg - 1)
+    xx = 2.0 * (t * num_seg - s) - 1.0
+    nodes = np.array([-1.0, -0.5, 0.5, 1.0])
+    L = np.array([np.prod([(xx - nodes[k]) / (nodes[j] - nodes[k]) for k in range(4) if k != j]) for j in range(4)])
+    x = L @ xs[3 * s:3 * s + 4]
+    return x, bool(np.abs(x - xf).max() <= eps_target)
+
+
+def test_rh_advance_multi_single_arm_is_orc_rh_advance_bitwise():
+    rng = np.random.default_rng(11)
+    for nseg in (4, 6, 8):
+        cfg = o.default_config(nseg, 2, margins=MARGINS)
+        N = 3 * nseg + 1
+        for trial in range(20):
+            xs, us = rng.normal(size=(N, 14)), rng.normal(size=(N, 7))
+            x_now = rng.normal(size=14)
+            T = rng.uniform(0.05, 3.0); dt = rng.uniform(0.01, 1.0)
+            st = int(rng.choice([0, 0, 0, 8, 16, 1, 2, 4, 32]))
+            xf = xs[-1] + rng.normal(size=14) * (cfg.eps_target if trial % 2 else 1.0)
+            a = o.rh_advance(cfg, xs, us, T, st, dt, xf, x_now)
+            b = _rh_advance_raw(cfg, 1, xs, T, st, dt, xf, x_now)
+            assert a[1] == b[1] and np.array_equal(a[0], b[0]), (nseg, trial)
+
+
+def test_rh_advance_dual_arm_vs_numpy_restatement():
+    rng = np.random.default_rng(12)
+    for nseg in (6, 8):
+        cfg = o.default_config(nseg, 2, margins=MARGINS)
+        N = 3 * nseg + 1
+        for trial in range(30):
+            xs, us = rng.normal(size=(N, 28)), rng.normal(size=(N, 14))
+            x_now = rng.normal(size=28)
+            T = rng.uniform(0.05, 3.0); dt = rng.uniform(0.01, 1.0) if trial else T      # (T == dt: the end of the plan)
+            st = int(rng.choice([0, 0, 0, 8, 16, 2, 32]))
+            x, r = o.rh_advance(cfg, xs, us, T, st, dt, rng.normal(size=28), x_now)
+            xr, rr = _rh_advance_numpy(nseg, cfg.eps_target, xs, T, st, dt, np.zeros(28) + np.inf, x_now)
+            assert np.abs(x - xr).max() <= 1e-13 * max(1.0, np.abs(xr).max()), (nseg, trial)
+            if st & (1 | 2 | 4 | 32):
+                assert not r and np.array_equal(x, x_now)
+            elif T <= dt:
+                assert r and np.array_equal(x, xs[-1])
+            # the same target placed at the advanced state: inside the box -> retired
+            x2, r2 = o.rh_advance(cfg, xs, us, T, st, dt, xr + 0.5 * cfg.eps_target, x_now)
+            assert r2 == (not (st & (1 | 2 | 4 | 32))) and np.array_equal(x2, x)
+
+
+def test_rh_advance_dual_arm_retires_only_when_both_arms_arrive():
+    """the terminal box is |x - xf|_inf over all 28 components, q and qd of both arms: one arm inside and the other outside is not retired —
+    whichever arm is out, and whether its joint angle or its joint velocity is out"""
+    rng = np.random.default_rng(13)
+    cfg = o.default_config(8, 2, margins=MARGINS)
+    N = 25
+    xs, us = rng.normal(size=(N, 28)), rng.normal(size=(N, 14))
+    T, dt = 2.0, 0.3
+    x_adv, _ = _rh_advance_numpy(8, cfg.eps_target, xs, T, 0, dt, np.zeros(28), np.zeros(28))
+    xf = x_adv + 0.5 * cfg.eps_target * rng.uniform(-1, 1, size=28)
+    x, r = o.rh_advance(cfg, xs, us, T, 0, dt, xf, np.zeros(28))
+    assert r                                                            # both arms inside
+    arm_cols = {0: list(range(0, 7)) + list(range(14, 21)), 1: list(range(7, 14)) + list(range(21, 28))}
+    for arm in (0, 1):
+        for c in (arm_cols[arm][2], arm_cols[arm][10]):                 # a joint angle, a joint velocity of that arm
+            xf_out = xf.copy(); xf_out[c] = x_adv[c] + 3.0 * cfg.eps_target
+            x, r = o.rh_advance(cfg, xs, us, T, 0, dt, xf_out, np.zeros(28))
+            assert not r and np.abs(x - x_adv).max() <= 1e-13 * max(1.0, np.abs(x_adv).max()), (arm, c)
+
+
+def test_rh_start_guess_dual_arm_is_warm_start_jerk_multi_with_the_device_limits():
+    """the chain's start guess for two arms: warm_start_jerk_multi with the configuration's velocity (ubx[7:14]) and acceleration (ubu[:7]) bounds and
+    0.1 x max jerk (the device: warm_start_jerk_device with narm = 2, mpcmp_rh_run's jerk margin); and the dual-arm chain's first solve starts from it"""
+    for nseg in (6, 8):
+        cfg = o.default_config(nseg, 2, margins=MARGINS, carry_multipliers=1, qp_warm_start=1)
+        x0, xf, _ = _states(2, off=50)
+        lim = o.default_limits()
+        assert np.allclose(np.array(cfg.ubx[7:14]), MARGINS[1] * lim["vmax"]) and np.allclose(np.array(cfg.ubu[:7]), MARGINS[2] * lim["amax"])
+        for b in range(2):
+            g = o.rh_start_guess(cfg, x0[b], xf[b])
+            r = o.warm_start_jerk_multi(nseg, np.array(cfg.ubx[7:14]), np.array(cfg.ubu[:7]), 0.1 * lim["jmax"], x0[b], xf[b])
+            assert np.array_equal(g[0], r[0]) and np.array_equal(g[1], r[1]) and g[2] == r[2]
+            assert g[0].shape == (3 * nseg + 1, 28) and np.array_equal(g[0][0], x0[b]) and np.array_equal(g[0][-1], xf[b])
+    # the chain's first step: one solve per instance from that guess, then the advance
+    models = o.arm_models(o.DUAL_BASES)
+    cfg = o.default_config(6, 2, margins=MARGINS, carry_multipliers=1, qp_warm_start=1)
+    x0, xf, _ = _states(1, off=50)
+    ch = o.rh_chain(cfg, x0, xf, 1, 0.05, models=models)
+    wx, wu, wT = o.rh_start_guess(cfg, x0[0], xf[0])
+    xs, us, T, oi, _ = o.solve_carry_multi(models, cfg, x0[0], xf[0], wx, wu, wT)
+    xa, ra = o.rh_advance(cfg, xs, us, T, oi.status, 0.05, xf[0], x0[0])
+    assert ch["T"][0] == T and ch["its"][0] == oi.qp_iters_total and ch["status"][0] == oi.status and ch["n_solves"] == 1
+    assert np.array_equal(ch["x"][0], xa) and ch["retired"][0] == ra and ch["restarts"][0] == 0
+    assert len(ch["hist_x"]) == 1 and np.array_equal(ch["hist_x"][0], ch["x"])
