@@ -267,8 +267,31 @@ int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const double *xf);
  * duals of the one before) unless the configuration sets a flag to -1.  mpcmp_solve_batch is unaffected (0 = off there). */
 int mpcmp_rh_run(mpcmp_ctx *ctx, int steps, double dt, int use_graph);
 int mpcmp_rh_get(mpcmp_ctx *ctx, double *x0_now, double *sol_x, double *sol_u, double *sol_T, mpcmp_info *info);
-/* counters since mpcmp_rh_init: re-solves actually executed (instance-steps of live instances) and instances retired so far; either may be NULL */
+/* counters since mpcmp_rh_init: re-solves actually executed (instance-steps of live instances) and instances retired now (retired by a step and not
+ * revived by mpcmp_rh_update since; without updates: instances retired so far); either may be NULL */
 int mpcmp_rh_stats(mpcmp_ctx *ctx, long long *resolves_done, long long *arrived);
+/* Feedback: the loop closed from outside, between two mpcmp_rh_run calls (MotionPlanner::set_current_state / set_target_state, then
+ * solve_trajectory(false): motionPlanner.cpp:27-53,177-208).  Overwrites the current state and / or the target of n instances of the loop started by
+ * mpcmp_rh_init; the update applies to the next step mpcmp_rh_run executes (eager or graph replay: the captured step stays valid).
+ * idx [n]: instance indices (NULL: n == B and instance i = row i); x [n][14 narm] measured states, xf [n][14 narm] targets (either may be NULL =
+ * unchanged; not both).  What the next solve of a listed instance starts from:
+ *   instance before the update   given                          next solve
+ *   live                         x only, no flag                re-guess from its previous solution, head := new state, tail := target, carried
+ *                                                               multipliers kept (the rule of every step, fed with a measured state)
+ *   live                         xf, or MPCMP_RH_RESTART        restart: the driver's start guess (jerk-limited, current state -> current target)
+ *                                                               and zero multipliers, as a first or a failed solve gets
+ *   retired (arrived)            anything                       revived: MPCMP_STATUS_ARRIVED leaves its record at once, mpcmp_rh_stats' `arrived`
+ *                                                               drops by one, and a restart as above; the arrival rule applies again after the solve
+ * An update before the first mpcmp_rh_run replaces what mpcmp_rh_init set.  mpcmp_rh_update is synchronous and returns MPCMP_EINVAL, writing
+ * nothing, before mpcmp_rh_init, for n outside [1, B], an index out of range or repeated, x and xf both NULL, a value that is not finite, or an
+ * unknown flag bit. */
+#define MPCMP_RH_RESTART 1   /* flag: the listed instances restart from the driver's start guess even if only their state changed */
+int mpcmp_rh_update(mpcmp_ctx *ctx, int n, const int *idx, const double *x, const double *xf, int flags);
+/* the same with DEVICE pointers: ordered after the work already on hip_stream and before the next mpcmp_rh_run (work enqueued on hip_stream
+ * afterwards waits for the update's reads of d_idx, d_x, d_xf); no host synchronisation.  The indices and values are not read on the host and not
+ * checked (n, NULL pointers and flags are): an index out of range is undefined behaviour, and one listed twice takes one of its rows (a retired
+ * instance is still revived and counted once). */
+int mpcmp_rh_update_device(mpcmp_ctx *ctx, int n, const int *d_idx, const double *d_x, const double *d_xf, int flags, void *hip_stream);
 
 /* ---- measurement hooks used by bench.py ---- */
 /* name and accumulated device time (ms, HIP events on the solve stream) of the dominant kernel since the

@@ -41,6 +41,7 @@ class Info(C.Structure):
 # status bits of mpcmp_info.status (include/mpcmp.h)
 STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED, STATUS_OUTSIDE_TOL, STATUS_T_OUT_OF_BOX, STATUS_ARRIVED = 1, 2, 4, 8, 16, 32, 64
 STATUS_HARD = STATUS_NAN | STATUS_NOT_PD | STATUS_XCH_DEAD        # the solve itself failed (the other bits grade the returned iterate)
+RH_RESTART = 1      # flag of mpcmp_rh_update[_device]: the listed instances restart from the driver's start guess
 
 INFO_DTYPE = np.dtype([("T", "f8"), ("viol_l1", "f8"), ("defect_inf", "f8"), ("path_viol_inf", "f8"),
                        ("term_err_inf", "f8"), ("last_alpha", "f8"), ("qp_iters_total", "i4"),
@@ -57,7 +58,8 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_warm_start_jerk_batch", "mpcmp_warm_start_jerk_batch_device", "mpcmp_jerk_trajectory_batch",
            "mpcmp_jerk_point_batch", "mpcmp_mpc_point_batch", "mpcmp_debug_fetch",
            "mpcmp_warm_start_jerk_acc_batch", "mpcmp_warm_start_jerk_acc_batch_device", "mpcmp_jerk_trajectory_acc_batch", "mpcmp_jerk_point_acc_batch",
-           "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats"]
+           "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats",
+           "mpcmp_rh_update", "mpcmp_rh_update_device"]
 
 
 def library_path():
@@ -113,6 +115,8 @@ def lib():
         L.mpcmp_version.restype = C.c_char_p
         L.mpcmp_last_error.restype = C.c_char_p
         L.mpcmp_last_error.argtypes = [C.c_void_p]
+        L.mpcmp_rh_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
+        L.mpcmp_rh_update_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 

@@ -99,7 +99,8 @@ struct mpcmp_ctx {
     hipGraphExec_t rh_exec = nullptr;
     double rh_dt = 0.0;
     int *d_retired = nullptr;                    // [max_batch] arrived instances of the receding-horizon loop (k_advance); not re-solved
-    unsigned long long *d_rh_count = nullptr;    // [2] re-solves executed, instances retired (since mpcmp_rh_init)
+    unsigned long long *d_rh_count = nullptr;    // [2] re-solves executed, instances retired now (since mpcmp_rh_init)
+    hipEvent_t ev_upd[2] = {nullptr, nullptr};   // mpcmp_rh_update_device: the caller's stream -> ctx->stream, and back
     bool rh_step = false;                        // the solve being enqueued is a step of the receding-horizon driver (defaults of its flags, retired instances)
     // diagnostics read from the environment ONCE PER CONTEXT, in mpcmp_create (never process-global state)
     bool force_v1 = false, single_stream = false, debug_occ = false;
@@ -585,6 +586,7 @@ extern "C" int mpcmp_destroy(mpcmp_ctx *ctx) {
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (int k = 0; k < 3; k++) { if (ctx->stream_x[k]) (void)hipStreamDestroy(ctx->stream_x[k]); if (ctx->ev_join[k]) (void)hipEventDestroy(ctx->ev_join[k]); }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
+    for (auto &e : ctx->ev_upd) if (e) (void)hipEventDestroy(e);
     delete ctx;
     return MPCMP_OK;
 }
@@ -632,6 +634,7 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
         HIPTRY(hipEventCreateWithFlags(&ctx->ev_join[k], hipEventDisableTiming));
     }
     HIPTRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    for (auto &e : ctx->ev_upd) HIPTRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     mpcmp_model mdl[2];
     for (int a = 0; a < narm; a++) { if (model) mdl[a] = model[a]; else mpcmp_default_model(&mdl[a]); }
     TRY(dalloc(ctx, &ctx->d_model, narm));
@@ -1507,14 +1510,14 @@ static int rh_enqueue_step(mpcmp_ctx *ctx, double dt, bool first, hipStream_t st
     // The driver's start guess, every step, from every instance's current state: the jerk-limited time-synchronised trajectory the reference takes from
     // Ruckig for solve_trajectory(true) (motionPlanner.cpp:146-175), with the velocity / acceleration limits of the configuration and the jerk
     // margin every example of the reference uses (0.1 x max jerk: examples/offline_trajectory.cpp:9, benchmark.cpp).  It starts the first solve and
-    // RE-starts an instance whose previous solve is no guess (hard failure, T outside its box: k_init); the other re-solves re-guess from the
-    // previous solution (solve_trajectory(false), motionPlanner.cpp:199-207).
+    // RE-starts an instance whose previous solve is no guess (hard failure, T outside its box, or a restart asked for by mpcmp_rh_update: k_init); the
+    // other re-solves re-guess from the previous solution (solve_trajectory(false), motionPlanner.cpp:199-207).
     double jm[7];
     mpcmp_default_limits(nullptr, nullptr, nullptr, nullptr, jm, nullptr);
     for (int j = 0; j < 7; j++) jm[j] *= 0.1;
     // (after the first step only for the instances that restart: the generator costs ~ 0.15 ms per 512 instances, 4 % of a step)
     if (int rc = warm_start_jerk_device(ctx, B, ctx->d_x0, ctx->d_xf, nullptr, nullptr, nullptr, nullptr, jm, ctx->d_wx, ctx->d_wu, ctx->d_wT, st,
-                                        first ? nullptr : ctx->ws.status, MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX))
+                                        first ? nullptr : ctx->ws.status, MPCMP_ST_NO_GUESS))
         return rc;
     const double *wx = first ? ctx->d_wx : ctx->d_sx, *wu = first ? ctx->d_wu : ctx->d_su, *wT = first ? ctx->d_wT : ctx->d_sT;
     ctx->rh_step = true;           // the driver's defaults of the start flags (run_config) and the retired instances (WS.retired)
@@ -1556,6 +1559,68 @@ extern "C" int mpcmp_rh_run(mpcmp_ctx *ctx, int steps, double dt, int use_graph)
             if (int rc = rh_enqueue_step(ctx, dt, false, st)) return rc;
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+// Between two steps: new measured states and / or targets of listed instances (k_rh_update).  Only buffer contents change: a captured step graph
+// stays valid, and the next step reads the new values through the pointers it was captured with.
+static int rh_update_check(mpcmp_ctx *ctx, int n, const int *idx, const double *x, const double *xf, int flags) {
+    if (!ctx) { g_err = "mpcmp_rh_update: no context"; return MPCMP_EINVAL; }
+    if (ctx->rh_B < 1) { ctx->err = "mpcmp_rh_update: no receding-horizon loop (mpcmp_rh_init first)"; return MPCMP_EINVAL; }
+    if (n < 1 || n > ctx->rh_B) { ctx->err = "mpcmp_rh_update: n must be in [1, B] of mpcmp_rh_init"; return MPCMP_EINVAL; }
+    if (!idx && n != ctx->rh_B) { ctx->err = "mpcmp_rh_update: idx NULL needs n == B"; return MPCMP_EINVAL; }
+    if (!x && !xf) { ctx->err = "mpcmp_rh_update: x and xf are both NULL"; return MPCMP_EINVAL; }
+    if (flags & ~MPCMP_RH_RESTART) { ctx->err = "mpcmp_rh_update: unknown flag bits"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
+static int rh_update_enqueue(mpcmp_ctx *ctx, int n, const int *d_idx, const double *d_x, const double *d_xf, int flags, hipStream_t st) {
+    hipLaunchKernelGGL(k_rh_update, dim3((n + 255) / 256), dim3(256), 0, st, ctx->nx, n, d_idx, d_x, d_xf, (flags & MPCMP_RH_RESTART) ? 1 : 0,
+                       ctx->d_x0, ctx->d_xf, ctx->d_retired, ctx->ws.status, ctx->d_info, ctx->d_rh_count);
+    HIPCHK(ctx, hipGetLastError());
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_rh_update(mpcmp_ctx *ctx, int n, const int *idx, const double *x, const double *xf, int flags) {
+    if (int rc = rh_update_check(ctx, n, idx, x, xf, flags)) return rc;
+    const int B = ctx->rh_B;
+    const size_t nx = ctx->nx;
+    if (idx) {
+        std::vector<char> seen(B, 0);
+        for (int i = 0; i < n; i++) {
+            if (idx[i] < 0 || idx[i] >= B) { ctx->err = "mpcmp_rh_update: instance index out of range"; return MPCMP_EINVAL; }
+            if (seen[idx[i]]++) { ctx->err = "mpcmp_rh_update: instance index repeated"; return MPCMP_EINVAL; }
+        }
+    }
+    for (const double *v : {x, xf})
+        if (v)
+            for (size_t k = 0; k < n * nx; k++)
+                if (!std::isfinite(v[k])) { ctx->err = "mpcmp_rh_update: a state or target value is not finite"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TmpBuf tb(ctx, (size_t)n * sizeof(int) + 2 * n * nx * sizeof(double));
+    int *di = idx ? tb.get<int>(n) : nullptr;
+    double *dx = x ? tb.get<double>(n * nx) : nullptr, *dxf = xf ? tb.get<double>(n * nx) : nullptr;
+    if (!tb.ok) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    if (di) HIPCHK(ctx, hipMemcpyAsync(di, idx, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    if (dx) HIPCHK(ctx, hipMemcpyAsync(dx, x, sizeof(double) * n * nx, hipMemcpyHostToDevice, st));
+    if (dxf) HIPCHK(ctx, hipMemcpyAsync(dxf, xf, sizeof(double) * n * nx, hipMemcpyHostToDevice, st));
+    if (int rc = rh_update_enqueue(ctx, n, di, dx, dxf, flags, st)) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_rh_update_device(mpcmp_ctx *ctx, int n, const int *d_idx, const double *d_x, const double *d_xf, int flags, void *hip_stream) {
+    if (int rc = rh_update_check(ctx, n, d_idx, d_x, d_xf, flags)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // after the caller's work on its stream (which writes the inputs), before the next step on ctx->stream; the caller's later work waits for the
+    // update's reads of its buffers
+    hipStream_t cs = (hipStream_t)hip_stream;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+    if (int rc = rh_update_enqueue(ctx, n, d_idx, d_x, d_xf, flags, ctx->stream)) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+    HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
     return MPCMP_OK;
 }
 

@@ -152,8 +152,8 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
         if (NARM == 2) for (int i = tid; i < 2 * MPCMP_XCH_STRIDE; i += NT) xch.buf[(size_t)b * 2 * MPCMP_XCH_STRIDE + i] = MPCMP_XCH_EMPTY;
         return;
     }
-    // (the slot's previous solve, as in k_init: a failed solve leaves neither a re-guess nor multipliers behind)
-    const bool prev_bad = (ws.status[b] & (MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX)) != 0;
+    // (the slot's previous solve, as in k_init: a failed solve, or a restart asked for by mpcmp_rh_update, leaves neither a re-guess nor multipliers behind)
+    const bool prev_bad = (ws.status[b] & MPCMP_ST_NO_GUESS) != 0;
     __syncthreads();
     if (tid == 0) { ws.perm[b] = b; ws.okey[b] = 0; if (b == 0) *ws.done = 0; ws.qp_total[b] = 0; ws.status[b] = 0; ws.alpha[b] = 0.0; }
     const double *x0 = ws.x0 + (size_t)b * 14 * NARM, *xf = ws.xf + (size_t)b * 14 * NARM;

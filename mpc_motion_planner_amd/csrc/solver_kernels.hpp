@@ -49,9 +49,15 @@ struct WS {
 // a retired instance of the receding-horizon loop: the whole workgroup leaves (uniform)
 #define MPCMP_RETIRED(ws_, b_) ((ws_).retired != nullptr && (ws_).retired[b_] != 0)
 
-// ws.status[b] while a solve runs: bits 0..7 = status bits of mpcmp_info (include/mpcmp.h), bits 8..30 = number of QPs that ran out of
-// iterations (every QP kernel adds MPCMP_ST_CAP_ONE then); k_step / k_step_m fold it into the record
+// ws.status[b] while a solve runs: bits 0..6 = status bits of mpcmp_info (include/mpcmp.h), bits 8..30 = number of QPs that ran out of
+// iterations (every QP kernel adds MPCMP_ST_CAP_ONE then); k_step / k_step_m fold it into the record.  Bit 7 (MPCMP_ST_RESTART) is set between two
+// steps of the receding-horizon driver only (k_rh_update: new target, revival, MPCMP_RH_RESTART) and cleared by k_init / k_init_m with the whole word
 #define MPCMP_ST_CAP_ONE 0x100
+#define MPCMP_ST_RESTART 0x80
+// the solve failed hard or left the box of T: there is no trajectory to follow (k_advance holds the state)
+#define MPCMP_ST_FAILED (MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX)
+// the slot's previous solve is no start for the next one (neither a re-guess nor carried multipliers): it failed, or the caller asked for a restart
+#define MPCMP_ST_NO_GUESS (MPCMP_ST_FAILED | MPCMP_ST_RESTART)
 // tools/isa_phases.py compiles with -DMPCMP_NOCHECK: the ADMM loops then contain no termination-test block, so that the hot path of every role is the
 // straight-line text between its barriers (diagnostic build: the QPs never converge early)
 #ifdef MPCMP_NOCHECK
@@ -263,9 +269,10 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
     if (tid == 0) { ws.perm[b] = b; ws.okey[b] = 0; if (b == 0) *ws.done = 0; }     // no history yet: problems are solved in batch order
     if (MPCMP_RETIRED(ws, b)) return;      // arrived: state, solution and record stay as the last solve left them
     const double *x0 = ws.x0 + 14 * b, *xf = ws.xf + 14 * b;
-    // the slot's previous solve (0 in a fresh context): after a hard failure or a final time outside its box neither its iterate (re-guess of the
-    // receding-horizon loop) nor its multipliers (mpcmp_config.carry_multipliers) are a start: built-in initialiser, lambda_0 = 0
-    const bool prev_bad = (ws.status[b] & (MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX)) != 0;
+    // the slot's previous solve (0 in a fresh context): after a hard failure, a final time outside its box or a restart asked for by
+    // mpcmp_rh_update neither its iterate (re-guess of the receding-horizon loop) nor its multipliers (mpcmp_config.carry_multipliers) are a
+    // start: built-in initialiser, lambda_0 = 0
+    const bool prev_bad = (ws.status[b] & MPCMP_ST_NO_GUESS) != 0;
     __syncthreads();                                      // (thread 0 resets the status word below)
     if (reguess && prev_bad) { warm_x = ws.alt_x; warm_u = ws.alt_u; warm_T = ws.alt_T; reguess = 0; }      // (null: the built-in initialiser below)
     if (warm_x) {
@@ -1140,7 +1147,7 @@ __global__ __launch_bounds__(256) void k_advance(int nseg, int nx, int B, double
     if (b >= B) return;
     if (retired[b]) return;
     atomicAdd(&count[0], 1ull);
-    if (status[b] & (MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX)) return;
+    if (status[b] & MPCMP_ST_FAILED) return;
     const int N = 3 * nseg + 1;
     const double T = sT[b];
     const double *X = sx + (size_t)b * N * nx;
@@ -1179,6 +1186,30 @@ __global__ __launch_bounds__(256) void k_advance(int nseg, int nx, int B, double
         if (info) info[b].status |= MPCMP_STATUS_ARRIVED;
         atomicAdd(&count[1], 1ull);
     }
+}
+
+// Receding horizon, between two steps (mpcmp_rh_update[_device]), one thread per listed instance b = idx[i] (idx null: b = i): the measured state
+// x [n][nx] and / or the target xf [n][nx] (either may be null) overwrite the loop's current state x0 / target xt of b
+// (MotionPlanner::set_current_state / set_target_state, motionPlanner.cpp:27-53).  What the next solve of b starts from:
+//   * live, a state only                -> nothing more: k_init re-guesses from the previous solution with the new head (solve_trajectory(false));
+//   * live, a target or `restart`       -> MPCMP_ST_RESTART: the driver's start guess and zero multipliers (k_init / k_init_m: prev_bad);
+//   * retired (arrived)                 -> revived: retired := 0, MPCMP_STATUS_ARRIVED leaves its record now, count[1] -= 1, and a restart.
+// The revival is an atomic exchange, so that an index listed twice (the device entry point cannot check) is counted once.
+__global__ __launch_bounds__(256) void k_rh_update(int nx, int n, const int *idx, const double *x, const double *xf, int restart,
+                                                   double *x0, double *xt, int *retired, int *status, mpcmp_info *info,
+                                                   unsigned long long *count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = idx ? idx[i] : i;
+    if (x) for (int r = 0; r < nx; r++) x0[(size_t)b * nx + r] = x[(size_t)i * nx + r];
+    if (xf) for (int r = 0; r < nx; r++) xt[(size_t)b * nx + r] = xf[(size_t)i * nx + r];
+    bool rs = restart || xf;
+    if (atomicExch(&retired[b], 0) != 0) {
+        atomicAnd(&info[b].status, ~MPCMP_STATUS_ARRIVED);
+        atomicAdd(&count[1], ~0ull);                          // (- 1 modulo 2^64)
+        rs = true;
+    }
+    if (rs) atomicOr(&status[b], MPCMP_ST_RESTART);
 }
 
 

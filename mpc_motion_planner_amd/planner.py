@@ -204,6 +204,26 @@ class Solver:
         check(lib().mpcmp_rh_stats(self._ctx, C.byref(done), C.byref(arr)), self._ctx)
         return int(done.value), int(arr.value)
 
+    def rh_update(self, idx=None, x=None, xf=None, restart=False):
+        """between two rh_run calls: new measured states x [n][nx] and / or targets xf [n][nx] of the instances idx [n] (None: all B, in order);
+        a new target, restart=True or a retired instance restarts from the driver's start guess (mpcmp_rh_update, include/mpcmp.h)"""
+        x, xf = [None if v is None else f64(v).reshape(-1, self.nx) for v in (x, xf)]
+        if idx is not None:
+            idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+        rows = [v.shape[0] for v in (idx, x, xf) if v is not None]
+        if len(set(rows)) > 1:
+            raise ValueError("idx, x and xf must list the same number of instances, got %s" % rows)
+        n = rows[0] if rows else getattr(self, "_rh_B", 0)
+        ip = idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None
+        check(lib().mpcmp_rh_update(self._ctx, int(n), ip, dp(x), dp(xf), capi.RH_RESTART if restart else 0), self._ctx)
+
+    def rh_update_device(self, n, idx, x, xf, restart=False, stream=0):
+        """rh_update with raw device pointers (idx: int32 [n], x / xf: double [n][nx]; 0 = NULL), ordered after the work on `stream`
+        (mpcmp_rh_update_device: indices and values are not checked)"""
+        vp = C.c_void_p
+        check(lib().mpcmp_rh_update_device(self._ctx, int(n), vp(idx or None), vp(x or None), vp(xf or None), capi.RH_RESTART if restart else 0,
+                                           vp(stream or None)), self._ctx)
+
     def debug_fetch(self, which, count):
         """diagnostics: first `count` doubles of a workspace array (0 z, 1 lambda, 2 c_eq, 3 g, 4 p, 5 y), device layout"""
         out = np.zeros(int(count))
