@@ -237,6 +237,40 @@ int mpcmp_inverse_velocities(const mpcmp_model *model, const double *q, const do
 int mpcmp_inverse_kinematics(const mpcmp_model *model, const double *R, const double *p, const double *q_init, double *q,
                              int *iters);
 
+/* ---- batched tool-pose targets: multi-start inverse kinematics on the GPU ----
+ * B problems, each a desired pose of the model's tool frame in the world frame (the frame of mpcmp_tool_jacobian): R [B][9] row-major,
+ * p [B][3]; twist [B][6] the world-frame [linear; angular] tool velocity (NULL: qd = 0); q_seeds [B][S][7] the starts, 1 <= S <= 64;
+ * q_ref [B][7] optional.  xf [B][14 narm] in the layout mpcmp_solve_batch and mpcmp_rh_update take; only arm `arm`'s 14 columns are
+ * written: q at [7 arm, 7 arm + 7) and qd at [7 narm + 7 arm, 7 narm + 7 arm + 7) (a two-arm target is two calls into one buffer).
+ * arm selects the context's model; info [B] may be NULL.  Rules:
+ *   1. per start: the DLS loop of mpcmp_inverse_kinematics unchanged (eps 1e-4, IT_MAX 1000, DT 0.1, damp 1e-2, local-frame Jacobian);
+ *   2. wrap: each joint j is shifted to q_j + 2 pi k with the integer k of smallest |k| that puts it into [lbx_j, ubx_j], k = 0 when none
+ *      does; the bounds are the context configuration's margin-applied position rows (for two arms the per-arm rows apply to every arm);
+ *   3. a start qualifies if it converged (err < 1e-4) and all 7 of its wrapped joints lie within the bounds;
+ *   4. choice: if some start qualifies and q_ref is given, the qualifying start that minimises ||q - q_ref||_2 (wrapped q; ties to the
+ *      lowest index); if some start qualifies and q_ref is NULL, the lowest qualifying index; if none qualifies, the smallest err (ties
+ *      to the lowest index), with MPCMP_IK_NOT_CONVERGED and / or MPCMP_IK_Q_OUT_OF_BOUNDS set for that start;
+ *   5. velocity: qd = J^T (J J^T + 1e-5 I)^-1 twist at the chosen, wrapped q with the world-aligned J (mpcmp_inverse_velocities);
+ *      MPCMP_IK_QD_OUT_OF_BOUNDS if qd leaves the velocity rows of lbx / ubx.
+ * The host-pointer variant is synchronous and returns MPCMP_EINVAL, writing nothing, for B < 1, S outside [1, 64], arm outside [0, narm),
+ * a required pointer NULL, a value that is not finite, or an R that is not a rotation (max |(R^T R - I)_ij| > 1e-6 or det R <= 0).
+ * The device variant checks only the scalars and NULL pointers and is ordered on hip_stream. */
+typedef struct {
+    double err;    /* ||log6(oMdes^-1 oMf)|| of the chosen start's last iterate */
+    int    seed;   /* index of the chosen start */
+    int    iters;  /* DLS iterations of the chosen start */
+    int    status; /* 0 or MPCMP_IK_* bits */
+    int    pad;
+} mpcmp_ik_info;
+#define MPCMP_IK_NOT_CONVERGED     1
+#define MPCMP_IK_Q_OUT_OF_BOUNDS   2
+#define MPCMP_IK_QD_OUT_OF_BOUNDS  4
+int mpcmp_pose_targets_batch(mpcmp_ctx *ctx, int B, int arm, const double *R, const double *p, const double *twist,
+                             int S, const double *q_seeds, const double *q_ref, double *xf, mpcmp_ik_info *info);
+int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_R, const double *d_p, const double *d_twist,
+                                    int S, const double *d_q_seeds, const double *d_q_ref, double *d_xf, mpcmp_ik_info *d_info,
+                                    void *hip_stream);
+
 /* ---- trajectory checks of the reference benchmark (examples/benchmark.cpp:58-160) ---- */
 /* out [B][74] = min(28) | max(28) of q,qd,qdd,tau over n_pts+1 uniform samples | x(T) - target (14) |
  * flags (4; 1 = pass): jerk (|d qdd/dt| <= 10 max_jerk), linear task velocity <= 1.7, angular <= 2.5, tool z >= 0.

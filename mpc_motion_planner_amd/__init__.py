@@ -5,15 +5,17 @@ binding used by bench.py and the parity tests, plus `BatchMotionPlanner`, a batc
 reference's `MotionPlanner` façade (mpc_solver/motionPlanner.hpp:16-176).  There is no CPU fallback:
 loading fails loudly when the HIP library is missing, and every solver call fails when no GPU is present.
 (The scenario helpers of the robot wrapper — Jacobian, velocity maps, inverse kinematics — are host code in the
-reference and here; they are not part of the batched solve.)
+reference and here; they are not part of the batched solve.  Their batched form for targets, `Solver.pose_targets`, runs
+multi-start inverse kinematics on the GPU.)
 """
 from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED, STATUS_OUTSIDE_TOL, STATUS_T_OUT_OF_BOX, STATUS_ARRIVED, STATUS_HARD,
-                   RH_RESTART, Config, Info, Model, INFO_DTYPE, MpcmpError, DUAL_BASES, arm_models, build_library, default_config, default_limits,
+                   RH_RESTART, IK_NOT_CONVERGED, IK_Q_OUT_OF_BOUNDS, IK_QD_OUT_OF_BOUNDS, IK_INFO_DTYPE, Config, Info, Model, INFO_DTYPE, MpcmpError, DUAL_BASES, arm_models, build_library, default_config, default_limits,
                    default_model, forward_velocities, inverse_kinematic, inverse_velocities, lib, library_path,
                    model_from_urdf, models_from_urdf, num_nodes, time_nodes, tool_jacobian)
 from .planner import BatchMotionPlanner, Solver
 
 __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED", "STATUS_OUTSIDE_TOL", "STATUS_T_OUT_OF_BOX", "STATUS_ARRIVED", "STATUS_HARD", "RH_RESTART",
+           "IK_NOT_CONVERGED", "IK_Q_OUT_OF_BOUNDS", "IK_QD_OUT_OF_BOUNDS", "IK_INFO_DTYPE",
            "Config", "Info", "Model", "INFO_DTYPE", "MpcmpError", "build_library", "default_config",
            "default_limits", "default_model", "lib", "library_path", "model_from_urdf", "models_from_urdf", "num_nodes",
            "time_nodes", "BatchMotionPlanner", "Solver", "forward_velocities", "inverse_kinematic",

@@ -47,6 +47,10 @@ INFO_DTYPE = np.dtype([("T", "f8"), ("viol_l1", "f8"), ("defect_inf", "f8"), ("p
                        ("term_err_inf", "f8"), ("last_alpha", "f8"), ("qp_iters_total", "i4"),
                        ("sqp_iters", "i4"), ("status", "i4"), ("qp_capped", "i4")])
 
+# record and status bits of mpcmp_pose_targets_batch[_device] (mpcmp_ik_info, include/mpcmp.h)
+IK_NOT_CONVERGED, IK_Q_OUT_OF_BOUNDS, IK_QD_OUT_OF_BOUNDS = 1, 2, 4
+IK_INFO_DTYPE = np.dtype([("err", "f8"), ("seed", "i4"), ("iters", "i4"), ("status", "i4"), ("pad", "i4")])
+
 # every symbol include/mpcmp.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_urdf", "mpcmp_default_limits", "mpcmp_default_config",
            "mpcmp_set_margins", "mpcmp_set_min_height", "mpcmp_num_nodes", "mpcmp_time_nodes", "mpcmp_version",
@@ -59,7 +63,7 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_jerk_point_batch", "mpcmp_mpc_point_batch", "mpcmp_debug_fetch",
            "mpcmp_warm_start_jerk_acc_batch", "mpcmp_warm_start_jerk_acc_batch_device", "mpcmp_jerk_trajectory_acc_batch", "mpcmp_jerk_point_acc_batch",
            "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats",
-           "mpcmp_rh_update", "mpcmp_rh_update_device"]
+           "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device"]
 
 
 def library_path():
@@ -117,6 +121,8 @@ def lib():
         L.mpcmp_last_error.argtypes = [C.c_void_p]
         L.mpcmp_rh_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
         L.mpcmp_rh_update_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.mpcmp_pose_targets_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
+        L.mpcmp_pose_targets_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5
         _lib = L
     return _lib
 

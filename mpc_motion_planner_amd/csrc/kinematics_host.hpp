@@ -1,15 +1,20 @@
-// kinematics_host.hpp — host-side scenario helpers of the reference's robot wrapper (robot_utils/pandaWrapper.cpp:14-107):
+// kinematics_host.hpp — scenario helpers of the reference's robot wrapper (robot_utils/pandaWrapper.cpp:14-107):
 // tool-frame Jacobian, task <-> joint velocity maps and the damped least-squares inverse kinematics that
-// examples/benchmark.cpp:19-42 uses to draw target states.  These run once per scenario on the host in the reference and
-// do so here; the batched solve never calls them.
+// examples/benchmark.cpp:19-42 uses to draw target states.  The reference runs them once per scenario on the host; so do the
+// single-problem entry points here (mpcmp_tool_jacobian, mpcmp_inverse_*).  The same functions are __host__ __device__: the
+// batched multi-start IK kernel (ik_device.hpp) runs this source, one DLS step at a time, so host and device share one
+// implementation.  The batched solve never calls them.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <cmath>
 #include "../../include/mpcmp.h"
+
+#define MPCMP_HD __host__ __device__ inline
 
 namespace mpcmp_host {
 
 // forward kinematics of the tool frame; zax/org: joint axes and origins in the world frame
-inline void fk_chain(const mpcmp_model &M, const double *q, double R[9], double p[3], double zax[7][3], double org[7][3]) {
+MPCMP_HD void fk_chain(const mpcmp_model &M, const double *q, double R[9], double p[3], double zax[7][3], double org[7][3]) {
     double Rw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pw[3] = {0, 0, 0};
     for (int i = 0; i < 7; i++) {
         for (int r = 0; r < 3; r++) pw[r] += Rw[3 * r] * M.p[i][0] + Rw[3 * r + 1] * M.p[i][1] + Rw[3 * r + 2] * M.p[i][2];
@@ -31,7 +36,7 @@ inline void fk_chain(const mpcmp_model &M, const double *q, double R[9], double 
 
 // world-aligned Jacobian of the tool frame, rows [linear(3); angular(3)], row-major 6x7: what the reference obtains by
 // rotating Pinocchio's LOCAL frame Jacobian with blockdiag(R, R) (pandaWrapper.cpp:70-75,97-101)
-inline void tool_jacobian(const mpcmp_model &M, const double *q, double J[42], double p[3], double R[9]) {
+MPCMP_HD void tool_jacobian(const mpcmp_model &M, const double *q, double J[42], double p[3], double R[9]) {
     double zax[7][3], org[7][3];
     fk_chain(M, q, R, p, zax, org);
     for (int i = 0; i < 7; i++) {
@@ -44,7 +49,7 @@ inline void tool_jacobian(const mpcmp_model &M, const double *q, double J[42], d
 }
 
 // x = (J J^T + damp I)^-1 b for a 6x7 J (Cholesky of the 6x6 normal matrix; it is SPD for damp > 0)
-inline bool solve_normal(const double J[42], double damp, const double b[6], double x[6]) {
+MPCMP_HD bool solve_normal(const double J[42], double damp, const double b[6], double x[6]) {
     double A[36];
     for (int r = 0; r < 6; r++)
         for (int c = 0; c < 6; c++) {
@@ -67,7 +72,7 @@ inline bool solve_normal(const double J[42], double damp, const double b[6], dou
 }
 
 // rotation vector of R (SO(3) logarithm)
-inline void log3(const double R[9], double w[3], double *theta) {
+MPCMP_HD void log3(const double R[9], double w[3], double *theta) {
     const double tr = R[0] + R[4] + R[8];
     double ct = 0.5 * (tr - 1.0);
     ct = ct > 1.0 ? 1.0 : (ct < -1.0 ? -1.0 : ct);
@@ -86,7 +91,7 @@ inline void log3(const double R[9], double w[3], double *theta) {
 }
 
 // se(3) logarithm of (R, p), output [v(3); w(3)] (the ordering of pinocchio::log6(...).toVector())
-inline void log6(const double R[9], const double p[3], double out[6]) {
+MPCMP_HD void log6(const double R[9], const double p[3], double out[6]) {
     double w[3], th;
     log3(R, w, &th);
     double alpha, beta;
@@ -105,6 +110,59 @@ inline void log6(const double R[9], const double p[3], double out[6]) {
     out[1] = alpha * p[1] - 0.5 * cy + beta * wp * w[1];
     out[2] = alpha * p[2] - 0.5 * cz + beta * wp * w[2];
     out[3] = w[0]; out[4] = w[1]; out[5] = w[2];
+}
+
+// PandaWrapper::inverse_velocities (pandaWrapper.cpp:62-88): qd = J^T (J J^T + 1e-5 I)^-1 v, v = [linear(3); angular(3)], world-aligned J at q
+MPCMP_HD bool inverse_velocities(const mpcmp_model &M, const double q[7], const double v[6], double qd[7]) {
+    double J[42], p[3], R[9], x[6];
+    tool_jacobian(M, q, J, p, R);
+    if (!solve_normal(J, 1e-5, v, x)) return false;
+    for (int k = 0; k < 7; k++) { double s = 0; for (int r = 0; r < 6; r++) s += J[r * 7 + k] * x[r]; qd[k] = s; }
+    return true;
+}
+
+// PandaWrapper::inverse_kinematic (pandaWrapper.cpp:14-60): its constants, and one iteration of its loop
+constexpr double IK_EPS = 1e-4, IK_DT = 1e-1, IK_DAMP = 1e-2;
+constexpr int IK_IT_MAX = 1000;
+enum { IK_CONVERGED = 0, IK_CAPPED = 1, IK_STEPPED = 2, IK_NOT_PD = 3 };
+
+// Iteration `it` at the iterate q: *enorm = ||log6(oMdes^-1 oMf(q))||; then IK_CONVERGED (enorm < IK_EPS), IK_CAPPED (it >= IK_IT_MAX), or
+// q -= DT J_local^T (J J^T + damp I)^-1 err and IK_STEPPED (IK_NOT_PD, q unchanged, if the normal matrix lost positive definiteness).
+MPCMP_HD int ik_dls_step(const mpcmp_model &M, const double Rdes[9], const double pdes[3], double q[7], int it, double *enorm) {
+    double J[42], p[3], R[9];
+    tool_jacobian(M, q, J, p, R);
+    // dMf = oMdes^-1 * oMf
+    double dR[9], dp[3], err[6];
+    const double t[3] = {p[0] - pdes[0], p[1] - pdes[1], p[2] - pdes[2]};
+    for (int r = 0; r < 3; r++) {
+        dp[r] = Rdes[0 * 3 + r] * t[0] + Rdes[1 * 3 + r] * t[1] + Rdes[2 * 3 + r] * t[2];
+        for (int c = 0; c < 3; c++) dR[3 * r + c] = Rdes[0 * 3 + r] * R[0 * 3 + c] + Rdes[1 * 3 + r] * R[1 * 3 + c] + Rdes[2 * 3 + r] * R[2 * 3 + c];
+    }
+    log6(dR, dp, err);
+    double nrm = 0;
+    for (int k = 0; k < 6; k++) nrm += err[k] * err[k];
+    *enorm = std::sqrt(nrm);
+    if (*enorm < IK_EPS) return IK_CONVERGED;
+    if (it >= IK_IT_MAX) return IK_CAPPED;
+    // LOCAL-frame Jacobian: rotate the world-aligned rows back with R^T
+    double Jl[42], x[6];
+    for (int i = 0; i < 7; i++)
+        for (int r = 0; r < 3; r++) {
+            Jl[r * 7 + i] = R[0 * 3 + r] * J[0 * 7 + i] + R[1 * 3 + r] * J[1 * 7 + i] + R[2 * 3 + r] * J[2 * 7 + i];
+            Jl[(3 + r) * 7 + i] = R[0 * 3 + r] * J[3 * 7 + i] + R[1 * 3 + r] * J[4 * 7 + i] + R[2 * 3 + r] * J[5 * 7 + i];
+        }
+    if (!solve_normal(Jl, IK_DAMP, err, x)) return IK_NOT_PD;
+    for (int k = 0; k < 7; k++) { double s = 0; for (int r = 0; r < 6; r++) s += Jl[r * 7 + k] * x[r]; q[k] -= IK_DT * s; }
+    return IK_STEPPED;
+}
+
+// q + 2 pi k with the integer k of smallest |k| that puts it into [lo, hi]; q itself when no k does
+MPCMP_HD double wrap_joint(double q, double lo, double hi) {
+    const double tp = 2.0 * M_PI;
+    const double klo = std::ceil((lo - q) / tp), khi = std::floor((hi - q) / tp);
+    if (klo > khi) return q;
+    const double k = klo > 0.0 ? klo : (khi < 0.0 ? khi : 0.0);
+    return q + tp * k;
 }
 
 }  // namespace mpcmp_host

@@ -26,6 +26,7 @@
 #include "multi_kernels.hpp"
 #include "kinematics_host.hpp"
 #include "jerk_device.hpp"
+#include "ik_device.hpp"
 
 #ifdef MPCMP_SPLIT_N25
 // the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
@@ -237,45 +238,22 @@ extern "C" int mpcmp_forward_velocities(const mpcmp_model *model, const double *
 
 extern "C" int mpcmp_inverse_velocities(const mpcmp_model *model, const double *q, const double *lin, const double *ang, double *qd) {
     if (!model || !q || !lin || !ang || !qd) return MPCMP_EINVAL;
-    double J[42], p[3], R[9], x[6];
-    mpcmp_host::tool_jacobian(*model, q, J, p, R);
     const double b[6] = {lin[0], lin[1], lin[2], ang[0], ang[1], ang[2]};
-    if (!mpcmp_host::solve_normal(J, 1e-5, b, x)) return MPCMP_ERUNTIME;
-    for (int k = 0; k < 7; k++) { double s = 0; for (int r = 0; r < 6; r++) s += J[r * 7 + k] * x[r]; qd[k] = s; }
-    return MPCMP_OK;
+    return mpcmp_host::inverse_velocities(*model, q, b, qd) ? MPCMP_OK : MPCMP_ERUNTIME;
 }
 
+// the loop of PandaWrapper::inverse_kinematic around the DLS step the batched kernel shares (kinematics_host.hpp)
 extern "C" int mpcmp_inverse_kinematics(const mpcmp_model *model, const double *Rdes, const double *pdes, const double *q_init,
                                         double *q, int *iters) {
     if (!model || !Rdes || !pdes || !q) return MPCMP_EINVAL;
-    const double eps = 1e-4, DT = 1e-1, damp = 1e-2;
-    const int IT_MAX = 1000;
     for (int k = 0; k < 7; k++) q[k] = q_init ? q_init[k] : 0.0;
     for (int it = 0;; it++) {
-        double J[42], p[3], R[9];
-        mpcmp_host::tool_jacobian(*model, q, J, p, R);
-        // dMf = oMdes^-1 * oMf
-        double dR[9], dp[3], err[6];
-        const double t[3] = {p[0] - pdes[0], p[1] - pdes[1], p[2] - pdes[2]};
-        for (int r = 0; r < 3; r++) {
-            dp[r] = Rdes[0 * 3 + r] * t[0] + Rdes[1 * 3 + r] * t[1] + Rdes[2 * 3 + r] * t[2];
-            for (int c = 0; c < 3; c++) dR[3 * r + c] = Rdes[0 * 3 + r] * R[0 * 3 + c] + Rdes[1 * 3 + r] * R[1 * 3 + c] + Rdes[2 * 3 + r] * R[2 * 3 + c];
-        }
-        mpcmp_host::log6(dR, dp, err);
-        double nrm = 0;
-        for (int k = 0; k < 6; k++) nrm += err[k] * err[k];
+        double en;
+        const int r = mpcmp_host::ik_dls_step(*model, Rdes, pdes, q, it, &en);
         if (iters) *iters = it;
-        if (std::sqrt(nrm) < eps) return MPCMP_OK;
-        if (it >= IT_MAX) return 1;
-        // LOCAL-frame Jacobian: rotate the world-aligned rows back with R^T
-        double Jl[42], x[6];
-        for (int i = 0; i < 7; i++)
-            for (int r = 0; r < 3; r++) {
-                Jl[r * 7 + i] = R[0 * 3 + r] * J[0 * 7 + i] + R[1 * 3 + r] * J[1 * 7 + i] + R[2 * 3 + r] * J[2 * 7 + i];
-                Jl[(3 + r) * 7 + i] = R[0 * 3 + r] * J[3 * 7 + i] + R[1 * 3 + r] * J[4 * 7 + i] + R[2 * 3 + r] * J[5 * 7 + i];
-            }
-        if (!mpcmp_host::solve_normal(Jl, damp, err, x)) return MPCMP_ERUNTIME;
-        for (int k = 0; k < 7; k++) { double s = 0; for (int r = 0; r < 6; r++) s += Jl[r * 7 + k] * x[r]; q[k] -= DT * s; }
+        if (r == mpcmp_host::IK_CONVERGED) return MPCMP_OK;
+        if (r == mpcmp_host::IK_CAPPED) return 1;
+        if (r == mpcmp_host::IK_NOT_PD) return MPCMP_ERUNTIME;
     }
 }
 
@@ -1470,6 +1448,77 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
     hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, st, ctx->d_model, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 74 * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// batched tool-pose targets (ik_device.hpp): B problems x S starts of the DLS inverse kinematics, one start chosen per problem, xf columns of one arm
+static int pose_targets_check(mpcmp_ctx *ctx, int B, int arm, const double *R, const double *p, int S, const double *seeds, const double *xf) {
+    if (!ctx) { g_err = "mpcmp_pose_targets: no context"; return MPCMP_EINVAL; }
+    if (B < 1) { ctx->err = "mpcmp_pose_targets: B must be >= 1"; return MPCMP_EINVAL; }
+    if (S < 1 || S > 64) { ctx->err = "mpcmp_pose_targets: S must be in [1, 64]"; return MPCMP_EINVAL; }
+    if (arm < 0 || arm >= ctx->narm) { ctx->err = "mpcmp_pose_targets: arm must be in [0, narm)"; return MPCMP_EINVAL; }
+    if (!R || !p || !seeds || !xf) { ctx->err = "mpcmp_pose_targets: R, p, q_seeds and xf are required"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_R, const double *d_p, const double *d_twist,
+                                               int S, const double *d_seeds, const double *d_q_ref, double *d_xf, mpcmp_ik_info *d_info, void *hip_stream) {
+    if (int rc = pose_targets_check(ctx, B, arm, d_R, d_p, S, d_seeds, d_xf)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    IkBounds bd;
+    for (int j = 0; j < 7; j++) { bd.lq[j] = ctx->cfg.lbx[j]; bd.uq[j] = ctx->cfg.ubx[j]; bd.lv[j] = ctx->cfg.lbx[7 + j]; bd.uv[j] = ctx->cfg.ubx[7 + j]; }
+    int P = 1;
+    while (P < S) P <<= 1;
+    const long threads = (long)B * P;
+    hipLaunchKernelGGL(k_pose_targets, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, ctx->d_model + arm, bd, B, S, P,
+                       ctx->nx, 7 * arm, 7 * ctx->narm + 7 * arm, d_R, d_p, d_twist, d_seeds, d_q_ref, d_xf, d_info);
+    HIPCHK(ctx, hipGetLastError());
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_pose_targets_batch(mpcmp_ctx *ctx, int B, int arm, const double *R, const double *p, const double *twist,
+                                        int S, const double *seeds, const double *q_ref, double *xf, mpcmp_ik_info *info) {
+    if (int rc = pose_targets_check(ctx, B, arm, R, p, S, seeds, xf)) return rc;
+    const size_t nb = B, nx = ctx->nx;
+    const struct { const double *v; size_t n; } in[5] = {{R, 9 * nb}, {p, 3 * nb}, {twist, 6 * nb}, {seeds, 7 * nb * S}, {q_ref, 7 * nb}};
+    for (const auto &a : in)
+        if (a.v)
+            for (size_t k = 0; k < a.n; k++)
+                if (!std::isfinite(a.v[k])) { ctx->err = "mpcmp_pose_targets: an input value is not finite"; return MPCMP_EINVAL; }
+    for (size_t b = 0; b < nb; b++) {
+        const double *r = R + 9 * b;
+        double dev = 0.0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const double g = r[i] * r[j] + r[3 + i] * r[3 + j] + r[6 + i] * r[6 + j] - (i == j ? 1.0 : 0.0);
+                dev = std::max(dev, std::fabs(g));
+            }
+        const double det = r[0] * (r[4] * r[8] - r[5] * r[7]) - r[1] * (r[3] * r[8] - r[5] * r[6]) + r[2] * (r[3] * r[7] - r[4] * r[6]);
+        if (dev > 1e-6 || !(det > 0.0)) {
+            std::ostringstream os;
+            os << "mpcmp_pose_targets: R of problem " << b << " is not a rotation";
+            ctx->err = os.str();
+            return MPCMP_EINVAL;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TmpBuf tb(ctx, (9 + 3 + 6 + 7 * (size_t)S + 7 + nx) * nb * sizeof(double) + nb * sizeof(mpcmp_ik_info));
+    double *dR = tb.get<double>(9 * nb), *dp_ = tb.get<double>(3 * nb), *dtw = twist ? tb.get<double>(6 * nb) : nullptr,
+           *dsd = tb.get<double>(7 * nb * S), *dqr = q_ref ? tb.get<double>(7 * nb) : nullptr, *dxf = tb.get<double>(nx * nb);
+    mpcmp_ik_info *dinfo = info ? tb.get<mpcmp_ik_info>(nb) : nullptr;
+    if (!tb.ok) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(dR, R, sizeof(double) * 9 * nb, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dp_, p, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, st));
+    if (dtw) HIPCHK(ctx, hipMemcpyAsync(dtw, twist, sizeof(double) * 6 * nb, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dsd, seeds, sizeof(double) * 7 * nb * S, hipMemcpyHostToDevice, st));
+    if (dqr) HIPCHK(ctx, hipMemcpyAsync(dqr, q_ref, sizeof(double) * 7 * nb, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dxf, xf, sizeof(double) * nx * nb, hipMemcpyHostToDevice, st));     // the other arm's columns come back as they were
+    if (int rc = mpcmp_pose_targets_batch_device(ctx, B, arm, dR, dp_, dtw, S, dsd, dqr, dxf, dinfo, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(xf, dxf, sizeof(double) * nx * nb, hipMemcpyDeviceToHost, st));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, dinfo, sizeof(mpcmp_ik_info) * nb, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }

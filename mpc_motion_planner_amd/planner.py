@@ -224,6 +224,38 @@ class Solver:
         check(lib().mpcmp_rh_update_device(self._ctx, int(n), vp(idx or None), vp(x or None), vp(xf or None), capi.RH_RESTART if restart else 0,
                                            vp(stream or None)), self._ctx)
 
+    def pose_targets(self, R, p, seeds, q_ref=None, twist=None, arm=0, xf=None):
+        """Joint-space targets from tool poses: multi-start DLS inverse kinematics on the GPU (mpcmp_pose_targets_batch, include/mpcmp.h).
+        R [B][3][3], p [B][3] desired tool poses; seeds [B][S][7] starts (scenarios.ik_seeds); q_ref [B][7] prefers the qualifying start
+        closest to it; twist [B][6] tool velocity [linear; angular] (None: qd = 0).  Writes arm `arm`'s q and qd columns of xf [B][nx]
+        (None: a new zero array; else a C-contiguous float64 array, filled in place).  Returns (xf, info) with info of IK_INFO_DTYPE."""
+        seeds = f64(seeds)
+        if seeds.ndim == 2:
+            seeds = seeds[:, None, :]
+        B, S = seeds.shape[0], seeds.shape[1]
+        if seeds.shape[2] != 7:
+            raise ValueError("seeds must be [B][S][7], got %s" % (seeds.shape,))
+        R, p = f64(R).reshape(B, 9), f64(p).reshape(B, 3)
+        q_ref = None if q_ref is None else f64(q_ref).reshape(B, 7)
+        twist = None if twist is None else f64(twist).reshape(B, 6)
+        if xf is None:
+            xf = np.zeros((B, self.nx))
+        elif not (isinstance(xf, np.ndarray) and xf.dtype == np.float64 and xf.flags.c_contiguous and xf.shape == (B, self.nx)):
+            raise ValueError("xf must be a C-contiguous float64 array of shape (%d, %d)" % (B, self.nx))
+        info = np.zeros(B, dtype=capi.IK_INFO_DTYPE)
+        vp = C.c_void_p
+        check(lib().mpcmp_pose_targets_batch(self._ctx, int(B), int(arm), vp(R.ctypes.data), vp(p.ctypes.data),
+                                             vp(twist.ctypes.data if twist is not None else None), int(S), vp(seeds.ctypes.data),
+                                             vp(q_ref.ctypes.data if q_ref is not None else None), vp(xf.ctypes.data), vp(info.ctypes.data)), self._ctx)
+        return xf, info
+
+    def pose_targets_device(self, B, arm, R, p, twist, S, seeds, q_ref, xf, info, stream=0):
+        """pose_targets with raw device pointers (0 = NULL for twist, q_ref and info), ordered on `stream`; values are not checked
+        (mpcmp_pose_targets_batch_device)"""
+        vp = C.c_void_p
+        check(lib().mpcmp_pose_targets_batch_device(self._ctx, int(B), int(arm), vp(R), vp(p), vp(twist or None), int(S), vp(seeds),
+                                                    vp(q_ref or None), vp(xf), vp(info or None), vp(stream or None)), self._ctx)
+
     def debug_fetch(self, which, count):
         """diagnostics: first `count` doubles of a workspace array (0 z, 1 lambda, 2 c_eq, 3 g, 4 p, 5 y), device layout"""
         out = np.zeros(int(count))

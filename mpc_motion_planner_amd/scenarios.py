@@ -67,6 +67,17 @@ def sample_states(B, margins, seed=SEED, stream_offset=0, min_height=0.05, model
     return np.concatenate([q, v], axis=1)
 
 
+def ik_seeds(B, S, cfg, seed=SEED):
+    """[B][S][7] starts of Solver.pose_targets: uniform within the position rows of cfg (lbx / ubx, margins applied).  Problem i draws
+    from its own SplitMix64 stream (seed, i), so its starts do not depend on B."""
+    lo, hi = np.array(cfg.lbx[:7]), np.array(cfg.ubx[:7])
+    base = (int(seed) * 0x100000001B3 + (1 << 40)) & _M64         # far from the (start, target) streams of sample_states (salts 0 and 1)
+    with np.errstate(over="ignore"):
+        state = np.uint64(base) + np.arange(B, dtype=np.uint64) * np.uint64(2)
+    _, u = _uniform(state, 7 * int(S))
+    return (0.5 * (u.reshape(B, S, 7) * (hi - lo) + (hi + lo))).copy()
+
+
 def make_batch(B, margins=(0.9, 0.9, 0.5, 0.9, 0.1), seed=SEED, stream_offset=0):
     """(x0 [B,14], xf [B,14]) — margins default to examples/offline_trajectory.cpp:9."""
     x0 = sample_states(B, margins, seed, stream_offset, salt=0)
