@@ -52,7 +52,10 @@ typedef struct {
     double gravity[3];
 } mpcmp_model;
 
-/* Solver settings + bounds; replaces mpc.settings()/qp_settings()/..._bounds() (motionPlanner.cpp:15-20,56-100). */
+/* Solver settings + bounds; replaces mpc.settings()/qp_settings()/..._bounds() (motionPlanner.cpp:15-20,56-100).
+ * mpcmp_create[_multi] and mpcmp_set_config reject with MPCMP_EINVAL: NaN or negative eps_abs, eps_rel, eps_target, hess_reg; rho_eq_scale <= 0;
+ * ls_eta or ls_tau outside (0, 1); quirk_dtau_dT other than 0 / 1; in any bound pair NaN, lb > ub, lb = +inf or ub = -inf (infinite ends
+ * otherwise switch a bound off); and for num_seg 1, 2, 4 a general row (lbg / ubg) narrower than 1e-4. */
 typedef struct {
     int    num_seg;          /* NUM_SEG, robot_ocp.hpp:32 (4 -> 13 nodes, 6 -> 19 nodes as shipped, 8 -> 25)*/
     int    sqp_iters;        /* mpc.settings().max_iter,             motionPlanner.cpp:15 (2 as shipped)   */

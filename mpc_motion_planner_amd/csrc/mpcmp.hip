@@ -548,6 +548,22 @@ static int validate(const mpcmp_config *c, std::string &err) {
     if (c->ls_iters < 2 || c->ls_iters > 10) { err = "ls_iters must be in [2,10]"; return MPCMP_EINVAL; }
     if (!(c->rho > 0) || !(c->sigma > 0) || !(c->alpha > 0 && c->alpha < 2)) { err = "rho, sigma > 0 and 0 < alpha < 2 required"; return MPCMP_EINVAL; }
     if (c->qp_warm_start < -1 || c->qp_warm_start > 1 || c->carry_multipliers < -1 || c->carry_multipliers > 1) { err = "qp_warm_start and carry_multipliers are -1, 0 or 1"; return MPCMP_EINVAL; }
+    // (written as !(x >= 0) and the like, so that a NaN fails every test)
+    if (!(c->eps_abs >= 0) || !(c->eps_rel >= 0) || !(c->eps_target >= 0) || !(c->hess_reg >= 0)) { err = "eps_abs, eps_rel, eps_target and hess_reg must be >= 0"; return MPCMP_EINVAL; }
+    if (!(c->rho_eq_scale > 0)) { err = "rho_eq_scale must be > 0"; return MPCMP_EINVAL; }
+    if (!(c->ls_eta > 0 && c->ls_eta < 1) || !(c->ls_tau > 0 && c->ls_tau < 1)) { err = "ls_eta and ls_tau must lie in (0, 1)"; return MPCMP_EINVAL; }
+    if (c->quirk_dtau_dT != 0 && c->quirk_dtau_dT != 1) { err = "quirk_dtau_dT is 0 or 1"; return MPCMP_EINVAL; }
+    // bounds: infinite ends are allowed (a row or box switched off); NaN, lb > ub and an empty box (lb = +inf or ub = -inf) are not
+    auto box_ok = [](double lb, double ub) { return lb <= ub && lb < INFINITY && ub > -INFINITY; };
+    for (int i = 0; i < 14; i++) if (!box_ok(c->lbx[i], c->ubx[i])) { err = "lbx[" + std::to_string(i) + "] <= ubx[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 7; i++) if (!box_ok(c->lbu[i], c->ubu[i])) { err = "lbu[" + std::to_string(i) + "] <= ubu[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 8; i++) if (!box_ok(c->lbg[i], c->ubg[i])) { err = "lbg[" + std::to_string(i) + "] <= ubg[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    if (!box_ok(c->lbT, c->ubT)) { err = "lbT <= ubT required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    // A general row narrower than 1e-4 takes rho_eq (oracle/ocp.c: u - l < 1e-4).  The assembly of k_qp and k_qp2 (num_seg 1, 2, 4) gives every
+    // general row the plain rho, so its factor would not be the matrix its iteration uses: such rows are supported from num_seg 6 on (k_qp3, k_qp5)
+    if (c->num_seg <= 4)
+        for (int i = 0; i < 8; i++)
+            if (c->ubg[i] - c->lbg[i] < 1e-4) { err = "num_seg 1, 2 and 4: ubg[" + std::to_string(i) + "] - lbg[" + std::to_string(i) + "] must be >= 1e-4 (narrower general rows need num_seg 6 or 8)"; return MPCMP_EINVAL; }
     return MPCMP_OK;
 }
 
@@ -1729,7 +1745,8 @@ extern "C" int mpcmp_kernel_timing(mpcmp_ctx *ctx, int reset, const char **name,
     }
     ctx->ev_used = 0;
     ctx->timing = true;            // event recording starts with the first call (bench.py calls it once before the timed region)
-    if (name) *name = (ctx->nseg == 6 && ctx->narm == 1 && ctx->qp19 == 5) ? "k_qp5" : ctx->nseg >= 6 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 3 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 4 ? "k_qp4" : ((ctx->nseg == 2 || ctx->nseg == 4) ? "k_qp2" : "k_qp")));
+    // (the loop kernel KSel picks: MPCMP_FORCE_V1 sends num_seg 2 and 4 to the generic k_qp)
+    if (name) *name = (ctx->nseg == 6 && ctx->narm == 1 && ctx->qp19 == 5) ? "k_qp5" : ctx->nseg >= 6 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 3 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 4 ? "k_qp4" : ((ctx->nseg == 2 || ctx->nseg == 4) && !ctx->force_v1 ? "k_qp2" : "k_qp")));
     if (ms_total) *ms_total = ctx->qp_ms;
     if (launches) *launches = ctx->qp_launches;
     if (reset) { ctx->qp_ms = 0.0; ctx->qp_launches = 0; }

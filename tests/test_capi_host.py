@@ -121,6 +121,65 @@ def test_bad_config_rejected_before_touching_the_gpu(M):
     assert M.lib().mpcmp_create(None, None, 0, 4, C.byref(ctx)) == -1
 
 
+def _edit(c, field, v):
+    """field: a name, or (name, index) of a bound table entry"""
+    if isinstance(field, tuple):
+        getattr(c, field[0])[field[1]] = v
+    else:
+        setattr(c, field, v)
+
+
+NAN, INF = float("nan"), float("inf")
+# (field, a value no kernel or oracle gives a meaning to, a valid value of the same field)
+BAD_SETTINGS = [("eps_abs", NAN, 0.0), ("eps_abs", -1e-3, 0.0), ("eps_rel", NAN, 0.0), ("eps_rel", -1e-6, 0.0), ("eps_target", NAN, 0.0),
+                ("eps_target", -1e-2, 0.0), ("hess_reg", NAN, 0.0), ("hess_reg", -1e-3, 0.0), ("rho_eq_scale", 0.0, 1.0), ("rho_eq_scale", -1e3, 1.0),
+                ("rho_eq_scale", NAN, 1.0), ("ls_eta", 0.0, 0.1), ("ls_eta", 1.0, 0.9), ("ls_eta", NAN, 0.25), ("ls_tau", 0.0, 0.7), ("ls_tau", 1.0, 0.7),
+                ("ls_tau", -0.5, 0.5), ("ls_tau", NAN, 0.5), ("quirk_dtau_dT", 2, 0), ("quirk_dtau_dT", -1, 1),
+                (("lbx", 3), 5.0, -INF), (("ubx", 9), NAN, INF), (("lbx", 0), NAN, 0.25), (("lbu", 2), 1e9, -INF), (("ubu", 6), NAN, 0.0),
+                (("lbg", 4), 1e3, -INF), (("ubg", 0), -1e3, INF), (("lbg", 7), NAN, -INF), (("ubg", 7), NAN, INF), (("lbg", 7), INF, 0.05),
+                (("ubx", 1), -INF, INF), ("lbT", 11.0, 0.0), ("ubT", NAN, INF), ("lbT", NAN, -INF), ("ubT", -1.0, 10.0)]
+
+
+@pytest.mark.parametrize("field,bad,good", BAD_SETTINGS, ids=["%s=%s" % (f if isinstance(f, str) else "%s[%d]" % f, b) for f, b, _ in BAD_SETTINGS])
+def test_meaningless_settings_rejected_before_touching_the_gpu(M, field, bad, good):
+    """validate() runs before mpcmp_create looks for a device: a meaningless setting (NaN, a negative tolerance or shift, rho_eq_scale <= 0, a line
+    search fraction outside (0, 1), quirk_dtau_dT not 0 / 1, lb > ub, NaN or an empty box in any bound) is MPCMP_EINVAL with a message, for one arm
+    and two; the same configuration with a valid value (infinite bound ends included) passes validation: -2 without a GPU (0 with one)"""
+    import torch
+    gpu = torch.cuda.is_available()
+    models = M.arm_models(M.DUAL_BASES)
+    for narm in (1, 2):
+        c = M.default_config(6, 2, margins=(0.9, 0.9, 0.5, 0.9))
+        _edit(c, field, bad)
+        ctx = C.c_void_p()
+        rc = M.lib().mpcmp_create(C.byref(c), None, 0, 1, C.byref(ctx)) if narm == 1 else M.lib().mpcmp_create_multi(C.byref(c), models, 2, 0, 1, C.byref(ctx))
+        assert rc == -1 and not ctx.value, (narm, field, bad, rc)
+        assert M.lib().mpcmp_last_error(None), (narm, field, bad)
+        _edit(c, field, good)
+        rc = M.lib().mpcmp_create(C.byref(c), None, 0, 1, C.byref(ctx)) if narm == 1 else M.lib().mpcmp_create_multi(C.byref(c), models, 2, 0, 1, C.byref(ctx))
+        assert rc == (0 if gpu else -2), (narm, field, good, rc, M.lib().mpcmp_last_error(None))
+        if ctx.value:
+            M.lib().mpcmp_destroy(ctx)
+
+
+def test_narrow_general_rows_rejected_below_num_seg_6(M):
+    """a general row narrower than 1e-4 (rho_eq in the oracle) is EINVAL for num_seg 1, 2, 4 (k_qp / k_qp2 assemble every general row with the
+    plain rho); num_seg 6 and 8 take it, and a row of 2e-4 passes everywhere"""
+    import torch
+    gpu = torch.cuda.is_available()
+    for nseg in (1, 2, 4, 6, 8):
+        for q, w in ((2, 5e-5), (7, 0.0), (2, 2e-4)):
+            c = M.default_config(nseg, 2, margins=(0.9, 0.9, 0.5, 0.9))
+            c.lbg[q], c.ubg[q] = 0.05 - w / 2, 0.05 + w / 2
+            ctx = C.c_void_p()
+            rc = M.lib().mpcmp_create(C.byref(c), None, 0, 1, C.byref(ctx))
+            assert rc == (-1 if nseg <= 4 and w < 1e-4 else (0 if gpu else -2)), (nseg, q, w, rc)
+            if rc == -1:
+                assert b"lbg" in M.lib().mpcmp_last_error(None)
+            if ctx.value:
+                M.lib().mpcmp_destroy(ctx)
+
+
 def test_cpp_shim_and_example_compile(M, tmp_path):
     """the header-only MotionPlanner mirror and the offline_trajectory counterpart build with plain g++"""
     exe = str(tmp_path / "offline_trajectory")
