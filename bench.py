@@ -12,10 +12,14 @@ no data-path collective, one RCCL gather of the solutions to rank 0 inside the t
   --scaling weak   (default)  --batch problems PER GPU          (what the driver's N=1,2,4,8 sweep measures)
   --scaling strong            --batch problems in the WHOLE job (slice [r*B/G, (r+1)*B/G))
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scaling weak|strong] [--workload ...] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--scaling weak|strong] [--workload ...] [--dump-outputs DIR] [--full]
     (N>1 without WORLD_SIZE in the environment: bench.py starts its own N ranks — `python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N` as a child process, before anything touches the GPU — and
      forwards rank 0's JSON line and the exit code; under torchrun it is a rank.)
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; `roofline` and `quality` come from that run and
+from committed profiles.  --full adds what takes runs of its own: the host->host repeats, the CPU baselines of the oracle and, for the
+default workload on one GPU, the brief `secondary` runs of the other workloads.
 """
 import argparse
 import json
@@ -371,7 +375,7 @@ def bench_receding_horizon(args, M, scenarios, rank, world, local, dist, flags=N
                             note="status of every instance's LAST executed re-solve (an arrived instance keeps the record of the solve it arrived with)")}
     if dumped is not None:
         line["dump_outputs"] = dumped
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # CPU baseline: the oracle's loop (same rule: re-guess, carried multipliers, advance + arrival) on a bounded sample of the instances
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py as o
@@ -506,7 +510,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=None, help="problems per GPU (weak) or in the whole job (strong); default 1024 (4096 for dual14)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: host->host repeats, CPU baselines of the oracle and, for the default "
+                         "workload on one GPU, the brief `secondary` runs of the other workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-sample", type=int, default=512, help="problems of the multi-thread CPU leg (single-thread leg: a quarter)")
     ap.add_argument("--warm", choices=["jerk", "quintic"], default="jerk",
                     help="initial guess of every OCP: jerk = the jerk-limited time-synchronised trajectory the reference gets from Ruckig "
@@ -516,7 +523,7 @@ def main():
                          "solver depth (N=19, 2 SQP iterations; SURVEY.md 8d); dual14: configs[3], 14-DoF dual-Panda, N=25")
     ap.add_argument("--rh-cold", action="store_true", help="rh workload: both start flags off (-1): every re-solve from lambda = 0 with cold QPs; default = the driver's defaults (carried multipliers, warm QP duals)")
     ap.add_argument("--qp-warm-start", action="store_true", help="mpcmp_config.qp_warm_start = 1 (opt-in: QPs start from the NLP multipliers); the contract line keeps the default 0")
-    ap.add_argument("--no-secondary", action="store_true", help="default workload only: skip the brief runs of the three other workloads")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full, default workload only: skip the brief runs of the three other workloads")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step (solutions, final times, info fields) "
                          "as DIR/<name>.npy, float64, at most 64 MB (a fixed, seeded sample of problems beyond that)")
@@ -554,7 +561,7 @@ def main():
     else:
         line = run_batch_workload(args, args.workload, args.steps, args.warmup, rank, world, local, dist, args.cpu_sample, args.batch or 1024,
                                   dump=args.dump_outputs)
-    if line is not None and args.workload == "batch" and world == 1 and not args.no_secondary:
+    if args.full and line is not None and args.workload == "batch" and world == 1 and not args.no_secondary:
         # the other three workloads, briefly, inside the ONE contract line: value, ms_per_step, roofline fractions, CPU baseline
         import bench_dual14
         sec = {}
@@ -716,7 +723,7 @@ def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, 
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and host_to_host:
+        if args.full and world == 1 and host_to_host:
             # host -> host (inputs and outputs in host memory, PCIe inclusive): warm, median of 5 repeats
             ts = []
             for _ in range(6):
@@ -726,7 +733,7 @@ def run_batch_workload(args, workload, steps, warmup, rank, world, local, dist, 
             ts = sorted(ts[1:])
             out["host_to_host"] = {"trajectories_per_s": B / ts[len(ts) // 2], "repeats": len(ts), "min_ms": 1e3 * ts[0], "max_ms": 1e3 * ts[-1],
                                    "note": "SURVEY.md 8(d) defines the metric host->host; `value` is the device-resident rate the bench contract asks for"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, T_cpu = cpu_baseline(nseg, sqp, x0_h, xf_h, args.warm, cpu_sample, max(16, cpu_sample // 4), qp_warm_start=qws)
             out["cpu_baseline"] = cb
             out["quality"]["max_rel_dT_vs_cpu_sample"] = float(np.max(np.abs(inf["T"][:len(T_cpu)] - T_cpu) / np.abs(T_cpu)))

@@ -142,7 +142,7 @@ def run(args, rank, world, local, dist, steps=None, warmup=None, batch=None, dum
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py as o
         ocfg = o.default_config(nseg, sqp, margins=margins)

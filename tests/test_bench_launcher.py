@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -89,3 +91,25 @@ def test_dump_outputs_writes_float64_within_the_cap(tmp_path, monkeypatch):
         assert np.array_equal(np.load(tmp_path / d / "sol_x.npy"), big[rows]) and np.array_equal(np.load(tmp_path / d / "sol_T.npy"), big[rows, 0])
         runs.append(rows)
     assert np.array_equal(runs[0], runs[1])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_adds_the_extra_measurements():
+    """a plain run prints the headline line without the host->host repeats and the CPU baseline; --full adds both (and, without --no-secondary,
+    the secondary workloads); the headline fields are there in either case"""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "8"]
+    lines = []
+    for extra in ([], ["--full", "--no-secondary", "--cpu-sample", "8"]):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1]))
+    plain, full = lines
+    for d in lines:
+        assert d["unit"] == "trajectories/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert plain["metric"] == full["metric"]
+    assert not any(k in plain for k in ("host_to_host", "cpu_baseline", "secondary")) and "max_rel_dT_vs_cpu_sample" not in plain["quality"]
+    assert "host_to_host" in full and "cpu_baseline" in full and "secondary" not in full
+    assert full["quality"]["max_rel_dT_vs_cpu_sample"] < 1e-6
