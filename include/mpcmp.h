@@ -114,6 +114,17 @@ typedef struct {
 
 /* ---- configuration helpers (host, no GPU needed) ---- */
 int mpcmp_default_model(mpcmp_model *m);                                    /* Panda arm, panda_arm.urdf */
+/* Payload: a rigid body attached to the flange, ADDED to whatever body 7 of a model already holds (the compiled-in Panda lumps its 1 kg tool
+ * there).  mass >= 0; com and I (rotational inertia about the COM, row-major) in the joint-7 frame, the frame of mpcmp_model.tool and link8. */
+typedef struct {
+    double mass;
+    double com[3];
+    double I[9];
+} mpcmp_payload;
+/* body 7 of `m` with the payload lumped in (parallel-axis theorem, the arithmetic that lumps the Panda's fixed children); m == out is allowed.
+ * A payload with mass 0 and I == 0 returns `m` unchanged, bit for bit.  Host and device (mpcmp_set_payloads*) results agree bit for bit.
+ * MPCMP_EINVAL: mass < 0 or not finite, a non-finite com / I entry, I not symmetric, a negative diagonal entry of I. */
+int mpcmp_model_add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out);
 int mpcmp_model_from_urdf(const char *urdf_path, mpcmp_model *m);           /* MotionPlanner(std::string urdf_path), motionPlanner.cpp:3 */
 /* General form (robot_utils/pandaWrapper.cpp:3-12 hands any URDF to Pinocchio): every serial chain of seven revolute joints that
  * hangs on the root link, in file order.  Fixed joints anywhere (rotated or not) are folded into the next joint placement and
@@ -145,6 +156,21 @@ int mpcmp_create_multi(const mpcmp_config *cfg, const mpcmp_model *models, int n
 int mpcmp_destroy(mpcmp_ctx *ctx);
 int mpcmp_set_config(mpcmp_ctx *ctx, const mpcmp_config *cfg);             /* num_seg must not change */
 const char *mpcmp_last_error(const mpcmp_ctx *ctx);
+
+/* ---- per-problem payloads ----
+ * p [n][narm]: row i holds one payload per arm and applies to problem i (instance i of the receding-horizon driver, point i of the leaf calls)
+ * of every later call that evaluates dynamics: mpcmp_solve_batch[_device], mpcmp_qp_batch, mpcmp_sample_batch[_device] (torque column),
+ * mpcmp_mpc_point_batch, mpcmp_traj_stats_batch, mpcmp_rnea_batch, mpcmp_eval_constraints_batch and mpcmp_rh_init / mpcmp_rh_run.  Problem i is
+ * solved with mpcmp_model_add_payload(model of the context, row i) for every arm.  Such a call with more problems than rows returns MPCMP_EINVAL
+ * and writes nothing; so does mpcmp_rh_init with B > n.  The jerk-limited generators and mpcmp_pose_targets_* are kinematic and do not read the
+ * rows.  n == 0 with p == NULL clears the rows (back to the context's model: outputs bit for bit those of a context that never set any).
+ * mpcmp_set_payloads is synchronous and checks every row as mpcmp_model_add_payload does; it returns MPCMP_EINVAL, changing nothing, for n outside
+ * [1, max_batch] (other than the clear), a bad row, or n below the B of a running receding-horizon loop.  Like mpcmp_set_config it drops a
+ * captured receding-horizon graph (the next mpcmp_rh_run captures again); for the loop's instances see mpcmp_rh_update. */
+int mpcmp_set_payloads(mpcmp_ctx *ctx, int n, const mpcmp_payload *p);
+/* the same from DEVICE memory d_p [n][narm], ordered on hip_stream after the work already on it and before later work of the context; the values are
+ * not read on the host and not checked (as mpcmp_rh_update_device) */
+int mpcmp_set_payloads_device(mpcmp_ctx *ctx, int n, const mpcmp_payload *d_p, void *hip_stream);
 
 /* ---- the hot path: B independent OCPs == B calls of MotionPlanner::solve_trajectory ---- */
 /* warm_x/warm_u/warm_T: x_guess/u_guess/p_guess (motionPlanner.cpp:172-174); all NULL -> built-in
@@ -319,6 +345,10 @@ int mpcmp_rh_stats(mpcmp_ctx *ctx, long long *resolves_done, long long *arrived)
  *                                                               and zero multipliers, as a first or a failed solve gets
  *   retired (arrived)            anything                       revived: MPCMP_STATUS_ARRIVED leaves its record at once, mpcmp_rh_stats' `arrived`
  *                                                               drops by one, and a restart as above; the arrival rule applies again after the solve
+ *   live                         new payload (mpcmp_set_payloads no restart: re-guess from its previous solution with its carried multipliers;
+ *                                [_device] between two runs)    only its linearisation sees the new model (a grasp or a release mid-motion)
+ *   retired (arrived)            new payload                    stays retired
+ * Payload rows set between two mpcmp_rh_run calls apply to the next step, eager or graph replay.
  * An update before the first mpcmp_rh_run replaces what mpcmp_rh_init set.  mpcmp_rh_update is synchronous and returns MPCMP_EINVAL, writing
  * nothing, before mpcmp_rh_init, for n outside [1, B], an index out of range or repeated, x and xf both NULL, a value that is not finite, or an
  * unknown flag bit. */

@@ -299,6 +299,18 @@ class MotionPlanner {
         }
     }
     void set_min_height(double min_height) { mpcmp_set_min_height(&config, min_height); push_config(); }  // :92-100
+    // extension beyond the reference's members: the load the gripper carries, added to body 7 of the robot's model for every later solve and MPC
+    // sample (mass [kg] >= 0; com [3] and the inertia about the COM [9, row-major] in the joint-7 frame, the frame of the tool point).  mass 0 with
+    // a zero inertia is the empty gripper.  The jerk-limited guess (get_ruckig_trajectory, get_RK_point) stays the unloaded model's.
+    void set_payload(double mass, const double com[3], const double I[9]) {
+        mpcmp_payload p{};
+        p.mass = mass;
+        for (int d = 0; d < 3; d++) p.com[d] = com[d];
+        for (int q = 0; q < 9; q++) p.I[q] = I[q];
+        mpcmp_model check;
+        if (mpcmp_model_add_payload(&robot.model, &p, &check) != MPCMP_OK) throw std::runtime_error(std::string("mpcmp: ") + mpcmp_last_error(nullptr));
+        payload_ = p; has_payload_ = true; payload_rows_ = 0;
+    }
 
     // one draw in [-1,1) of the planner's seeded stream: what `Matrix<...>::Random()` coefficients are in the reference's examples
     double random_unit() { return uniform(); }
@@ -384,6 +396,7 @@ class MotionPlanner {
 
     // B independent problems in one call (the loop of examples/benchmark.cpp:16). x0/xf: [B][14]
     void solve_batch(int B, const double *x0, const double *xf, double *sol_x, double *sol_u, double *sol_T, mpcmp_info *info) {
+        use_payload(B);
         chk(mpcmp_solve_batch(ctx_, B, x0, xf, nullptr, nullptr, nullptr, sol_x, sol_u, sol_T, info));
     }
 
@@ -393,6 +406,7 @@ class MotionPlanner {
                             mpcmp_shim::Mat<7, NP + 1> &velocity_trajectory, mpcmp_shim::Mat<7, NP + 1> &acceleration_trajectory,
                             mpcmp_shim::Mat<7, NP + 1> &torque_trajectory) {
         std::vector<double> out((size_t)(NP + 1) * 29);
+        use_payload(1);
         chk(mpcmp_sample_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, NP, out.data()));
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
     }
@@ -409,6 +423,7 @@ class MotionPlanner {
                                                 guess_in_.max_jerk.data(), NP, tr.data(), nullptr));
             for (int i = 0; i <= NP; i++)
                 for (int j = 0; j < 7; j++) { q[(size_t)i * 7 + j] = tr[(size_t)i * 22 + 1 + j]; v[(size_t)i * 7 + j] = tr[(size_t)i * 22 + 8 + j]; a[(size_t)i * 7 + j] = tr[(size_t)i * 22 + 15 + j]; }
+            use_payload(0);
             chk(mpcmp_rnea_batch(ctx_, NP + 1, q.data(), v.data(), a.data(), tau.data()));
             for (int i = 0; i <= NP; i++) {
                 out[(size_t)i * 29] = tr[(size_t)i * 22];
@@ -418,6 +433,7 @@ class MotionPlanner {
                 }
             }
         } else {
+            use_payload(1);
             chk(mpcmp_sample_batch(ctx_, 1, guess_x_.data(), guess_u_.data(), &guess_T_, NP, out.data()));
         }
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
@@ -425,6 +441,7 @@ class MotionPlanner {
     // motionPlanner.hpp:118-128, including its clamp: for time >= T the normalised time is set to T (not 1)
     void get_MPC_point(double time, Vec7 &position, Vec7 &velocity, Vec7 &acceleration, Vec7 &torque) {
         double o[28];
+        use_payload(1);
         chk(mpcmp_mpc_point_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, &time, o));       // one launch: clamp, interpolation, RNEA
         for (int j = 0; j < 7; j++) { position(j) = o[j]; velocity(j) = o[7 + j]; acceleration(j) = o[14 + j]; torque(j) = o[21 + j]; }
     }
@@ -481,6 +498,7 @@ class MotionPlanner {
         for (int b = 0; b < B; b++) for (int r = 0; r < 14; r++) x0[(size_t)b * 14 + r] = current_state(r);
         chk(mpcmp_warm_start_jerk_lim_batch(ctx_, B, x0.data(), xf, nullptr, nullptr, input.max_velocity.data(), input.max_acceleration.data(), input.max_jerk.data(),
                                             gx.data(), gu.data(), gT.data()));     // benchmark.cpp:46-47
+        use_payload(B);
         chk(mpcmp_solve_batch(ctx_, B, x0.data(), xf, gx.data(), gu.data(), gT.data(), sx.data(), su.data(), sT.data(), info.data()));
         chk(mpcmp_traj_stats_batch(ctx_, B, gx.data(), gu.data(), gT.data(), xf, n_pts, sg.data()));
         chk(mpcmp_traj_stats_batch(ctx_, B, sx.data(), su.data(), sT.data(), xf, n_pts, sm.data()));
@@ -515,9 +533,21 @@ class MotionPlanner {
     }
     bool have_warm_ = false;
     uint64_t rng_ = 20240001ull;
+    mpcmp_payload payload_{};                       // set_payload
+    bool has_payload_ = false;
+    int payload_rows_ = 0;                          // rows of it the context holds now (0: none, the model's own dynamics)
+    // `rows` copies of the payload into the context before a call on `rows` problems; rows = 0: the unloaded model
+    void use_payload(int rows) {
+        if (!has_payload_) rows = 0;
+        if (rows == payload_rows_) return;
+        if (rows == 0) chk(mpcmp_set_payloads(ctx_, 0, nullptr));
+        else { std::vector<mpcmp_payload> t((size_t)rows, payload_); chk(mpcmp_set_payloads(ctx_, rows, t.data())); }
+        payload_rows_ = rows;
+    }
 
     // mpc.solve() from (guess_x_, guess_u_, guess_T_), then "Fix initial and final point at correct place" (motionPlanner.cpp:184-207)
     void solve_from_guess() {
+        use_payload(1);
         chk(mpcmp_solve_batch(ctx_, 1, current_state.data(), target_state.data(), guess_x_.data(), guess_u_.data(), &guess_T_,
                               sol_x_.data(), sol_u_.data(), &sol_T_, &last_info));
         warm_x_ = sol_x_; warm_u_ = sol_u_; warm_T_ = sol_T_; have_warm_ = true;

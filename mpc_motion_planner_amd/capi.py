@@ -21,6 +21,11 @@ class Model(C.Structure):
                 ("link8", C.c_double * 3), ("gravity", C.c_double * 3)]
 
 
+class Payload(C.Structure):
+    """mpcmp_payload: a rigid body on the flange (mass, COM and rotational inertia about the COM, in the joint-7 frame), added to body 7"""
+    _fields_ = [("mass", C.c_double), ("com", C.c_double * 3), ("I", C.c_double * 9)]
+
+
 class Config(C.Structure):
     _fields_ = [("num_seg", C.c_int), ("sqp_iters", C.c_int), ("qp_iters", C.c_int), ("ls_iters", C.c_int),
                 ("check_every", C.c_int), ("quirk_dtau_dT", C.c_int),
@@ -63,7 +68,8 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_jerk_point_batch", "mpcmp_mpc_point_batch", "mpcmp_debug_fetch",
            "mpcmp_warm_start_jerk_acc_batch", "mpcmp_warm_start_jerk_acc_batch_device", "mpcmp_jerk_trajectory_acc_batch", "mpcmp_jerk_point_acc_batch",
            "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats",
-           "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device"]
+           "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device",
+           "mpcmp_model_add_payload", "mpcmp_set_payloads", "mpcmp_set_payloads_device"]
 
 
 def library_path():
@@ -123,6 +129,8 @@ def lib():
         L.mpcmp_rh_update_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.mpcmp_pose_targets_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
         L.mpcmp_pose_targets_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5
+        L.mpcmp_set_payloads.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.mpcmp_set_payloads_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -163,6 +171,22 @@ def arm_models(bases, model=None):
 
 
 DUAL_BASES = ((0.0, (0.0, 0.0, 0.0)), (np.pi, (1.0, 0.0, 0.0)))      # two Pandas facing each other, 1 m apart (configs[3] stand-in)
+
+
+def payload(mass, com=(0.0, 0.0, 0.0), inertia=None):
+    """a Payload from a mass, a COM [3] and a rotational inertia about the COM [3, 3] (default 0), all in the joint-7 frame"""
+    p = Payload(); p.mass = float(mass)
+    c = f64(com).reshape(3); I = np.zeros(9) if inertia is None else f64(inertia).reshape(9)
+    for d in range(3):
+        p.com[d] = c[d]
+    for q in range(9):
+        p.I[q] = I[q]
+    return p
+
+
+def model_add_payload(model, p):
+    """mpcmp_model_add_payload: a copy of `model` with the Payload `p` lumped into body 7 (parallel-axis theorem)"""
+    out = Model(); check(lib().mpcmp_model_add_payload(C.byref(model), C.byref(p), C.byref(out))); return out
 
 
 def model_from_urdf(path):

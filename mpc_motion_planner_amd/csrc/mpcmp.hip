@@ -27,6 +27,7 @@
 #include "kinematics_host.hpp"
 #include "jerk_device.hpp"
 #include "ik_device.hpp"
+#include "payload.hpp"
 
 #ifdef MPCMP_SPLIT_N25
 // the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
@@ -60,6 +61,11 @@ struct mpcmp_ctx {
     // device buffers
     mpcmp_model *d_model = nullptr;   // [narm]
     mpcmp_model model;             // host copy: passed by value to the kernels that run the rigid-body recursions
+    // per-problem payloads (mpcmp_set_payloads): d_pmodel [max_batch][narm] = the context's models with row b's payloads lumped in, written by
+    // k_lump_payloads from d_pay [max_batch][narm]; both allocated by the first mpcmp_set_payloads.  pay_rows = 0: every problem reads d_model
+    mpcmp_model *d_pmodel = nullptr;
+    mpcmp_payload *d_pay = nullptr;
+    int pay_rows = 0;
     int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
     uint32_t *d_terms = nullptr;
     WS ws{};
@@ -118,6 +124,20 @@ static mpcmp_config run_config(const mpcmp_ctx *ctx) {
 }
 
 static thread_local std::string g_err;
+
+// the models the dynamics of a call read: the context's [narm], or the per-problem copies [rows][narm] (problem b, arm a: base + b * stride + a)
+static const mpcmp_model *run_models(const mpcmp_ctx *ctx, int *stride) {
+    *stride = ctx->pay_rows > 0 ? ctx->narm : 0;
+    return ctx->pay_rows > 0 ? ctx->d_pmodel : ctx->d_model;
+}
+// a call that evaluates dynamics for B problems needs a payload row for each of them (when rows are set)
+static int payload_rows_ok(mpcmp_ctx *ctx, int B) {
+    if (ctx->pay_rows > 0 && B > ctx->pay_rows) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than payload rows (" + std::to_string(ctx->pay_rows) + "): see mpcmp_set_payloads";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
 
 #define HIPCHK(ctx, call)                                                                     \
     do {                                                                                      \
@@ -191,22 +211,6 @@ extern "C" int mpcmp_default_config(mpcmp_config *c, int num_seg, int sqp_iters)
     c->rho = 0.02; c->sigma = 1e-6; c->alpha = 1.4; c->rho_eq_scale = 1e3;      // fitted to the reference's stored solve: tools/polympc_param_fit.py
     c->ls_eta = 0.25; c->ls_tau = 0.5; c->hess_reg = 1e-3; c->eps_target = 1e-2;
     return mpcmp_set_margins(c, 1.0, 1.0, 1.0, 1.0);              // motionPlanner.cpp:24
-}
-
-static void lump_last_body(mpcmp_model *m, const double mk[3], const double ck[3][3], const double Ik[3][9]) {
-    double M = mk[0] + mk[1] + mk[2], c[3] = {0, 0, 0};
-    for (int k = 0; k < 3; k++) for (int d = 0; d < 3; d++) c[d] += mk[k] * ck[k][d];
-    for (int d = 0; d < 3; d++) c[d] /= M;
-    double It[9] = {0};
-    for (int k = 0; k < 3; k++) {
-        const double d[3] = {ck[k][0] - c[0], ck[k][1] - c[1], ck[k][2] - c[2]};
-        const double d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        for (int r = 0; r < 3; r++) for (int s = 0; s < 3; s++)
-            It[3 * r + s] += Ik[k][3 * r + s] + mk[k] * ((r == s ? d2 : 0.0) - d[r] * d[s]);
-    }
-    m->mass[6] = M;
-    std::memcpy(m->com[6], c, sizeof c);
-    std::memcpy(m->I[6], It, sizeof It);
 }
 
 static void rpy_to_R(const double rpy[3], double R[9]) {
@@ -295,7 +299,7 @@ extern "C" int mpcmp_default_model(mpcmp_model *m) {
     double Ik[3][9];
     std::memcpy(Ik[0], m->I[6], sizeof Ik[0]);
     for (int k = 1; k < 3; k++) { std::memset(Ik[k], 0, sizeof Ik[k]); Ik[k][0] = Ik[k][4] = Ik[k][8] = 1e-3; }
-    lump_last_body(m, mk, ck, Ik);
+    lump_last_body(m, 3, mk, ck, Ik);
     return MPCMP_OK;
 }
 
@@ -775,6 +779,91 @@ extern "C" int mpcmp_set_config(mpcmp_ctx *ctx, const mpcmp_config *cfg) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-problem payloads (payload.hpp: the lumping, shared by the host and k_lump_payloads)
+static int check_payload(const mpcmp_payload *p, std::string &err) {
+    if (!(p->mass >= 0.0) || !std::isfinite(p->mass)) { err = "payload mass must be finite and >= 0"; return MPCMP_EINVAL; }
+    for (int d = 0; d < 3; d++) if (!std::isfinite(p->com[d])) { err = "payload com must be finite"; return MPCMP_EINVAL; }
+    for (int q = 0; q < 9; q++) if (!std::isfinite(p->I[q])) { err = "payload inertia must be finite"; return MPCMP_EINVAL; }
+    for (int r = 0; r < 3; r++) {
+        if (p->I[4 * r] < 0.0) { err = "payload inertia: negative diagonal entry"; return MPCMP_EINVAL; }
+        for (int c = r + 1; c < 3; c++) if (p->I[3 * r + c] != p->I[3 * c + r]) { err = "payload inertia must be symmetric"; return MPCMP_EINVAL; }
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_model_add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out) {
+    if (!m || !p || !out) return MPCMP_EINVAL;
+    if (int rc = check_payload(p, g_err)) return rc;
+    add_payload(m, p, out);
+    return MPCMP_OK;
+}
+
+// n rows of narm payloads at d_p (device) -> ctx->d_pmodel on stream st; the scalar checks are the caller's
+static int payloads_enqueue(mpcmp_ctx *ctx, int n, const mpcmp_payload *d_p, hipStream_t st) {
+    const int threads = n * ctx->narm;
+    hipLaunchKernelGGL(k_lump_payloads, dim3((threads + 255) / 256), dim3(256), 0, st, (const mpcmp_model *)ctx->d_model, ctx->narm, n, d_p, ctx->d_pmodel);
+    HIPCHK(ctx, hipGetLastError());
+    return MPCMP_OK;
+}
+
+static int payloads_check(mpcmp_ctx *ctx, int n, const mpcmp_payload *p) {
+    if (!ctx) { g_err = "mpcmp_set_payloads: no context"; return MPCMP_EINVAL; }
+    if (n == 0 && !p) return MPCMP_OK;
+    if (n < 1 || n > ctx->max_batch || !p) { ctx->err = "mpcmp_set_payloads: n must be in [1, max_batch] with p given (or 0 with p NULL: clear)"; return MPCMP_EINVAL; }
+    if (ctx->rh_B > 0 && n < ctx->rh_B) { ctx->err = "mpcmp_set_payloads: fewer rows than the instances of the receding-horizon loop"; return MPCMP_EINVAL; }
+    if (!ctx->d_pmodel) {          // first use: [max_batch][narm] models and payloads (1,472 + 104 B each)
+        void *q = nullptr;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMalloc(&q, sizeof(mpcmp_model) * ctx->max_batch * ctx->narm));
+        ctx->allocs.push_back(q); ctx->d_pmodel = (mpcmp_model *)q;
+        HIPCHK(ctx, hipMalloc(&q, sizeof(mpcmp_payload) * ctx->max_batch * ctx->narm));
+        ctx->allocs.push_back(q); ctx->d_pay = (mpcmp_payload *)q;
+    }
+    return MPCMP_OK;
+}
+
+// the rows change what a captured receding-horizon step reads (its kernel arguments hold the model pointer and stride): capture again
+static void drop_rh_graph(mpcmp_ctx *ctx) {
+    if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
+    if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
+}
+
+extern "C" int mpcmp_set_payloads(mpcmp_ctx *ctx, int n, const mpcmp_payload *p) {
+    if (int rc = payloads_check(ctx, n, p)) return rc;
+    if (n > 0)
+        for (int i = 0; i < n * ctx->narm; i++)
+            if (int rc = check_payload(p + i, ctx->err)) { ctx->err = "mpcmp_set_payloads: row " + std::to_string(i / ctx->narm) + ": " + ctx->err; return rc; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (n > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_pay, p, sizeof(mpcmp_payload) * n * ctx->narm, hipMemcpyHostToDevice, st));
+        if (int rc = payloads_enqueue(ctx, n, ctx->d_pay, st)) return rc;
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    ctx->pay_rows = n;
+    drop_rh_graph(ctx);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_payloads_device(mpcmp_ctx *ctx, int n, const mpcmp_payload *d_p, void *hip_stream) {
+    if (int rc = payloads_check(ctx, n, d_p)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        // after the caller's work on its stream (which writes d_p) and the context's own (solves that read the current models), before the
+        // context's later work; the caller's later work waits for the reads of d_p
+        hipStream_t cs = (hipStream_t)hip_stream;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+        if (int rc = payloads_enqueue(ctx, n, d_p, ctx->stream)) return rc;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+    }
+    ctx->pay_rows = n;
+    drop_rh_graph(ctx);
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launches
 template <typename K>
 static int set_lds(mpcmp_ctx *ctx, K kern, size_t bytes) {
@@ -851,6 +940,7 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
     const mpcmp_config cfg = run_config(ctx);
     WS w = ctx->ws;
     w.x0 = d_x0; w.xf = d_xf;
+    w.model = run_models(ctx, &w.mstride);
     w.retired = ctx->rh_step ? ctx->d_retired : nullptr;
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_init = InitLds<NSEG>::size * sizeof(double), l_qp = QpLds<S::N1>::size * sizeof(double),
@@ -883,6 +973,7 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
         v.x0 += 14 * b0; v.xf += 14 * b0; v.z += D::n * b0; v.lam += D::mn * b0; v.ceq += D::meq * b0; v.g += 8 * D::N * b0;
         v.Gk += (size_t)D::N * 176 * b0; v.p += D::n * b0; v.y += D::mn * b0; v.qpit += b0; v.perm += b0; v.okey += b0; v.done += h;
         v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
+        v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
         if (v.retired) v.retired += b0;
         if (v.alt_x) { v.alt_x += 14 * D::N * b0; v.alt_u += 7 * D::N * b0; v.alt_T += b0; }
         wh[h] = v;
@@ -968,6 +1059,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
     const mpcmp_config cfg = run_config(ctx);
     WS w = ctx->ws;
     w.x0 = d_x0; w.xf = d_xf;
+    w.model = run_models(ctx, &w.mstride);
     w.retired = ctx->rh_step ? ctx->d_retired : nullptr;
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_m = D::size * sizeof(double), l_qp3 = Qp3<NSEG>::sizeL * sizeof(double), l_qp3f = Qp3<NSEG>::sizeF * sizeof(double);
@@ -988,6 +1080,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
         v.x0 += 14 * NARM * b0; v.xf += 14 * NARM * b0; v.z += D::n * b0; v.lam += D::mn * b0; v.ceq += (size_t)NARM * D::meq * b0;
         v.g += (size_t)NARM * 8 * N * b0; v.Gk += (size_t)NARM * N * 176 * b0; v.p += D::n * b0; v.y += D::mn * b0; v.qpit += b0; v.perm += b0;
         v.okey += b0; v.done += h; v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
+        v.model += (size_t)v.mstride * b0;      // (see solve_impl)
         if (v.retired) v.retired += b0;
         if (v.alt_x) { v.alt_x += (size_t)14 * NARM * N * b0; v.alt_u += (size_t)7 * NARM * N * b0; v.alt_T += b0; }
         wh[h] = v;
@@ -998,7 +1091,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
     }
     if (nhalf > 1) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st)); HIPCHK(ctx, hipStreamWaitEvent(sh[1], ctx->ev_fork, 0)); }
     for (int h = 0; h < nhalf; h++)
-        hipLaunchKernelGGL((k_init_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, ctx->d_model, wh[h], xh[h], hx[h], hu[h], hT[h], reguess);
+        hipLaunchKernelGGL((k_init_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, wh[h].model, wh[h], xh[h], hx[h], hu[h], hT[h], reguess);
     const int iters = only_qp ? 1 : cfg.sqp_iters;
     for (int it = 0; it < iters; it++) {
         for (int h = 0; h < nhalf; h++) {
@@ -1010,7 +1103,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
             hipLaunchKernelGGL((k_qp3<NSEG, NARM>), dim3(grid), dim3(512), l_qp3, sh[h], cfg, wh[h], ctx->d_pat, xh[h], Bh[h], (const double *)fh);
             if (ev) HIPCHK(ctx, hipEventRecord(ev[1], sh[h]));
             if (only_qp) continue;
-            hipLaunchKernelGGL((k_step_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, ctx->d_model, wh[h], xh[h],
+            hipLaunchKernelGGL((k_step_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, wh[h].model, wh[h], xh[h],
                                it == iters - 1 ? 1 : 0, it, ox[h], ou[h], oT[h], oi[h]);
         }
     }
@@ -1025,6 +1118,7 @@ static int solve_dispatch(mpcmp_ctx *ctx, int B, const double *d_x0, const doubl
     if (!ctx) return MPCMP_EINVAL;
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     if (!d_x0 || !d_xf) return MPCMP_EINVAL;
     if ((d_wx != nullptr) != (d_wu != nullptr) || (d_wx != nullptr) != (d_wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1056,6 +1150,7 @@ extern "C" int mpcmp_solve_batch(mpcmp_ctx *ctx, int B, const double *x0, const 
     if (!ctx || !x0 || !xf || !sx || !su || !sT) return MPCMP_EINVAL;
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
@@ -1326,6 +1421,7 @@ extern "C" int mpcmp_mpc_point_batch(mpcmp_ctx *ctx, int B, const double *sx, co
                                      double *out) {
     if (!ctx || !sx || !su || !sT || !time || !out || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N;
     TmpBuf tb(ctx, (21 * N + 2 + 28) * (size_t)B * sizeof(double));
@@ -1337,7 +1433,9 @@ extern "C" int mpcmp_mpc_point_batch(mpcmp_ctx *ctx, int B, const double *sx, co
     HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * B, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(dt, time, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mpc_point, dim3((B + 63) / 64), dim3(64), 0, st, ctx->d_model, ctx->nseg, B, dx, du, dT, dt, dout);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    hipLaunchKernelGGL(k_mpc_point, dim3((B + 63) / 64), dim3(64), 0, st, md, ms, ctx->nseg, B, dx, du, dT, dt, dout);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 28 * B, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -1349,6 +1447,7 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
     if (!ctx || !x0 || !xf || !xs || !us || !T || !p || !y || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N;
     hipStream_t st = ctx->stream;
@@ -1371,6 +1470,7 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
 // leaf kernels
 extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const double *qd, const double *qdd, double *tau) {
     if (!ctx || n < 1 || !q || !qd || !qdd || !tau) return MPCMP_EINVAL;
+    if (int rc = payload_rows_ok(ctx, n)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TmpBuf tb(ctx, 28 * (size_t)n * sizeof(double));
     double *dq = tb.get<double>(7 * (size_t)n), *dv = tb.get<double>(7 * (size_t)n), *da = tb.get<double>(7 * (size_t)n), *dt = tb.get<double>(7 * (size_t)n);
@@ -1379,7 +1479,9 @@ extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const do
     HIPCHK(ctx, hipMemcpyAsync(dq, q, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(dv, qd, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(da, qdd, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rnea_batch, dim3((n + 63) / 64), dim3(64), 0, st, ctx->d_model, n, dq, dv, da, dt);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    hipLaunchKernelGGL(k_rnea_batch, dim3((n + 63) / 64), dim3(64), 0, st, md, ms, n, dq, dv, da, dt);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(tau, dt, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -1388,6 +1490,7 @@ extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const do
 
 extern "C" int mpcmp_eval_constraints_batch(mpcmp_ctx *ctx, int n, const double *x, const double *u, double *g, double *G) {
     if (!ctx || n < 1 || !x || !u || !g || !G) return MPCMP_EINVAL;
+    if (int rc = payload_rows_ok(ctx, n)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TmpBuf tb(ctx, (14 + 7 + 8 + 176) * (size_t)n * sizeof(double));
     double *dx = tb.get<double>(14 * (size_t)n), *du = tb.get<double>(7 * (size_t)n), *dg = tb.get<double>(8 * (size_t)n), *dG = tb.get<double>(176 * (size_t)n);
@@ -1398,8 +1501,10 @@ extern "C" int mpcmp_eval_constraints_batch(mpcmp_ctx *ctx, int n, const double 
     constexpr int NS = 4;
     const size_t l = EvalLds<NS>::size * sizeof(double);
     if (int rc = set_lds(ctx, k_eval_constraints<NS>, l)) return rc;
-    const int N = Dim<NS>::N;
-    hipLaunchKernelGGL(k_eval_constraints<NS>, dim3((n + N - 1) / N), dim3(Dim<NS>::NT), l, st, ctx->cfg, (const mpcmp_model *)ctx->d_model, n, dx, du, dg, dG);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    const int per = ms ? 1 : Dim<NS>::N;           // points per workgroup: one with per-point models (k_eval_constraints)
+    hipLaunchKernelGGL(k_eval_constraints<NS>, dim3((n + per - 1) / per), dim3(Dim<NS>::NT), l, st, ctx->cfg, md, ms, n, dx, du, dg, dG);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(g, dg, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(G, dG, sizeof(double) * 176 * n, hipMemcpyDeviceToHost, st));
@@ -1411,9 +1516,12 @@ extern "C" int mpcmp_sample_batch_device(mpcmp_ctx *ctx, int B, const double *d_
                                          int n_pts, double *d_out, void *hip_stream) {
     if (!ctx || B < 1 || n_pts < 1 || !d_sx || !d_su || !d_sT || !d_out) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long total = (long)B * (n_pts + 1);
-    hipLaunchKernelGGL(k_sample, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, (hipStream_t)hip_stream, ctx->d_model,
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    hipLaunchKernelGGL(k_sample, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, (hipStream_t)hip_stream, md, ms,
                        ctx->nseg, B, n_pts, d_sx, d_su, d_sT, d_out);
     HIPCHK(ctx, hipGetLastError());
     return MPCMP_OK;
@@ -1421,6 +1529,7 @@ extern "C" int mpcmp_sample_batch_device(mpcmp_ctx *ctx, int B, const double *d_
 
 extern "C" int mpcmp_sample_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_pts, double *out) {
     if (!ctx || B < 1 || n_pts < 1 || !sx || !su || !sT || !out) return MPCMP_EINVAL;
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, np = (size_t)B * (n_pts + 1) * 29;
     TmpBuf tb(ctx, (21 * N * B + B + np) * sizeof(double));
@@ -1442,6 +1551,7 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
                                       int n_pts, double *out) {
     if (!ctx || B < 1 || n_pts < 1 || !sx || !su || !sT || !xf || !out) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     // the kernel keeps the n_pts+1 samples of one trajectory (28 doubles each) in LDS: 160 KB per workgroup on gfx950
     if (sizeof(double) * 28 * (size_t)(n_pts + 1) > 150 * 1024) { ctx->err = "mpcmp_traj_stats_batch: n_pts must be <= 684 (the samples of one trajectory are held in LDS)"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1461,7 +1571,9 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
     HIPCHK(ctx, hipMemcpyAsync(dj, j10, sizeof j10, hipMemcpyHostToDevice, st));
     const size_t lds = sizeof(double) * 28 * (size_t)(n_pts + 1);
     if (int rc = set_lds(ctx, k_traj_stats, lds)) return rc;
-    hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, st, ctx->d_model, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, st, md, ms, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 74 * B, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -1555,6 +1667,7 @@ extern "C" int mpcmp_reset_multipliers(mpcmp_ctx *ctx) {
 extern "C" int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const double *xf) {
     if (!ctx || !x0 || !xf || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(ctx->ws.lam, 0, sizeof(double) * ctx->lam_count, st));       // new instances: no multipliers to carry, no failed solve behind them

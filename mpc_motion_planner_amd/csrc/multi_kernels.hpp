@@ -238,7 +238,7 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
     const double T = zl[n - 1];
 #pragma nounroll
     for (int a = 0; a < NARM; a++)
-        linearise_arm<NSEG, NT>(cfg, models + a, zl + a * na, T, scr, ws.g + ((size_t)b * NARM + a) * 8 * N,
+        linearise_arm<NSEG, NT>(cfg, problem_model(models, b, ws.mstride) + a, zl + a * na, T, scr, ws.g + ((size_t)b * NARM + a) * 8 * N,
                                 ws.Gk + ((size_t)b * NARM + a) * N * 176, ws.ceq + ((size_t)b * NARM + a) * D::meq, tid);
 }
 
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
 #pragma nounroll
     for (int a = 0; a < NARM; a++) {
         const double *za = zl + a * na, *pa = pl + a * na;
-        const mpcmp_model *mdl_a = models + a;
+        const mpcmp_model *mdl_a = problem_model(models, b, ws.mstride) + a;
         for (int t = tid; t < ntr * N * 7; t += NT) {
             const int tr = t / (N * 7), kj = t % (N * 7), k = kj / 7, j = kj % 7;
             double al = 1.0;
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
     double *gout = ws.g + (size_t)b * NARM * 8 * N, *ceqo = ws.ceq + (size_t)b * NARM * meq;
 #pragma nounroll
     for (int a = 0; a < NARM; a++)
-        linearise_arm<NSEG, NT>(cfg, models + a, zl + a * na, Tn, scr, gout + a * 8 * N, ws.Gk + ((size_t)b * NARM + a) * N * 176,
+        linearise_arm<NSEG, NT>(cfg, problem_model(models, b, ws.mstride) + a, zl + a * na, Tn, scr, gout + a * 8 * N, ws.Gk + ((size_t)b * NARM + a) * N * 176,
                                 ceqo + a * meq, tid);
     if (tid == 0) ws.alpha[b] = alpha;
     if (final_iter) {

@@ -91,6 +91,14 @@ __device__ __forceinline__ void joint_consts(const mpcmp_model *__restrict__ M, 
         }
     }
 }
+// The model of problem b (b wave-uniform, e.g. blockIdx.x) in a table of per-problem models, `stride` models apart (0: one model for all).  Read
+// through readfirstlane, so that the address provably lives in SGPRs: the "+s" operand of RELOAD needs it (a VGPR copy does not compile).
+__device__ __forceinline__ const mpcmp_model *problem_model(const mpcmp_model *base, int b, int stride) {
+    const unsigned long long a = (unsigned long long)(base + (size_t)b * stride);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (const mpcmp_model *)(((unsigned long long)hi << 32) | lo);
+}
+
 template <bool TANGENT, bool TW_LDS = false, bool RELOAD = false>
 __device__ __forceinline__ void rnea_dir(const mpcmp_model *__restrict__ M, const double *sc, const double *v,
                                          const double *a, int type, int j, double *tau, double *dtau,

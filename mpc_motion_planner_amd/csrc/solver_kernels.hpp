@@ -45,6 +45,8 @@ struct WS {
     const int *retired;       // [B] or null: receding-horizon instances that have arrived (k_advance) are not re-solved: every solve kernel returns at once (at N = 25 the QP kernels k_qp3f / k_qp3 still run, results discarded)
     const double *alt_x, *alt_u, *alt_T;   // or null: the receding-horizon driver's start guess (jerk-limited trajectory from the current state) for an instance
                                            // that cannot be re-guessed from its previous solve (k_init: reguess && prev_bad); null = the built-in initialiser
+    int mstride;              // models per problem behind `model`: 0 = one model (per arm) for every problem; narm = per-problem models
+                              // (mpcmp_set_payloads): problem b of the launch, arm a reads model + b * mstride + a
 };
 // a retired instance of the receding-horizon loop: the whole workgroup leaves (uniform)
 #define MPCMP_RETIRED(ws_, b_) ((ws_).retired != nullptr && (ws_).retired[b_] != 0)
@@ -344,7 +346,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
     for (int v = tid; v < n; v += D::NT) ws.z[(size_t)b * n + v] = zl[v];
     if (!cfg.carry_multipliers || prev_bad) for (int i = tid; i < D::mn; i += D::NT) ws.lam[(size_t)b * D::mn + i] = 0.0;      // (carried: the slot's multipliers of the previous solve stay)
     if (tid == 0) { ws.qp_total[b] = 0; ws.status[b] = 0; ws.alpha[b] = 0.0; }
-    linearise_block<NSEG, true>(cfg, ws.model, zl, scr, ws.g + (size_t)b * 8 * N, ws.Gk + (size_t)b * N * 176,
+    linearise_block<NSEG, true>(cfg, problem_model(ws.model, b, ws.mstride), zl, scr, ws.g + (size_t)b * 8 * N, ws.Gk + (size_t)b * N * 176,
                           ws.ceq + (size_t)b * D::meq, tid);
 }
 template <int NSEG>
@@ -914,9 +916,10 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
             v[j] = zl[14 * k + 7 + j] + al * pl[14 * k + 7 + j];
             a[j] = zl[14 * N + 7 * k + j] + al * pl[14 * N + 7 * k + j];
         }
-        rnea_dir<false, false, true>(ws.model, sct + 14 * t, v, a, 0, 0, tau, nullptr);
+        const mpcmp_model *mdl = problem_model(ws.model, b, ws.mstride);
+        rnea_dir<false, false, true>(mdl, sct + 14 * t, v, a, 0, 0, tau, nullptr);
         V3 ptool;
-        fk_tool(ws.model, sct + 14 * t, &ptool, nullptr, nullptr, nullptr);
+        fk_tool(mdl, sct + 14 * t, &ptool, nullptr, nullptr, nullptr);
         double s = viol(ptool.z, cfg.lbg[7], cfg.ubg[7]);
 #pragma unroll
         for (int j = 0; j < 7; j++) s += viol(tau[j], cfg.lbg[j], cfg.ubg[j]);
@@ -967,9 +970,9 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
     double *gout = ws.g + (size_t)b * 8 * N, *ceqo = ws.ceq + (size_t)b * meq;
     KSTAMP(5);
 #ifdef MPCMP_STAMPS
-    linearise_block<NSEG, true>(cfg, ws.model, zl, scr, gout, ws.Gk + (size_t)b * N * 176, ceqo, tid, ws.dbg + (size_t)b * MPCMP_DBG_WORDS + 152);
+    linearise_block<NSEG, true>(cfg, problem_model(ws.model, b, ws.mstride), zl, scr, gout, ws.Gk + (size_t)b * N * 176, ceqo, tid, ws.dbg + (size_t)b * MPCMP_DBG_WORDS + 152);
 #else
-    linearise_block<NSEG, true>(cfg, ws.model, zl, scr, gout, ws.Gk + (size_t)b * N * 176, ceqo, tid);
+    linearise_block<NSEG, true>(cfg, problem_model(ws.model, b, ws.mstride), zl, scr, gout, ws.Gk + (size_t)b * N * 176, ceqo, tid);
 #endif
     KSTAMP(6);
     if (tid == 0) ws.alpha[b] = alpha;
@@ -1007,10 +1010,13 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
 #ifndef MPCMP_V3_TU     /* (the leaf kernels below are not templates: they belong to the main translation unit only) */
 // ------------------------------------------------------------------------------------------------
 // leaf kernels
-__global__ __launch_bounds__(64) void k_rnea_batch(const mpcmp_model *mdl, int n, const double *q, const double *v, const double *a,
+// (mstride: models per point behind mdl — 0, or narm with per-problem payload rows, WS::mstride; point / problem i reads arm 0 of row i.  Every
+//  leaf kernel below that evaluates dynamics takes one)
+__global__ __launch_bounds__(64) void k_rnea_batch(const mpcmp_model *mdl, int mstride, int n, const double *q, const double *v, const double *a,
                              double *tau) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    mdl += (size_t)i * mstride;
     double sc[14], vv[7], aa[7], t[7];
 #pragma unroll
     for (int j = 0; j < 7; j++) { sincos(q[7 * i + j], &sc[2 * j], &sc[2 * j + 1]); vv[j] = v[7 * i + j]; aa[j] = a[7 * i + j]; }
@@ -1021,16 +1027,19 @@ __global__ __launch_bounds__(64) void k_rnea_batch(const mpcmp_model *mdl, int n
 
 // evalConstraints AD overload for a list of (x,u): processed in chunks of N "nodes" per workgroup
 template <int NSEG>
-__global__ __launch_bounds__(Dim<NSEG>::NT) void k_eval_constraints(mpcmp_config cfg, const mpcmp_model *mdl, int total,
+__global__ __launch_bounds__(Dim<NSEG>::NT) void k_eval_constraints(mpcmp_config cfg, const mpcmp_model *mdl, int mstride, int total,
                                                                     const double *x, const double *u, double *g,
                                                                     double *G) {
     using D = Dim<NSEG>;
     constexpr int N = D::N;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *zl = lds, *scr = lds + D::n;
-    const int tid = threadIdx.x, base = blockIdx.x * N;
+    // N points per workgroup with one model; with per-point models (mstride != 0) one point per workgroup, its model at a uniform address
+    // (the nodes of linearise_block are independent: a point's outputs do not depend on its neighbours in the chunk)
+    const int per = mstride ? 1 : N, tid = threadIdx.x, base = blockIdx.x * per;
+    mdl += (size_t)base * mstride;
     for (int t = tid; t < N * 21; t += D::NT) {
-        const int k = t / 21, c = t % 21, src = (base + k < total) ? base + k : total - 1;
+        const int k = t / 21, c = t % 21, kk = k < per ? k : 0, src = (base + kk < total) ? base + kk : total - 1;
         if (c < 14) zl[14 * k + c] = x[(size_t)14 * src + c];
         else zl[14 * N + 7 * k + c - 14] = u[(size_t)7 * src + c - 14];
     }
@@ -1039,7 +1048,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_eval_constraints(mpcmp_config
     double *gl = scr + LinLds<NSEG>::size, *Gl = gl + 8 * N;
     // write into LDS staging first (tail chunk may be partial), then copy the valid part out
     linearise_block<NSEG, true>(cfg, mdl, zl, scr, gl, Gl, nullptr, tid);
-    const int valid = (total - base < N) ? total - base : N;
+    const int valid = (total - base < per) ? total - base : per;
     for (int t = tid; t < valid * 8; t += D::NT) g[(size_t)base * 8 + t] = gl[t];
     for (int t = tid; t < valid * 176; t += D::NT) G[(size_t)base * 176 + t] = Gl[t];
 }
@@ -1047,12 +1056,13 @@ template <int NSEG>
 struct EvalLds { static constexpr int size = Dim<NSEG>::n + LinLds<NSEG>::size + Dim<NSEG>::N * (8 + 176); };
 
 // get_MPC_trajectory<n_pts> (motionPlanner.hpp:99-116): Lagrange interpolation on the segment + RNEA
-__global__ __launch_bounds__(128) void k_sample(const mpcmp_model *mdl, int nseg, int B, int n_pts, const double *sx, const double *su,
+__global__ __launch_bounds__(128) void k_sample(const mpcmp_model *mdl, int mstride, int nseg, int B, int n_pts, const double *sx, const double *su,
                          const double *sT, double *out) {
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)B * (n_pts + 1);
     if (gid >= total) return;
     const int b = (int)(gid / (n_pts + 1)), ip = (int)(gid % (n_pts + 1));
+    mdl += (size_t)b * mstride;
     const int N = 3 * nseg + 1;
     const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
     const double t = (double)ip / n_pts;
@@ -1091,10 +1101,11 @@ __global__ __launch_bounds__(128) void k_sample(const mpcmp_model *mdl, int nseg
 
 // MotionPlanner::get_MPC_point (motionPlanner.hpp:118-128) for one physical time per problem, including the reference's clamp
 // (time >= T: the normalised time becomes T, not 1), plus the RNEA torque.  out [B][28] = q(7), v(7), a(7), tau(7).
-__global__ __launch_bounds__(64) void k_mpc_point(const mpcmp_model *mdl, int nseg, int B, const double *sx, const double *su, const double *sT,
+__global__ __launch_bounds__(64) void k_mpc_point(const mpcmp_model *mdl, int mstride, int nseg, int B, const double *sx, const double *su, const double *sT,
                                                   const double *time, double *out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    mdl += (size_t)b * mstride;
     const int N = 3 * nseg + 1;
     const double T = sT[b];
     const double t = (time[b] < T) ? time[b] / T : T;
@@ -1216,13 +1227,14 @@ __global__ __launch_bounds__(256) void k_rh_update(int nx, int n, const int *idx
 // Per-trajectory checks of examples/benchmark.cpp:58-160 in one pass: resample at n_pts+1 uniform times (interpolation + RNEA),
 // min / max of the 28 channels, terminal error, and the four pass flags (jerk, linear / angular task velocity, table
 // collision).  One workgroup per trajectory; out [B][74] = mins(28) | maxs(28) | x(T) - x_target (14) | flags (4, 1 = pass).
-__global__ __launch_bounds__(256) void k_traj_stats(const mpcmp_model *mdl, int nseg, int n_pts, const double *sx, const double *su,
+__global__ __launch_bounds__(256) void k_traj_stats(const mpcmp_model *mdl, int mstride, int nseg, int n_pts, const double *sx, const double *su,
                                                     const double *sT, const double *xf, double max_lin, double max_ang,
                                                     const double *jerk10 /*[7] = 10 x max_jerk*/, double *out) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *smp = lds;                          // [n_pts+1][28]
     __shared__ int fl[4];
     const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1;
+    mdl += (size_t)b * mstride;
     const double *X = sx + (size_t)b * 14 * N, *U = su + (size_t)b * 7 * N;
     const double T = sT[b];
     if (tid < 4) fl[tid] = 1;

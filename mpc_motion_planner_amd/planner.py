@@ -24,6 +24,7 @@ class Solver:
         self.m = (14 * (self.N - 1) + 8 * self.N) * self.narm
         self.max_batch = int(max_batch)
         self._ctx = C.c_void_p()
+        self._models = [models[a] for a in range(self.narm)] if models is not None else [model if model is not None else capi.default_model()]
         if models is not None:
             rc = lib().mpcmp_create_multi(C.byref(cfg), models, self.narm, int(device), int(max_batch), C.byref(self._ctx))
         else:
@@ -43,6 +44,53 @@ class Solver:
 
     def set_config(self, cfg):
         check(lib().mpcmp_set_config(self._ctx, C.byref(cfg)), self._ctx); self.cfg = cfg
+
+    # -- per-problem payloads (mpcmp_set_payloads)
+    PAYLOAD_DTYPE = np.dtype([("mass", "f8"), ("com", "f8", 3), ("I", "f8", 9)])      # mpcmp_payload
+
+    def payload_table(self, mass, com=None, inertia=None):
+        """[n][narm] mpcmp_payload records from mass [n] / com [n,3] / inertia [n,3,3] (one arm) or [n,narm] / [n,narm,3] / [n,narm,3,3];
+        com defaults to the model's tool point, inertia to 0"""
+        mass = f64(mass)
+        if self.narm == 1 and mass.ndim == 1:
+            mass = mass[:, None]
+        if mass.ndim != 2 or mass.shape[1] != self.narm or mass.shape[0] < 1:
+            raise ValueError("mass must be [n]%s, got %s" % ("" if self.narm == 1 else "[%d]" % self.narm, mass.shape))
+        n = mass.shape[0]
+        lead = (n,) if self.narm == 1 else (n, self.narm)
+        if com is None:
+            com = np.broadcast_to(np.array([m.tool[:] for m in self._models]), (n, self.narm, 3))
+        else:
+            com = f64(com)
+            if com.shape != lead + (3,):
+                raise ValueError("com must be %s, got %s" % (list(lead + (3,)), com.shape))
+        if inertia is None:
+            inertia = np.zeros((n, self.narm, 3, 3))
+        else:
+            inertia = f64(inertia)
+            if inertia.shape != lead + (3, 3):
+                raise ValueError("inertia must be %s, got %s" % (list(lead + (3, 3)), inertia.shape))
+        t = np.zeros((n, self.narm), dtype=self.PAYLOAD_DTYPE)
+        t["mass"] = mass
+        t["com"] = np.reshape(com, (n, self.narm, 3))
+        t["I"] = np.reshape(inertia, (n, self.narm, 9))
+        return t
+
+    def set_payloads(self, mass, com=None, inertia=None):
+        """row i applies to problem i of every later call that evaluates dynamics (include/mpcmp.h, mpcmp_set_payloads); see payload_table"""
+        t = self.payload_table(mass, com, inertia)
+        check(lib().mpcmp_set_payloads(self._ctx, t.shape[0], t.ctypes.data_as(C.c_void_p)), self._ctx)
+        self.payload_rows = t.shape[0]
+
+    def clear_payloads(self):
+        """back to the context's model for every problem"""
+        check(lib().mpcmp_set_payloads(self._ctx, 0, None), self._ctx)
+        self.payload_rows = 0
+
+    def set_payloads_device(self, n, ptr, stream=0):
+        """n rows of narm mpcmp_payload records (104 bytes each) at the device pointer ptr, ordered on `stream` (values not checked)"""
+        check(lib().mpcmp_set_payloads_device(self._ctx, int(n), C.c_void_p(ptr or None), C.c_void_p(stream or None)), self._ctx)
+        self.payload_rows = int(n)
 
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
@@ -290,6 +338,7 @@ class BatchMotionPlanner:
         self._warm = None
         self._sol = None
         self._rk = None
+        self._payload = None
 
     # motionPlanner.cpp:56-90
     def set_constraint_margins(self, margin_position, margin_velocity, margin_acceleration, margin_torque, margin_jerk):
@@ -330,9 +379,30 @@ class BatchMotionPlanner:
         idx = np.floor(capi.time_nodes(self.cfg.num_seg) * (nP - 1) + 0.5).astype(int)     # std::round, motionPlanner.hpp:157
         self._warm = (np.concatenate([q[:, idx], v[:, idx]], axis=-1), a[:, idx], f64(final_time).reshape(-1))
 
+    # extension beyond the reference's members: the load the gripper carries (include/mpcmp.h, mpcmp_set_payloads)
+    def set_payload(self, mass, com=None, inertia=None):
+        """payload for the next solve_trajectory and the MPC samples of its solution: mass scalar or [B], com [3] or [B,3] (joint-7 frame,
+        default the tool point), inertia about the COM [3,3] or [B,3,3] (default 0); mass None removes it.  Scalars apply to every problem."""
+        if mass is None:
+            self._payload = None
+            self._solver.clear_payloads()
+            return
+        m = f64(mass).reshape(-1)
+        c = None if com is None else f64(com).reshape(-1, 3)
+        I = None if inertia is None else f64(inertia).reshape(-1, 3, 3)
+        self._payload = (m, c, I)
+
+    def _apply_payload(self, B):
+        if self._payload is None:
+            return
+        m, c, I = self._payload
+        self._solver.set_payloads(np.broadcast_to(m, (B,)), None if c is None else np.broadcast_to(c, (B, 3)),
+                                  None if I is None else np.broadcast_to(I, (B, 3, 3)))
+
     # motionPlanner.cpp:177-208
     def solve_trajectory(self, use_builtin_warm_start=True):
         B = max(self.current_state.shape[0], self.target_state.shape[0])
+        self._apply_payload(B)
         x0 = np.broadcast_to(self.current_state, (B, 14)); xf = np.broadcast_to(self.target_state, (B, 14))
         if use_builtin_warm_start:      # what the reference gets from Ruckig (warm_start_RK, motionPlanner.cpp:146-175)
             self._rk = (np.array(x0), np.array(xf))
@@ -363,7 +433,13 @@ class BatchMotionPlanner:
     def get_ruckig_trajectory(self, n_pts=200):
         out, _ = self._solver.jerk_trajectory(self._rk[0], self._rk[1], self.margin_jerk_ * self.limits["jmax"], n_pts)
         q, v, a = out[..., 1:8], out[..., 8:15], out[..., 15:22]
-        tau = self._solver.rnea(q.reshape(-1, 7), v.reshape(-1, 7), a.reshape(-1, 7)).reshape(q.shape)
+        if self._payload is not None:          # (the jerk-limited trajectory is the unloaded comparison: its torques are the model's own)
+            self._solver.clear_payloads()
+        try:
+            tau = self._solver.rnea(q.reshape(-1, 7), v.reshape(-1, 7), a.reshape(-1, 7)).reshape(q.shape)
+        finally:
+            if self._payload is not None and self._sol is not None:
+                self._apply_payload(self._sol[2].shape[0])
         return out[..., 0], q, v, a, tau
 
     # motionPlanner.hpp:99-116
