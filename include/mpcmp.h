@@ -186,6 +186,54 @@ int mpcmp_solve_batch_device(mpcmp_ctx *ctx, int B, const double *d_x0, const do
 int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf,
                            double *warm_x, double *warm_u, double *warm_T);
 
+/* ---- per-problem final-time windows ----
+ * Row i = [lbT[i], ubT[i]] applies to problem i of every later mpcmp_solve_batch[_device], mpcmp_warm_start_batch, mpcmp_qp_batch and
+ * mpcmp_solve_batch_synced[_device]: those calls read it wherever they read cfg.lbT / cfg.ubT (the box of T, the rho of the T row: a window narrower
+ * than 1e-4 takes rho_eq, and MPCMP_STATUS_T_OUT_OF_BOX).  In a two-arm context the row applies to the problem; its arms share T.  Built-in
+ * initialiser (warm_* NULL, and mpcmp_warm_start_batch): with rows set its geometric grid stops at the row's ubT instead of cfg.ubT, and a duration
+ * below the row's lbT is raised to it (T = fmax(T, lbT) before the quintic's coefficients); without rows it is unchanged.  A caller's start guess is
+ * never changed.  Such a call with more problems than rows returns MPCMP_EINVAL and writes nothing.  n == 0 with both pointers NULL clears the rows
+ * (outputs bit for bit those of a context that never set any).  mpcmp_set_time_windows is synchronous; it returns MPCMP_EINVAL, changing nothing,
+ * for n outside [1, max_batch] (other than the clear) and for a row that is not 0 <= lbT <= ubT, lbT < +inf, ubT > -inf (no NaN).  The receding-
+ * horizon driver does not read the rows: with rows set mpcmp_rh_init returns MPCMP_EINVAL, and after mpcmp_rh_init both setters do. */
+int mpcmp_set_time_windows(mpcmp_ctx *ctx, int n, const double *lbT, const double *ubT);
+/* the same from DEVICE memory, ordered on hip_stream after the work already on it and before later work of the context; not checked */
+int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double *d_lbT, const double *d_ubT, void *hip_stream);
+
+/* ---- time scaling of a trajectory ----
+ * Collocation is in normalised time, so a solution stretched to T_new keeps its node positions.  Per problem b, exactly as the kernel computes it:
+ *   s = sT[b] / T_new[b]                                   (one IEEE division)
+ *   nodes 1 .. N-2:  ox[k][c] = sx[k][c]                   for c <  7 narm (joint positions)
+ *                    ox[k][c] = sx[k][c] * s               for c >= 7 narm (joint velocities)
+ *   node 0: ox[0] = x0[b];  node N-1: ox[N-1] = xf[b]     (the re-guess rule, motionPlanner.cpp:199-207: a stretch is exact only between states at rest)
+ *   every node:      ou[k][j] = su[k][j] * (s * s)
+ *   oT[b] = T_new[b]
+ * Layouts as mpcmp_solve_batch (x [B][N][14 narm], u [B][N][7 narm]); both arm layouts.  The outputs may be the inputs (ox == sx, ou == su,
+ * oT == sT: every entry of a problem is formed from its inputs before oT is written). */
+int mpcmp_time_scale_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *sx, const double *su, const double *sT,
+                           const double *T_new, double *ox, double *ou, double *oT);
+int mpcmp_time_scale_batch_device(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_sx, const double *d_su,
+                                  const double *d_sT, const double *d_T_new, double *d_ox, double *d_ou, double *d_oT, void *hip_stream);
+
+/* ---- time-synchronised solve: independent problems of a group arrive together ----
+ * 1. pass 1 = mpcmp_solve_batch[_device] with the same arguments and the rows in force.
+ * 2. problem i is ELIGIBLE if 0 <= group[i] < n_groups and its pass-1 status has none of MPCMP_STATUS_NAN, _NOT_PD, _XCH_DEAD, _T_OUT_OF_BOX.
+ *    group_T[g] = max of the pass-1 T over the group's eligible members (an order-independent atomic maximum: deterministic), NaN if it has none.
+ *    group[i] == -1: not synchronised.  The host variant returns MPCMP_EINVAL for any other id outside [0, n_groups); the device variant treats
+ *    such ids as -1.  n_groups in [0, max_batch].
+ * 3. pass 2 re-solves every eligible member whose pass-1 T < group_T[g], from mpcmp_time_scale of its pass-1 solution to group_T[g], with the window
+ *    [group_T[g], group_T[g]] (a context-internal row: the caller's rows do not change).  Multipliers follow carry_multipliers as in any solve.
+ *    Every other problem keeps its pass-1 outputs bit for bit.
+ * The device variant makes no host round trip: pass 2 is a launch over all B slots in which the problems not re-solved return at once (at N = 25 the
+ * QP kernels still run for them, results discarded, and their status words are put back as pass 1 left them, so that the next solve of the context
+ * (mpcmp_config.carry_multipliers, the re-guess rule) sees the state a plain solve leaves).  group_T [n_groups] or NULL; info may be NULL. */
+int mpcmp_solve_batch_synced(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *warm_x, const double *warm_u,
+                             const double *warm_T, const int *group, int n_groups,
+                             double *sol_x, double *sol_u, double *sol_T, mpcmp_info *info, double *group_T);
+int mpcmp_solve_batch_synced_device(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_warm_x, const double *d_warm_u,
+                                    const double *d_warm_T, const int *d_group, int n_groups,
+                                    double *d_sol_x, double *d_sol_u, double *d_sol_T, mpcmp_info *d_info, double *d_group_T, void *hip_stream);
+
 /* ---- leaf kernels exposed for parity tests and for callers that only need the rigid-body layer ---- */
 /* pinocchio::rnea (robot_ocp.hpp:91; motionPlanner.hpp:92,111,127,141): n x [q7],[qd7],[qdd7] -> n x [tau7] */
 int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const double *qd, const double *qdd, double *tau);

@@ -69,7 +69,19 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_warm_start_jerk_acc_batch", "mpcmp_warm_start_jerk_acc_batch_device", "mpcmp_jerk_trajectory_acc_batch", "mpcmp_jerk_point_acc_batch",
            "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats",
            "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device",
-           "mpcmp_model_add_payload", "mpcmp_set_payloads", "mpcmp_set_payloads_device"]
+           "mpcmp_model_add_payload", "mpcmp_set_payloads", "mpcmp_set_payloads_device",
+           "mpcmp_set_time_windows", "mpcmp_set_time_windows_device", "mpcmp_time_scale_batch", "mpcmp_time_scale_batch_device",
+           "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device"]
+
+# prototypes of the final-time entry points (include/mpcmp.h): the argument kinds, "i" = int, "p" = pointer
+PROTOTYPES = {
+    "mpcmp_set_time_windows": "pi" + "p" * 2,
+    "mpcmp_set_time_windows_device": "pi" + "p" * 3,
+    "mpcmp_time_scale_batch": "pi" + "p" * 9,
+    "mpcmp_time_scale_batch_device": "pi" + "p" * 10,
+    "mpcmp_solve_batch_synced": "pi" + "p" * 6 + "i" + "p" * 5,
+    "mpcmp_solve_batch_synced_device": "pi" + "p" * 6 + "i" + "p" * 6,
+}
 
 
 def library_path():
@@ -131,6 +143,9 @@ def lib():
         L.mpcmp_pose_targets_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5
         L.mpcmp_set_payloads.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mpcmp_set_payloads_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for name, kinds in PROTOTYPES.items():
+            getattr(L, name).argtypes = [C.c_int if k == "i" else C.c_void_p for k in kinds]
+            getattr(L, name).restype = C.c_int
         _lib = L
     return _lib
 

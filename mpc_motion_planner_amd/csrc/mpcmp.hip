@@ -28,6 +28,7 @@
 #include "jerk_device.hpp"
 #include "ik_device.hpp"
 #include "payload.hpp"
+#include "time_sync.hpp"
 
 #ifdef MPCMP_SPLIT_N25
 // the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
@@ -66,6 +67,17 @@ struct mpcmp_ctx {
     mpcmp_model *d_pmodel = nullptr;
     mpcmp_payload *d_pay = nullptr;
     int pay_rows = 0;
+    // per-problem final-time windows (mpcmp_set_time_windows): d_tbox [max_batch][2] = (lbT, ubT), allocated by the first call; tw_rows = 0: cfg.lbT / ubT.
+    // tw_pass: rows of the solve being enqueued that override them (the second pass of a synchronised solve), null otherwise
+    double *d_tbox = nullptr;
+    int tw_rows = 0;
+    const double *tw_pass = nullptr;
+    // the synchronised solve's buffers (mpcmp_solve_batch_synced*), [max_batch] each, allocated by its first call: group ids (host staging), group
+    // keys, member counts and times, the pass-2 mask (WS::retired of pass 2), the pass-1 status words, rows, T_new and stretched start guess
+    int *d_sg_group = nullptr, *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
+    unsigned long long *d_sg_key = nullptr;
+    double *d_sg_T = nullptr, *d_sg_rows = nullptr, *d_sg_Tn = nullptr, *d_sg_wx = nullptr, *d_sg_wu = nullptr, *d_sg_wT = nullptr;
+    const int *sync_skip = nullptr;   // pass 2 being enqueued: problems that are not re-solved
     int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
     uint32_t *d_terms = nullptr;
     WS ws{};
@@ -129,6 +141,18 @@ static thread_local std::string g_err;
 static const mpcmp_model *run_models(const mpcmp_ctx *ctx, int *stride) {
     *stride = ctx->pay_rows > 0 ? ctx->narm : 0;
     return ctx->pay_rows > 0 ? ctx->d_pmodel : ctx->d_model;
+}
+// the final-time rows a solve reads (WS::tbox): the second pass's, the caller's, or none (cfg.lbT / ubT; always none for the receding-horizon driver)
+static const double *run_rows(const mpcmp_ctx *ctx) {
+    if (ctx->tw_pass) return ctx->tw_pass;
+    return (ctx->tw_rows > 0 && !ctx->rh_step) ? ctx->d_tbox : nullptr;
+}
+static int time_rows_ok(mpcmp_ctx *ctx, int B) {
+    if (ctx->tw_rows > 0 && B > ctx->tw_rows) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than final-time rows (" + std::to_string(ctx->tw_rows) + "): see mpcmp_set_time_windows";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
 }
 // a call that evaluates dynamics for B problems needs a payload row for each of them (when rows are set)
 static int payload_rows_ok(mpcmp_ctx *ctx, int B) {
@@ -864,6 +888,58 @@ extern "C" int mpcmp_set_payloads_device(mpcmp_ctx *ctx, int n, const mpcmp_payl
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-problem final-time windows
+static int time_windows_check(mpcmp_ctx *ctx, int n, const double *lb, const double *ub) {
+    if (!ctx) { g_err = "mpcmp_set_time_windows: no context"; return MPCMP_EINVAL; }
+    if (ctx->rh_B > 0) { ctx->err = "mpcmp_set_time_windows: the receding-horizon driver does not read final-time rows (a loop is running)"; return MPCMP_EINVAL; }
+    if (n == 0 && !lb && !ub) return MPCMP_OK;
+    if (n < 1 || n > ctx->max_batch || !lb || !ub) { ctx->err = "mpcmp_set_time_windows: n must be in [1, max_batch] with lbT and ubT given (or 0 with both NULL: clear)"; return MPCMP_EINVAL; }
+    if (!ctx->d_tbox) {
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        if (int rc = dalloc(ctx, &ctx->d_tbox, (size_t)2 * ctx->max_batch)) return rc;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_time_windows(mpcmp_ctx *ctx, int n, const double *lbT, const double *ubT) {
+    if (int rc = time_windows_check(ctx, n, lbT, ubT)) return rc;
+    std::vector<double> rows((size_t)2 * n);
+    for (int i = 0; i < n; i++) {
+        // the rule validate() applies to the configuration's pair (no NaN, lb <= ub, not empty), and lbT >= 0
+        if (!(lbT[i] <= ubT[i] && lbT[i] < INFINITY && ubT[i] > -INFINITY && lbT[i] >= 0.0)) {
+            ctx->err = "mpcmp_set_time_windows: row " + std::to_string(i) + ": 0 <= lbT <= ubT required (no NaN, no empty window)";
+            return MPCMP_EINVAL;
+        }
+        rows[2 * i] = lbT[i]; rows[2 * i + 1] = ubT[i];
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_tbox, rows.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->tw_rows = n;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double *d_lbT, const double *d_ubT, void *hip_stream) {
+    if (int rc = time_windows_check(ctx, n, d_lbT, d_ubT)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        // after the caller's work on its stream (which writes the rows) and the context's own (solves that read the current rows), before the
+        // context's later work; the caller's later work waits for the reads
+        hipStream_t cs = (hipStream_t)hip_stream;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+        HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox, 2 * sizeof(double), d_lbT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox + 1, 2 * sizeof(double), d_ubT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+    }
+    ctx->tw_rows = n;
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launches
 template <typename K>
 static int set_lds(mpcmp_ctx *ctx, K kern, size_t bytes) {
@@ -941,7 +1017,8 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
     WS w = ctx->ws;
     w.x0 = d_x0; w.xf = d_xf;
     w.model = run_models(ctx, &w.mstride);
-    w.retired = ctx->rh_step ? ctx->d_retired : nullptr;
+    w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
+    w.tbox = run_rows(ctx);
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_init = InitLds<NSEG>::size * sizeof(double), l_qp = QpLds<S::N1>::size * sizeof(double),
                  l_step = StepLds<NSEG>::size * sizeof(double);
@@ -975,6 +1052,7 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
         v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
         v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
         if (v.retired) v.retired += b0;
+        if (v.tbox) v.tbox += 2 * b0;
         if (v.alt_x) { v.alt_x += 14 * D::N * b0; v.alt_u += 7 * D::N * b0; v.alt_T += b0; }
         wh[h] = v;
         if (d_wx) { hx[h] = d_wx + 14 * D::N * b0; hu[h] = d_wu + 7 * D::N * b0; hT[h] = d_wT + b0; }
@@ -1060,7 +1138,8 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
     WS w = ctx->ws;
     w.x0 = d_x0; w.xf = d_xf;
     w.model = run_models(ctx, &w.mstride);
-    w.retired = ctx->rh_step ? ctx->d_retired : nullptr;
+    w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
+    w.tbox = run_rows(ctx);
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_m = D::size * sizeof(double), l_qp3 = Qp3<NSEG>::sizeL * sizeof(double), l_qp3f = Qp3<NSEG>::sizeF * sizeof(double);
     // two parts on two streams once one part alone fills the chip (one CU per arm): see solve_impl
@@ -1082,6 +1161,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
         v.okey += b0; v.done += h; v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
         v.model += (size_t)v.mstride * b0;      // (see solve_impl)
         if (v.retired) v.retired += b0;
+        if (v.tbox) v.tbox += 2 * b0;
         if (v.alt_x) { v.alt_x += (size_t)14 * NARM * N * b0; v.alt_u += (size_t)7 * NARM * N * b0; v.alt_T += b0; }
         wh[h] = v;
         xh[h].buf = ctx->xch.buf ? ctx->xch.buf + (size_t)2 * MPCMP_XCH_STRIDE * b0 : nullptr;
@@ -1119,6 +1199,7 @@ static int solve_dispatch(mpcmp_ctx *ctx, int B, const double *d_x0, const doubl
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (!ctx->rh_step) if (int rc = time_rows_ok(ctx, B)) return rc;
     if (!d_x0 || !d_xf) return MPCMP_EINVAL;
     if ((d_wx != nullptr) != (d_wu != nullptr) || (d_wx != nullptr) != (d_wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1151,6 +1232,7 @@ extern "C" int mpcmp_solve_batch(mpcmp_ctx *ctx, int B, const double *x0, const 
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = time_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
@@ -1179,6 +1261,7 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     if (!ctx || !x0 || !xf || !wx || !wu || !wT || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
+    if (int rc = time_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, n = ctx->n;
     hipStream_t st = ctx->stream;
@@ -1186,7 +1269,7 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
     // k_init alone: the built-in initialiser writes the iterate z = [xs|us|T]
     const mpcmp_config save = run_config(ctx);
-    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf;
+    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx);
 #define LAUNCH_INIT(NS) { const size_t l = InitLds<NS>::size * sizeof(double); \
         hipLaunchKernelGGL(k_init<NS>, dim3(B), dim3(Dim<NS>::NT), l, st, save, w, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0); }
     switch (ctx->nseg) { case 1: LAUNCH_INIT(1) break; case 2: LAUNCH_INIT(2) break; case 4: LAUNCH_INIT(4) break; case 6: LAUNCH_INIT(6) break;
@@ -1230,6 +1313,138 @@ struct TmpBuf {
         return r;
     }
 };
+
+// ---- time scaling and the time-synchronised solve (time_sync.hpp) ----
+static int time_scale_enqueue(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_sx, const double *d_su, const double *d_sT,
+                              const double *d_Tn, const int *d_skip, double *d_ox, double *d_ou, double *d_oT, hipStream_t st) {
+    hipLaunchKernelGGL(k_time_scale, dim3(B), dim3(256), 0, st, ctx->N, ctx->narm, d_x0, d_xf, d_sx, d_su, d_sT, d_Tn, d_skip, d_ox, d_ou, d_oT);
+    HIPCHK(ctx, hipGetLastError());
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_time_scale_batch_device(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_sx, const double *d_su,
+                                             const double *d_sT, const double *d_Tn, double *d_ox, double *d_ou, double *d_oT, void *hip_stream) {
+    if (!ctx || B < 1 || !d_x0 || !d_xf || !d_sx || !d_su || !d_sT || !d_Tn || !d_ox || !d_ou || !d_oT) return MPCMP_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return time_scale_enqueue(ctx, B, d_x0, d_xf, d_sx, d_su, d_sT, d_Tn, nullptr, d_ox, d_ou, d_oT, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_time_scale_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *sx, const double *su, const double *sT,
+                                      const double *Tn, double *ox, double *ou, double *oT) {
+    if (!ctx || B < 1 || !x0 || !xf || !sx || !su || !sT || !Tn || !ox || !ou || !oT) return MPCMP_EINVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+    TmpBuf tb(ctx, ((2 * nx + 2 * (nx + nu) * N + 3) * (size_t)B) * sizeof(double));
+    double *d0 = tb.get<double>(nx * B), *d1 = tb.get<double>(nx * B), *dx = tb.get<double>(nx * N * B), *du = tb.get<double>(nu * N * B),
+           *dT = tb.get<double>(B), *dn = tb.get<double>(B), *qx = tb.get<double>(nx * N * B), *qu = tb.get<double>(nu * N * B), *qT = tb.get<double>(B);
+    if (!qT) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d1, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dn, Tn, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    if (int rc = time_scale_enqueue(ctx, B, d0, d1, dx, du, dT, dn, nullptr, qx, qu, qT, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ox, qx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ou, qu, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(oT, qT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, const double *wu, const double *wT) {
+    if (B < 1) return MPCMP_EINVAL;
+    if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
+    if (n_groups < 0 || n_groups > ctx->max_batch) { ctx->err = "mpcmp_solve_batch_synced: n_groups must be in [0, max_batch]"; return MPCMP_EINVAL; }
+    if ((wx != nullptr) != (wu != nullptr) || (wx != nullptr) != (wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
+    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = time_rows_ok(ctx, B)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_sg_group) {            // first use
+        const size_t M = ctx->max_batch, N = ctx->N;
+        if (int rc = dalloc(ctx, &ctx->d_sg_group, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_count, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_skip, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_status, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_key, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_T, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_rows, 2 * M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_Tn, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_wx, M * ctx->nx * N)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_wu, M * ctx->nu * N)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sg_wT, M)) return rc;
+    }
+    return MPCMP_OK;
+}
+
+// pass 1, the group times, the pass-2 mask / rows / start guess, pass 2: all on stream st, no host round trip
+static int synced_enqueue(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx, const double *d_wu, const double *d_wT,
+                          const int *d_group, int n_groups, double *d_sx, double *d_su, double *d_sT, mpcmp_info *d_info, double *d_gT, hipStream_t st) {
+    if (int rc = solve_dispatch(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, 0)) return rc;
+    const int G = n_groups > 0 ? n_groups : 1;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_sg_key, 0, sizeof(unsigned long long) * G, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_sg_count, 0, sizeof(int) * G, st));
+    hipLaunchKernelGGL(k_sync_tmax, dim3((B + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)d_sT,
+                       ctx->d_sg_key, ctx->d_sg_count);
+    const int np = B > n_groups ? B : n_groups;
+    hipLaunchKernelGGL(k_sync_prepare, dim3((np + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)d_sT,
+                       (const unsigned long long *)ctx->d_sg_key, (const int *)ctx->d_sg_count, d_gT, ctx->d_sg_skip, ctx->d_sg_rows, ctx->d_sg_Tn,
+                       ctx->d_sg_status);
+    HIPCHK(ctx, hipGetLastError());
+    if (int rc = time_scale_enqueue(ctx, B, d_x0, d_xf, d_sx, d_su, d_sT, ctx->d_sg_Tn, ctx->d_sg_skip, ctx->d_sg_wx, ctx->d_sg_wu, ctx->d_sg_wT, st))
+        return rc;
+    // pass 2: every slot is launched; the ones not re-solved return at once (WS::retired) and keep their pass-1 outputs
+    ctx->tw_pass = ctx->d_sg_rows; ctx->sync_skip = ctx->d_sg_skip;
+    const int rc = solve_dispatch(ctx, B, d_x0, d_xf, ctx->d_sg_wx, ctx->d_sg_wu, ctx->d_sg_wT, d_sx, d_su, d_sT, d_info, st, 0);
+    ctx->tw_pass = nullptr; ctx->sync_skip = nullptr;
+    if (rc) return rc;
+    // (at N = 25 the skipped slots' QP kernels ran in pass 2 and added to their status words: the next solve sees pass 1's, as after a plain solve)
+    hipLaunchKernelGGL(k_sync_restore, dim3((B + 255) / 256), dim3(256), 0, st, B, (const int *)ctx->d_sg_skip, (const int *)ctx->d_sg_status,
+                       ctx->ws.status);
+    HIPCHK(ctx, hipGetLastError());
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_solve_batch_synced_device(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx, const double *d_wu,
+                                               const double *d_wT, const int *d_group, int n_groups, double *d_sx, double *d_su, double *d_sT,
+                                               mpcmp_info *d_info, double *d_group_T, void *hip_stream) {
+    if (!ctx || !d_x0 || !d_xf || !d_group || !d_sx || !d_su || !d_sT) return MPCMP_EINVAL;
+    if (int rc = synced_check(ctx, B, n_groups, d_wx, d_wu, d_wT)) return rc;
+    return synced_enqueue(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_group, n_groups, d_sx, d_su, d_sT, d_info, d_group_T ? d_group_T : ctx->d_sg_T,
+                          (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_solve_batch_synced(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *wx, const double *wu, const double *wT,
+                                        const int *group, int n_groups, double *sx, double *su, double *sT, mpcmp_info *info, double *group_T) {
+    if (!ctx || !x0 || !xf || !group || !sx || !su || !sT) return MPCMP_EINVAL;
+    if (int rc = synced_check(ctx, B, n_groups, wx, wu, wT)) return rc;
+    for (int i = 0; i < B; i++)
+        if (group[i] < -1 || group[i] >= n_groups) {
+            ctx->err = "mpcmp_solve_batch_synced: group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
+        }
+    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sg_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    const bool warm = wx != nullptr;
+    if (warm) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wx, wx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wu, wu, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wT, wT, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    }
+    if (int rc = synced_enqueue(ctx, B, ctx->d_x0, ctx->d_xf, warm ? ctx->d_wx : nullptr, warm ? ctx->d_wu : nullptr, warm ? ctx->d_wT : nullptr,
+                                ctx->d_sg_group, n_groups, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, ctx->d_sg_T, st))
+        return rc;
+    HIPCHK(ctx, hipMemcpyAsync(sx, ctx->d_sx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(su, ctx->d_su, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(sT, ctx->d_sT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_info, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    if (group_T && n_groups > 0) HIPCHK(ctx, hipMemcpyAsync(group_T, ctx->d_sg_T, sizeof(double) * n_groups, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
 
 // ---- jerk-limited, time-synchronised warm start / comparison trajectory (stands in for Ruckig) ----
 // vmax / amax: NULL = the context's margin-applied bounds (the *_lim_* entry points pass a caller's own: ruckig::InputParameter::max_velocity / max_acceleration)
@@ -1448,6 +1663,7 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = time_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N;
     hipStream_t st = ctx->stream;
@@ -1668,6 +1884,7 @@ extern "C" int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const doub
     if (!ctx || !x0 || !xf || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (ctx->tw_rows > 0) { ctx->err = "mpcmp_rh_init: the receding-horizon driver does not read final-time rows (clear them: mpcmp_set_time_windows(ctx, 0, NULL, NULL))"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(ctx->ws.lam, 0, sizeof(double) * ctx->lam_count, st));       // new instances: no multipliers to carry, no failed solve behind them

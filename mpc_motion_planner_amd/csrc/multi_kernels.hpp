@@ -177,7 +177,8 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
         if (tid == 0) zl[n - 1] = warm_T[b];
     } else {
         // stand-in for the warm start when none is given: per-joint quintic, zero boundary accelerations, common duration on a
-        // geometric grid (same rule as k_init / the oracle's orc_warm_start, over all 7 NARM joints)
+        // geometric grid (same rule as k_init / the oracle's orc_warm_start, over all 7 NARM joints; per-problem windows as in k_init)
+        const TWin tw = t_window(cfg, ws.tbox, b);
         double T = 0.05;
         double *coef = scr;   // [7 NARM][6]
         constexpr int NJ = 7 * NARM;
@@ -206,9 +207,10 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
                 if (fabs(vv) > cfg.ubx[7 + j] || fabs(aa) > cfg.ubu[j]) bad = 1;
             }
             const int anybad = __syncthreads_or(bad);
-            if (!anybad || T * 1.05 > cfg.ubT) break;
+            if (!anybad || T * 1.05 > tw.hi) break;
             T *= 1.05;
         }
+        if (ws.tbox) T = fmax(T, tw.lo);
         __syncthreads();
         set_coef();
         __syncthreads();
@@ -273,7 +275,7 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
     reduce_m<NT, 1, true>(r2, red, tid);      // (also publishes zl / pl / xa)
     const double mu = r2[0];
     auto box_of = [&](int v, double &lo, double &hi) {
-        if (v == n - 1) { lo = cfg.lbT; hi = cfg.ubT; }
+        if (v == n - 1) { const TWin tw = t_window(cfg, ws.tbox, b); lo = tw.lo; hi = tw.hi; }
         else { const int a = v / na; arm_box<NSEG>(cfg, xa + 14 * a, xa + 14 * (NARM + a), v % na, lo, hi); }
     };
     // l1 violation at the current iterate (:79)
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
             mpcmp_info o;
             o.T = zl[n - 1]; o.viol_l1 = s1[0]; o.defect_inf = mxs[0]; o.path_viol_inf = mxs[1]; o.term_err_inf = mxs[2];
             o.last_alpha = alpha; o.qp_iters_total = ws.qp_total[b]; o.sqp_iters = sqp_it + 1;
-            report_status(cfg, ws.status[b], anybad, o);
+            report_status(cfg, t_window_lane(cfg, ws.tbox, b), ws.status[b], anybad, o);
             if (info) info[b] = o;
             ws.status[b] |= o.status & (MPCMP_STATUS_NAN | MPCMP_STATUS_T_OUT_OF_BOX);      // (hard bits of the final iterate, as in k_step)
         }

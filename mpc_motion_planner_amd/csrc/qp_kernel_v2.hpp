@@ -708,7 +708,7 @@ __device__ __forceinline__ VarRole make_var_role(const mpcmp_config &cfg, const 
         vr.rpos = ipos < nJ ? L::oRhsJ + 56 * (ipos / 49) + ipos % 49
                             : ((ia >= 14 * (NSEG + 1) && ia < D::nI - 1) ? L::oRI + ia : L::oRhsI + ia);
         double lo, hi;
-        var_box<NSEG>(cfg, ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
+        var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
         vr.rb = (hi - lo < 1e-4) ? rho_eq : rho_in;
         const double zv = zg_[v];
         vr.lb = lo - zv; vr.ub = hi - zv;

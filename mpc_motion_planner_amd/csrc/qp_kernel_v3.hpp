@@ -914,8 +914,9 @@ __global__ __launch_bounds__(512) void k_qp3(mpcmp_config cfg, WS ws, const Qp3P
             lds[L::oLg + r] = lg; lds[L::oUg + r] = ug; lds[L::oCf + r] = cf;
         }
         if (tid == 0) {
-            misc[L::M_lbT] = cfg.lbT - T; misc[L::M_ubT] = cfg.ubT - T;
-            misc[L::M_rbT] = (cfg.ubT - cfg.lbT < 1e-4) ? rho_eq : rho_in;
+            const TWin tw = t_window_lane(cfg, ws.tbox, b);   // (the window also chooses the T row's rho: a fixed T changes the factor)
+            misc[L::M_lbT] = tw.lo - T; misc[L::M_ubT] = tw.hi - T;
+            misc[L::M_rbT] = (tw.hi - tw.lo < 1e-4) ? rho_eq : rho_in;
         }
         __syncthreads();
         for (int ip = tid; ip < na; ip += NT) lds[rhs_slot(ip)] = lds[L::lKT + ip];

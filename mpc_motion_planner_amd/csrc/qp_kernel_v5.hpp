@@ -916,8 +916,9 @@ __global__ __launch_bounds__(768) void k_qp5(mpcmp_config cfg, WS ws, const Qp3P
             }
             f[4] = node_slot(v) | (rhs_slot(int3_of_ext(NSEG, v)) << 16);
         } else {                                              // T
-            lo = cfg.lbT - T; hi = cfg.ubT - T;
-            rb = (cfg.ubT - cfg.lbT < 1e-4) ? rho_eq : rho_in;
+            const TWin tw = t_window(cfg, ws.tbox, b);
+            lo = tw.lo - T; hi = tw.hi - T;
+            rb = (tw.hi - tw.lo < 1e-4) ? rho_eq : rho_in;
             f[4] = 21 | ((L::vXn + NX) << 16);                // (x~_T is read from slot 21 of node 0; no rhs entry: b_T is formed by the border)
             misc[L::M_rbT] = rb;
         }

@@ -47,6 +47,8 @@ struct WS {
                                            // that cannot be re-guessed from its previous solve (k_init: reguess && prev_bad); null = the built-in initialiser
     int mstride;              // models per problem behind `model`: 0 = one model (per arm) for every problem; narm = per-problem models
                               // (mpcmp_set_payloads): problem b of the launch, arm a reads model + b * mstride + a
+    const double *tbox;       // [B][2] or null: final-time window (lbT, ubT) of problem b (mpcmp_set_time_windows, the second pass of a synchronised
+                              // solve); null = cfg.lbT / cfg.ubT for every problem.  Indexed by the problem (after perm), offset by a part's b0 like retired
 };
 // a retired instance of the receding-horizon loop: the whole workgroup leaves (uniform)
 #define MPCMP_RETIRED(ws_, b_) ((ws_).retired != nullptr && (ws_).retired[b_] != 0)
@@ -113,19 +115,40 @@ __device__ __forceinline__ double viol(double v, double lo, double hi) {
     return v < lo ? lo - v : (v > hi ? v - hi : 0.0);
 }
 __device__ __forceinline__ double clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// status word and capped-QP count of the result record (include/mpcmp.h: MPCMP_STATUS_*; the oracle's orc_solve_multi does the same)
-__device__ __forceinline__ void report_status(const mpcmp_config &cfg, int st, int anybad, mpcmp_info &o) {
+// final-time window of problem b (wave-uniform): its row of WS::tbox, or the configuration's pair.  The row's address goes through readfirstlane, so
+// that the two values come in by a scalar load; every kernel reads it in its prologue (or its final report), never inside a loop.  The row is read
+// through a global-address-space pointer: with two generic pointers the compiler merges the two loads into one load from a selected address, and
+// the by-value configuration then has to live in scratch memory (600 B per lane in every kernel)
+struct TWin { double lo, hi; };
+typedef const __attribute__((address_space(1))) double *gdouble_ptr;
+__device__ __forceinline__ TWin t_window(const mpcmp_config &cfg, const double *tbox, int b) {
+    if (tbox == nullptr) return {cfg.lbT, cfg.ubT};
+    const unsigned long long a = (unsigned long long)(tbox + 2 * (size_t)b);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    const gdouble_ptr r = (gdouble_ptr)(((unsigned long long)hi << 32) | lo);
+    return {r[0], r[1]};
+}
+// the same as a plain load of the lanes that call it (one lane of a workgroup): the form for kernels at the edge of their register file, where the
+// scalar form costs spills (k_qp3<8, 1>: 4 B more scratch per lane)
+__device__ __forceinline__ TWin t_window_lane(const mpcmp_config &cfg, const double *tbox, int b) {
+    TWin w = {cfg.lbT, cfg.ubT};
+    if (tbox != nullptr) { const gdouble_ptr r = (gdouble_ptr)(tbox + 2 * b); w.lo = r[0]; w.hi = r[1]; }
+    return w;
+}
+// status word and capped-QP count of the result record (include/mpcmp.h: MPCMP_STATUS_*; the oracle's orc_solve_multi does the same); tw: the
+// problem's final-time window
+__device__ __forceinline__ void report_status(const mpcmp_config &cfg, TWin tw, int st, int anybad, mpcmp_info &o) {
     int s = (st & 0xFF) | (anybad ? MPCMP_STATUS_NAN : 0);
     o.qp_capped = (st >> 8) & 0x7FFFFF;      // (23 bits: the count cannot wrap for any sqp_iters a solve can run)
     if (o.qp_capped) s |= MPCMP_STATUS_QP_CAPPED;
     if (o.defect_inf > cfg.eps_abs || o.path_viol_inf > cfg.eps_abs || o.term_err_inf > cfg.eps_target + cfg.eps_abs) s |= MPCMP_STATUS_OUTSIDE_TOL;
-    if (!(o.T >= cfg.lbT - 1e-9 && o.T <= cfg.ubT + 1e-9)) s |= MPCMP_STATUS_T_OUT_OF_BOX;
+    if (!(o.T >= tw.lo - 1e-9 && o.T <= tw.hi + 1e-9)) s |= MPCMP_STATUS_T_OUT_OF_BOX;
     o.status = s;
 }
 
-// variable box of external variable v (motionPlanner.cpp:33,47,66-79)
+// variable box of external variable v (motionPlanner.cpp:33,47,66-79); tw: the problem's final-time window (t_window)
 template <int NSEG>
-__device__ __forceinline__ void var_box(const mpcmp_config &c, const double *x0, const double *xf, int v, double &lo,
+__device__ __forceinline__ void var_box(const mpcmp_config &c, TWin tw, const double *x0, const double *xf, int v, double &lo,
                                         double &hi) {
     using D = Dim<NSEG>;
     if (v < 14 * D::N) {
@@ -136,7 +159,7 @@ __device__ __forceinline__ void var_box(const mpcmp_config &c, const double *x0,
     } else if (v < 21 * D::N) {
         const int r = (v - 14 * D::N) % 7;
         lo = c.lbu[r]; hi = c.ubu[r];
-    } else { lo = c.lbT; hi = c.ubT; }
+    } else { lo = tw.lo; hi = tw.hi; }
 }
 
 template <int NSEG>
@@ -289,7 +312,9 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
             zl[v] = val;
         }
     } else {
-        // stand-in for Ruckig: per-joint quintic, zero boundary accelerations, common duration on a geometric grid
+        // stand-in for Ruckig: per-joint quintic, zero boundary accelerations, common duration on a geometric grid up to ubT.  With per-problem
+        // windows (WS::tbox) the grid stops at the row's ubT and a duration below the row's lbT is raised to it; without them cfg.lbT is not read
+        const TWin tw = t_window(cfg, ws.tbox, b);
         double T = 0.05;
         double *coef = scr;   // [7][6]
         for (int it = 0; it < 200; it++) {
@@ -313,9 +338,10 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
                 if (fabs(vv) > cfg.ubx[7 + j] || fabs(aa) > cfg.ubu[j]) bad = 1;
             }
             const int anybad = __syncthreads_or(bad);
-            if (!anybad || T * 1.05 > cfg.ubT) break;
+            if (!anybad || T * 1.05 > tw.hi) break;
             T *= 1.05;
         }
+        if (ws.tbox) T = fmax(T, tw.lo);
         __syncthreads();
         if (tid < 7) {
             const int j = tid;
@@ -407,7 +433,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_qp(mpcmp_config cfg, WS ws) {
         const int v = tid;
         ipos = int_of_ext(NSEG, v);
         double lo, hi;
-        var_box<NSEG>(cfg, ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
+        var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
         rb = (hi - lo < 1e-4) ? rho_eq : rho_in;
         const double zv = zg_[v];
         lb = lo - zv; ub = hi - zv;
@@ -880,7 +906,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
     const double mu = r2[0];
     const bool isVar = tid < n, isDyn = tid < meq;
     double lo = 0, hi = 0;
-    if (isVar) var_box<NSEG>(cfg, x0, xf, tid, lo, hi);
+    if (isVar) var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), x0, xf, tid, lo, hi);
     double c0[1] = {0.0};
     if (isDyn) c0[0] += fabs(ws.ceq[(size_t)b * meq + tid]);
     if (tid < 8 * N) c0[0] += viol(ws.g[(size_t)b * 8 * N + tid], cfg.lbg[tid % 8], cfg.ubg[tid % 8]);
@@ -996,7 +1022,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
             mpcmp_info o;
             o.T = zl[n - 1]; o.viol_l1 = s1[0]; o.defect_inf = mxs[0]; o.path_viol_inf = mxs[1]; o.term_err_inf = mxs[2];
             o.last_alpha = alpha; o.qp_iters_total = ws.qp_total[b]; o.sqp_iters = sqp_it + 1;
-            report_status(cfg, ws.status[b], anybad, o);
+            report_status(cfg, t_window_lane(cfg, ws.tbox, b), ws.status[b], anybad, o);      // (read again here: kept from the prologue it spills)
             if (info) info[b] = o;
             // the hard bits of the FINAL iterate (NaN, T outside its box) exist only here: written back, so that the slot's next k_init (no re-guess
             // from it, no carried multipliers) and k_advance (state held) see them like the bits the QP kernels set during the solve

@@ -92,6 +92,69 @@ class Solver:
         check(lib().mpcmp_set_payloads_device(self._ctx, int(n), C.c_void_p(ptr or None), C.c_void_p(stream or None)), self._ctx)
         self.payload_rows = int(n)
 
+    # -- per-problem final-time windows, time scaling, time-synchronised solves (include/mpcmp.h)
+    def set_time_windows(self, lbT, ubT):
+        """row i = [lbT[i], ubT[i]] applies to problem i of every later solve, warm_start, qp and solve_synced (mpcmp_set_time_windows)"""
+        lbT, ubT = f64(lbT).reshape(-1), f64(ubT).reshape(-1)
+        if lbT.shape != ubT.shape or lbT.shape[0] < 1:
+            raise ValueError("lbT and ubT must be [n] arrays of one length, got %s and %s" % (lbT.shape, ubT.shape))
+        check(lib().mpcmp_set_time_windows(self._ctx, lbT.shape[0], dp(lbT), dp(ubT)), self._ctx)
+        self.time_window_rows = lbT.shape[0]
+
+    def clear_time_windows(self):
+        """back to the configuration's [lbT, ubT] for every problem"""
+        check(lib().mpcmp_set_time_windows(self._ctx, 0, None, None), self._ctx)
+        self.time_window_rows = 0
+
+    def set_time_windows_device(self, n, p_lb, p_ub, stream=0):
+        """n rows from the device pointers p_lb / p_ub (doubles), ordered on `stream` (values not checked)"""
+        vp = C.c_void_p
+        check(lib().mpcmp_set_time_windows_device(self._ctx, int(n), vp(p_lb or None), vp(p_ub or None), vp(stream or None)), self._ctx)
+        self.time_window_rows = int(n)
+
+    def time_scale(self, x0, xf, sx, su, sT, T_new):
+        """trajectories stretched to T_new, end nodes pinned to x0 / xf (mpcmp_time_scale_batch): (ox, ou, oT)"""
+        x0, xf = self._states(x0, xf)
+        sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
+        T_new = f64(np.broadcast_to(np.asarray(T_new, dtype=np.float64), (B,)))
+        if x0.shape[0] != B:
+            raise ValueError("states are for %d problems, trajectories for %d" % (x0.shape[0], B))
+        ox, ou, oT = np.zeros_like(sx), np.zeros_like(su), np.zeros(B)
+        check(lib().mpcmp_time_scale_batch(self._ctx, B, dp(x0), dp(xf), dp(sx), dp(su), dp(sT), dp(T_new), dp(ox), dp(ou), dp(oT)), self._ctx)
+        return ox, ou, oT
+
+    def time_scale_device(self, B, x0, xf, sx, su, sT, T_new, ox, ou, oT, stream=0):
+        vp = C.c_void_p
+        check(lib().mpcmp_time_scale_batch_device(self._ctx, int(B), vp(x0), vp(xf), vp(sx), vp(su), vp(sT), vp(T_new), vp(ox), vp(ou), vp(oT),
+                                                  vp(stream or None)), self._ctx)
+
+    def solve_synced(self, x0, xf, group, warm=None, n_groups=None):
+        """mpcmp_solve_batch_synced: the members of each group (group[i] in [0, n_groups); -1 = on its own) that solved cleanly end at their group's
+        largest final time.  Returns (sx, su, sT, info, group_T); n_groups defaults to max(group) + 1"""
+        x0, xf = self._states(x0, xf); B = x0.shape[0]
+        group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if group.shape[0] != B:
+            raise ValueError("group must be [B] = [%d], got %s" % (B, group.shape))
+        if n_groups is None:
+            n_groups = max(int(group.max()) + 1, 0)
+        wx = wu = wT = None
+        if warm is not None:
+            wx, wu, wT = self._traj(*warm)
+            if wT.shape[0] != B:
+                raise ValueError("warm start is for %d problems, states for %d" % (wT.shape[0], B))
+        sx, su, sT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
+        info = np.zeros(B, dtype=capi.INFO_DTYPE)
+        gT = np.zeros(max(n_groups, 1))
+        check(lib().mpcmp_solve_batch_synced(self._ctx, B, dp(x0), dp(xf), dp(wx), dp(wu), dp(wT), group.ctypes.data_as(C.c_void_p), n_groups,
+                                             dp(sx), dp(su), dp(sT), info.ctypes.data_as(C.c_void_p), dp(gT)), self._ctx)
+        return sx, su, sT, info, gT[:n_groups]
+
+    def solve_synced_device(self, B, x0, xf, group, n_groups, sol_x, sol_u, sol_T, info=0, group_T=0, warm=(0, 0, 0), stream=0):
+        vp = C.c_void_p
+        check(lib().mpcmp_solve_batch_synced_device(self._ctx, int(B), vp(x0), vp(xf), vp(warm[0] or None), vp(warm[1] or None), vp(warm[2] or None),
+                                                    vp(group), int(n_groups), vp(sol_x), vp(sol_u), vp(sol_T), vp(info or None), vp(group_T or None),
+                                                    vp(stream or None)), self._ctx)
+
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
         x0, xf = f64(x0), f64(xf)
@@ -399,10 +462,21 @@ class BatchMotionPlanner:
         self._solver.set_payloads(np.broadcast_to(m, (B,)), None if c is None else np.broadcast_to(c, (B, 3)),
                                   None if I is None else np.broadcast_to(I, (B, 3, 3)))
 
+    # extension beyond the reference's members: a final-time window per problem (include/mpcmp.h, mpcmp_set_time_windows)
+    def set_final_time_window(self, lbT, ubT=None):
+        """window of the final time for the next solve_trajectory: scalars or [B] (lbT == ubT: exactly that duration); lbT None removes it"""
+        if lbT is None:
+            self._twin = None
+            self._solver.clear_time_windows()
+            return
+        self._twin = (f64(lbT).reshape(-1), f64(lbT if ubT is None else ubT).reshape(-1))
+
     # motionPlanner.cpp:177-208
     def solve_trajectory(self, use_builtin_warm_start=True):
         B = max(self.current_state.shape[0], self.target_state.shape[0])
         self._apply_payload(B)
+        if getattr(self, "_twin", None) is not None:
+            self._solver.set_time_windows(np.broadcast_to(self._twin[0], (B,)), np.broadcast_to(self._twin[1], (B,)))
         x0 = np.broadcast_to(self.current_state, (B, 14)); xf = np.broadcast_to(self.target_state, (B, 14))
         if use_builtin_warm_start:      # what the reference gets from Ruckig (warm_start_RK, motionPlanner.cpp:146-175)
             self._rk = (np.array(x0), np.array(xf))
