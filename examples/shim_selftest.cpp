@@ -109,6 +109,17 @@ int main() {
             std::printf("\"rk_duration_input\": %.17g, \"guess_T_input\": %.17g, \"rk_a0_ratio\": %.17g, ", tr4.get_duration(), planner.guess_T(), a(2) / planner.input.max_acceleration[2]);
             planner.input = keep;
         }
+        // extension: the last solution checked against a floor 5 cm below the base and a ball beside the arm (skeleton spheres of the model)
+        {
+            mpcmp_obstacle world[2] = {};
+            world[0].type = MPCMP_OBS_HALFSPACE; world[0].a[2] = 1.0; world[0].b[0] = -0.05;
+            world[1].type = MPCMP_OBS_SPHERE; world[1].a[0] = 0.55; world[1].a[2] = 0.75; world[1].r = 0.10;
+            planner.set_obstacles(world, 2);
+            const mpcmp_clearance c = planner.clearance(200, 0.02);
+            std::printf("\"clr_d_min\": %.17g, \"clr_t_min\": %.17g, \"clr_sphere\": %d, \"clr_other\": %d, \"clr_n_hit\": %d, \"clr_status\": %d, ",
+                        c.d_min, c.t_min, c.sphere, c.other, c.n_hit, c.status);
+            planner.set_obstacles(nullptr, 0);
+        }
         // robot.data look-alike (examples/benchmark.cpp:108-110)
         pinocchio::forwardKinematics(planner.robot.model, planner.robot.data, qT);
         pinocchio::updateFramePlacement(planner.robot.model, planner.robot.data, planner.robot.frame_id);

@@ -356,6 +356,85 @@ int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, const double
 int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sol_x, const double *sol_u, const double *sol_T,
                            const double *xf, int n_pts, double *out);
 
+/* ---- clearance: robot spheres against obstacles and against the other arm ----
+ * A CHECKER of finished trajectories, not a constraint of the OCP: no solve, warm start or receding-horizon entry point reads any of this, and a
+ * context that never calls the setters behaves bit for bit as one built without them.  mpcmp_create[_multi] adds one fixed-size table (128 sphere
+ * records, 5 KB); obstacles are allocated by mpcmp_set_obstacles[_device] when they grow; mpcmp_clearance_batch_device allocates nothing;
+ * mpcmp_select_clear_batch[_device] allocates its scratch (five arrays of max_batch entries) in its first call and nothing afterwards.
+ * Streams.  The tables and the selection's scratch belong to the context, the *_device calls run on the caller's stream.  The synchronous setters
+ * (mpcmp_set_robot_spheres, mpcmp_set_obstacles) wait for all work of the device before they write, so they may be called at any time.
+ * mpcmp_set_obstacles_device is ordered against the context's own stream and hip_stream only: a check in flight on ANOTHER stream must be ordered
+ * against it by the caller.  mpcmp_select_clear_batch_device uses one scratch per context: enqueue selections of one context on one stream at a
+ * time (or order them with events); a context per stream has no such limit.
+ * The robot is a set of spheres fixed to joint frames, the world a set of primitives.  Signed distance sd(x, obstacle) of a world point x:
+ *   sphere      |x - a| - r
+ *   capsule     t = clamp((x - a).(b - a) / |b - a|^2, 0, 1)  (t = 0 when a == b),  |x - a - t (b - a)| - r
+ *   box         d = |x - a| - b componentwise,  |max(d, 0)| + min(max(d.x, d.y, d.z), 0) - r
+ *   half-space  a.x - b[0]
+ * Clearance of robot sphere s at world centre c_s: sd(c_s, obstacle) - r_s; of a robot pair: |c_s - c_t| - r_s - r_t.  World centres follow the chain
+ * of the whole library: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i), c_s = p_w[joint] + R_w[joint] c.
+ * Pairs: every robot sphere x every obstacle; with two arms every sphere of arm 0 x every sphere of arm 1; and, if self_gap > 0, the spheres of one
+ * arm whose joint indices differ by at least self_gap.  Spheres are numbered arm-major in table order; a robot pair is named (s, t) with s < t. */
+typedef struct { int joint; int pad; double c[3]; double r; } mpcmp_sphere;
+/* joint 0..6: centre c in the frame of that joint (the frame mpcmp_model.com[joint] is given in); r > 0 */
+#define MPCMP_OBS_SPHERE    0   /* a = centre, r = radius                                                    */
+#define MPCMP_OBS_CAPSULE   1   /* segment a..b, r = radius                                                  */
+#define MPCMP_OBS_BOX       2   /* axis-aligned: a = centre, b = half extents (> 0), r >= 0 rounds the edges */
+#define MPCMP_OBS_HALFSPACE 3   /* solid { x : a.x <= b[0] }, a = unit normal pointing into free space       */
+typedef struct { int type; int pad; double a[3], b[3]; double r; } mpcmp_obstacle;   /* world frame */
+
+/* host helpers (no GPU needed) */
+/* A SKELETON sphere model from the model alone (not a fitted hull: it follows the lines between the joint origins and knows nothing of the link
+ * shapes): for joint i = 0..5 spheres of radius `radius` on the segment from the origin of joint i to p[i+1], for joint 6 from its origin to `tool`
+ * (all in joint i's frame); on a segment of length L, ceil(L / spacing) + 1 centres equally spaced including both ends (one when L == 0).
+ * MPCMP_EINVAL, writing nothing: radius <= 0, spacing <= 0, more than `max` spheres. */
+int mpcmp_link_spheres(const mpcmp_model *model, double radius, double spacing, int max, mpcmp_sphere *out, int *n);
+/* minimum clearance of ONE configuration q [7 narm] on the host: the pair set, formulas and tie order of mpcmp_clearance_batch for one sample.
+ * spheres [n_spheres[0] + .. ] arm-major; *sphere / *other (may be NULL) as in mpcmp_clearance; d_min = +inf, sphere = -1 when there is no pair. */
+int mpcmp_clearance_config(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                           const mpcmp_obstacle *obs, int self_gap, const double *q, double *d_min, int *sphere, int *other);
+
+/* sphere table of one arm: 0 <= n <= 64; n == 0 clears.  Synchronous.  MPCMP_EINVAL, changing nothing: arm outside [0, narm), n out of range, a joint
+ * outside 0..6, a value that is not finite, r <= 0. */
+int mpcmp_set_robot_spheres(mpcmp_ctx *ctx, int arm, int n, const mpcmp_sphere *spheres);
+/* obs [n_sets][n_obs], n_obs <= 256.  n_sets == 1: one world for every problem.  n_sets > 1 (<= max_batch): set i applies to problem i, and a
+ * clearance call with B > n_sets returns MPCMP_EINVAL and writes nothing.  n_sets == 0 (or n_obs == 0) clears.  The host variant is synchronous and
+ * rejects, changing nothing: unknown types, values that are not finite, r < 0, box half extents <= 0, a half-space normal with | |a| - 1 | > 1e-9.
+ * The device variant is ordered on hip_stream after the work already on it and before later work of the context; its values are not checked. */
+int mpcmp_set_obstacles(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *obs);
+int mpcmp_set_obstacles_device(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *d_obs, void *hip_stream);
+
+typedef struct {
+    double d_min;    /* smallest clearance over all samples and pairs (+inf when there is no pair)                          */
+    double t_min;    /* physical time of that sample, ip / n_pts * sol_T[b] (-1 when there is no pair)                       */
+    double t_first;  /* physical time of the first sample with a clearance < margin; -1 if none                             */
+    int    sphere;   /* at d_min: robot sphere, numbered arm-major over the context's sphere tables (-1 when there is no pair) */
+    int    other;    /* at d_min: obstacle index >= 0, or -1 - (index of the second robot sphere)                            */
+    int    n_hit;    /* number of samples with some clearance < margin                                                       */
+    int    status;   /* 0, MPCMP_CLR_HIT (n_hit > 0), MPCMP_CLR_NAN (a non-finite sample: d_min = NaN, the rest as for no pair) */
+} mpcmp_clearance;
+#define MPCMP_CLR_HIT 1
+#define MPCMP_CLR_NAN 2
+/* B trajectories sol_x [B][N][14 narm] (positions of arm a in columns [7a, 7a + 7)), sol_T [B], checked at the n_pts + 1 uniform normalised times of
+ * mpcmp_sample_batch (the same Lagrange interpolation on the segment), 1 <= n_pts <= 4096; out [B].  Both arm layouts, every num_seg.  Ties of d_min:
+ * lowest sample, then lowest sphere, then obstacles before robot pairs, then lowest index; a problem's record does not depend on the batch around
+ * it.  Kinematic: payload rows and time windows are not read.  MPCMP_EINVAL, writing nothing: B < 1, n_pts out of range, a NULL pointer, margin not
+ * finite, self_gap < 0, more problems than obstacle sets.  The forward kinematics run once per (problem, sample); the tables live in LDS, whose use
+ * does not grow with n_pts. */
+int mpcmp_clearance_batch(mpcmp_ctx *ctx, int B, const double *sol_x, const double *sol_T, int n_pts, double margin, int self_gap,
+                          mpcmp_clearance *out);
+int mpcmp_clearance_batch_device(mpcmp_ctx *ctx, int B, const double *d_sol_x, const double *d_sol_T, int n_pts, double margin, int self_gap,
+                                 mpcmp_clearance *d_out, void *hip_stream);
+/* "plan K candidates, keep the fastest one that hits nothing": group [B], n_groups in [0, max_batch] with the id rules of mpcmp_solve_batch_synced
+ * (-1: in no group; the host variant returns MPCMP_EINVAL for other ids outside [0, n_groups), the device variant treats them as -1).  A member is
+ * admissible if info[i].status has none of MPCMP_STATUS_NAN, _NOT_PD, _XCH_DEAD, _OUTSIDE_TOL, _T_OUT_OF_BOX and clr[i].status == 0.
+ * chosen [n_groups] = the admissible member with the smallest sol_T, ties to the lowest problem index, -1 if the group has none.  Deterministic
+ * (integer minima); the device variant makes no host round trip. */
+int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sol_T, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
+                             int n_groups, int *chosen);
+int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sol_T, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
+                                    const int *d_group, int n_groups, int *d_chosen, void *hip_stream);
+
 /* ---- receding-horizon driver (BASELINE.json config #5) ---- */
 /* B instances; every step = re-solve warm-started from the previous solution with the reference's re-guess rule
  * (head := current state, tail := target; motionPlanner.cpp:199-207), then the current state advances along the

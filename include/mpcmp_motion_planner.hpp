@@ -312,6 +312,26 @@ class MotionPlanner {
         payload_ = p; has_payload_ = true; payload_rows_ = 0;
     }
 
+    // extension beyond the reference's members: the world the plan runs in (include/mpcmp.h, clearance).  The robot is the skeleton of
+    // mpcmp_link_spheres(model, sphere_radius, sphere_spacing): spheres on the lines between the joint origins, not a fitted hull.
+    // n_obs == 0 removes the obstacles.
+    void set_obstacles(const mpcmp_obstacle *obs, int n_obs, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        if (n_obs > 0) {
+            mpcmp_sphere sph[64];
+            int n = 0;
+            if (mpcmp_link_spheres(&robot.model, sphere_radius, sphere_spacing, 64, sph, &n) != MPCMP_OK)
+                throw std::runtime_error("mpcmp: set_obstacles: sphere radius and spacing must be > 0 and give at most 64 spheres");
+            chk(mpcmp_set_robot_spheres(ctx_, 0, n, sph));
+        }
+        chk(mpcmp_set_obstacles(ctx_, n_obs > 0 ? 1 : 0, n_obs, obs));
+    }
+    // clearance record of the last solution at n_pts + 1 uniform samples (status 0: no sample closer than `margin` to anything)
+    mpcmp_clearance clearance(int n_pts = 200, double margin = 0.0, int self_gap = 0) {
+        mpcmp_clearance r;
+        chk(mpcmp_clearance_batch(ctx_, 1, sol_x_.data(), &sol_T_, n_pts, margin, self_gap, &r));
+        return r;
+    }
+
     // one draw in [-1,1) of the planner's seeded stream: what `Matrix<...>::Random()` coefficients are in the reference's examples
     double random_unit() { return uniform(); }
     // motionPlanner.cpp:102-114 (Eigen::Random replaced by a SplitMix64 stream owned by the planner)

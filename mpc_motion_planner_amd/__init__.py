@@ -11,7 +11,9 @@ multi-start inverse kinematics on the GPU.)
 from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED, STATUS_OUTSIDE_TOL, STATUS_T_OUT_OF_BOX, STATUS_ARRIVED, STATUS_HARD,
                    RH_RESTART, IK_NOT_CONVERGED, IK_Q_OUT_OF_BOUNDS, IK_QD_OUT_OF_BOUNDS, IK_INFO_DTYPE, Config, Info, Model, Payload, INFO_DTYPE, MpcmpError, DUAL_BASES, arm_models, build_library, default_config, default_limits,
                    default_model, forward_velocities, inverse_kinematic, inverse_velocities, lib, library_path,
-                   model_add_payload, model_from_urdf, models_from_urdf, num_nodes, payload, time_nodes, tool_jacobian)
+                   model_add_payload, model_from_urdf, models_from_urdf, num_nodes, payload, time_nodes, tool_jacobian,
+                   SPHERE_DTYPE, OBSTACLE_DTYPE, CLEARANCE_DTYPE, OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE, CLR_HIT, CLR_NAN,
+                   spheres, obstacle, link_spheres, clearance_config)
 from .planner import BatchMotionPlanner, Solver
 
 __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED", "STATUS_OUTSIDE_TOL", "STATUS_T_OUT_OF_BOX", "STATUS_ARRIVED", "STATUS_HARD", "RH_RESTART",
@@ -19,4 +21,6 @@ __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED",
            "Config", "Info", "Model", "INFO_DTYPE", "MpcmpError", "build_library", "default_config",
            "default_limits", "default_model", "lib", "library_path", "model_from_urdf", "models_from_urdf", "num_nodes",
            "time_nodes", "BatchMotionPlanner", "Solver", "forward_velocities", "inverse_kinematic",
-           "inverse_velocities", "tool_jacobian", "arm_models", "DUAL_BASES", "Payload", "payload", "model_add_payload"]
+           "inverse_velocities", "tool_jacobian", "arm_models", "DUAL_BASES", "Payload", "payload", "model_add_payload",
+           "SPHERE_DTYPE", "OBSTACLE_DTYPE", "CLEARANCE_DTYPE", "OBS_SPHERE", "OBS_CAPSULE", "OBS_BOX", "OBS_HALFSPACE", "CLR_HIT", "CLR_NAN",
+           "spheres", "obstacle", "link_spheres", "clearance_config"]

@@ -56,6 +56,14 @@ INFO_DTYPE = np.dtype([("T", "f8"), ("viol_l1", "f8"), ("defect_inf", "f8"), ("p
 IK_NOT_CONVERGED, IK_Q_OUT_OF_BOUNDS, IK_QD_OUT_OF_BOUNDS = 1, 2, 4
 IK_INFO_DTYPE = np.dtype([("err", "f8"), ("seed", "i4"), ("iters", "i4"), ("status", "i4"), ("pad", "i4")])
 
+# records of the clearance checks (mpcmp_sphere, mpcmp_obstacle, mpcmp_clearance; include/mpcmp.h)
+SPHERE_DTYPE = np.dtype([("joint", "i4"), ("pad", "i4"), ("c", "f8", 3), ("r", "f8")])
+OBSTACLE_DTYPE = np.dtype([("type", "i4"), ("pad", "i4"), ("a", "f8", 3), ("b", "f8", 3), ("r", "f8")])
+CLEARANCE_DTYPE = np.dtype([("d_min", "f8"), ("t_min", "f8"), ("t_first", "f8"), ("sphere", "i4"), ("other", "i4"), ("n_hit", "i4"), ("status", "i4")])
+OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE = 0, 1, 2, 3
+CLR_HIT, CLR_NAN = 1, 2
+MAX_SPHERES, MAX_OBSTACLES = 64, 256
+
 # every symbol include/mpcmp.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_urdf", "mpcmp_default_limits", "mpcmp_default_config",
            "mpcmp_set_margins", "mpcmp_set_min_height", "mpcmp_num_nodes", "mpcmp_time_nodes", "mpcmp_version",
@@ -71,7 +79,9 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device",
            "mpcmp_model_add_payload", "mpcmp_set_payloads", "mpcmp_set_payloads_device",
            "mpcmp_set_time_windows", "mpcmp_set_time_windows_device", "mpcmp_time_scale_batch", "mpcmp_time_scale_batch_device",
-           "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device"]
+           "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device",
+           "mpcmp_link_spheres", "mpcmp_clearance_config", "mpcmp_set_robot_spheres", "mpcmp_set_obstacles", "mpcmp_set_obstacles_device",
+           "mpcmp_clearance_batch", "mpcmp_clearance_batch_device", "mpcmp_select_clear_batch", "mpcmp_select_clear_batch_device"]
 
 # prototypes of the final-time entry points (include/mpcmp.h): the argument kinds, "i" = int, "p" = pointer
 PROTOTYPES = {
@@ -82,6 +92,19 @@ PROTOTYPES = {
     "mpcmp_solve_batch_synced": "pi" + "p" * 6 + "i" + "p" * 5,
     "mpcmp_solve_batch_synced_device": "pi" + "p" * 6 + "i" + "p" * 6,
 }
+# prototypes of the clearance entry points, with "d" = double
+CLEARANCE_PROTOTYPES = {
+    "mpcmp_link_spheres": "pddipp",
+    "mpcmp_clearance_config": "pippipippp" + "p",
+    "mpcmp_set_robot_spheres": "piip",
+    "mpcmp_set_obstacles": "piip",
+    "mpcmp_set_obstacles_device": "piipp",
+    "mpcmp_clearance_batch": "pippidip",
+    "mpcmp_clearance_batch_device": "pippidipp",
+    "mpcmp_select_clear_batch": "pippppip",
+    "mpcmp_select_clear_batch_device": "pippppipp",
+}
+_KINDS = {"i": C.c_int, "p": C.c_void_p, "d": C.c_double}
 
 
 def library_path():
@@ -146,6 +169,9 @@ def lib():
         for name, kinds in PROTOTYPES.items():
             getattr(L, name).argtypes = [C.c_int if k == "i" else C.c_void_p for k in kinds]
             getattr(L, name).restype = C.c_int
+        for name, kinds in CLEARANCE_PROTOTYPES.items():
+            getattr(L, name).argtypes = [_KINDS[k] for k in kinds]
+            getattr(L, name).restype = C.c_int
         _lib = L
     return _lib
 
@@ -202,6 +228,57 @@ def payload(mass, com=(0.0, 0.0, 0.0), inertia=None):
 def model_add_payload(model, p):
     """mpcmp_model_add_payload: a copy of `model` with the Payload `p` lumped into body 7 (parallel-axis theorem)"""
     out = Model(); check(lib().mpcmp_model_add_payload(C.byref(model), C.byref(p), C.byref(out))); return out
+
+
+def spheres(joint, c, r):
+    """SPHERE_DTYPE records from joint [n], centres c [n][3] (in the joint's frame) and radii r (scalar or [n])"""
+    joint = np.asarray(joint, dtype=np.int32).reshape(-1)
+    t = np.zeros(joint.shape[0], dtype=SPHERE_DTYPE)
+    t["joint"] = joint; t["c"] = f64(c).reshape(-1, 3); t["r"] = r
+    return t
+
+
+def obstacle(kind, a, b=(0.0, 0.0, 0.0), r=0.0):
+    """one OBSTACLE_DTYPE record: OBS_SPHERE (a centre, r), OBS_CAPSULE (a..b, r), OBS_BOX (a centre, b half extents, r rounding),
+    OBS_HALFSPACE (a unit normal into free space, b[0] offset: solid where a.x <= b[0])"""
+    t = np.zeros((), dtype=OBSTACLE_DTYPE)
+    t["type"] = kind; t["a"] = f64(a).reshape(3); t["b"] = f64(b).reshape(3); t["r"] = r
+    return t
+
+
+def _records(a, dtype, what):
+    a = np.ascontiguousarray(a)
+    if a.dtype != dtype:
+        raise ValueError("%s must be an array of %s records" % (what, what.upper() + "_DTYPE"))
+    return a
+
+
+def link_spheres(model, radius, spacing, max_spheres=MAX_SPHERES):
+    """mpcmp_link_spheres: a SKELETON sphere model from the joint origins alone (not a fitted hull), SPHERE_DTYPE [n]"""
+    out = np.zeros(max(int(max_spheres), 1), dtype=SPHERE_DTYPE); n = C.c_int(0)
+    check(lib().mpcmp_link_spheres(C.addressof(model), float(radius), float(spacing), int(max_spheres), out.ctypes.data, C.addressof(n)))
+    return out[:n.value].copy()
+
+
+def clearance_config(models, spheres_per_arm, obstacles, q, self_gap=0):
+    """mpcmp_clearance_config: minimum clearance of ONE configuration q [7 narm] on the host.  models: a Model or a sequence of them;
+    spheres_per_arm: one SPHERE_DTYPE array per arm; obstacles: OBSTACLE_DTYPE [n_obs] or None.  Returns (d_min, sphere, other)."""
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models)
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    obs = np.zeros(0, dtype=OBSTACLE_DTYPE) if obstacles is None else _records(obstacles, OBSTACLE_DTYPE, "obstacle").reshape(-1)
+    q = f64(q).reshape(7 * narm)
+    d, sp, ot = C.c_double(0), C.c_int(0), C.c_int(0)
+    check(lib().mpcmp_clearance_config(C.addressof(arr), narm, cnt.ctypes.data, tab.ctypes.data if tab.shape[0] else None, obs.shape[0],
+                                       obs.ctypes.data if obs.shape[0] else None, int(self_gap), q.ctypes.data, C.addressof(d), C.addressof(sp),
+                                       C.addressof(ot)))
+    return d.value, sp.value, ot.value
 
 
 def model_from_urdf(path):

@@ -1,0 +1,344 @@
+// clearance.hip — batched clearance checks (include/mpcmp.h, "clearance"): robot spheres against obstacles and against the other arm, over the
+// uniform samples of B trajectories; the choice of the fastest clear member of a group; and the host helpers that need no context.
+// A translation unit of its own, so that the register-bound QP kernels of mpcmp.hip compile exactly as before.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include "clearance.hpp"
+
+namespace mpcmp {
+
+// One workgroup per trajectory.  Staged in LDS once: the joint placements of the arms, the node positions of the trajectory, the sphere tables and
+// the problem's obstacles (in the form of clr_obs_prepare).  Then the n_pts + 1 samples in chunks of `chunk`, four phases per chunk:
+//   A1  one thread per (sample, joint): Lagrange interpolation of the joint position (the rule of k_sample) and its sine / cosine;
+//   A2  one thread per (sample, arm): the forward-kinematics chain, once per sample: world rotation and origin of the 7 joint frames;
+//   B   one thread per (sample, sphere): world centre, then every obstacle (a uniform loop: all lanes read one obstacle, broadcast from LDS);
+//   C   one thread per (sample, sphere s): every partner sphere t > s that clr_pair admits.
+// Every thread keeps its best (clearance, packed index) pair in registers over all chunks; one workgroup reduction at the end orders them by
+// clr_better, so the record does not depend on the launch or on the batch.  No atomics.  LDS use depends on the tables, not on n_pts.
+__global__ __launch_bounds__(CLR_NT) void k_clearance(const mpcmp_model *__restrict__ mdl, int narm, int nseg, int n_pts,
+                                                      const ClrSphere *__restrict__ sph, int n0, int n1,
+                                                      const mpcmp_obstacle *__restrict__ obs, int n_obs, int obs_stride,
+                                                      const double *__restrict__ sx, const double *__restrict__ sT, double margin, int self_gap,
+                                                      int chunk, mpcmp_clearance *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red_d[CLR_NT / 64];
+    __shared__ unsigned red_k[CLR_NT / 64];
+    __shared__ int nan_flag;
+    const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm, nsph = n0 + n1;
+    double *mk_ = lds;                                   // [narm][7][12] = R0 (9), p (3)
+    double *nodes = mk_ + 84 * narm;                     // [N][nq]
+    double *sk = nodes + (size_t)nq * N;                 // [nsph][4] = c, r
+    double *ok = sk + 4 * nsph;                          // [n_obs][8]
+    double *sc = ok + 8 * n_obs;                         // [chunk][nq][2]
+    double *fr = sc + (size_t)chunk * nq * 2;            // [chunk][nq][12] = Rw (9), pw (3)
+    double *cen = fr + (size_t)chunk * nq * 12;          // [chunk][nsph][3]
+    int *sj = reinterpret_cast<int *>(cen + (size_t)chunk * nsph * 3);   // [nsph] arm * 7 + joint
+    int *sa = sj + nsph;                                 // [nsph] arm
+    int *ot = sa + nsph;                                 // [n_obs] type
+    int *hit = ot + n_obs;                               // [chunk]
+
+    for (int e = tid; e < 84 * narm; e += CLR_NT) {
+        const int a = e / 84, i = (e % 84) / 12, c = e % 12;
+        mk_[e] = c < 9 ? mdl[a].R0[i][c] : mdl[a].p[i][c - 9];
+    }
+    const double *X = sx + (size_t)b * N * 2 * nq;
+    for (int e = tid; e < nq * N; e += CLR_NT) nodes[e] = X[(size_t)(e / nq) * 2 * nq + e % nq];
+    for (int s = tid; s < nsph; s += CLR_NT) {
+        const ClrSphere S = sph[s];
+        sk[4 * s] = S.c[0]; sk[4 * s + 1] = S.c[1]; sk[4 * s + 2] = S.c[2]; sk[4 * s + 3] = S.r;
+        sj[s] = 7 * S.arm + S.joint; sa[s] = S.arm;
+    }
+    const mpcmp_obstacle *O = obs + (size_t)b * obs_stride;
+    for (int o = tid; o < n_obs; o += CLR_NT) {
+        clr_obs_prepare(O[o], ok + 8 * o);
+        ot[o] = O[o].type;
+    }
+    for (int e = tid; e < chunk; e += CLR_NT) hit[e] = 0;
+    if (tid == 0) nan_flag = 0;
+    __syncthreads();
+
+    double best_d = INFINITY;
+    unsigned best_k = CLR_NO_PAIR;
+    int n_hit = 0, first = -1;                           // (thread 0 only)
+    const bool pairs = narm > 1 || self_gap > 0;
+    for (int ip0 = 0; ip0 <= n_pts; ip0 += chunk) {
+        const int ns = (n_pts + 1 - ip0 < chunk) ? n_pts + 1 - ip0 : chunk;      // samples of this chunk
+        // A1
+        for (int it = tid; it < ns * nq; it += CLR_NT) {
+            const int sl = it / nq, j = it % nq;
+            const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
+            const double t = (double)(ip0 + sl) / n_pts;
+            int s = (int)floor(t * nseg);
+            if (s >= nseg) s = nseg - 1;
+            if (s < 0) s = 0;
+            const double xx = 2.0 * (t * nseg - s) - 1.0;
+            double q = 0.0;
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) {
+                double v = 1.0;
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (k != jj) v *= (xx - xi[k]) / (xi[jj] - xi[k]);
+                q += v * nodes[(3 * s + jj) * nq + j];
+            }
+            if (!isfinite(q)) nan_flag = 1;
+            double sn, cs;
+            sincos(q, &sn, &cs);
+            sc[2 * it] = sn; sc[2 * it + 1] = cs;
+        }
+        __syncthreads();
+        // A2: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i)
+        for (int it = tid; it < ns * narm; it += CLR_NT) {
+            const int sl = it / narm, a = it % narm;
+            const double *M = mk_ + 84 * a, *SC = sc + (size_t)(sl * nq + 7 * a) * 2;
+            double *F = fr + (size_t)(sl * nq + 7 * a) * 12;
+            double Rw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pw[3] = {0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 7; i++) {
+                const double *A = M + 12 * i;
+                const double s = SC[2 * i], c = SC[2 * i + 1];
+                double R[9], Rn[9];
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    R[3 * r] = A[3 * r] * c + A[3 * r + 1] * s;
+                    R[3 * r + 1] = -A[3 * r] * s + A[3 * r + 1] * c;
+                    R[3 * r + 2] = A[3 * r + 2];
+                }
+#pragma unroll
+                for (int r = 0; r < 3; r++) pw[r] += Rw[3 * r] * A[9] + Rw[3 * r + 1] * A[10] + Rw[3 * r + 2] * A[11];
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int c2 = 0; c2 < 3; c2++) Rn[3 * r + c2] = Rw[3 * r] * R[c2] + Rw[3 * r + 1] * R[3 + c2] + Rw[3 * r + 2] * R[6 + c2];
+#pragma unroll
+                for (int k = 0; k < 9; k++) { Rw[k] = Rn[k]; F[12 * i + k] = Rn[k]; }
+#pragma unroll
+                for (int r = 0; r < 3; r++) F[12 * i + 9 + r] = pw[r];
+            }
+        }
+        __syncthreads();
+        // B
+        for (int it = tid; it < ns * nsph; it += CLR_NT) {
+            const int sl = it / nsph, s = it % nsph;
+            const double *F = fr + (size_t)(sl * nq + sj[s]) * 12, *S = sk + 4 * s;
+            const double cx = F[9] + F[0] * S[0] + F[1] * S[1] + F[2] * S[2];
+            const double cy = F[10] + F[3] * S[0] + F[4] * S[1] + F[5] * S[2];
+            const double cz = F[11] + F[6] * S[0] + F[7] * S[1] + F[8] * S[2];
+            cen[3 * it] = cx; cen[3 * it + 1] = cy; cen[3 * it + 2] = cz;
+            double dm = INFINITY;
+            int om = 0;
+            for (int o = 0; o < n_obs; o++) {
+                const double d = clr_sd(ot[o], ok + 8 * o, cx, cy, cz) - S[3];
+                if (d < dm) { dm = d; om = o; }
+            }
+            if (dm < margin) hit[sl] = 1;
+            const unsigned k = clr_pack(ip0 + sl, s, 0, om);
+            if (dm < INFINITY && clr_better(dm, k, best_d, best_k)) { best_d = dm; best_k = k; }
+        }
+        __syncthreads();
+        // C
+        if (pairs) {
+            for (int it = tid; it < ns * nsph; it += CLR_NT) {
+                const int sl = it / nsph, s = it % nsph;
+                const double *C = cen + (size_t)sl * nsph * 3;
+                const double cx = C[3 * s], cy = C[3 * s + 1], cz = C[3 * s + 2], rs = sk[4 * s + 3];
+                const int as = sa[s], js = sj[s];
+                double dm = INFINITY;
+                int tm = 0;
+                for (int t = s + 1; t < nsph; t++) {
+                    if (!clr_pair(as, js, sa[t], sj[t], self_gap)) continue;      // (sj holds arm * 7 + joint: differences within one arm are joint differences)
+                    const double ex = cx - C[3 * t], ey = cy - C[3 * t + 1], ez = cz - C[3 * t + 2];
+                    const double d = sqrt(ex * ex + ey * ey + ez * ez) - rs - sk[4 * t + 3];
+                    if (d < dm) { dm = d; tm = t; }
+                }
+                if (dm < margin) hit[sl] = 1;
+                const unsigned k = clr_pack(ip0 + sl, s, 1, tm);
+                if (dm < INFINITY && clr_better(dm, k, best_d, best_k)) { best_d = dm; best_k = k; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0)
+            for (int sl = 0; sl < ns; sl++) {
+                if (hit[sl]) { if (first < 0) first = ip0 + sl; n_hit++; }
+                hit[sl] = 0;
+            }
+    }
+    // workgroup reduction of (clearance, packed index) by clr_better
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double od = __shfl_down(best_d, off);
+        const unsigned okk = __shfl_down(best_k, off);
+        if (clr_better(od, okk, best_d, best_k)) { best_d = od; best_k = okk; }
+    }
+    if ((tid & 63) == 0) { red_d[tid >> 6] = best_d; red_k[tid >> 6] = best_k; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < CLR_NT / 64; w++)
+            if (clr_better(red_d[w], red_k[w], best_d, best_k)) { best_d = red_d[w]; best_k = red_k[w]; }
+        const double T = sT[b];
+        mpcmp_clearance r;
+        if (nan_flag) {
+            r.d_min = __longlong_as_double(0x7FF8000000000000ll); r.t_min = -1.0; r.t_first = -1.0;
+            r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
+        } else {
+            r.d_min = best_d;
+            if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
+            else {
+                const int ip = (int)(best_k >> 17), idx = (int)(best_k & 0xFFu);
+                r.t_min = ((double)ip / n_pts) * T;
+                r.sphere = (int)((best_k >> 9) & 0x7Fu);
+                r.other = (best_k & 0x100u) ? -1 - idx : idx;
+            }
+            r.t_first = first >= 0 ? ((double)first / n_pts) * T : -1.0;
+            r.n_hit = n_hit;
+            r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
+        }
+        out[b] = r;
+    }
+}
+
+// ---- choice of the fastest admissible member of each group (mpcmp_select_clear_batch) ----
+__device__ __forceinline__ bool sel_admissible(int i, const int *group, int n_groups, const mpcmp_info *info, const mpcmp_clearance *clr) {
+    const int g = group[i];
+    const int bad = MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_OUTSIDE_TOL | MPCMP_STATUS_T_OUT_OF_BOX;
+    return g >= 0 && g < n_groups && (info[i].status & bad) == 0 && clr[i].status == 0;
+}
+// keys [n_groups] preset to all ones: the smallest ordered key of the admissible members' final times (an integer minimum: order-independent)
+__global__ __launch_bounds__(256) void k_select_tmin(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
+                                                     int n_groups, unsigned long long *keys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B || !sel_admissible(i, group, n_groups, info, clr)) return;
+    atomicMin(keys + group[i], clr_tkey(sT[i]));
+}
+// chosen [n_groups] preset to 0x7F7F7F7F: the lowest index among the members that hold the group's key
+__global__ __launch_bounds__(256) void k_select_index(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
+                                                      int n_groups, const unsigned long long *keys, int *chosen) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B || !sel_admissible(i, group, n_groups, info, clr)) return;
+    if (clr_tkey(sT[i]) == keys[group[i]]) atomicMin(chosen + group[i], i);
+}
+__global__ __launch_bounds__(256) void k_select_finish(int n_groups, int *chosen) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n_groups && chosen[g] == 0x7F7F7F7F) chosen[g] = -1;
+}
+
+hipError_t clearance_prepare() {
+    // the largest tables need more than the 64 KB a kernel may use without asking: the ceiling over every sphere count (the chunk shrinks as the
+    // sphere tables grow), two arms, 25 nodes, 256 obstacles: 96 KB
+    size_t mx = 0;
+    for (int s = 0; s <= 2 * CLR_MAX_SPH; s++) {
+        const size_t b = clr_lds_bytes(2, 25, s, CLR_MAX_OBS, clr_chunk(s));
+        if (b > mx) mx = b;
+    }
+    return hipFuncSetAttribute((const void *)k_clearance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx);
+}
+
+hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
+                            mpcmp_clearance *d_out, hipStream_t st) {
+    const int nsph = t.n_sph[0] + t.n_sph[1], chunk = clr_chunk(nsph);
+    const size_t lds = clr_lds_bytes(t.narm, 3 * t.nseg + 1, nsph, t.n_obs, chunk);
+    hipLaunchKernelGGL(k_clearance, dim3(B), dim3(CLR_NT), lds, st, t.d_model, t.narm, t.nseg, n_pts, t.d_sph, t.n_sph[0], t.n_sph[1], t.d_obs, t.n_obs,
+                       t.obs_stride, d_sx, d_sT, margin, self_gap, chunk, d_out);
+    return hipGetLastError();
+}
+
+hipError_t select_clear_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const int *d_group, int n_groups,
+                               unsigned long long *d_keys, int *d_chosen, hipStream_t st) {
+    if (n_groups < 1) return hipSuccess;
+    hipError_t e = hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_groups, st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d_chosen, 0x7F, sizeof(int) * n_groups, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_select_tmin, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_group, n_groups, d_keys);
+    hipLaunchKernelGGL(k_select_index, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_group, n_groups,
+                       (const unsigned long long *)d_keys, d_chosen);
+    hipLaunchKernelGGL(k_select_finish, dim3((n_groups + 255) / 256), dim3(256), 0, st, n_groups, d_chosen);
+    return hipGetLastError();
+}
+
+}  // namespace mpcmp
+
+using namespace mpcmp;
+
+// ---- host helpers (no GPU) ----
+extern "C" int mpcmp_link_spheres(const mpcmp_model *model, double radius, double spacing, int max, mpcmp_sphere *out, int *n) {
+    if (!model || !out || !n || !(radius > 0.0) || !(spacing > 0.0) || !std::isfinite(radius) || !std::isfinite(spacing) || max < 0) return MPCMP_EINVAL;
+    int cnt = 0;
+    for (int pass = 0; pass < 2; pass++) {          // count first: nothing is written when the spheres do not fit
+        cnt = 0;
+        for (int i = 0; i < 7; i++) {
+            const double *e = i < 6 ? model->p[i + 1] : model->tool;
+            const double L = std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+            const int k = L > 0.0 ? (int)std::ceil(L / spacing) + 1 : 1;
+            for (int c = 0; c < k; c++, cnt++) {
+                if (!pass) continue;
+                const double f = k > 1 ? (double)c / (k - 1) : 0.0;
+                mpcmp_sphere &s = out[cnt];
+                s.joint = i; s.pad = 0; s.r = radius;
+                for (int d = 0; d < 3; d++) s.c[d] = f * e[d];
+            }
+        }
+        if (cnt > max) return MPCMP_EINVAL;
+    }
+    *n = cnt;
+    return MPCMP_OK;
+}
+
+// world placement of every joint frame: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i)
+static void fk_frames(const mpcmp_model *m, const double *q, double Rw[7][9], double pw[7][3]) {
+    double Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pp[3] = {0, 0, 0};
+    for (int i = 0; i < 7; i++) {
+        const double s = std::sin(q[i]), c = std::cos(q[i]), *A = m->R0[i];
+        double R[9];
+        for (int r = 0; r < 3; r++) { R[3 * r] = A[3 * r] * c + A[3 * r + 1] * s; R[3 * r + 1] = -A[3 * r] * s + A[3 * r + 1] * c; R[3 * r + 2] = A[3 * r + 2]; }
+        for (int r = 0; r < 3; r++) pw[i][r] = pp[r] + Rp[3 * r] * m->p[i][0] + Rp[3 * r + 1] * m->p[i][1] + Rp[3 * r + 2] * m->p[i][2];
+        for (int r = 0; r < 3; r++)
+            for (int c2 = 0; c2 < 3; c2++) Rw[i][3 * r + c2] = Rp[3 * r] * R[c2] + Rp[3 * r + 1] * R[3 + c2] + Rp[3 * r + 2] * R[6 + c2];
+        std::memcpy(Rp, Rw[i], sizeof Rp); std::memcpy(pp, pw[i], sizeof pp);
+    }
+}
+
+extern "C" int mpcmp_clearance_config(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                                      const mpcmp_obstacle *obs, int self_gap, const double *q, double *d_min, int *sphere, int *other) {
+    if (!models || narm < 1 || narm > 2 || !n_spheres || !q || !d_min || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_obs > 0 && !obs) || self_gap < 0)
+        return MPCMP_EINVAL;
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
+    double cen[2 * CLR_MAX_SPH][3], rad[2 * CLR_MAX_SPH];
+    int arm[2 * CLR_MAX_SPH], jnt[2 * CLR_MAX_SPH];
+    for (int a = 0, s = 0; a < narm; a++) {
+        double Rw[7][9], pw[7][3];
+        fk_frames(models + a, q + 7 * a, Rw, pw);
+        for (int k = 0; k < n_spheres[a]; k++, s++) {
+            const mpcmp_sphere &S = spheres[s];
+            if (S.joint < 0 || S.joint > 6) return MPCMP_EINVAL;
+            const double *R = Rw[S.joint];
+            for (int r = 0; r < 3; r++) cen[s][r] = pw[S.joint][r] + R[3 * r] * S.c[0] + R[3 * r + 1] * S.c[1] + R[3 * r + 2] * S.c[2];
+            rad[s] = S.r; arm[s] = a; jnt[s] = S.joint;
+        }
+    }
+    double best = INFINITY;
+    unsigned bk = CLR_NO_PAIR;
+    for (int s = 0; s < nsph; s++) {
+        for (int o = 0; o < n_obs; o++) {
+            double k[8];
+            clr_obs_prepare(obs[o], k);
+            const double d = clr_sd(obs[o].type, k, cen[s][0], cen[s][1], cen[s][2]) - rad[s];
+            const unsigned key = clr_pack(0, s, 0, o);
+            if (clr_better(d, key, best, bk)) { best = d; bk = key; }
+        }
+        for (int t = s + 1; t < nsph; t++) {
+            if (!clr_pair(arm[s], jnt[s], arm[t], jnt[t], self_gap)) continue;
+            const double ex = cen[s][0] - cen[t][0], ey = cen[s][1] - cen[t][1], ez = cen[s][2] - cen[t][2];
+            const double d = std::sqrt(ex * ex + ey * ey + ez * ez) - rad[s] - rad[t];
+            const unsigned key = clr_pack(0, s, 1, t);
+            if (clr_better(d, key, best, bk)) { best = d; bk = key; }
+        }
+    }
+    *d_min = best;
+    const int idx = (int)(bk & 0xFFu);
+    if (sphere) *sphere = bk == CLR_NO_PAIR ? -1 : (int)((bk >> 9) & 0x7Fu);
+    if (other) *other = bk == CLR_NO_PAIR ? 0 : ((bk & 0x100u) ? -1 - idx : idx);
+    return MPCMP_OK;
+}

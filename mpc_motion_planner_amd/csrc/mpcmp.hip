@@ -29,6 +29,7 @@
 #include "ik_device.hpp"
 #include "payload.hpp"
 #include "time_sync.hpp"
+#include "clearance.hpp"
 
 #ifdef MPCMP_SPLIT_N25
 // the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
@@ -78,6 +79,21 @@ struct mpcmp_ctx {
     unsigned long long *d_sg_key = nullptr;
     double *d_sg_T = nullptr, *d_sg_rows = nullptr, *d_sg_Tn = nullptr, *d_sg_wx = nullptr, *d_sg_wu = nullptr, *d_sg_wT = nullptr;
     const int *sync_skip = nullptr;   // pass 2 being enqueued: problems that are not re-solved
+    // clearance checks (mpcmp_clearance_batch*): the sphere tables of the arms (host copies; d_clr_sph [128] holds them arm-major, allocated by
+    // mpcmp_create), the obstacle sets d_clr_obs [clr_sets][clr_nobs] (allocated and grown by mpcmp_set_obstacles*), the selection's scratch
+    // (keys / staging, [max_batch], allocated by its first call).  Read by no other entry point
+    mpcmp_sphere clr_sph[2][CLR_MAX_SPH];
+    int clr_nsph[2] = {0, 0};
+    ClrSphere *d_clr_sph = nullptr;
+    mpcmp_obstacle *d_clr_obs = nullptr;
+    size_t clr_obs_cap = 0;
+    int clr_sets = 0, clr_nobs = 0;
+    bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
+    unsigned long long *d_sel_key = nullptr;
+    int *d_sel_group = nullptr, *d_sel_chosen = nullptr;
+    mpcmp_clearance *d_sel_clr = nullptr;
+    double *d_sel_T = nullptr;
+    mpcmp_info *d_sel_info = nullptr;
     int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
     uint32_t *d_terms = nullptr;
     WS ws{};
@@ -782,6 +798,7 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
     ctx->debug_occ = std::getenv("MPCMP_DEBUG_OCC") != nullptr;
     if (const char *e = std::getenv("MPCMP_STREAMS")) ctx->parts_env = std::atoi(e);
     TRY(prepare_kernels(ctx));
+    TRY(dalloc(ctx, &ctx->d_clr_sph, 2 * CLR_MAX_SPH));
 #undef TRY
 #undef HIPTRY
     *out = ctx;
@@ -1792,6 +1809,192 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
     hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, st, md, ms, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 74 * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// clearance checks (clearance.hpp; the kernels are in clearance.hip)
+extern "C" int mpcmp_set_robot_spheres(mpcmp_ctx *ctx, int arm, int n, const mpcmp_sphere *sp) {
+    if (!ctx) { g_err = "mpcmp_set_robot_spheres: no context"; return MPCMP_EINVAL; }
+    if (arm < 0 || arm >= ctx->narm || n < 0 || n > CLR_MAX_SPH || (n > 0 && !sp)) {
+        ctx->err = "mpcmp_set_robot_spheres: arm must be in [0, narm) and n in [0, 64] with the spheres given"; return MPCMP_EINVAL;
+    }
+    for (int i = 0; i < n; i++) {
+        const mpcmp_sphere &s = sp[i];
+        if (s.joint < 0 || s.joint > 6 || !std::isfinite(s.c[0]) || !std::isfinite(s.c[1]) || !std::isfinite(s.c[2]) || !std::isfinite(s.r) || !(s.r > 0.0)) {
+            ctx->err = "mpcmp_set_robot_spheres: sphere " + std::to_string(i) + ": joint in 0..6, finite centre and r > 0 required"; return MPCMP_EINVAL;
+        }
+    }
+    int cnt[2] = {ctx->clr_nsph[0], ctx->clr_nsph[1]};
+    cnt[arm] = n;
+    ClrSphere tab[2 * CLR_MAX_SPH];
+    int k = 0;
+    for (int a = 0; a < ctx->narm; a++)
+        for (int i = 0; i < cnt[a]; i++, k++) {
+            const mpcmp_sphere &s = a == arm ? sp[i] : ctx->clr_sph[a][i];
+            tab[k].c[0] = s.c[0]; tab[k].c[1] = s.c[1]; tab[k].c[2] = s.c[2]; tab[k].r = s.r; tab[k].joint = s.joint; tab[k].arm = a;
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());          // (checks may be in flight on any stream of the caller: they read this table)
+    if (k > 0) HIPCHK(ctx, hipMemcpy(ctx->d_clr_sph, tab, sizeof(ClrSphere) * k, hipMemcpyHostToDevice));
+    for (int i = 0; i < n; i++) ctx->clr_sph[arm][i] = sp[i];
+    ctx->clr_nsph[arm] = n;
+    return MPCMP_OK;
+}
+
+static int obstacles_check(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *obs) {
+    if (!ctx) { g_err = "mpcmp_set_obstacles: no context"; return MPCMP_EINVAL; }
+    if (n_sets < 0 || n_sets > ctx->max_batch || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_sets > 0 && n_obs > 0 && !obs)) {
+        ctx->err = "mpcmp_set_obstacles: n_sets must be in [0, max_batch] and n_obs in [0, 256] with the obstacles given"; return MPCMP_EINVAL;
+    }
+    const size_t want = (size_t)n_sets * n_obs;
+    if (want > ctx->clr_obs_cap) {          // grow: later launches read the new buffer; wait for the ones that read the old one
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        void *q = nullptr;
+        HIPCHK(ctx, hipMalloc(&q, want * sizeof(mpcmp_obstacle)));
+        if (ctx->d_clr_obs) {
+            HIPCHK(ctx, hipDeviceSynchronize());
+            ctx->allocs.erase(std::find(ctx->allocs.begin(), ctx->allocs.end(), (void *)ctx->d_clr_obs));
+            (void)hipFree(ctx->d_clr_obs);
+        }
+        ctx->allocs.push_back(q); ctx->d_clr_obs = (mpcmp_obstacle *)q; ctx->clr_obs_cap = want;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_obstacles(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *obs) {
+    if (ctx && n_sets > 0 && n_sets <= ctx->max_batch && n_obs > 0 && n_obs <= CLR_MAX_OBS && obs)
+        for (size_t i = 0; i < (size_t)n_sets * n_obs; i++) {
+            const mpcmp_obstacle &o = obs[i];
+            bool ok = o.type >= MPCMP_OBS_SPHERE && o.type <= MPCMP_OBS_HALFSPACE && std::isfinite(o.r);
+            for (int d = 0; d < 3 && ok; d++) ok = std::isfinite(o.a[d]) && std::isfinite(o.b[d]);
+            if (ok && o.type != MPCMP_OBS_HALFSPACE) ok = o.r >= 0.0;
+            if (ok && o.type == MPCMP_OBS_BOX) ok = o.b[0] > 0.0 && o.b[1] > 0.0 && o.b[2] > 0.0;
+            if (ok && o.type == MPCMP_OBS_HALFSPACE) ok = std::fabs(std::sqrt(o.a[0] * o.a[0] + o.a[1] * o.a[1] + o.a[2] * o.a[2]) - 1.0) <= 1e-9;
+            if (!ok) {
+                ctx->err = "mpcmp_set_obstacles: set " + std::to_string(i / n_obs) + ", obstacle " + std::to_string(i % n_obs) +
+                           ": known type, finite values, r >= 0, box half extents > 0 and a unit half-space normal required";
+                return MPCMP_EINVAL;
+            }
+        }
+    if (int rc = obstacles_check(ctx, n_sets, n_obs, obs)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());          // (checks may be in flight on any stream of the caller: they read these sets)
+    if (n_sets > 0 && n_obs > 0) HIPCHK(ctx, hipMemcpy(ctx->d_clr_obs, obs, sizeof(mpcmp_obstacle) * n_sets * n_obs, hipMemcpyHostToDevice));
+    ctx->clr_sets = n_obs > 0 ? n_sets : 0; ctx->clr_nobs = n_sets > 0 ? n_obs : 0;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_obstacles_device(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *d_obs, void *hip_stream) {
+    if (int rc = obstacles_check(ctx, n_sets, n_obs, d_obs)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n_sets > 0 && n_obs > 0) {
+        // after the caller's work on its stream (which writes d_obs) and the context's own, before the context's later work; the caller's later
+        // work (a clearance check on that stream) waits for the copy
+        hipStream_t cs = (hipStream_t)hip_stream;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_clr_obs, d_obs, sizeof(mpcmp_obstacle) * n_sets * n_obs, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+    }
+    ctx->clr_sets = n_obs > 0 ? n_sets : 0; ctx->clr_nobs = n_sets > 0 ? n_obs : 0;
+    return MPCMP_OK;
+}
+
+static int clearance_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, int self_gap, const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_pts < 1 || n_pts > CLR_MAX_PTS || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0) {
+        ctx->err = "mpcmp_clearance_batch: B >= 1, 1 <= n_pts <= 4096, a finite margin, self_gap >= 0 and all pointers required"; return MPCMP_EINVAL;
+    }
+    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+static int clearance_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
+                             mpcmp_clearance *d_out, hipStream_t st) {
+    ClrTables t;
+    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
+    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
+    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    if (!ctx->clr_ready) { HIPCHK(ctx, clearance_prepare()); ctx->clr_ready = true; }
+    HIPCHK(ctx, clearance_launch(t, B, d_sx, d_sT, n_pts, margin, self_gap, d_out, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
+                                            mpcmp_clearance *d_out, void *hip_stream) {
+    if (int rc = clearance_check(ctx, B, d_sx, d_sT, n_pts, margin, self_gap, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return clearance_enqueue(ctx, B, d_sx, d_sT, n_pts, margin, self_gap, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_clearance_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, int self_gap,
+                                     mpcmp_clearance *out) {
+    if (int rc = clearance_check(ctx, B, sx, sT, n_pts, margin, self_gap, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nx = (size_t)ctx->nx * ctx->N * B;
+    TmpBuf tb(ctx, (nx + B) * sizeof(double) + sizeof(mpcmp_clearance) * (size_t)B);
+    double *dx = tb.get<double>(nx), *dT = tb.get<double>(B);
+    mpcmp_clearance *dout = tb.get<mpcmp_clearance>(B);
+    if (!dx || !dT || !dout) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    if (int rc = clearance_enqueue(ctx, B, dx, dT, n_pts, margin, self_gap, dout, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(mpcmp_clearance) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+static int select_check(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group, int n_groups,
+                        const int *chosen) {
+    if (!ctx) { g_err = "mpcmp_select_clear_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_groups < 0 || n_groups > ctx->max_batch || !sT || !info || !clr || !group || (n_groups > 0 && !chosen)) {
+        ctx->err = "mpcmp_select_clear_batch: B >= 1, n_groups in [0, max_batch] and all pointers required"; return MPCMP_EINVAL;
+    }
+    if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
+    if (!ctx->d_sel_key) {            // first use
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t M = ctx->max_batch;
+        if (int rc = dalloc(ctx, &ctx->d_sel_key, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_group, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_chosen, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_clr, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_T, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_info, M)) return rc;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
+                                               const int *d_group, int n_groups, int *d_chosen, void *hip_stream) {
+    if (int rc = select_check(ctx, B, d_sT, d_info, d_clr, d_group, n_groups, d_chosen)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, select_clear_launch(B, d_sT, d_info, d_clr, d_group, n_groups, ctx->d_sel_key, d_chosen, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
+                                        int n_groups, int *chosen) {
+    if (int rc = select_check(ctx, B, sT, info, clr, group, n_groups, chosen)) return rc;
+    for (int i = 0; i < B; i++)
+        if (group[i] < -1 || group[i] >= n_groups) {
+            ctx->err = "mpcmp_select_clear_batch: group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
+        }
+    if (n_groups == 0) return MPCMP_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_T, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_info, info, sizeof(mpcmp_info) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_clr, clr, sizeof(mpcmp_clearance) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, select_clear_launch(B, ctx->d_sel_T, ctx->d_sel_info, ctx->d_sel_clr, ctx->d_sel_group, n_groups, ctx->d_sel_key, ctx->d_sel_chosen, st));
+    HIPCHK(ctx, hipMemcpyAsync(chosen, ctx->d_sel_chosen, sizeof(int) * n_groups, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }

@@ -155,6 +155,62 @@ class Solver:
                                                     vp(group), int(n_groups), vp(sol_x), vp(sol_u), vp(sol_T), vp(info or None), vp(group_T or None),
                                                     vp(stream or None)), self._ctx)
 
+    # -- clearance checks: robot spheres against obstacles and against the other arm (include/mpcmp.h)
+    def set_robot_spheres(self, spheres, arm=0):
+        """sphere table of one arm: capi.SPHERE_DTYPE [n], n <= 64 (capi.link_spheres, capi.spheres); None or an empty table clears it"""
+        t = np.zeros(0, dtype=capi.SPHERE_DTYPE) if spheres is None else capi._records(spheres, capi.SPHERE_DTYPE, "sphere").reshape(-1)
+        check(lib().mpcmp_set_robot_spheres(self._ctx, int(arm), t.shape[0], t.ctypes.data if t.shape[0] else None), self._ctx)
+
+    def set_obstacles(self, obstacles):
+        """obstacles: capi.OBSTACLE_DTYPE [n_obs] (one world for every problem) or [n_sets][n_obs] (set i for problem i)"""
+        t = capi._records(obstacles, capi.OBSTACLE_DTYPE, "obstacle")
+        if t.ndim == 1:
+            t = t[None, :]
+        if t.ndim != 2:
+            raise ValueError("obstacles must be [n_obs] or [n_sets][n_obs], got %s" % (t.shape,))
+        check(lib().mpcmp_set_obstacles(self._ctx, t.shape[0], t.shape[1], t.ctypes.data if t.size else None), self._ctx)
+
+    def clear_obstacles(self):
+        check(lib().mpcmp_set_obstacles(self._ctx, 0, 0, None), self._ctx)
+
+    def set_obstacles_device(self, n_sets, n_obs, ptr, stream=0):
+        """[n_sets][n_obs] mpcmp_obstacle records (64 bytes each) at the device pointer ptr, ordered on `stream` (values not checked)"""
+        check(lib().mpcmp_set_obstacles_device(self._ctx, int(n_sets), int(n_obs), C.c_void_p(ptr or None), C.c_void_p(stream or None)), self._ctx)
+
+    def clearance(self, sx, sT, n_pts=200, margin=0.0, self_gap=0):
+        """mpcmp_clearance_batch: capi.CLEARANCE_DTYPE [B] for the trajectories sx [B][N][nx], sT [B] at n_pts + 1 uniform samples"""
+        sx, sT = f64(sx), f64(sT).reshape(-1); B = sT.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
+        out = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
+        check(lib().mpcmp_clearance_batch(self._ctx, B, sx.ctypes.data, sT.ctypes.data, int(n_pts), float(margin), int(self_gap), out.ctypes.data), self._ctx)
+        return out
+
+    def clearance_device(self, B, sol_x, sol_T, n_pts, margin, self_gap, out, stream=0):
+        vp = C.c_void_p
+        check(lib().mpcmp_clearance_batch_device(self._ctx, int(B), vp(sol_x), vp(sol_T), int(n_pts), float(margin), int(self_gap), vp(out),
+                                                 vp(stream or None)), self._ctx)
+
+    def select_clear(self, sT, info, clr, group, n_groups=None):
+        """mpcmp_select_clear_batch: per group the admissible member (clean solve status, clearance status 0) with the smallest final time,
+        ties to the lowest index, -1 if none.  n_groups defaults to max(group) + 1"""
+        sT = f64(sT).reshape(-1); B = sT.shape[0]
+        info = np.ascontiguousarray(info); clr = np.ascontiguousarray(clr)
+        group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if info.dtype != capi.INFO_DTYPE or clr.dtype != capi.CLEARANCE_DTYPE or info.shape != (B,) or clr.shape != (B,) or group.shape != (B,):
+            raise ValueError("info (INFO_DTYPE), clr (CLEARANCE_DTYPE) and group must be [B] = [%d]" % B)
+        if n_groups is None:
+            n_groups = max(int(group.max()) + 1, 0)
+        chosen = np.full(max(int(n_groups), 1), -1, dtype=np.int32)
+        check(lib().mpcmp_select_clear_batch(self._ctx, B, sT.ctypes.data, info.ctypes.data, clr.ctypes.data, group.ctypes.data, int(n_groups),
+                                             chosen.ctypes.data), self._ctx)
+        return chosen[:n_groups]
+
+    def select_clear_device(self, B, sol_T, info, clr, group, n_groups, chosen, stream=0):
+        vp = C.c_void_p
+        check(lib().mpcmp_select_clear_batch_device(self._ctx, int(B), vp(sol_T), vp(info), vp(clr), vp(group), int(n_groups), vp(chosen),
+                                                    vp(stream or None)), self._ctx)
+
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
         x0, xf = f64(x0), f64(xf)
@@ -470,6 +526,20 @@ class BatchMotionPlanner:
             self._solver.clear_time_windows()
             return
         self._twin = (f64(lbT).reshape(-1), f64(lbT if ubT is None else ubT).reshape(-1))
+
+    # extension beyond the reference's members: the world the plans run in (include/mpcmp.h, clearance)
+    def set_obstacles(self, obstacles, sphere_radius=0.06, sphere_spacing=0.08, spheres=None):
+        """obstacles: capi.OBSTACLE_DTYPE [n_obs] or [B][n_obs]; None removes them.  The robot is `spheres` (capi.SPHERE_DTYPE) or, by default,
+        the skeleton of capi.link_spheres(model, sphere_radius, sphere_spacing)"""
+        if obstacles is None:
+            self._solver.clear_obstacles()
+            return
+        self._solver.set_robot_spheres(capi.link_spheres(self.model, sphere_radius, sphere_spacing) if spheres is None else spheres)
+        self._solver.set_obstacles(obstacles)
+
+    def check_clearance(self, n_pts=200, margin=0.0, self_gap=0):
+        """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions"""
+        return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
 
     # motionPlanner.cpp:177-208
     def solve_trajectory(self, use_builtin_warm_start=True):
