@@ -200,6 +200,34 @@ int mpcmp_set_time_windows(mpcmp_ctx *ctx, int n, const double *lbT, const doubl
 /* the same from DEVICE memory, ordered on hip_stream after the work already on it and before later work of the context; not checked */
 int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double *d_lbT, const double *d_ubT, void *hip_stream);
 
+/* ---- per-problem bounds ----
+ * One row = the six bound tables of mpcmp_config, in the configuration's order (58 doubles, 464 bytes).  Row i applies to problem i of every later
+ * mpcmp_solve_batch[_device], mpcmp_solve_batch_synced[_device] (both passes), mpcmp_qp_batch and mpcmp_warm_start_batch: those calls read the row
+ * wherever they read the six tables of the configuration — the variable boxes, the path rows, the rho of a row or box (narrower than 1e-4 takes
+ * rho_eq, so a locked joint, lbx[j] == ubx[j], changes the factor as well as the projection), viol_l1, path_viol_inf, MPCMP_STATUS_OUTSIDE_TOL and
+ * the built-in initialiser's feasibility test (|qd| <= ubx[7 + j], |qdd| <= ubu[j]).  eps_target, the solver settings and [lbT, ubT] stay where
+ * they are (configuration, final-time rows).  In a two-arm context a row applies to every arm of its problem, as the configuration's tables do.
+ * mpcmp_pose_targets_batch[_device]: with rows set, rules 2, 3 and 5 (wrap, qualify, MPCMP_IK_QD_OUT_OF_BOUNDS) use problem i's position and velocity
+ * rows, so that a target generated for a problem lies inside the box the problem is then solved in.
+ * Not read by: the jerk-limited generators (the *_lim_* entry points take caller limits), the leaf calls, sampling, mpcmp_traj_stats_batch, the
+ * clearance checks.  The receding-horizon driver does not read the rows either (its start guess comes from the generator with limits by value, and
+ * a captured step holds kernel arguments): with rows set mpcmp_rh_init returns MPCMP_EINVAL, and after mpcmp_rh_init both setters do.
+ * A call with more problems than rows returns MPCMP_EINVAL and writes nothing.  n == 0 with rows == NULL clears the rows: outputs then are bit for
+ * bit those of a context that never set any.  The table (max_batch x 464 B) is allocated by the first setter call, never in a solve.
+ * mpcmp_set_bounds is synchronous and applies to every row the rule the configuration's tables obey (mpcmp_create, mpcmp_set_config): in every pair
+ * no NaN, lb <= ub, lb < +inf, ub > -inf; and for num_seg 1, 2, 4 a general row ubg - lbg >= 1e-4.  For a bad row, or n outside [1, max_batch]
+ * (other than the clear), it returns MPCMP_EINVAL, names the row and field in mpcmp_last_error, and changes nothing.  mpcmp_set_config keeps working
+ * with rows set: the rows win for the six tables. */
+typedef struct { double lbx[14], ubx[14], lbu[7], ubu[7], lbg[8], ubg[8]; } mpcmp_bounds;
+/* host helpers (no GPU needed): the configuration's six tables, bit for bit; and the tables of mpcmp_default_config + mpcmp_set_margins +
+ * mpcmp_set_min_height(min_height), bit for bit */
+int mpcmp_bounds_from_config(const mpcmp_config *c, mpcmp_bounds *out);
+int mpcmp_bounds_from_margins(double margin_position, double margin_velocity, double margin_acceleration, double margin_torque,
+                              double min_height, mpcmp_bounds *out);
+int mpcmp_set_bounds(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows);
+/* the same from DEVICE memory d_rows [n], ordered on hip_stream after the work already on it and before later work of the context; not checked */
+int mpcmp_set_bounds_device(mpcmp_ctx *ctx, int n, const mpcmp_bounds *d_rows, void *hip_stream);
+
 /* ---- time scaling of a trajectory ----
  * Collocation is in normalised time, so a solution stretched to T_new keeps its node positions.  Per problem b, exactly as the kernel computes it:
  *   s = sT[b] / T_new[b]                                   (one IEEE division)
@@ -322,7 +350,8 @@ int mpcmp_inverse_kinematics(const mpcmp_model *model, const double *R, const do
  * arm selects the context's model; info [B] may be NULL.  Rules:
  *   1. per start: the DLS loop of mpcmp_inverse_kinematics unchanged (eps 1e-4, IT_MAX 1000, DT 0.1, damp 1e-2, local-frame Jacobian);
  *   2. wrap: each joint j is shifted to q_j + 2 pi k with the integer k of smallest |k| that puts it into [lbx_j, ubx_j], k = 0 when none
- *      does; the bounds are the context configuration's margin-applied position rows (for two arms the per-arm rows apply to every arm);
+ *      does; the bounds are the context configuration's margin-applied position rows (for two arms the per-arm rows apply to every arm), or
+ *      problem i's row once mpcmp_set_bounds[_device] has set rows (B above their number: MPCMP_EINVAL);
  *   3. a start qualifies if it converged (err < 1e-4) and all 7 of its wrapped joints lie within the bounds;
  *   4. choice: if some start qualifies and q_ref is given, the qualifying start that minimises ||q - q_ref||_2 (wrapped q; ties to the
  *      lowest index); if some start qualifies and q_ref is NULL, the lowest qualifying index; if none qualifies, the smallest err (ties

@@ -64,6 +64,9 @@ OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE = 0, 1, 2, 3
 CLR_HIT, CLR_NAN = 1, 2
 MAX_SPHERES, MAX_OBSTACLES = 64, 256
 
+# one row of mpcmp_set_bounds[_device] (mpcmp_bounds, include/mpcmp.h): the six bound tables of Config, in its order
+BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7), ("ubu", "f8", 7), ("lbg", "f8", 8), ("ubg", "f8", 8)])
+
 # every symbol include/mpcmp.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_urdf", "mpcmp_default_limits", "mpcmp_default_config",
            "mpcmp_set_margins", "mpcmp_set_min_height", "mpcmp_num_nodes", "mpcmp_time_nodes", "mpcmp_version",
@@ -81,7 +84,8 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_set_time_windows", "mpcmp_set_time_windows_device", "mpcmp_time_scale_batch", "mpcmp_time_scale_batch_device",
            "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device",
            "mpcmp_link_spheres", "mpcmp_clearance_config", "mpcmp_set_robot_spheres", "mpcmp_set_obstacles", "mpcmp_set_obstacles_device",
-           "mpcmp_clearance_batch", "mpcmp_clearance_batch_device", "mpcmp_select_clear_batch", "mpcmp_select_clear_batch_device"]
+           "mpcmp_clearance_batch", "mpcmp_clearance_batch_device", "mpcmp_select_clear_batch", "mpcmp_select_clear_batch_device",
+           "mpcmp_bounds_from_config", "mpcmp_bounds_from_margins", "mpcmp_set_bounds", "mpcmp_set_bounds_device"]
 
 # prototypes of the final-time entry points (include/mpcmp.h): the argument kinds, "i" = int, "p" = pointer
 PROTOTYPES = {
@@ -103,6 +107,13 @@ CLEARANCE_PROTOTYPES = {
     "mpcmp_clearance_batch_device": "pippidipp",
     "mpcmp_select_clear_batch": "pippppip",
     "mpcmp_select_clear_batch_device": "pippppipp",
+}
+# prototypes of the per-problem bounds (kept apart from PROTOTYPES, whose entries are int / pointer only)
+BOUNDS_PROTOTYPES = {
+    "mpcmp_bounds_from_config": "pp",
+    "mpcmp_bounds_from_margins": "dddddp",
+    "mpcmp_set_bounds": "pip",
+    "mpcmp_set_bounds_device": "pipp",
 }
 _KINDS = {"i": C.c_int, "p": C.c_void_p, "d": C.c_double}
 
@@ -169,7 +180,7 @@ def lib():
         for name, kinds in PROTOTYPES.items():
             getattr(L, name).argtypes = [C.c_int if k == "i" else C.c_void_p for k in kinds]
             getattr(L, name).restype = C.c_int
-        for name, kinds in CLEARANCE_PROTOTYPES.items():
+        for name, kinds in list(CLEARANCE_PROTOTYPES.items()) + list(BOUNDS_PROTOTYPES.items()):
             getattr(L, name).argtypes = [_KINDS[k] for k in kinds]
             getattr(L, name).restype = C.c_int
         _lib = L
@@ -341,6 +352,21 @@ def default_config(num_seg=4, sqp_iters=20, margins=None, **kw):
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+def bounds_from_config(cfg):
+    """mpcmp_bounds_from_config: the six bound tables of a Config as one BOUNDS_DTYPE record (bit for bit)"""
+    out = np.zeros((), dtype=BOUNDS_DTYPE)
+    check(lib().mpcmp_bounds_from_config(C.addressof(cfg), out.ctypes.data))
+    return out
+
+
+def bounds_from_margins(margin_position=1.0, margin_velocity=1.0, margin_acceleration=1.0, margin_torque=1.0, min_height=0.05):
+    """mpcmp_bounds_from_margins: the tables of default_config + mpcmp_set_margins + mpcmp_set_min_height as one BOUNDS_DTYPE record"""
+    out = np.zeros((), dtype=BOUNDS_DTYPE)
+    check(lib().mpcmp_bounds_from_margins(float(margin_position), float(margin_velocity), float(margin_acceleration), float(margin_torque),
+                                          float(min_height), out.ctypes.data))
+    return out
 
 
 def num_nodes(num_seg):

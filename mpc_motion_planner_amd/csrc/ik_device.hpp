@@ -14,9 +14,9 @@
 
 namespace mpcmp {
 
-struct IkBounds { double lq[7], uq[7], lv[7], uv[7]; };   // margin-applied position and velocity rows of lbx / ubx (one arm)
+struct IkBounds { double lq[7], uq[7], lv[7], uv[7]; };   // margin-applied position and velocity rows of lbx / ubx (one arm); `rows` of the kernel overrides them per problem
 
-__global__ __launch_bounds__(256) void k_pose_targets(const mpcmp_model *__restrict__ model, IkBounds bd, int B, int S, int P, int nx, int col_q, int col_v,
+__global__ __launch_bounds__(256) void k_pose_targets(const mpcmp_model *__restrict__ model, IkBounds bd, const mpcmp_bounds *__restrict__ rows, int B, int S, int P, int nx, int col_q, int col_v,
                                                       const double *__restrict__ Rd, const double *__restrict__ pd, const double *__restrict__ twist,
                                                       const double *__restrict__ seeds, const double *__restrict__ q_ref, double *__restrict__ xf,
                                                       mpcmp_ik_info *__restrict__ info) {
@@ -35,10 +35,13 @@ __global__ __launch_bounds__(256) void k_pose_targets(const mpcmp_model *__restr
         for (;; it++)
             if (mpcmp_host::ik_dls_step(M, R, p, q, it, &en) != mpcmp_host::IK_STEPPED) break;
     // wrap into the position rows; qualification and the key of the choice
+    // (per-problem bounds, mpcmp_set_bounds: the problem's position and velocity rows instead of the configuration's, loaded where they are used:
+    //  a per-lane copy of the four tables would live in 56 more registers through the whole iteration)
     bool inb = true;
     for (int j = 0; j < 7; j++) {
-        q[j] = mpcmp_host::wrap_joint(q[j], bd.lq[j], bd.uq[j]);
-        inb = inb && q[j] >= bd.lq[j] && q[j] <= bd.uq[j];
+        const double lq = rows ? rows[b].lbx[j] : bd.lq[j], uq = rows ? rows[b].ubx[j] : bd.uq[j];
+        q[j] = mpcmp_host::wrap_joint(q[j], lq, uq);
+        inb = inb && q[j] >= lq && q[j] <= uq;
     }
     const bool conv = en < mpcmp_host::IK_EPS;
     int cls = !live ? 2 : (conv && inb ? 0 : 1);
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256) void k_pose_targets(const mpcmp_model *__restr
             for (int k = 0; k < 7; k++) qd[k] = NAN;
     }
     bool vin = true;
-    for (int j = 0; j < 7; j++) vin = vin && qd[j] >= bd.lv[j] && qd[j] <= bd.uv[j];
+    for (int j = 0; j < 7; j++) vin = vin && qd[j] >= (rows ? rows[b].lbx[7 + j] : bd.lv[j]) && qd[j] <= (rows ? rows[b].ubx[7 + j] : bd.uv[j]);
     if (!vin) status |= MPCMP_IK_QD_OUT_OF_BOUNDS;
     double *row = xf + (long)b * nx;
     for (int j = 0; j < 7; j++) { row[col_q + j] = q[j]; row[col_v + j] = qd[j]; }

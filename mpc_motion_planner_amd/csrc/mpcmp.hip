@@ -3,6 +3,7 @@
 // entry point fails with MPCMP_ENODEVICE.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +74,10 @@ struct mpcmp_ctx {
     double *d_tbox = nullptr;
     int tw_rows = 0;
     const double *tw_pass = nullptr;
+    // per-problem bounds (mpcmp_set_bounds): d_bnd [max_batch] rows of the six bound tables, allocated by the first setter call; bnd_rows = 0: the
+    // tables of cfg for every problem
+    mpcmp_bounds *d_bnd = nullptr;
+    int bnd_rows = 0;
     // the synchronised solve's buffers (mpcmp_solve_batch_synced*), [max_batch] each, allocated by its first call: group ids (host staging), group
     // keys, member counts and times, the pass-2 mask (WS::retired of pass 2), the pass-1 status words, rows, T_new and stretched start guess
     int *d_sg_group = nullptr, *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
@@ -163,6 +168,15 @@ static const double *run_rows(const mpcmp_ctx *ctx) {
     if (ctx->tw_pass) return ctx->tw_pass;
     return (ctx->tw_rows > 0 && !ctx->rh_step) ? ctx->d_tbox : nullptr;
 }
+// the bound rows a solve reads (WS::bnd): the caller's, or none (the tables of cfg; always none for the receding-horizon driver)
+static const mpcmp_bounds *run_bounds(const mpcmp_ctx *ctx) { return (ctx->bnd_rows > 0 && !ctx->rh_step) ? ctx->d_bnd : nullptr; }
+static int bound_rows_ok(mpcmp_ctx *ctx, int B) {
+    if (ctx->bnd_rows > 0 && B > ctx->bnd_rows) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than bound rows (" + std::to_string(ctx->bnd_rows) + "): see mpcmp_set_bounds";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
 static int time_rows_ok(mpcmp_ctx *ctx, int B) {
     if (ctx->tw_rows > 0 && B > ctx->tw_rows) {
         ctx->err = "more problems (" + std::to_string(B) + ") than final-time rows (" + std::to_string(ctx->tw_rows) + "): see mpcmp_set_time_windows";
@@ -251,6 +265,30 @@ extern "C" int mpcmp_default_config(mpcmp_config *c, int num_seg, int sqp_iters)
     c->rho = 0.02; c->sigma = 1e-6; c->alpha = 1.4; c->rho_eq_scale = 1e3;      // fitted to the reference's stored solve: tools/polympc_param_fit.py
     c->ls_eta = 0.25; c->ls_tau = 0.5; c->hess_reg = 1e-3; c->eps_target = 1e-2;
     return mpcmp_set_margins(c, 1.0, 1.0, 1.0, 1.0);              // motionPlanner.cpp:24
+}
+
+// per-problem bounds: a row is the six tables of the configuration, which lie there in the row's order without a gap
+static_assert(sizeof(mpcmp_bounds) == 58 * sizeof(double), "mpcmp_bounds: 58 doubles");
+static_assert(offsetof(mpcmp_config, ubg) + sizeof(double[8]) - offsetof(mpcmp_config, lbx) == sizeof(mpcmp_bounds) &&
+              offsetof(mpcmp_config, ubx) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubx) &&
+              offsetof(mpcmp_config, lbu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbu) &&
+              offsetof(mpcmp_config, ubu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubu) &&
+              offsetof(mpcmp_config, lbg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbg) &&
+              offsetof(mpcmp_config, ubg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubg),
+              "mpcmp_bounds has the layout of the six tables of mpcmp_config");
+extern "C" int mpcmp_bounds_from_config(const mpcmp_config *c, mpcmp_bounds *out) {
+    if (!c || !out) return MPCMP_EINVAL;
+    std::memcpy(out, c->lbx, sizeof *out);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_bounds_from_margins(double mp, double mv, double ma, double mt, double min_height, mpcmp_bounds *out) {
+    if (!out) return MPCMP_EINVAL;
+    mpcmp_config c;
+    if (int rc = mpcmp_default_config(&c, 4, 1)) return rc;      // (the tables do not depend on num_seg or sqp_iters)
+    if (int rc = mpcmp_set_margins(&c, mp, mv, ma, mt)) return rc;
+    if (int rc = mpcmp_set_min_height(&c, min_height)) return rc;
+    return mpcmp_bounds_from_config(&c, out);
 }
 
 static void rpy_to_R(const double rpy[3], double R[9]) {
@@ -586,6 +624,24 @@ static int dalloc(mpcmp_ctx *ctx, T **p, size_t count) {
     return MPCMP_OK;
 }
 
+// the rule of the six bound tables (of the configuration, and of every row of mpcmp_set_bounds): infinite ends are allowed (a row or box switched
+// off); NaN, lb > ub and an empty box (lb = +inf or ub = -inf) are not.  A general row narrower than 1e-4 takes rho_eq (oracle/ocp.c: u - l < 1e-4);
+// the assembly of k_qp and k_qp2 (num_seg 1, 2, 4) gives every general row the plain rho, so its factor would not be the matrix its iteration uses:
+// such rows are supported from num_seg 6 on (k_qp3, k_qp5)
+static int validate_boxes(const mpcmp_bounds *t, std::string &err) {
+    auto box_ok = [](double lb, double ub) { return lb <= ub && lb < INFINITY && ub > -INFINITY; };
+    for (int i = 0; i < 14; i++) if (!box_ok(t->lbx[i], t->ubx[i])) { err = "lbx[" + std::to_string(i) + "] <= ubx[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 7; i++) if (!box_ok(t->lbu[i], t->ubu[i])) { err = "lbu[" + std::to_string(i) + "] <= ubu[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 8; i++) if (!box_ok(t->lbg[i], t->ubg[i])) { err = "lbg[" + std::to_string(i) + "] <= ubg[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+static int validate_general_rows(const mpcmp_bounds *t, int num_seg, std::string &err) {
+    if (num_seg <= 4)
+        for (int i = 0; i < 8; i++)
+            if (t->ubg[i] - t->lbg[i] < 1e-4) { err = "num_seg 1, 2 and 4: ubg[" + std::to_string(i) + "] - lbg[" + std::to_string(i) + "] must be >= 1e-4 (narrower general rows need num_seg 6 or 8)"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
 static int validate(const mpcmp_config *c, std::string &err) {
     if (c->num_seg != 1 && c->num_seg != 2 && c->num_seg != 4 && c->num_seg != 6 && c->num_seg != 8) { err = "num_seg must be 1, 2, 4, 6 or 8 on the HIP backend"; return MPCMP_EINVAL; }
     if (c->sqp_iters < 1 || c->qp_iters < 1 || c->check_every < 1) { err = "iteration counts must be >= 1"; return MPCMP_EINVAL; }
@@ -597,17 +653,11 @@ static int validate(const mpcmp_config *c, std::string &err) {
     if (!(c->rho_eq_scale > 0)) { err = "rho_eq_scale must be > 0"; return MPCMP_EINVAL; }
     if (!(c->ls_eta > 0 && c->ls_eta < 1) || !(c->ls_tau > 0 && c->ls_tau < 1)) { err = "ls_eta and ls_tau must lie in (0, 1)"; return MPCMP_EINVAL; }
     if (c->quirk_dtau_dT != 0 && c->quirk_dtau_dT != 1) { err = "quirk_dtau_dT is 0 or 1"; return MPCMP_EINVAL; }
-    // bounds: infinite ends are allowed (a row or box switched off); NaN, lb > ub and an empty box (lb = +inf or ub = -inf) are not
-    auto box_ok = [](double lb, double ub) { return lb <= ub && lb < INFINITY && ub > -INFINITY; };
-    for (int i = 0; i < 14; i++) if (!box_ok(c->lbx[i], c->ubx[i])) { err = "lbx[" + std::to_string(i) + "] <= ubx[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    for (int i = 0; i < 7; i++) if (!box_ok(c->lbu[i], c->ubu[i])) { err = "lbu[" + std::to_string(i) + "] <= ubu[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    for (int i = 0; i < 8; i++) if (!box_ok(c->lbg[i], c->ubg[i])) { err = "lbg[" + std::to_string(i) + "] <= ubg[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    if (!box_ok(c->lbT, c->ubT)) { err = "lbT <= ubT required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    // A general row narrower than 1e-4 takes rho_eq (oracle/ocp.c: u - l < 1e-4).  The assembly of k_qp and k_qp2 (num_seg 1, 2, 4) gives every
-    // general row the plain rho, so its factor would not be the matrix its iteration uses: such rows are supported from num_seg 6 on (k_qp3, k_qp5)
-    if (c->num_seg <= 4)
-        for (int i = 0; i < 8; i++)
-            if (c->ubg[i] - c->lbg[i] < 1e-4) { err = "num_seg 1, 2 and 4: ubg[" + std::to_string(i) + "] - lbg[" + std::to_string(i) + "] must be >= 1e-4 (narrower general rows need num_seg 6 or 8)"; return MPCMP_EINVAL; }
+    mpcmp_bounds t;
+    mpcmp_bounds_from_config(c, &t);
+    if (int rc = validate_boxes(&t, err)) return rc;
+    if (!(c->lbT <= c->ubT && c->lbT < INFINITY && c->ubT > -INFINITY)) { err = "lbT <= ubT required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    if (int rc = validate_general_rows(&t, c->num_seg, err)) return rc;
     return MPCMP_OK;
 }
 
@@ -957,6 +1007,55 @@ extern "C" int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-problem bounds
+static int bounds_check(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows) {
+    if (!ctx) { g_err = "mpcmp_set_bounds: no context"; return MPCMP_EINVAL; }
+    if (ctx->rh_B > 0) { ctx->err = "mpcmp_set_bounds: the receding-horizon driver does not read bound rows (a loop is running)"; return MPCMP_EINVAL; }
+    if (n == 0 && !rows) return MPCMP_OK;
+    if (n < 1 || n > ctx->max_batch || !rows) { ctx->err = "mpcmp_set_bounds: n must be in [1, max_batch] with rows given (or 0 with NULL: clear)"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+static int bounds_alloc(mpcmp_ctx *ctx) {
+    if (ctx->d_bnd) return MPCMP_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return dalloc(ctx, &ctx->d_bnd, (size_t)ctx->max_batch);
+}
+
+extern "C" int mpcmp_set_bounds(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows) {
+    if (int rc = bounds_check(ctx, n, rows)) return rc;
+    for (int i = 0; i < n; i++) {
+        std::string why;
+        if (validate_boxes(rows + i, why) || validate_general_rows(rows + i, ctx->nseg, why)) { ctx->err = "mpcmp_set_bounds: row " + std::to_string(i) + ": " + why; return MPCMP_EINVAL; }
+    }
+    if (n > 0) {
+        if (int rc = bounds_alloc(ctx)) return rc;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_bnd, rows, sizeof(mpcmp_bounds) * n, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->bnd_rows = n;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_bounds_device(mpcmp_ctx *ctx, int n, const mpcmp_bounds *d_rows, void *hip_stream) {
+    if (int rc = bounds_check(ctx, n, d_rows)) return rc;
+    if (n > 0) {
+        if (int rc = bounds_alloc(ctx)) return rc;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        // after the caller's work on its stream (which writes the rows) and the context's own (solves that read the current rows), before the
+        // context's later work; the caller's later work waits for the reads
+        hipStream_t cs = (hipStream_t)hip_stream;
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_bnd, d_rows, sizeof(mpcmp_bounds) * n, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+    }
+    ctx->bnd_rows = n;
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launches
 template <typename K>
 static int set_lds(mpcmp_ctx *ctx, K kern, size_t bytes) {
@@ -1036,6 +1135,7 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
     w.model = run_models(ctx, &w.mstride);
     w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
     w.tbox = run_rows(ctx);
+    w.bnd = run_bounds(ctx);
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_init = InitLds<NSEG>::size * sizeof(double), l_qp = QpLds<S::N1>::size * sizeof(double),
                  l_step = StepLds<NSEG>::size * sizeof(double);
@@ -1070,6 +1170,7 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
         v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
         if (v.retired) v.retired += b0;
         if (v.tbox) v.tbox += 2 * b0;
+        if (v.bnd) v.bnd += b0;
         if (v.alt_x) { v.alt_x += 14 * D::N * b0; v.alt_u += 7 * D::N * b0; v.alt_T += b0; }
         wh[h] = v;
         if (d_wx) { hx[h] = d_wx + 14 * D::N * b0; hu[h] = d_wu + 7 * D::N * b0; hT[h] = d_wT + b0; }
@@ -1157,6 +1258,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
     w.model = run_models(ctx, &w.mstride);
     w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
     w.tbox = run_rows(ctx);
+    w.bnd = run_bounds(ctx);
     if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
     const size_t l_m = D::size * sizeof(double), l_qp3 = Qp3<NSEG>::sizeL * sizeof(double), l_qp3f = Qp3<NSEG>::sizeF * sizeof(double);
     // two parts on two streams once one part alone fills the chip (one CU per arm): see solve_impl
@@ -1179,6 +1281,7 @@ static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double 
         v.model += (size_t)v.mstride * b0;      // (see solve_impl)
         if (v.retired) v.retired += b0;
         if (v.tbox) v.tbox += 2 * b0;
+        if (v.bnd) v.bnd += b0;
         if (v.alt_x) { v.alt_x += (size_t)14 * NARM * N * b0; v.alt_u += (size_t)7 * NARM * N * b0; v.alt_T += b0; }
         wh[h] = v;
         xh[h].buf = ctx->xch.buf ? ctx->xch.buf + (size_t)2 * MPCMP_XCH_STRIDE * b0 : nullptr;
@@ -1217,6 +1320,7 @@ static int solve_dispatch(mpcmp_ctx *ctx, int B, const double *d_x0, const doubl
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (int rc = payload_rows_ok(ctx, B)) return rc;
     if (!ctx->rh_step) if (int rc = time_rows_ok(ctx, B)) return rc;
+    if (!ctx->rh_step) if (int rc = bound_rows_ok(ctx, B)) return rc;
     if (!d_x0 || !d_xf) return MPCMP_EINVAL;
     if ((d_wx != nullptr) != (d_wu != nullptr) || (d_wx != nullptr) != (d_wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1250,6 +1354,7 @@ extern "C" int mpcmp_solve_batch(mpcmp_ctx *ctx, int B, const double *x0, const 
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (int rc = payload_rows_ok(ctx, B)) return rc;
     if (int rc = time_rows_ok(ctx, B)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
@@ -1279,6 +1384,7 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     if (int rc = time_rows_ok(ctx, B)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, n = ctx->n;
     hipStream_t st = ctx->stream;
@@ -1286,7 +1392,7 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
     // k_init alone: the built-in initialiser writes the iterate z = [xs|us|T]
     const mpcmp_config save = run_config(ctx);
-    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx);
+    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx); w.bnd = run_bounds(ctx);
 #define LAUNCH_INIT(NS) { const size_t l = InitLds<NS>::size * sizeof(double); \
         hipLaunchKernelGGL(k_init<NS>, dim3(B), dim3(Dim<NS>::NT), l, st, save, w, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0); }
     switch (ctx->nseg) { case 1: LAUNCH_INIT(1) break; case 2: LAUNCH_INIT(2) break; case 4: LAUNCH_INIT(4) break; case 6: LAUNCH_INIT(6) break;
@@ -1377,6 +1483,7 @@ static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, c
     if ((wx != nullptr) != (wu != nullptr) || (wx != nullptr) != (wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
     if (int rc = payload_rows_ok(ctx, B)) return rc;
     if (int rc = time_rows_ok(ctx, B)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_sg_group) {            // first use
         const size_t M = ctx->max_batch, N = ctx->N;
@@ -1681,6 +1788,7 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     if (int rc = payload_rows_ok(ctx, B)) return rc;
     if (int rc = time_rows_ok(ctx, B)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N;
     hipStream_t st = ctx->stream;
@@ -2013,13 +2121,14 @@ static int pose_targets_check(mpcmp_ctx *ctx, int B, int arm, const double *R, c
 extern "C" int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_R, const double *d_p, const double *d_twist,
                                                int S, const double *d_seeds, const double *d_q_ref, double *d_xf, mpcmp_ik_info *d_info, void *hip_stream) {
     if (int rc = pose_targets_check(ctx, B, arm, d_R, d_p, S, d_seeds, d_xf)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     IkBounds bd;
     for (int j = 0; j < 7; j++) { bd.lq[j] = ctx->cfg.lbx[j]; bd.uq[j] = ctx->cfg.ubx[j]; bd.lv[j] = ctx->cfg.lbx[7 + j]; bd.uv[j] = ctx->cfg.ubx[7 + j]; }
     int P = 1;
     while (P < S) P <<= 1;
     const long threads = (long)B * P;
-    hipLaunchKernelGGL(k_pose_targets, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, ctx->d_model + arm, bd, B, S, P,
+    hipLaunchKernelGGL(k_pose_targets, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, ctx->d_model + arm, bd, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, B, S, P,
                        ctx->nx, 7 * arm, 7 * ctx->narm + 7 * arm, d_R, d_p, d_twist, d_seeds, d_q_ref, d_xf, d_info);
     HIPCHK(ctx, hipGetLastError());
     return MPCMP_OK;
@@ -2028,6 +2137,7 @@ extern "C" int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, c
 extern "C" int mpcmp_pose_targets_batch(mpcmp_ctx *ctx, int B, int arm, const double *R, const double *p, const double *twist,
                                         int S, const double *seeds, const double *q_ref, double *xf, mpcmp_ik_info *info) {
     if (int rc = pose_targets_check(ctx, B, arm, R, p, S, seeds, xf)) return rc;
+    if (int rc = bound_rows_ok(ctx, B)) return rc;
     const size_t nb = B, nx = ctx->nx;
     const struct { const double *v; size_t n; } in[5] = {{R, 9 * nb}, {p, 3 * nb}, {twist, 6 * nb}, {seeds, 7 * nb * S}, {q_ref, 7 * nb}};
     for (const auto &a : in)
@@ -2087,6 +2197,7 @@ extern "C" int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const doub
     if (!ctx || !x0 || !xf || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (ctx->bnd_rows > 0) { ctx->err = "mpcmp_rh_init: the receding-horizon driver does not read bound rows (clear them: mpcmp_set_bounds(ctx, 0, NULL))"; return MPCMP_EINVAL; }
     if (ctx->tw_rows > 0) { ctx->err = "mpcmp_rh_init: the receding-horizon driver does not read final-time rows (clear them: mpcmp_set_time_windows(ctx, 0, NULL, NULL))"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;

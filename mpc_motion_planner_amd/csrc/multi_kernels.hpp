@@ -20,7 +20,7 @@ struct DimM {
     // LDS (doubles): z | p | per-arm scratch (sin/cos N*14, raw N*147, trial sin/cos 9*N*14, trial violations 9*N) | x0/xf per arm | red
     static constexpr int oZ = 0, oP = oZ + n + 1, oScr = oP + n + 1;
     static constexpr int scr = N * 14 + N * 147;
-    static constexpr int oSct = oScr + scr, oPv = oSct + 9 * N * 14, oX0 = oPv + 9 * N, oRed = oX0 + 2 * 14 * NARM, size = oRed + NW * 12 + 8;
+    static constexpr int oSct = oScr + scr, oPv = oSct + 9 * N * 14, oX0 = oPv + 9 * N, oRed = oX0 + 2 * 14 * NARM, oBg = oRed + NW * 12 + 8, size = oBg + 16;
 };
 
 // index of component r in [0,14) of arm a in an external state vector [q(7 NARM); qd(7 NARM)]
@@ -29,16 +29,16 @@ __device__ __forceinline__ int ext_x(int a, int r) { return r < 7 ? 7 * a + r : 
 
 // variable box of arm variable v (external arm order) — motionPlanner.cpp:33,47,66-79
 template <int NSEG>
-__device__ __forceinline__ void arm_box(const mpcmp_config &c, const double *x0a, const double *xfa, int v, double &lo, double &hi) {
+__device__ __forceinline__ void arm_box(const mpcmp_config &c, const Bnd &bd, const double *x0a, const double *xfa, int v, double &lo, double &hi) {
     constexpr int N = 3 * NSEG + 1;
     if (v < 14 * N) {
         const int k = v / 14, r = v % 14;
         if (k == 0) { lo = hi = x0a[r]; }
         else if (k == N - 1) { lo = xfa[r] - c.eps_target; hi = xfa[r] + c.eps_target; }
-        else { lo = c.lbx[r]; hi = c.ubx[r]; }
+        else { lo = bd.lbx(r); hi = bd.ubx(r); }
     } else {
         const int r = (v - 14 * N) % 7;
-        lo = c.lbu[r]; hi = c.ubu[r];
+        lo = bd.lbu(r); hi = bd.ubu(r);
     }
 }
 
@@ -179,6 +179,7 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
         // stand-in for the warm start when none is given: per-joint quintic, zero boundary accelerations, common duration on a
         // geometric grid (same rule as k_init / the oracle's orc_warm_start, over all 7 NARM joints; per-problem windows as in k_init)
         const TWin tw = t_window(cfg, ws.tbox, b);
+        const Bnd bd = bounds_of(cfg, ws.bnd, b);     // (the problem's row applies to every arm)
         double T = 0.05;
         double *coef = scr;   // [7 NARM][6]
         constexpr int NJ = 7 * NARM;
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(512) void k_init_m(mpcmp_config cfg, const mpcmp_mo
                 const double tt = T * s / 64.0;
                 const double vv = c[1] + tt * (2 * c[2] + tt * (3 * c[3] + tt * (4 * c[4] + tt * 5 * c[5])));
                 const double aa = 2 * c[2] + tt * (6 * c[3] + tt * (12 * c[4] + tt * 20 * c[5]));
-                if (fabs(vv) > cfg.ubx[7 + j] || fabs(aa) > cfg.ubu[j]) bad = 1;
+                if (fabs(vv) > bd.ubx(7 + j) || fabs(aa) > bd.ubu(j)) bad = 1;
             }
             const int anybad = __syncthreads_or(bad);
             if (!anybad || T * 1.05 > tw.hi) break;
@@ -274,14 +275,17 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
     for (int i = tid; i < D::mn; i += NT) r2[0] = fmax(r2[0], fabs(lam[i]));
     reduce_m<NT, 1, true>(r2, red, tid);      // (also publishes zl / pl / xa)
     const double mu = r2[0];
+    const Bnd bd = bounds_of(cfg, ws.bnd, b);         // (the problem's row applies to every arm)
+    double *pbl = lds + D::oBg;                       // lbg | ubg in LDS for the trial evaluations (see k_step); published by the next reduction
+    if (tid < 16) pbl[tid] = tid < 8 ? bd.lbg(tid) : bd.ubg(tid - 8);
     auto box_of = [&](int v, double &lo, double &hi) {
         if (v == n - 1) { const TWin tw = t_window(cfg, ws.tbox, b); lo = tw.lo; hi = tw.hi; }
-        else { const int a = v / na; arm_box<NSEG>(cfg, xa + 14 * a, xa + 14 * (NARM + a), v % na, lo, hi); }
+        else { const int a = v / na; arm_box<NSEG>(cfg, bd, xa + 14 * a, xa + 14 * (NARM + a), v % na, lo, hi); }
     };
     // l1 violation at the current iterate (:79)
     double c0[1] = {0.0};
     for (int i = tid; i < NARM * meq; i += NT) c0[0] += fabs(ws.ceq[(size_t)b * NARM * meq + i]);
-    for (int i = tid; i < NARM * 8 * N; i += NT) c0[0] += viol(ws.g[(size_t)b * NARM * 8 * N + i], cfg.lbg[i % 8], cfg.ubg[i % 8]);
+    for (int i = tid; i < NARM * 8 * N; i += NT) c0[0] += viol(ws.g[(size_t)b * NARM * 8 * N + i], bd.lbg(i % 8), bd.ubg(i % 8));
     for (int v = tid; v < n; v += NT) { double lo, hi; box_of(v, lo, hi); c0[0] += viol(zl[v], lo, hi); }
     reduce_m<NT, 1, false>(c0, red, tid);
     const double constr = c0[0];
@@ -322,9 +326,9 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
             rnea_dir<false>(mdl, sct + 14 * t, v, ac, 0, 0, tau, nullptr);
             V3 ptool;
             fk_tool(mdl, sct + 14 * t, &ptool, nullptr, nullptr, nullptr);
-            double s = viol(ptool.z, cfg.lbg[7], cfg.ubg[7]);
+            double s = viol(ptool.z, pbl[7], pbl[15]);
 #pragma unroll
-            for (int j = 0; j < 7; j++) s += viol(tau[j], cfg.lbg[j], cfg.ubg[j]);
+            for (int j = 0; j < 7; j++) s += viol(tau[j], pbl[j], pbl[8 + j]);
             pv[t] = s;
         }
         __syncthreads();
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
         double s1[1] = {0.0}, mxs[3] = {0, 0, 0};
         int bad = 0;
         for (int i = tid; i < NARM * meq; i += NT) { const double c = ceqo[i]; s1[0] += fabs(c); mxs[0] = fmax(mxs[0], fabs(c)); }
-        for (int i = tid; i < NARM * 8 * N; i += NT) { const double vv = viol(gout[i], cfg.lbg[i % 8], cfg.ubg[i % 8]); s1[0] += vv; mxs[1] = fmax(mxs[1], vv); }
+        for (int i = tid; i < NARM * 8 * N; i += NT) { const double vv = viol(gout[i], bd.lbg(i % 8), bd.ubg(i % 8)); s1[0] += vv; mxs[1] = fmax(mxs[1], vv); }
         for (int v = tid; v < n; v += NT) { double lo, hi; box_of(v, lo, hi); s1[0] += viol(zl[v], lo, hi); if (!isfinite(zl[v])) bad = 1; }
         if (tid < 14 * NARM) { const int a = tid / 14, r = tid % 14; mxs[2] = fabs(zl[a * na + 14 * (N - 1) + r] - xa[14 * (NARM + a) + r]); }
         reduce_m<NT, 1, false>(s1, red, tid);

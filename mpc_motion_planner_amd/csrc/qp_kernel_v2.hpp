@@ -510,7 +510,8 @@ __device__ __forceinline__ void qp2_role_a2(const Qp2Ctx<NSEG> &c) {
         const int q = 2 * prp + pq;
         myrow = meq + 8 * pk + q;
         const double gv = c.ws.g[(size_t)b * 8 * N + 8 * pk + q];
-        const double lg = cfg.lbg[q] - gv, ug = cfg.ubg[q] - gv;
+        const Bnd bd = bounds_of(cfg, c.ws.bnd, b);
+        const double lg = bd.lbg(q) - gv, ug = bd.ubg(q) - gv;
         pcl[0] = lg; pcl[L::NA2] = ug;
         pcl[2 * L::NA2] = (ug - lg < 1e-4) ? c.rho_eq : c.rho_in;
         pcl[3 * L::NA2] = c.ws.Gk[((size_t)b * N + pk) * 176 + q * 22 + 21];
@@ -708,7 +709,7 @@ __device__ __forceinline__ VarRole make_var_role(const mpcmp_config &cfg, const 
         vr.rpos = ipos < nJ ? L::oRhsJ + 56 * (ipos / 49) + ipos % 49
                             : ((ia >= 14 * (NSEG + 1) && ia < D::nI - 1) ? L::oRI + ia : L::oRhsI + ia);
         double lo, hi;
-        var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
+        var_box<NSEG>(cfg, bounds_of(cfg, ws.bnd, b), t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
         vr.rb = (hi - lo < 1e-4) ? rho_eq : rho_in;
         const double zv = zg_[v];
         vr.lb = lo - zv; vr.ub = hi - zv;

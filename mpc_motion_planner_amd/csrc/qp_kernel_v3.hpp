@@ -357,7 +357,9 @@ __device__ __forceinline__ int q3_logical_tid() {
     if (tid < 32) cD[tid] = tid < 16 ? c_D[tid] : 0.0; \
     if (tid < 32) misc[tid] = tid == L::M_mtsT ? -tsT : 0.0; \
     double *cfl = lds + L::oCfg; \
-    if (tid < 14) { cfl[tid] = cfg.lbx[tid]; cfl[14 + tid] = cfg.ubx[tid]; } \
+    /* (per-problem rows, WS::bnd: the row has the layout of cfl, so one load per lane stages it; everything downstream reads LDS) */ \
+    if (ws.bnd != nullptr) { if (tid < 58) cfl[tid] = bounds_of(cfg, ws.bnd, b).r[tid]; } \
+    else if (tid < 14) { cfl[tid] = cfg.lbx[tid]; cfl[14 + tid] = cfg.ubx[tid]; } \
     else if (tid < 21) { cfl[28 + tid - 14] = cfg.lbu[tid - 14]; cfl[35 + tid - 14] = cfg.ubu[tid - 14]; } \
     else if (tid < 29) { cfl[42 + tid - 21] = cfg.lbg[tid - 21]; cfl[50 + tid - 21] = cfg.ubg[tid - 21]; } \
     { \

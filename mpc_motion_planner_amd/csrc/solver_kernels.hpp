@@ -49,6 +49,8 @@ struct WS {
                               // (mpcmp_set_payloads): problem b of the launch, arm a reads model + b * mstride + a
     const double *tbox;       // [B][2] or null: final-time window (lbT, ubT) of problem b (mpcmp_set_time_windows, the second pass of a synchronised
                               // solve); null = cfg.lbT / cfg.ubT for every problem.  Indexed by the problem (after perm), offset by a part's b0 like retired
+    const mpcmp_bounds *bnd;  // [B] or null: the six bound tables of problem b (mpcmp_set_bounds); null = the configuration's for every problem.  Indexed
+                              // and offset like tbox
 };
 // a retired instance of the receding-horizon loop: the whole workgroup leaves (uniform)
 #define MPCMP_RETIRED(ws_, b_) ((ws_).retired != nullptr && (ws_).retired[b_] != 0)
@@ -135,6 +137,32 @@ __device__ __forceinline__ TWin t_window_lane(const mpcmp_config &cfg, const dou
     if (tbox != nullptr) { const gdouble_ptr r = (gdouble_ptr)(tbox + 2 * b); w.lo = r[0]; w.hi = r[1]; }
     return w;
 }
+// bound tables of problem b: its row of WS::bnd as 58 doubles in the order of mpcmp_bounds (= the order of the six tables in mpcmp_config), or the
+// configuration's.  As for the window, the row's address goes through readfirstlane (a scalar base: no address registers per lane in kernels at the
+// edge of their register file) and the row is read through a global-address-space pointer (see t_window); an entry is loaded where it is used, by
+// the lanes that use it, in a prologue or a final report, never inside an ADMM loop.  Without rows no load is issued: the configuration is read
+// exactly as before
+#define MPCMP_BND_UBX 14
+#define MPCMP_BND_LBU 28
+#define MPCMP_BND_UBU 35
+#define MPCMP_BND_LBG 42
+#define MPCMP_BND_UBG 50
+struct Bnd {
+    const mpcmp_config &c;
+    gdouble_ptr r;      // the row, or null
+    __device__ __forceinline__ double lbx(int i) const { return r ? r[i] : c.lbx[i]; }
+    __device__ __forceinline__ double ubx(int i) const { return r ? r[MPCMP_BND_UBX + i] : c.ubx[i]; }
+    __device__ __forceinline__ double lbu(int i) const { return r ? r[MPCMP_BND_LBU + i] : c.lbu[i]; }
+    __device__ __forceinline__ double ubu(int i) const { return r ? r[MPCMP_BND_UBU + i] : c.ubu[i]; }
+    __device__ __forceinline__ double lbg(int i) const { return r ? r[MPCMP_BND_LBG + i] : c.lbg[i]; }
+    __device__ __forceinline__ double ubg(int i) const { return r ? r[MPCMP_BND_UBG + i] : c.ubg[i]; }
+};
+__device__ __forceinline__ Bnd bounds_of(const mpcmp_config &cfg, const mpcmp_bounds *bnd, int b) {
+    if (bnd == nullptr) return {cfg, (gdouble_ptr)0};
+    const unsigned long long a = (unsigned long long)(bnd + (size_t)b);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return {cfg, (gdouble_ptr)(((unsigned long long)hi << 32) | lo)};
+}
 // status word and capped-QP count of the result record (include/mpcmp.h: MPCMP_STATUS_*; the oracle's orc_solve_multi does the same); tw: the
 // problem's final-time window
 __device__ __forceinline__ void report_status(const mpcmp_config &cfg, TWin tw, int st, int anybad, mpcmp_info &o) {
@@ -146,19 +174,19 @@ __device__ __forceinline__ void report_status(const mpcmp_config &cfg, TWin tw, 
     o.status = s;
 }
 
-// variable box of external variable v (motionPlanner.cpp:33,47,66-79); tw: the problem's final-time window (t_window)
+// variable box of external variable v (motionPlanner.cpp:33,47,66-79); tw: the problem's final-time window (t_window), bd: its bound tables (bounds_of)
 template <int NSEG>
-__device__ __forceinline__ void var_box(const mpcmp_config &c, TWin tw, const double *x0, const double *xf, int v, double &lo,
+__device__ __forceinline__ void var_box(const mpcmp_config &c, const Bnd &bd, TWin tw, const double *x0, const double *xf, int v, double &lo,
                                         double &hi) {
     using D = Dim<NSEG>;
     if (v < 14 * D::N) {
         const int k = v / 14, r = v % 14;
         if (k == 0) { lo = hi = x0[r]; }
         else if (k == D::N - 1) { lo = xf[r] - c.eps_target; hi = xf[r] + c.eps_target; }
-        else { lo = c.lbx[r]; hi = c.ubx[r]; }
+        else { lo = bd.lbx(r); hi = bd.ubx(r); }
     } else if (v < 21 * D::N) {
         const int r = (v - 14 * D::N) % 7;
-        lo = c.lbu[r]; hi = c.ubu[r];
+        lo = bd.lbu(r); hi = bd.ubu(r);
     } else { lo = tw.lo; hi = tw.hi; }
 }
 
@@ -314,7 +342,9 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
     } else {
         // stand-in for Ruckig: per-joint quintic, zero boundary accelerations, common duration on a geometric grid up to ubT.  With per-problem
         // windows (WS::tbox) the grid stops at the row's ubT and a duration below the row's lbT is raised to it; without them cfg.lbT is not read
+        // the feasibility test reads the problem's velocity and acceleration rows (WS::bnd) where it read the configuration's
         const TWin tw = t_window(cfg, ws.tbox, b);
+        const Bnd bd = bounds_of(cfg, ws.bnd, b);
         double T = 0.05;
         double *coef = scr;   // [7][6]
         for (int it = 0; it < 200; it++) {
@@ -335,7 +365,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_init(mpcmp_config cfg, WS ws,
                 const double tt = T * s / 64.0;
                 const double vv = c[1] + tt * (2 * c[2] + tt * (3 * c[3] + tt * (4 * c[4] + tt * 5 * c[5])));
                 const double aa = 2 * c[2] + tt * (6 * c[3] + tt * (12 * c[4] + tt * 20 * c[5]));
-                if (fabs(vv) > cfg.ubx[7 + j] || fabs(aa) > cfg.ubu[j]) bad = 1;
+                if (fabs(vv) > bd.ubx(7 + j) || fabs(aa) > bd.ubu(j)) bad = 1;
             }
             const int anybad = __syncthreads_or(bad);
             if (!anybad || T * 1.05 > tw.hi) break;
@@ -433,7 +463,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_qp(mpcmp_config cfg, WS ws) {
         const int v = tid;
         ipos = int_of_ext(NSEG, v);
         double lo, hi;
-        var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
+        var_box<NSEG>(cfg, bounds_of(cfg, ws.bnd, b), t_window(cfg, ws.tbox, b), ws.x0 + 14 * b, ws.xf + 14 * b, v, lo, hi);
         rb = (hi - lo < 1e-4) ? rho_eq : rho_in;
         const double zv = zg_[v];
         lb = lo - zv; ub = hi - zv;
@@ -500,7 +530,8 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_qp(mpcmp_config cfg, WS ws) {
             grow_off = (k * 8 + q) * L::GS;
             coefT = Gkg[(k * 8 + q) * 22 + 21];
             const double gv = ws.g[(size_t)b * 8 * N + 8 * k + q];
-            lg = cfg.lbg[q] - gv; ug = cfg.ubg[q] - gv;
+            const Bnd bd = bounds_of(cfg, ws.bnd, b);
+            lg = bd.lbg(q) - gv; ug = bd.ubg(q) - gv;
             rr_ = (ug - lg < 1e-4) ? rho_eq : rho_in;
         }
     }
@@ -828,7 +859,7 @@ template <int NSEG>
 struct StepLds {
     using D = Dim<NSEG>;
     static constexpr int oZ = 0, oP = oZ + D::n, oPv = oP + D::n, oScr = oPv + 9 * D::N * 1,
-                         oRed = oScr + LinLds<NSEG>::size + 9 * D::N * 14, size = oRed + D::NW * 12;
+                         oRed = oScr + LinLds<NSEG>::size + 9 * D::N * 14, oBg = oRed + D::NW * 12, size = oBg + 16;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -906,10 +937,15 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
     const double mu = r2[0];
     const bool isVar = tid < n, isDyn = tid < meq;
     double lo = 0, hi = 0;
-    if (isVar) var_box<NSEG>(cfg, t_window(cfg, ws.tbox, b), x0, xf, tid, lo, hi);
+    const Bnd bd = bounds_of(cfg, ws.bnd, b);
+    // the path bounds lbg | ubg of the problem, in LDS for the trial evaluations below (published by the next reduction).  Read there from the row
+    // or the configuration directly, the sixteen values are live across the recursion: 416 B more scratch per lane and 480 more v_readlane_b32
+    double *pbl = lds + L::oBg;
+    if (tid < 16) pbl[tid] = tid < 8 ? bd.lbg(tid) : bd.ubg(tid - 8);
+    if (isVar) var_box<NSEG>(cfg, bd, t_window(cfg, ws.tbox, b), x0, xf, tid, lo, hi);
     double c0[1] = {0.0};
     if (isDyn) c0[0] += fabs(ws.ceq[(size_t)b * meq + tid]);
-    if (tid < 8 * N) c0[0] += viol(ws.g[(size_t)b * 8 * N + tid], cfg.lbg[tid % 8], cfg.ubg[tid % 8]);
+    if (tid < 8 * N) c0[0] += viol(ws.g[(size_t)b * 8 * N + tid], bd.lbg(tid % 8), bd.ubg(tid % 8));
     if (isVar) c0[0] += viol(zl[tid], lo, hi);
     block_reduce<D::NW, 1, false>(c0, red, tid);
     KSTAMP(0);
@@ -946,9 +982,9 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
         rnea_dir<false, false, true>(mdl, sct + 14 * t, v, a, 0, 0, tau, nullptr);
         V3 ptool;
         fk_tool(mdl, sct + 14 * t, &ptool, nullptr, nullptr, nullptr);
-        double s = viol(ptool.z, cfg.lbg[7], cfg.ubg[7]);
+        double s = viol(ptool.z, pbl[7], pbl[15]);
 #pragma unroll
-        for (int j = 0; j < 7; j++) s += viol(tau[j], cfg.lbg[j], cfg.ubg[j]);
+        for (int j = 0; j < 7; j++) s += viol(tau[j], pbl[j], pbl[8 + j]);
         pv[t] = s;
     }
     __syncthreads();
@@ -1007,7 +1043,7 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
         double s1[1] = {0.0}, mxs[3] = {0, 0, 0};
         int bad = 0;
         if (isDyn) { const double c = ceqo[tid]; s1[0] += fabs(c); mxs[0] = fabs(c); }
-        if (tid < 8 * N) { const double vv = viol(gout[tid], cfg.lbg[tid % 8], cfg.ubg[tid % 8]); s1[0] += vv; mxs[1] = vv; }
+        if (tid < 8 * N) { const double vv = viol(gout[tid], bd.lbg(tid % 8), bd.ubg(tid % 8)); s1[0] += vv; mxs[1] = vv; }
         if (isVar) { s1[0] += viol(zl[tid], lo, hi); if (!isfinite(zl[tid])) bad = 1; }
         if (tid < 14) mxs[2] = fabs(zl[14 * (N - 1) + tid] - xf[tid]);
         block_reduce<D::NW, 1, false>(s1, red, tid);

@@ -112,6 +112,55 @@ class Solver:
         check(lib().mpcmp_set_time_windows_device(self._ctx, int(n), vp(p_lb or None), vp(p_ub or None), vp(stream or None)), self._ctx)
         self.time_window_rows = int(n)
 
+    # -- per-problem bounds (include/mpcmp.h, mpcmp_set_bounds)
+    def bounds_table(self, n=None, margins=None, min_height=None, **tables):
+        """[n] BOUNDS_DTYPE records.  Start: every row = this solver's configuration; with margins [n, 4] or [4] (position, velocity, acceleration,
+        torque) row i = mpcmp_bounds_from_margins(*margins[i], min_height[i]) (min_height [n] or a scalar, default 0.05).  Then min_height
+        without margins overwrites lbg[7], and explicit tables lbx / ubx [n, 14] or [14], lbu / ubu [.., 7], lbg / ubg [.., 8] overwrite theirs.
+        Everything broadcasts along n; n defaults to the longest leading dimension given."""
+        unknown = set(tables) - set(capi.BOUNDS_DTYPE.names)
+        if unknown:
+            raise ValueError("unknown bound tables %s" % sorted(unknown))
+        lead = [f64(margins).shape[0]] if margins is not None and f64(margins).ndim == 2 else []
+        lead += [f64(min_height).shape[0]] if min_height is not None and f64(min_height).ndim == 1 else []
+        lead += [f64(v).shape[0] for v in tables.values() if f64(v).ndim == 2]
+        if n is None:
+            n = max(lead) if lead else 1
+        n = int(n)
+        if n < 1 or any(k not in (1, n) for k in lead):
+            raise ValueError("bounds_table: leading dimensions %s do not broadcast to n = %d" % (lead, n))
+        t = np.zeros(n, dtype=capi.BOUNDS_DTYPE)
+        if margins is not None:
+            mg = np.broadcast_to(f64(margins), (n, 4))
+            hs = np.broadcast_to(f64(0.05 if min_height is None else min_height), (n,))
+            for i in range(n):
+                t[i] = capi.bounds_from_margins(mg[i, 0], mg[i, 1], mg[i, 2], mg[i, 3], hs[i])
+        else:
+            t[:] = capi.bounds_from_config(self.cfg)
+            if min_height is not None:
+                t["lbg"][:, 7] = np.broadcast_to(f64(min_height), (n,))
+        for name, v in tables.items():
+            t[name] = np.broadcast_to(f64(v), t[name].shape)
+        return t
+
+    def set_bounds(self, rows):
+        """row i (BOUNDS_DTYPE, see bounds_table) applies to problem i of every later solve, solve_synced, qp, warm_start and pose_targets"""
+        rows = np.ascontiguousarray(rows).reshape(-1)
+        if rows.dtype != capi.BOUNDS_DTYPE:
+            raise ValueError("rows must be an array of BOUNDS_DTYPE records")
+        check(lib().mpcmp_set_bounds(self._ctx, rows.shape[0], rows.ctypes.data), self._ctx)
+        self.bound_rows = rows.shape[0]
+
+    def clear_bounds(self):
+        """back to the configuration's tables for every problem"""
+        check(lib().mpcmp_set_bounds(self._ctx, 0, None), self._ctx)
+        self.bound_rows = 0
+
+    def set_bounds_device(self, n, ptr, stream=0):
+        """n mpcmp_bounds records (464 bytes each) at the device pointer ptr, ordered on `stream` (values not checked)"""
+        check(lib().mpcmp_set_bounds_device(self._ctx, int(n), ptr or None, stream or None), self._ctx)
+        self.bound_rows = int(n)
+
     def time_scale(self, x0, xf, sx, su, sT, T_new):
         """trajectories stretched to T_new, end nodes pinned to x0 / xf (mpcmp_time_scale_batch): (ox, ou, oT)"""
         x0, xf = self._states(x0, xf)
