@@ -69,11 +69,9 @@ struct mpcmp_ctx {
     mpcmp_model *d_pmodel = nullptr;
     mpcmp_payload *d_pay = nullptr;
     int pay_rows = 0;
-    // per-problem final-time windows (mpcmp_set_time_windows): d_tbox [max_batch][2] = (lbT, ubT), allocated by the first call; tw_rows = 0: cfg.lbT / ubT.
-    // tw_pass: rows of the solve being enqueued that override them (the second pass of a synchronised solve), null otherwise
+    // per-problem final-time windows (mpcmp_set_time_windows): d_tbox [max_batch][2] = (lbT, ubT), allocated by the first call; tw_rows = 0: cfg.lbT / ubT
     double *d_tbox = nullptr;
     int tw_rows = 0;
-    const double *tw_pass = nullptr;
     // per-problem bounds (mpcmp_set_bounds): d_bnd [max_batch] rows of the six bound tables, allocated by the first setter call; bnd_rows = 0: the
     // tables of cfg for every problem
     mpcmp_bounds *d_bnd = nullptr;
@@ -83,7 +81,6 @@ struct mpcmp_ctx {
     int *d_sg_group = nullptr, *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
     unsigned long long *d_sg_key = nullptr;
     double *d_sg_T = nullptr, *d_sg_rows = nullptr, *d_sg_Tn = nullptr, *d_sg_wx = nullptr, *d_sg_wu = nullptr, *d_sg_wT = nullptr;
-    const int *sync_skip = nullptr;   // pass 2 being enqueued: problems that are not re-solved
     // clearance checks (mpcmp_clearance_batch*): the sphere tables of the arms (host copies; d_clr_sph [128] holds them arm-major, allocated by
     // mpcmp_create), the obstacle sets d_clr_obs [clr_sets][clr_nobs] (allocated and grown by mpcmp_set_obstacles*), the selection's scratch
     // (keys / staging, [max_batch], allocated by its first call).  Read by no other entry point
@@ -124,13 +121,13 @@ struct mpcmp_ctx {
     std::vector<EvPair> ev;          // at most MAX_EV pairs are ever created; launches beyond that are not timed until the
     size_t ev_used = 0;              // pairs have been folded by mpcmp_kernel_timing
     static constexpr size_t MAX_EV = 4096;
+    const char *loop_kernel = "";    // its name: KSel::loop_kernel_name, set with the kernels' LDS limits (prepare_kernels)
     double qp_ms = 0.0;
     int qp_launches = 0;
     bool timing = false;             // off until mpcmp_kernel_timing is first called: a plain solve records no events
     // growable device scratch of the host-buffer leaf entry points (no hipMalloc per call once it is large enough)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
-    bool capturing = false;
     // receding-horizon state (mpcmp_rh_*)
     int rh_B = 0;
     size_t lam_count = 0;          // doubles in ws.lam (max_batch x (m + n))
@@ -140,20 +137,49 @@ struct mpcmp_ctx {
     double rh_dt = 0.0;
     int *d_retired = nullptr;                    // [max_batch] arrived instances of the receding-horizon loop (k_advance); not re-solved
     unsigned long long *d_rh_count = nullptr;    // [2] re-solves executed, instances retired now (since mpcmp_rh_init)
-    hipEvent_t ev_upd[2] = {nullptr, nullptr};   // mpcmp_rh_update_device: the caller's stream -> ctx->stream, and back
-    bool rh_step = false;                        // the solve being enqueued is a step of the receding-horizon driver (defaults of its flags, retired instances)
+    hipEvent_t ev_upd[2] = {nullptr, nullptr};   // with_caller_stream: the caller's stream -> ctx->stream, and back
     // diagnostics read from the environment ONCE PER CONTEXT, in mpcmp_create (never process-global state)
     bool force_v1 = false, single_stream = false, debug_occ = false;
     int parts_env = 0;                           // MPCMP_STREAMS: parts of a large batch (0 = automatic, see solve_impl)
 };
 
+// the sizes of one problem (all arms): the context's buffers are allocated with them (create_impl) and sliced by them (split)
+struct Dims { int N, n, meq, m, mn; };
+static constexpr Dims dims_of(int nseg, int narm) {
+    const int N = 3 * nseg + 1, n = 21 * N * narm + 1, meq = 14 * (N - 1) * narm, m = meq + 8 * N * narm;
+    return {N, n, meq, m, m + n};
+}
+// ... and that they are the sizes the kernels index with, for every instantiated discretisation
+template <int NSEG>
+static constexpr bool dims_match() { constexpr Dims d = dims_of(NSEG, 1); using D = Dim<NSEG>; return d.N == D::N && d.n == D::n && d.meq == D::meq && d.m == D::m && d.mn == D::mn; }
+template <int NSEG, int NARM>
+static constexpr bool dims_match_m() { constexpr Dims d = dims_of(NSEG, NARM); using D = DimM<NSEG, NARM>; return d.N == D::N && d.n == D::n && d.meq == NARM * D::meq && d.m == D::m && d.mn == D::mn; }
+static_assert(dims_match<1>() && dims_match<2>() && dims_match<4>() && dims_match<6>(), "Dim<NSEG> and the context's strides differ");
+static_assert(dims_match_m<8, 1>() && dims_match_m<6, 2>() && dims_match_m<8, 2>(), "DimM<NSEG, NARM> and the context's strides differ");
+
+// One solve as the launch code sees it: B problems, device pointers, the stream it is enqueued on, and everything that makes it differ from a plain
+// mpcmp_solve_batch_device.  A call is built where the solve is asked for and passed down by reference: the context holds no mode of a solve in flight
+struct SolveCall {
+    int B = 0;
+    const double *x0 = nullptr, *xf = nullptr;                      // [B][nx]
+    const double *wx = nullptr, *wu = nullptr, *wT = nullptr;       // start guess: all three or none (the built-in initialiser)
+    double *sx = nullptr, *su = nullptr, *sT = nullptr;
+    mpcmp_info *info = nullptr;
+    hipStream_t stream = nullptr;
+    int only_qp = 0, reguess = 0;
+    bool rh_step = false;              // a step of the receding-horizon driver: its defaults of the start flags, its retired instances, no per-problem time / bound rows
+    const double *tw_rows = nullptr;   // final-time rows that override the context's (the second pass of a synchronised solve)
+    const int *skip = nullptr;         // problems that are not re-solved (the second pass of a synchronised solve)
+    bool capturing = false;            // the stream is being captured into a graph: no timing events
+};
+
 // the configuration the kernels of a solve see: the two start flags resolved to 0 / 1.  0 = the library default (off for mpcmp_solve_batch, ON for
 // the receding-horizon driver), 1 = on, -1 = off everywhere (include/mpcmp.h)
-static mpcmp_config run_config(const mpcmp_ctx *ctx) {
-    mpcmp_config c = ctx->cfg;
-    c.qp_warm_start = ctx->rh_step ? (c.qp_warm_start >= 0) : (c.qp_warm_start > 0);
-    c.carry_multipliers = ctx->rh_step ? (c.carry_multipliers >= 0) : (c.carry_multipliers > 0);
-    return c;
+static mpcmp_config run_config(const mpcmp_ctx *ctx, const SolveCall &c) {
+    mpcmp_config cfg = ctx->cfg;
+    cfg.qp_warm_start = c.rh_step ? (cfg.qp_warm_start >= 0) : (cfg.qp_warm_start > 0);
+    cfg.carry_multipliers = c.rh_step ? (cfg.carry_multipliers >= 0) : (cfg.carry_multipliers > 0);
+    return cfg;
 }
 
 static thread_local std::string g_err;
@@ -163,33 +189,37 @@ static const mpcmp_model *run_models(const mpcmp_ctx *ctx, int *stride) {
     *stride = ctx->pay_rows > 0 ? ctx->narm : 0;
     return ctx->pay_rows > 0 ? ctx->d_pmodel : ctx->d_model;
 }
-// the final-time rows a solve reads (WS::tbox): the second pass's, the caller's, or none (cfg.lbT / ubT; always none for the receding-horizon driver)
-static const double *run_rows(const mpcmp_ctx *ctx) {
-    if (ctx->tw_pass) return ctx->tw_pass;
-    return (ctx->tw_rows > 0 && !ctx->rh_step) ? ctx->d_tbox : nullptr;
+// the final-time rows a solve reads (WS::tbox): the call's own, the context's, or none (cfg.lbT / ubT; always none for the receding-horizon driver)
+static const double *run_rows(const mpcmp_ctx *ctx, const SolveCall &c) {
+    if (c.tw_rows) return c.tw_rows;
+    return (ctx->tw_rows > 0 && !c.rh_step) ? ctx->d_tbox : nullptr;
 }
-// the bound rows a solve reads (WS::bnd): the caller's, or none (the tables of cfg; always none for the receding-horizon driver)
-static const mpcmp_bounds *run_bounds(const mpcmp_ctx *ctx) { return (ctx->bnd_rows > 0 && !ctx->rh_step) ? ctx->d_bnd : nullptr; }
-static int bound_rows_ok(mpcmp_ctx *ctx, int B) {
-    if (ctx->bnd_rows > 0 && B > ctx->bnd_rows) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than bound rows (" + std::to_string(ctx->bnd_rows) + "): see mpcmp_set_bounds";
+// the bound rows a solve reads (WS::bnd): the context's, or none (the tables of cfg; always none for the receding-horizon driver)
+static const mpcmp_bounds *run_bounds(const mpcmp_ctx *ctx, const SolveCall &c) { return (ctx->bnd_rows > 0 && !c.rh_step) ? ctx->d_bnd : nullptr; }
+// the problems a solve leaves alone (WS::retired): the arrived instances of the receding-horizon loop, or the call's own mask
+static const int *run_retired(const mpcmp_ctx *ctx, const SolveCall &c) { return c.rh_step ? ctx->d_retired : c.skip; }
+
+// the three per-problem row tables of a context: where the count of rows in force lies, and the words of their messages
+struct RowTable { int mpcmp_ctx::*rows; const char *what, *setter, *usage; bool refused_in_loop; };
+static const RowTable PAYLOAD_ROWS = {&mpcmp_ctx::pay_rows, "payload", "mpcmp_set_payloads", "p given (or 0 with p NULL: clear)", false};
+static const RowTable TIME_ROWS = {&mpcmp_ctx::tw_rows, "final-time", "mpcmp_set_time_windows", "lbT and ubT given (or 0 with both NULL: clear)", true};
+static const RowTable BOUND_ROWS = {&mpcmp_ctx::bnd_rows, "bound", "mpcmp_set_bounds", "rows given (or 0 with NULL: clear)", true};
+// a call for B problems needs a row for each of them (when rows are set)
+static int rows_ok(mpcmp_ctx *ctx, int B, const RowTable &t) {
+    const int rows = ctx->*t.rows;
+    if (rows > 0 && B > rows) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than " + t.what + " rows (" + std::to_string(rows) + "): see " + t.setter;
         return MPCMP_EINVAL;
     }
     return MPCMP_OK;
 }
-static int time_rows_ok(mpcmp_ctx *ctx, int B) {
-    if (ctx->tw_rows > 0 && B > ctx->tw_rows) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than final-time rows (" + std::to_string(ctx->tw_rows) + "): see mpcmp_set_time_windows";
-        return MPCMP_EINVAL;
-    }
-    return MPCMP_OK;
+static int solve_rows_ok(mpcmp_ctx *ctx, int B) {
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
+    if (int rc = rows_ok(ctx, B, TIME_ROWS)) return rc;
+    return rows_ok(ctx, B, BOUND_ROWS);
 }
-// a call that evaluates dynamics for B problems needs a payload row for each of them (when rows are set)
-static int payload_rows_ok(mpcmp_ctx *ctx, int B) {
-    if (ctx->pay_rows > 0 && B > ctx->pay_rows) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than payload rows (" + std::to_string(ctx->pay_rows) + "): see mpcmp_set_payloads";
-        return MPCMP_EINVAL;
-    }
+static int warm_all_or_none(mpcmp_ctx *ctx, const double *wx, const double *wu, const double *wT) {
+    if ((wx != nullptr) != (wu != nullptr) || (wx != nullptr) != (wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
     return MPCMP_OK;
 }
 
@@ -710,8 +740,8 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
     mpcmp_ctx *ctx = new mpcmp_ctx();
     ctx->cfg = *cfg; ctx->device = device; ctx->max_batch = max_batch; ctx->nseg = cfg->num_seg; ctx->narm = narm;
     ctx->nx = 14 * narm; ctx->nu = 7 * narm;
-    ctx->N = 3 * cfg->num_seg + 1; ctx->n = 21 * ctx->N * narm + 1; ctx->meq = 14 * (ctx->N - 1) * narm;
-    ctx->m = ctx->meq + 8 * ctx->N * narm; ctx->mn = ctx->m + ctx->n;
+    const Dims d = dims_of(cfg->num_seg, narm);
+    ctx->N = d.N; ctx->n = d.n; ctx->meq = d.meq; ctx->m = d.m; ctx->mn = d.mn;
     auto fail = [&](int rc) { g_err = ctx->err; mpcmp_destroy(ctx); return rc; };
 #define TRY(x) do { int rc_ = (x); if (rc_) return fail(rc_); } while (0)
 #define HIPTRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e_); return fail(MPCMP_ERUNTIME); } } while (0)
@@ -855,6 +885,13 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
     return MPCMP_OK;
 }
 
+// a captured receding-horizon step holds what it was captured with as kernel arguments (the configuration by value, the model pointer and stride):
+// whoever changes one of them drops the graph, and the next mpcmp_rh_run with use_graph captures again
+static void drop_rh_graph(mpcmp_ctx *ctx) {
+    if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
+    if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
+}
+
 extern "C" int mpcmp_set_config(mpcmp_ctx *ctx, const mpcmp_config *cfg) {
     if (!ctx || !cfg) return MPCMP_EINVAL;
     if (cfg->num_seg != ctx->nseg) { ctx->err = "num_seg cannot change after mpcmp_create"; return MPCMP_EINVAL; }
@@ -863,10 +900,40 @@ extern "C" int mpcmp_set_config(mpcmp_ctx *ctx, const mpcmp_config *cfg) {
         ctx->err = "multi-arm OCPs: qp_iters too large for the exchange slots"; return MPCMP_EINVAL;
     }
     ctx->cfg = *cfg;
-    // a captured receding-horizon step holds the configuration by value as a kernel argument: re-capture on the next rh_run
-    if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
-    if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
+    drop_rh_graph(ctx);
     return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// what the *_device setters and mpcmp_rh_update_device share: body(ctx->stream) runs after the caller's work on its stream (which writes the inputs) and
+// the context's own (solves that read what body replaces), before the context's later work; the caller's later work waits for body's reads of its buffers
+template <typename F>
+static int with_caller_stream(mpcmp_ctx *ctx, void *hip_stream, F body) {
+    hipStream_t cs = (hipStream_t)hip_stream;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
+    if (int rc = body(ctx->stream)) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
+    HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+    return MPCMP_OK;
+}
+
+// the front half of the checks of the three row setters (host and device variant alike).  given / none: every row pointer of the call is set / is NULL
+static int rows_check(mpcmp_ctx *ctx, const RowTable &t, int n, bool given, bool none) {
+    if (!ctx) { g_err = std::string(t.setter) + ": no context"; return MPCMP_EINVAL; }
+    if (t.refused_in_loop && ctx->rh_B > 0) {
+        ctx->err = std::string(t.setter) + ": the receding-horizon driver does not read " + t.what + " rows (a loop is running)"; return MPCMP_EINVAL;
+    }
+    if (n == 0 && none) return MPCMP_OK;
+    if (n < 1 || n > ctx->max_batch || !given) { ctx->err = std::string(t.setter) + ": n must be in [1, max_batch] with " + t.usage; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+// first use of a row table: [max_batch] rows of `per_row` entries
+template <typename T>
+static int rows_alloc(mpcmp_ctx *ctx, T **p, size_t per_row) {
+    if (*p) return MPCMP_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return dalloc(ctx, p, per_row * ctx->max_batch);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -897,26 +964,13 @@ static int payloads_enqueue(mpcmp_ctx *ctx, int n, const mpcmp_payload *d_p, hip
     return MPCMP_OK;
 }
 
+// (payload rows may change while a receding-horizon loop runs, as long as every instance keeps one; the setters then drop the captured step)
 static int payloads_check(mpcmp_ctx *ctx, int n, const mpcmp_payload *p) {
-    if (!ctx) { g_err = "mpcmp_set_payloads: no context"; return MPCMP_EINVAL; }
-    if (n == 0 && !p) return MPCMP_OK;
-    if (n < 1 || n > ctx->max_batch || !p) { ctx->err = "mpcmp_set_payloads: n must be in [1, max_batch] with p given (or 0 with p NULL: clear)"; return MPCMP_EINVAL; }
+    if (int rc = rows_check(ctx, PAYLOAD_ROWS, n, p != nullptr, !p)) return rc;
+    if (n == 0) return MPCMP_OK;
     if (ctx->rh_B > 0 && n < ctx->rh_B) { ctx->err = "mpcmp_set_payloads: fewer rows than the instances of the receding-horizon loop"; return MPCMP_EINVAL; }
-    if (!ctx->d_pmodel) {          // first use: [max_batch][narm] models and payloads (1,472 + 104 B each)
-        void *q = nullptr;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        HIPCHK(ctx, hipMalloc(&q, sizeof(mpcmp_model) * ctx->max_batch * ctx->narm));
-        ctx->allocs.push_back(q); ctx->d_pmodel = (mpcmp_model *)q;
-        HIPCHK(ctx, hipMalloc(&q, sizeof(mpcmp_payload) * ctx->max_batch * ctx->narm));
-        ctx->allocs.push_back(q); ctx->d_pay = (mpcmp_payload *)q;
-    }
-    return MPCMP_OK;
-}
-
-// the rows change what a captured receding-horizon step reads (its kernel arguments hold the model pointer and stride): capture again
-static void drop_rh_graph(mpcmp_ctx *ctx) {
-    if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
-    if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
+    if (int rc = rows_alloc(ctx, &ctx->d_pmodel, ctx->narm)) return rc;      // (1,472 + 104 B per arm)
+    return rows_alloc(ctx, &ctx->d_pay, ctx->narm);
 }
 
 extern "C" int mpcmp_set_payloads(mpcmp_ctx *ctx, int n, const mpcmp_payload *p) {
@@ -939,16 +993,8 @@ extern "C" int mpcmp_set_payloads(mpcmp_ctx *ctx, int n, const mpcmp_payload *p)
 extern "C" int mpcmp_set_payloads_device(mpcmp_ctx *ctx, int n, const mpcmp_payload *d_p, void *hip_stream) {
     if (int rc = payloads_check(ctx, n, d_p)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n > 0) {
-        // after the caller's work on its stream (which writes d_p) and the context's own (solves that read the current models), before the
-        // context's later work; the caller's later work waits for the reads of d_p
-        hipStream_t cs = (hipStream_t)hip_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
-        if (int rc = payloads_enqueue(ctx, n, d_p, ctx->stream)) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
-    }
+    if (n > 0)
+        if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) { return payloads_enqueue(ctx, n, d_p, st); })) return rc;
     ctx->pay_rows = n;
     drop_rh_graph(ctx);
     return MPCMP_OK;
@@ -957,15 +1003,8 @@ extern "C" int mpcmp_set_payloads_device(mpcmp_ctx *ctx, int n, const mpcmp_payl
 // ------------------------------------------------------------------------------------------------
 // per-problem final-time windows
 static int time_windows_check(mpcmp_ctx *ctx, int n, const double *lb, const double *ub) {
-    if (!ctx) { g_err = "mpcmp_set_time_windows: no context"; return MPCMP_EINVAL; }
-    if (ctx->rh_B > 0) { ctx->err = "mpcmp_set_time_windows: the receding-horizon driver does not read final-time rows (a loop is running)"; return MPCMP_EINVAL; }
-    if (n == 0 && !lb && !ub) return MPCMP_OK;
-    if (n < 1 || n > ctx->max_batch || !lb || !ub) { ctx->err = "mpcmp_set_time_windows: n must be in [1, max_batch] with lbT and ubT given (or 0 with both NULL: clear)"; return MPCMP_EINVAL; }
-    if (!ctx->d_tbox) {
-        HIPCHK(ctx, hipSetDevice(ctx->device));
-        if (int rc = dalloc(ctx, &ctx->d_tbox, (size_t)2 * ctx->max_batch)) return rc;
-    }
-    return MPCMP_OK;
+    if (int rc = rows_check(ctx, TIME_ROWS, n, lb && ub, !lb && !ub)) return rc;
+    return n > 0 ? rows_alloc(ctx, &ctx->d_tbox, 2) : MPCMP_OK;
 }
 
 extern "C" int mpcmp_set_time_windows(mpcmp_ctx *ctx, int n, const double *lbT, const double *ubT) {
@@ -991,17 +1030,12 @@ extern "C" int mpcmp_set_time_windows(mpcmp_ctx *ctx, int n, const double *lbT, 
 extern "C" int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double *d_lbT, const double *d_ubT, void *hip_stream) {
     if (int rc = time_windows_check(ctx, n, d_lbT, d_ubT)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n > 0) {
-        // after the caller's work on its stream (which writes the rows) and the context's own (solves that read the current rows), before the
-        // context's later work; the caller's later work waits for the reads
-        hipStream_t cs = (hipStream_t)hip_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
-        HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox, 2 * sizeof(double), d_lbT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox + 1, 2 * sizeof(double), d_ubT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
-    }
+    if (n > 0)
+        if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+                HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox, 2 * sizeof(double), d_lbT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, st));
+                HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_tbox + 1, 2 * sizeof(double), d_ubT, sizeof(double), sizeof(double), n, hipMemcpyDeviceToDevice, st));
+                return MPCMP_OK;
+            })) return rc;
     ctx->tw_rows = n;
     return MPCMP_OK;
 }
@@ -1009,16 +1043,8 @@ extern "C" int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double
 // ------------------------------------------------------------------------------------------------
 // per-problem bounds
 static int bounds_check(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows) {
-    if (!ctx) { g_err = "mpcmp_set_bounds: no context"; return MPCMP_EINVAL; }
-    if (ctx->rh_B > 0) { ctx->err = "mpcmp_set_bounds: the receding-horizon driver does not read bound rows (a loop is running)"; return MPCMP_EINVAL; }
-    if (n == 0 && !rows) return MPCMP_OK;
-    if (n < 1 || n > ctx->max_batch || !rows) { ctx->err = "mpcmp_set_bounds: n must be in [1, max_batch] with rows given (or 0 with NULL: clear)"; return MPCMP_EINVAL; }
-    return MPCMP_OK;
-}
-static int bounds_alloc(mpcmp_ctx *ctx) {
-    if (ctx->d_bnd) return MPCMP_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    return dalloc(ctx, &ctx->d_bnd, (size_t)ctx->max_batch);
+    if (int rc = rows_check(ctx, BOUND_ROWS, n, rows != nullptr, !rows)) return rc;
+    return n > 0 ? rows_alloc(ctx, &ctx->d_bnd, 1) : MPCMP_OK;
 }
 
 extern "C" int mpcmp_set_bounds(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows) {
@@ -1028,7 +1054,6 @@ extern "C" int mpcmp_set_bounds(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows)
         if (validate_boxes(rows + i, why) || validate_general_rows(rows + i, ctx->nseg, why)) { ctx->err = "mpcmp_set_bounds: row " + std::to_string(i) + ": " + why; return MPCMP_EINVAL; }
     }
     if (n > 0) {
-        if (int rc = bounds_alloc(ctx)) return rc;
         HIPCHK(ctx, hipSetDevice(ctx->device));
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_bnd, rows, sizeof(mpcmp_bounds) * n, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1040,16 +1065,11 @@ extern "C" int mpcmp_set_bounds(mpcmp_ctx *ctx, int n, const mpcmp_bounds *rows)
 extern "C" int mpcmp_set_bounds_device(mpcmp_ctx *ctx, int n, const mpcmp_bounds *d_rows, void *hip_stream) {
     if (int rc = bounds_check(ctx, n, d_rows)) return rc;
     if (n > 0) {
-        if (int rc = bounds_alloc(ctx)) return rc;
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        // after the caller's work on its stream (which writes the rows) and the context's own (solves that read the current rows), before the
-        // context's later work; the caller's later work waits for the reads
-        hipStream_t cs = (hipStream_t)hip_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_bnd, d_rows, sizeof(mpcmp_bounds) * n, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
+        if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_bnd, d_rows, sizeof(mpcmp_bounds) * n, hipMemcpyDeviceToDevice, st));
+                return MPCMP_OK;
+            })) return rc;
     }
     ctx->bnd_rows = n;
     return MPCMP_OK;
@@ -1087,6 +1107,8 @@ struct KSel {
         V2 = V2C && !ctx->force_v1 && !V3C && !V4;
         V5 = NSEG == 6 && ctx->qp19 == 5;
     }
+    // the kernel that runs the ADMM loop, by the order of preference of solve_impl's launches
+    const char *loop_kernel_name() const { return V4 ? "k_qp4" : V5 ? "k_qp5" : V3C ? "k_qp3" : V2 ? "k_qp2" : "k_qp"; }
 };
 
 // dynamic-LDS limits of every kernel a context of this discretisation can launch: set ONCE, in mpcmp_create
@@ -1094,6 +1116,7 @@ template <int NSEG>
 static int prepare_impl(mpcmp_ctx *ctx) {
     using S = KSel<NSEG>;
     const S k(ctx);
+    ctx->loop_kernel = k.loop_kernel_name();
     if (int rc = set_lds(ctx, k_init<NSEG>, InitLds<NSEG>::size * sizeof(double))) return rc;
     if (int rc = set_lds(ctx, k_step<NSEG>, StepLds<NSEG>::size * sizeof(double))) return rc;
     if (k.V3C) {
@@ -1121,22 +1144,78 @@ static int prepare_impl(mpcmp_ctx *ctx) {
     return MPCMP_OK;
 }
 
+// ---- the parts of a solve ----
+// A large batch is solved as parts on as many streams (why: solve_impl).  A part is a contiguous range of the call's problems with every per-problem
+// pointer of the workspace, the exchange slots, the start guess and the outputs moved to its first problem
+struct Part {
+    int b0, B;
+    hipStream_t stream;
+    WS ws;
+    Xch xch;
+    const double *wx, *wu, *wT;
+    double *sx, *su, *sT;
+    mpcmp_info *info;
+};
+struct Parts {
+    int n = 0;
+    Part p[4];
+    const Part *begin() const { return p; }
+    const Part *end() const { return p + n; }
+};
+
+static Parts split(const mpcmp_ctx *ctx, const SolveCall &c, int nparts) {
+    WS w = ctx->ws;
+    w.x0 = c.x0; w.xf = c.xf;
+    w.model = run_models(ctx, &w.mstride);
+    w.retired = run_retired(ctx, c);
+    w.tbox = run_rows(ctx, c);
+    w.bnd = run_bounds(ctx, c);
+    if (c.rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
+    const size_t nx = ctx->nx, nu = ctx->nu, N = ctx->N, n = ctx->n, mn = ctx->mn, meq = ctx->meq, narm = ctx->narm;
+    const hipStream_t streams[4] = {c.stream, ctx->stream_x[0], ctx->stream_x[1], ctx->stream_x[2]};
+    Parts ps;
+    ps.n = nparts;
+    for (int h = 0, acc = 0; h < nparts; h++) {
+        Part &q = ps.p[h];
+        q.b0 = acc; q.B = (c.B - acc + (nparts - h) - 1) / (nparts - h); q.stream = streams[h];
+        acc += q.B;
+        const size_t b0 = (size_t)q.b0;
+        WS v = w;
+        v.x0 += nx * b0; v.xf += nx * b0; v.z += n * b0; v.lam += mn * b0; v.ceq += meq * b0; v.g += 8 * N * narm * b0;
+        v.Gk += 176 * N * narm * b0; v.p += n * b0; v.y += mn * b0; v.qpit += b0; v.perm += b0; v.okey += b0; v.done += h;
+        v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
+        v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
+        if (v.retired) v.retired += b0;
+        if (v.tbox) v.tbox += 2 * b0;
+        if (v.bnd) v.bnd += b0;
+        if (v.alt_x) { v.alt_x += nx * N * b0; v.alt_u += nu * N * b0; v.alt_T += b0; }
+        q.ws = v;
+        q.xch.buf = ctx->xch.buf ? ctx->xch.buf + (size_t)2 * MPCMP_XCH_STRIDE * b0 : nullptr;
+        q.wx = c.wx ? c.wx + nx * N * b0 : nullptr; q.wu = c.wx ? c.wu + nu * N * b0 : nullptr; q.wT = c.wx ? c.wT + b0 : nullptr;
+        q.sx = c.sx ? c.sx + nx * N * b0 : nullptr; q.su = c.su ? c.su + nu * N * b0 : nullptr;
+        q.sT = c.sT ? c.sT + b0 : nullptr; q.info = c.info ? c.info + b0 : nullptr;
+    }
+    return ps;
+}
+// the further parts' streams start behind the work already on the call's stream (fork) and the call's stream goes on behind them (join); under stream
+// capture the events carry the other streams into the graph
+static int fork_parts(mpcmp_ctx *ctx, const Parts &ps) {
+    if (ps.n > 1) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ps.p[0].stream));
+    for (int h = 1; h < ps.n; h++) HIPCHK(ctx, hipStreamWaitEvent(ps.p[h].stream, ctx->ev_fork, 0));
+    return MPCMP_OK;
+}
+static int join_parts(mpcmp_ctx *ctx, const Parts &ps) {
+    for (int h = 1; h < ps.n; h++) { HIPCHK(ctx, hipEventRecord(ctx->ev_join[h - 1], ps.p[h].stream)); HIPCHK(ctx, hipStreamWaitEvent(ps.p[0].stream, ctx->ev_join[h - 1], 0)); }
+    return MPCMP_OK;
+}
+
 template <int NSEG>
-static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx,
-                      const double *d_wu, const double *d_wT, double *d_sx, double *d_su, double *d_sT,
-                      mpcmp_info *d_info, hipStream_t st, int only_qp, int reguess = 0) {
+static int solve_impl(mpcmp_ctx *ctx, const SolveCall &c) {
     using D = Dim<NSEG>;
     using S = KSel<NSEG>;
     const S ks(ctx);
     const bool V3C = ks.V3C, V4 = ks.V4, V2 = ks.V2;
-    const mpcmp_config cfg = run_config(ctx);
-    WS w = ctx->ws;
-    w.x0 = d_x0; w.xf = d_xf;
-    w.model = run_models(ctx, &w.mstride);
-    w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
-    w.tbox = run_rows(ctx);
-    w.bnd = run_bounds(ctx);
-    if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
+    const mpcmp_config cfg = run_config(ctx, c);
     const size_t l_init = InitLds<NSEG>::size * sizeof(double), l_qp = QpLds<S::N1>::size * sizeof(double),
                  l_step = StepLds<NSEG>::size * sizeof(double);
     const size_t l_qp3 = Qp3<S::N3>::sizeL * sizeof(double), l_qp3f = Qp3<S::N3>::sizeF * sizeof(double);
@@ -1149,74 +1228,51 @@ static int solve_impl(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d
     // iterations, four workgroups per CU); with two independent chains in flight the tail of one half is filled by the other
     // half's next launch.  Replay of the bench workload's iteration counts: -5.8 % makespan.  Results are unaffected (problems
     // are independent); small batches stay on one stream.
-    const bool dual = !ctx->single_stream && !only_qp && B >= 512;      // (also under stream capture: the fork/join events carry the other streams into the graph)
+    const bool dual = !ctx->single_stream && !c.only_qp && c.B >= 512;      // (also under stream capture: see fork_parts)
     // parts: two; three for the N = 13 kernel from 1024 problems on (round 5, three repeats each: 15.74 - 15.77 k against 15.58 - 15.61 k traj/s on the
     // headline batch; 512 problems — the receding-horizon step — and N = 19 are faster with two: 135.7 k vs 130.0 k re-solves/s, 67.1 k vs 65.2 k traj/s)
-    const int parts_auto = (NSEG == 4 && V2 && B >= 1024) ? 3 : 2;
-    const int nhalf = dual ? (ctx->parts_env < 1 ? parts_auto : (ctx->parts_env > 4 ? 4 : ctx->parts_env)) : 1;
-    int Bh[4] = {0, 0, 0, 0}, boff[4] = {0, 0, 0, 0};
-    for (int h = 0, acc = 0; h < nhalf; h++) { Bh[h] = (B - acc + (nhalf - h) - 1) / (nhalf - h); boff[h] = acc; acc += Bh[h]; }
-    hipStream_t sh[4] = {st, ctx->stream_x[0], ctx->stream_x[1], ctx->stream_x[2]};
-    WS wh[4];
-    const double *hx[4] = {nullptr, nullptr, nullptr, nullptr}, *hu[4] = {nullptr, nullptr, nullptr, nullptr}, *hT[4] = {nullptr, nullptr, nullptr, nullptr};
-    double *ox[4], *ou[4], *oT[4];
-    mpcmp_info *oi[4];
-    for (int h = 0; h < nhalf; h++) {
-        const size_t b0 = (size_t)boff[h];
-        WS v = w;
-        v.x0 += 14 * b0; v.xf += 14 * b0; v.z += D::n * b0; v.lam += D::mn * b0; v.ceq += D::meq * b0; v.g += 8 * D::N * b0;
-        v.Gk += (size_t)D::N * 176 * b0; v.p += D::n * b0; v.y += D::mn * b0; v.qpit += b0; v.perm += b0; v.okey += b0; v.done += h;
-        v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
-        v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
-        if (v.retired) v.retired += b0;
-        if (v.tbox) v.tbox += 2 * b0;
-        if (v.bnd) v.bnd += b0;
-        if (v.alt_x) { v.alt_x += 14 * D::N * b0; v.alt_u += 7 * D::N * b0; v.alt_T += b0; }
-        wh[h] = v;
-        if (d_wx) { hx[h] = d_wx + 14 * D::N * b0; hu[h] = d_wu + 7 * D::N * b0; hT[h] = d_wT + b0; }
-        ox[h] = d_sx ? d_sx + 14 * D::N * b0 : nullptr; ou[h] = d_su ? d_su + 7 * D::N * b0 : nullptr;
-        oT[h] = d_sT ? d_sT + b0 : nullptr; oi[h] = d_info ? d_info + b0 : nullptr;
-    }
-    if (nhalf > 1) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st)); for (int h = 1; h < nhalf; h++) HIPCHK(ctx, hipStreamWaitEvent(sh[h], ctx->ev_fork, 0)); }
-    for (int h = 0; h < nhalf; h++)
-        hipLaunchKernelGGL(k_init<NSEG>, dim3(Bh[h]), dim3(D::NT), l_init, sh[h], cfg, wh[h], hx[h], hu[h], hT[h], reguess);
-    const int iters = only_qp ? 1 : cfg.sqp_iters;
+    const int parts_auto = (NSEG == 4 && V2 && c.B >= 1024) ? 3 : 2;
+    const Parts parts = split(ctx, c, dual ? (ctx->parts_env < 1 ? parts_auto : (ctx->parts_env > 4 ? 4 : ctx->parts_env)) : 1);
+    if (int rc = fork_parts(ctx, parts)) return rc;
+    for (const Part &p : parts)
+        hipLaunchKernelGGL(k_init<NSEG>, dim3(p.B), dim3(D::NT), l_init, p.stream, cfg, p.ws, p.wx, p.wu, p.wT, c.reguess);
+    const int iters = c.only_qp ? 1 : cfg.sqp_iters;
     for (int it = 0; it < iters; it++) {
-        for (int h = 0; h < nhalf; h++) {
-            hipEvent_t *ev = (ctx->timing && !ctx->capturing) ? next_events(ctx) : nullptr;
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], sh[h]));
+        for (const Part &p : parts) {
+            hipEvent_t *ev = (ctx->timing && !c.capturing) ? next_events(ctx) : nullptr;
+            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], p.stream));
 #ifdef MPCMP_WITH_QP4
             if (V4) {
-                WS w3 = wh[h];
+                WS w3 = p.ws;
                 w3.ext_of_int = ctx->d3_ext_of_int; w3.entry_ptr = ctx->d3_entry_ptr; w3.terms = ctx->d3_terms;
-                double *fh = ctx->d_fac + (size_t)boff[h] * Qp4Fac<4>::FAC;
-                hipLaunchKernelGGL((k_qp3f<4, 1, 4>), dim3(Bh[h]), dim3(1024), Qp3<4>::sizeF * sizeof(double), sh[h], cfg, w3, ctx->d_pat, ctx->xch, Bh[h], fh);
-                hipLaunchKernelGGL((k_qp4<4>), dim3(Bh[h]), dim3(384), l_qp4, sh[h], cfg, w3, (const uint32_t *)ctx->d_lane4, Bh[h], (const double *)fh);
+                double *fh = ctx->d_fac + (size_t)p.b0 * Qp4Fac<4>::FAC;
+                hipLaunchKernelGGL((k_qp3f<4, 1, 4>), dim3(p.B), dim3(1024), Qp3<4>::sizeF * sizeof(double), p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, fh);
+                hipLaunchKernelGGL((k_qp4<4>), dim3(p.B), dim3(384), l_qp4, p.stream, cfg, w3, (const uint32_t *)ctx->d_lane4, p.B, (const double *)fh);
             }
 #else
             if (V4) { ctx->err = "k_qp4 not built"; return MPCMP_EINVAL; }
 #endif
             else if (ks.V5) {
-                double *fh = ctx->d_fac + (size_t)boff[h] * Qp5Fac<6>::FAC;
-                hipLaunchKernelGGL((k_qp3f<6, 1, 5>), dim3(Bh[h]), dim3(1024), Qp3<6>::sizeF * sizeof(double), sh[h], cfg, wh[h], ctx->d_pat, ctx->xch, Bh[h], fh);
-                hipLaunchKernelGGL((k_qp5<6>), dim3(Bh[h]), dim3(768), Qp5<6>::size5 * sizeof(double), sh[h], cfg, wh[h], ctx->d_pat, ctx->xch, Bh[h], (const double *)fh);
+                double *fh = ctx->d_fac + (size_t)p.b0 * Qp5Fac<6>::FAC;
+                hipLaunchKernelGGL((k_qp3f<6, 1, 5>), dim3(p.B), dim3(1024), Qp3<6>::sizeF * sizeof(double), p.stream, cfg, p.ws, ctx->d_pat, ctx->xch, p.B, fh);
+                hipLaunchKernelGGL((k_qp5<6>), dim3(p.B), dim3(768), Qp5<6>::size5 * sizeof(double), p.stream, cfg, p.ws, ctx->d_pat, ctx->xch, p.B, (const double *)fh);
             }
             else if (V3C) {
-                WS w3 = wh[h];
+                WS w3 = p.ws;
                 if (NSEG == 4) { w3.ext_of_int = ctx->d3_ext_of_int; w3.entry_ptr = ctx->d3_entry_ptr; w3.terms = ctx->d3_terms; }
-                double *fh = ctx->d_fac + (size_t)boff[h] * Qp3<S::N3>::FAC;
-                hipLaunchKernelGGL((k_qp3f<S::N3, 1>), dim3(Bh[h]), dim3(1024), l_qp3f, sh[h], cfg, w3, ctx->d_pat, ctx->xch, Bh[h], fh);
-                hipLaunchKernelGGL((k_qp3<S::N3, 1>), dim3(Bh[h]), dim3(512), l_qp3, sh[h], cfg, w3, ctx->d_pat, ctx->xch, Bh[h], (const double *)fh);
+                double *fh = ctx->d_fac + (size_t)p.b0 * Qp3<S::N3>::FAC;
+                hipLaunchKernelGGL((k_qp3f<S::N3, 1>), dim3(p.B), dim3(1024), l_qp3f, p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, fh);
+                hipLaunchKernelGGL((k_qp3<S::N3, 1>), dim3(p.B), dim3(512), l_qp3, p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, (const double *)fh);
             }
-            else if (V2) hipLaunchKernelGGL((k_qp2<S::N2>), dim3(Bh[h]), dim3(1024), l_qp2, sh[h], cfg, wh[h], ctx->streams);
-            else hipLaunchKernelGGL((k_qp<S::N1>), dim3(Bh[h]), dim3(Dim<S::N1>::NT), l_qp, sh[h], cfg, wh[h]);
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], sh[h]));
-            if (only_qp) continue;
-            hipLaunchKernelGGL(k_step<NSEG>, dim3(Bh[h]), dim3(D::NT), l_step, sh[h], cfg, wh[h], it == iters - 1 ? 1 : 0, it,
-                               ox[h], ou[h], oT[h], oi[h]);
+            else if (V2) hipLaunchKernelGGL((k_qp2<S::N2>), dim3(p.B), dim3(1024), l_qp2, p.stream, cfg, p.ws, ctx->streams);
+            else hipLaunchKernelGGL((k_qp<S::N1>), dim3(p.B), dim3(Dim<S::N1>::NT), l_qp, p.stream, cfg, p.ws);
+            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], p.stream));
+            if (c.only_qp) continue;
+            hipLaunchKernelGGL(k_step<NSEG>, dim3(p.B), dim3(D::NT), l_step, p.stream, cfg, p.ws, it == iters - 1 ? 1 : 0, it,
+                               p.sx, p.su, p.sT, p.info);
         }
     }
-    for (int h = 1; h < nhalf; h++) { HIPCHK(ctx, hipEventRecord(ctx->ev_join[h - 1], sh[h])); HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join[h - 1], 0)); }
+    if (int rc = join_parts(ctx, parts)) return rc;
     HIPCHK(ctx, hipGetLastError());
     return MPCMP_OK;
 }
@@ -1225,6 +1281,7 @@ template <int NSEG, int NARM>
 static int prepare_impl_m(mpcmp_ctx *ctx) {
     using D = DimM<NSEG, NARM>;
     const size_t l_m = D::size * sizeof(double);
+    ctx->loop_kernel = "k_qp3";
     if (int rc = set_lds(ctx, k_init_m<NSEG, NARM>, l_m)) return rc;
     if (int rc = set_lds(ctx, k_step_m<NSEG, NARM>, l_m)) return rc;
     if (int rc = set_lds(ctx, k_qp3<NSEG, NARM>, Qp3<NSEG>::sizeL * sizeof(double))) return rc;
@@ -1247,104 +1304,95 @@ static int prepare_kernels(mpcmp_ctx *ctx) {
 
 // N = 25 and multi-arm OCPs: k_init_m -> K x [k_qp3 (one workgroup per arm), k_step_m]
 template <int NSEG, int NARM>
-static int solve_impl_m(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx, const double *d_wu,
-                        const double *d_wT, double *d_sx, double *d_su, double *d_sT, mpcmp_info *d_info, hipStream_t st,
-                        int only_qp, int reguess) {
+static int solve_impl_m(mpcmp_ctx *ctx, const SolveCall &c) {
     using D = DimM<NSEG, NARM>;
-    constexpr int N = D::N;
-    const mpcmp_config cfg = run_config(ctx);
-    WS w = ctx->ws;
-    w.x0 = d_x0; w.xf = d_xf;
-    w.model = run_models(ctx, &w.mstride);
-    w.retired = ctx->rh_step ? ctx->d_retired : ctx->sync_skip;
-    w.tbox = run_rows(ctx);
-    w.bnd = run_bounds(ctx);
-    if (ctx->rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
+    const mpcmp_config cfg = run_config(ctx, c);
     const size_t l_m = D::size * sizeof(double), l_qp3 = Qp3<NSEG>::sizeL * sizeof(double), l_qp3f = Qp3<NSEG>::sizeF * sizeof(double);
     // two parts on two streams once one part alone fills the chip (one CU per arm): see solve_impl
-    const bool dual = !ctx->single_stream && !only_qp && B * NARM >= 512;
-    const int nhalf = dual ? 2 : 1;
-    int Bh[2] = {0, 0}, boff[2] = {0, 0};
-    for (int h = 0, acc = 0; h < nhalf; h++) { Bh[h] = (B - acc + (nhalf - h) - 1) / (nhalf - h); boff[h] = acc; acc += Bh[h]; }
-    hipStream_t sh[2] = {st, ctx->stream_x[0]};
-    WS wh[2];
-    Xch xh[2];
-    const double *hx[2] = {nullptr, nullptr}, *hu[2] = {nullptr, nullptr}, *hT[2] = {nullptr, nullptr};
-    double *ox[2], *ou[2], *oT[2];
-    mpcmp_info *oi[2];
-    for (int h = 0; h < nhalf; h++) {
-        const size_t b0 = (size_t)boff[h];
-        WS v = w;
-        v.x0 += 14 * NARM * b0; v.xf += 14 * NARM * b0; v.z += D::n * b0; v.lam += D::mn * b0; v.ceq += (size_t)NARM * D::meq * b0;
-        v.g += (size_t)NARM * 8 * N * b0; v.Gk += (size_t)NARM * N * 176 * b0; v.p += D::n * b0; v.y += D::mn * b0; v.qpit += b0; v.perm += b0;
-        v.okey += b0; v.done += h; v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
-        v.model += (size_t)v.mstride * b0;      // (see solve_impl)
-        if (v.retired) v.retired += b0;
-        if (v.tbox) v.tbox += 2 * b0;
-        if (v.bnd) v.bnd += b0;
-        if (v.alt_x) { v.alt_x += (size_t)14 * NARM * N * b0; v.alt_u += (size_t)7 * NARM * N * b0; v.alt_T += b0; }
-        wh[h] = v;
-        xh[h].buf = ctx->xch.buf ? ctx->xch.buf + (size_t)2 * MPCMP_XCH_STRIDE * b0 : nullptr;
-        if (d_wx) { hx[h] = d_wx + (size_t)14 * NARM * N * b0; hu[h] = d_wu + (size_t)7 * NARM * N * b0; hT[h] = d_wT + b0; }
-        ox[h] = d_sx ? d_sx + (size_t)14 * NARM * N * b0 : nullptr; ou[h] = d_su ? d_su + (size_t)7 * NARM * N * b0 : nullptr;
-        oT[h] = d_sT ? d_sT + b0 : nullptr; oi[h] = d_info ? d_info + b0 : nullptr;
-    }
-    if (nhalf > 1) { HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st)); HIPCHK(ctx, hipStreamWaitEvent(sh[1], ctx->ev_fork, 0)); }
-    for (int h = 0; h < nhalf; h++)
-        hipLaunchKernelGGL((k_init_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, wh[h].model, wh[h], xh[h], hx[h], hu[h], hT[h], reguess);
-    const int iters = only_qp ? 1 : cfg.sqp_iters;
+    const bool dual = !ctx->single_stream && !c.only_qp && c.B * NARM >= 512;
+    const Parts parts = split(ctx, c, dual ? 2 : 1);
+    if (int rc = fork_parts(ctx, parts)) return rc;
+    for (const Part &p : parts)
+        hipLaunchKernelGGL((k_init_m<NSEG, NARM>), dim3(p.B), dim3(D::NT), l_m, p.stream, cfg, p.ws.model, p.ws, p.xch, p.wx, p.wu, p.wT, c.reguess);
+    const int iters = c.only_qp ? 1 : cfg.sqp_iters;
     for (int it = 0; it < iters; it++) {
-        for (int h = 0; h < nhalf; h++) {
-            hipEvent_t *ev = (ctx->timing && !ctx->capturing) ? next_events(ctx) : nullptr;
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], sh[h]));
-            const int grid = NARM == 1 ? Bh[h] : ((Bh[h] + 7) / 8) * 16;       // arm workgroups of one OCP are 8 apart (k_qp3)
-            double *fh = ctx->d_fac + (size_t)boff[h] * NARM * Qp3<NSEG>::FAC;
-            hipLaunchKernelGGL((k_qp3f<NSEG, NARM>), dim3(grid), dim3(1024), l_qp3f, sh[h], cfg, wh[h], ctx->d_pat, xh[h], Bh[h], fh);
-            hipLaunchKernelGGL((k_qp3<NSEG, NARM>), dim3(grid), dim3(512), l_qp3, sh[h], cfg, wh[h], ctx->d_pat, xh[h], Bh[h], (const double *)fh);
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], sh[h]));
-            if (only_qp) continue;
-            hipLaunchKernelGGL((k_step_m<NSEG, NARM>), dim3(Bh[h]), dim3(D::NT), l_m, sh[h], cfg, wh[h].model, wh[h], xh[h],
-                               it == iters - 1 ? 1 : 0, it, ox[h], ou[h], oT[h], oi[h]);
+        for (const Part &p : parts) {
+            hipEvent_t *ev = (ctx->timing && !c.capturing) ? next_events(ctx) : nullptr;
+            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], p.stream));
+            const int grid = NARM == 1 ? p.B : ((p.B + 7) / 8) * 16;       // arm workgroups of one OCP are 8 apart (k_qp3)
+            double *fh = ctx->d_fac + (size_t)p.b0 * NARM * Qp3<NSEG>::FAC;
+            hipLaunchKernelGGL((k_qp3f<NSEG, NARM>), dim3(grid), dim3(1024), l_qp3f, p.stream, cfg, p.ws, ctx->d_pat, p.xch, p.B, fh);
+            hipLaunchKernelGGL((k_qp3<NSEG, NARM>), dim3(grid), dim3(512), l_qp3, p.stream, cfg, p.ws, ctx->d_pat, p.xch, p.B, (const double *)fh);
+            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], p.stream));
+            if (c.only_qp) continue;
+            hipLaunchKernelGGL((k_step_m<NSEG, NARM>), dim3(p.B), dim3(D::NT), l_m, p.stream, cfg, p.ws.model, p.ws, p.xch,
+                               it == iters - 1 ? 1 : 0, it, p.sx, p.su, p.sT, p.info);
         }
     }
-    if (nhalf > 1) { HIPCHK(ctx, hipEventRecord(ctx->ev_join[0], sh[1])); HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0)); }
+    if (int rc = join_parts(ctx, parts)) return rc;
     HIPCHK(ctx, hipGetLastError());
     return MPCMP_OK;
 }
 
-static int solve_dispatch(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx,
-                          const double *d_wu, const double *d_wT, double *d_sx, double *d_su, double *d_sT,
-                          mpcmp_info *d_info, hipStream_t st, int only_qp, int reguess = 0) {
+static int solve_dispatch(mpcmp_ctx *ctx, const SolveCall &c) {
     if (!ctx) return MPCMP_EINVAL;
-    if (B < 1) return MPCMP_EINVAL;
-    if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
-    if (!ctx->rh_step) if (int rc = time_rows_ok(ctx, B)) return rc;
-    if (!ctx->rh_step) if (int rc = bound_rows_ok(ctx, B)) return rc;
-    if (!d_x0 || !d_xf) return MPCMP_EINVAL;
-    if ((d_wx != nullptr) != (d_wu != nullptr) || (d_wx != nullptr) != (d_wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
+    if (c.B < 1) return MPCMP_EINVAL;
+    if (c.B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
+    if (int rc = c.rh_step ? rows_ok(ctx, c.B, PAYLOAD_ROWS) : solve_rows_ok(ctx, c.B)) return rc;
+    if (!c.x0 || !c.xf) return MPCMP_EINVAL;
+    if (int rc = warm_all_or_none(ctx, c.wx, c.wu, c.wT)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (ctx->narm == 2) {
-        if (only_qp) { ctx->err = "mpcmp_qp_batch is defined for single-arm contexts only"; return MPCMP_EINVAL; }
-        if (!d_wx) { ctx->err = "multi-arm solves need a warm start (mpcmp_warm_start_jerk_batch)"; return MPCMP_EINVAL; }
-        if (ctx->nseg == 6) return solve_impl_m<6, 2>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
-        return solve_impl_m<8, 2>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
+        if (c.only_qp) { ctx->err = "mpcmp_qp_batch is defined for single-arm contexts only"; return MPCMP_EINVAL; }
+        if (!c.wx) { ctx->err = "multi-arm solves need a warm start (mpcmp_warm_start_jerk_batch)"; return MPCMP_EINVAL; }
+        return ctx->nseg == 6 ? solve_impl_m<6, 2>(ctx, c) : solve_impl_m<8, 2>(ctx, c);
     }
     switch (ctx->nseg) {
-        case 1: return solve_impl<1>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
-        case 2: return solve_impl<2>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
-        case 4: return solve_impl<4>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
-        case 6: return solve_impl<6>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
-        case 8: return solve_impl_m<8, 1>(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, only_qp, reguess);
+        case 1: return solve_impl<1>(ctx, c);
+        case 2: return solve_impl<2>(ctx, c);
+        case 4: return solve_impl<4>(ctx, c);
+        case 6: return solve_impl<6>(ctx, c);
+        case 8: return solve_impl_m<8, 1>(ctx, c);
     }
     return MPCMP_EINVAL;
+}
+
+// ---- the host-buffer entry points' staging: the context's d_x0 / d_xf / d_w* in, d_s* / d_info (or another triple) out ----
+static int upload_problems(mpcmp_ctx *ctx, size_t B, const double *x0, const double *xf, const double *wx, const double *wu, const double *wT, hipStream_t st) {
+    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    if (wx) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wx, wx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wu, wu, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wT, wT, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    }
+    return MPCMP_OK;
+}
+// (every host pointer may be NULL: not wanted)
+static int download_trajectories(mpcmp_ctx *ctx, size_t B, const double *d_x, const double *d_u, const double *d_T, double *x, double *u, double *T,
+                                 mpcmp_info *info, hipStream_t st) {
+    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+    if (x) HIPCHK(ctx, hipMemcpyAsync(x, d_x, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
+    if (u) HIPCHK(ctx, hipMemcpyAsync(u, d_u, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
+    if (T) HIPCHK(ctx, hipMemcpyAsync(T, d_T, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_info, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    return MPCMP_OK;
+}
+// the solve of the staged problems into the staged outputs; warm: with the staged start guess
+static SolveCall staged_call(const mpcmp_ctx *ctx, int B, bool warm, hipStream_t st) {
+    SolveCall c;
+    c.B = B; c.x0 = ctx->d_x0; c.xf = ctx->d_xf;
+    if (warm) { c.wx = ctx->d_wx; c.wu = ctx->d_wu; c.wT = ctx->d_wT; }
+    c.sx = ctx->d_sx; c.su = ctx->d_su; c.sT = ctx->d_sT; c.info = ctx->d_info; c.stream = st;
+    return c;
 }
 
 extern "C" int mpcmp_solve_batch_device(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf,
                                         const double *d_wx, const double *d_wu, const double *d_wT, double *d_sx,
                                         double *d_su, double *d_sT, mpcmp_info *d_info, void *hip_stream) {
     if (!d_sx || !d_su || !d_sT) return MPCMP_EINVAL;
-    return solve_dispatch(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, (hipStream_t)hip_stream, 0);
+    return solve_dispatch(ctx, SolveCall{B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, (hipStream_t)hip_stream});
 }
 
 extern "C" int mpcmp_solve_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *wx,
@@ -1352,27 +1400,13 @@ extern "C" int mpcmp_solve_batch(mpcmp_ctx *ctx, int B, const double *x0, const 
     if (!ctx || !x0 || !xf || !sx || !su || !sT) return MPCMP_EINVAL;
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
-    if (int rc = time_rows_ok(ctx, B)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = solve_rows_ok(ctx, B)) return rc;
+    if (int rc = warm_all_or_none(ctx, wx, wu, wT)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    const bool warm = wx && wu && wT;
-    if (warm) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wx, wx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wu, wu, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wT, wT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    } else if (wx || wu || wT) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
-    if (int rc = solve_dispatch(ctx, B, ctx->d_x0, ctx->d_xf, warm ? ctx->d_wx : nullptr, warm ? ctx->d_wu : nullptr,
-                                warm ? ctx->d_wT : nullptr, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, st, 0))
-        return rc;
-    HIPCHK(ctx, hipMemcpyAsync(sx, ctx->d_sx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(su, ctx->d_su, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(sT, ctx->d_sT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_info, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, wx, wu, wT, st)) return rc;
+    if (int rc = solve_dispatch(ctx, staged_call(ctx, B, wx != nullptr, st))) return rc;
+    if (int rc = download_trajectories(ctx, B, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }
@@ -1383,16 +1417,16 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     if (!ctx || !x0 || !xf || !wx || !wu || !wT || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
-    if (int rc = time_rows_ok(ctx, B)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, TIME_ROWS)) return rc;
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, n = ctx->n;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
     // k_init alone: the built-in initialiser writes the iterate z = [xs|us|T]
-    const mpcmp_config save = run_config(ctx);
-    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx); w.bnd = run_bounds(ctx);
+    const SolveCall plain;
+    const mpcmp_config save = run_config(ctx, plain);
+    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx, plain); w.bnd = run_bounds(ctx, plain);
 #define LAUNCH_INIT(NS) { const size_t l = InitLds<NS>::size * sizeof(double); \
         hipLaunchKernelGGL(k_init<NS>, dim3(B), dim3(Dim<NS>::NT), l, st, save, w, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0); }
     switch (ctx->nseg) { case 1: LAUNCH_INIT(1) break; case 2: LAUNCH_INIT(2) break; case 4: LAUNCH_INIT(4) break; case 6: LAUNCH_INIT(6) break;
@@ -1480,10 +1514,8 @@ static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, c
     if (B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (n_groups < 0 || n_groups > ctx->max_batch) { ctx->err = "mpcmp_solve_batch_synced: n_groups must be in [0, max_batch]"; return MPCMP_EINVAL; }
-    if ((wx != nullptr) != (wu != nullptr) || (wx != nullptr) != (wT != nullptr)) { ctx->err = "warm_x, warm_u, warm_T must be all given or all NULL"; return MPCMP_EINVAL; }
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
-    if (int rc = time_rows_ok(ctx, B)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = warm_all_or_none(ctx, wx, wu, wT)) return rc;
+    if (int rc = solve_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (!ctx->d_sg_group) {            // first use
         const size_t M = ctx->max_batch, N = ctx->N;
@@ -1502,27 +1534,28 @@ static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, c
     return MPCMP_OK;
 }
 
-// pass 1, the group times, the pass-2 mask / rows / start guess, pass 2: all on stream st, no host round trip
-static int synced_enqueue(mpcmp_ctx *ctx, int B, const double *d_x0, const double *d_xf, const double *d_wx, const double *d_wu, const double *d_wT,
-                          const int *d_group, int n_groups, double *d_sx, double *d_su, double *d_sT, mpcmp_info *d_info, double *d_gT, hipStream_t st) {
-    if (int rc = solve_dispatch(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, st, 0)) return rc;
+// pass 1 (the call as given), the group times, the pass-2 mask / rows / start guess, pass 2: all on the call's stream, no host round trip
+static int synced_enqueue(mpcmp_ctx *ctx, const SolveCall &pass1, const int *d_group, int n_groups, double *d_gT) {
+    const int B = pass1.B;
+    hipStream_t st = pass1.stream;
+    if (int rc = solve_dispatch(ctx, pass1)) return rc;
     const int G = n_groups > 0 ? n_groups : 1;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_sg_key, 0, sizeof(unsigned long long) * G, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_sg_count, 0, sizeof(int) * G, st));
-    hipLaunchKernelGGL(k_sync_tmax, dim3((B + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)d_sT,
+    hipLaunchKernelGGL(k_sync_tmax, dim3((B + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)pass1.sT,
                        ctx->d_sg_key, ctx->d_sg_count);
     const int np = B > n_groups ? B : n_groups;
-    hipLaunchKernelGGL(k_sync_prepare, dim3((np + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)d_sT,
+    hipLaunchKernelGGL(k_sync_prepare, dim3((np + 255) / 256), dim3(256), 0, st, B, d_group, n_groups, (const int *)ctx->ws.status, (const double *)pass1.sT,
                        (const unsigned long long *)ctx->d_sg_key, (const int *)ctx->d_sg_count, d_gT, ctx->d_sg_skip, ctx->d_sg_rows, ctx->d_sg_Tn,
                        ctx->d_sg_status);
     HIPCHK(ctx, hipGetLastError());
-    if (int rc = time_scale_enqueue(ctx, B, d_x0, d_xf, d_sx, d_su, d_sT, ctx->d_sg_Tn, ctx->d_sg_skip, ctx->d_sg_wx, ctx->d_sg_wu, ctx->d_sg_wT, st))
+    if (int rc = time_scale_enqueue(ctx, B, pass1.x0, pass1.xf, pass1.sx, pass1.su, pass1.sT, ctx->d_sg_Tn, ctx->d_sg_skip, ctx->d_sg_wx, ctx->d_sg_wu, ctx->d_sg_wT, st))
         return rc;
     // pass 2: every slot is launched; the ones not re-solved return at once (WS::retired) and keep their pass-1 outputs
-    ctx->tw_pass = ctx->d_sg_rows; ctx->sync_skip = ctx->d_sg_skip;
-    const int rc = solve_dispatch(ctx, B, d_x0, d_xf, ctx->d_sg_wx, ctx->d_sg_wu, ctx->d_sg_wT, d_sx, d_su, d_sT, d_info, st, 0);
-    ctx->tw_pass = nullptr; ctx->sync_skip = nullptr;
-    if (rc) return rc;
+    SolveCall pass2 = pass1;
+    pass2.wx = ctx->d_sg_wx; pass2.wu = ctx->d_sg_wu; pass2.wT = ctx->d_sg_wT;
+    pass2.tw_rows = ctx->d_sg_rows; pass2.skip = ctx->d_sg_skip;
+    if (int rc = solve_dispatch(ctx, pass2)) return rc;
     // (at N = 25 the skipped slots' QP kernels ran in pass 2 and added to their status words: the next solve sees pass 1's, as after a plain solve)
     hipLaunchKernelGGL(k_sync_restore, dim3((B + 255) / 256), dim3(256), 0, st, B, (const int *)ctx->d_sg_skip, (const int *)ctx->d_sg_status,
                        ctx->ws.status);
@@ -1535,8 +1568,8 @@ extern "C" int mpcmp_solve_batch_synced_device(mpcmp_ctx *ctx, int B, const doub
                                                mpcmp_info *d_info, double *d_group_T, void *hip_stream) {
     if (!ctx || !d_x0 || !d_xf || !d_group || !d_sx || !d_su || !d_sT) return MPCMP_EINVAL;
     if (int rc = synced_check(ctx, B, n_groups, d_wx, d_wu, d_wT)) return rc;
-    return synced_enqueue(ctx, B, d_x0, d_xf, d_wx, d_wu, d_wT, d_group, n_groups, d_sx, d_su, d_sT, d_info, d_group_T ? d_group_T : ctx->d_sg_T,
-                          (hipStream_t)hip_stream);
+    return synced_enqueue(ctx, SolveCall{B, d_x0, d_xf, d_wx, d_wu, d_wT, d_sx, d_su, d_sT, d_info, (hipStream_t)hip_stream}, d_group, n_groups,
+                          d_group_T ? d_group_T : ctx->d_sg_T);
 }
 
 extern "C" int mpcmp_solve_batch_synced(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *wx, const double *wu, const double *wT,
@@ -1547,24 +1580,11 @@ extern "C" int mpcmp_solve_batch_synced(mpcmp_ctx *ctx, int B, const double *x0,
         if (group[i] < -1 || group[i] >= n_groups) {
             ctx->err = "mpcmp_solve_batch_synced: group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
         }
-    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, wx, wu, wT, st)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_sg_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
-    const bool warm = wx != nullptr;
-    if (warm) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wx, wx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wu, wu, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_wT, wT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    }
-    if (int rc = synced_enqueue(ctx, B, ctx->d_x0, ctx->d_xf, warm ? ctx->d_wx : nullptr, warm ? ctx->d_wu : nullptr, warm ? ctx->d_wT : nullptr,
-                                ctx->d_sg_group, n_groups, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, ctx->d_sg_T, st))
-        return rc;
-    HIPCHK(ctx, hipMemcpyAsync(sx, ctx->d_sx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(su, ctx->d_su, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(sT, ctx->d_sT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_info, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    if (int rc = synced_enqueue(ctx, staged_call(ctx, B, wx != nullptr, st), ctx->d_sg_group, n_groups, ctx->d_sg_T)) return rc;
+    if (int rc = download_trajectories(ctx, B, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
     if (group_T && n_groups > 0) HIPCHK(ctx, hipMemcpyAsync(group_T, ctx->d_sg_T, sizeof(double) * n_groups, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
@@ -1659,18 +1679,14 @@ extern "C" int mpcmp_warm_start_jerk_lim_batch(mpcmp_ctx *ctx, int B, const doub
     if (!ctx || !x0 || !xf || !jmax || !wx || !wu || !wT || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
     TmpBuf tb(ctx, (acc0 || accT) ? 14 * (size_t)B * sizeof(double) : 0);
     const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
     if (int rc = stage_acc(ctx, tb, B, acc0, accT, st, &da0, &daT)) return rc;
     if (int rc = warm_start_jerk_device(ctx, B, ctx->d_x0, ctx->d_xf, da0, daT, vmax, amax, jmax, ctx->d_wx, ctx->d_wu, ctx->d_wT, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(wx, ctx->d_wx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(wu, ctx->d_wu, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(wT, ctx->d_wT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    if (int rc = download_trajectories(ctx, B, ctx->d_wx, ctx->d_wu, ctx->d_wT, wx, wu, wT, nullptr, st)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }
@@ -1697,8 +1713,7 @@ extern "C" int mpcmp_jerk_trajectory_lim_batch(mpcmp_ctx *ctx, int B, const doub
     double *dout = tb.get<double>(cnt);
     if (!dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
     const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
     if (int rc = stage_acc(ctx, tb, B, acc0, accT, st, &da0, &daT)) return rc;
@@ -1732,8 +1747,7 @@ extern "C" int mpcmp_jerk_point_lim_batch(mpcmp_ctx *ctx, int B, const double *x
     double *dt = tb.get<double>(B), *dout = tb.get<double>(28 * (size_t)B);
     if (!dt || !dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(dt, time, sizeof(double) * B, hipMemcpyHostToDevice, st));
     const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
@@ -1760,7 +1774,7 @@ extern "C" int mpcmp_mpc_point_batch(mpcmp_ctx *ctx, int B, const double *sx, co
                                      double *out) {
     if (!ctx || !sx || !su || !sT || !time || !out || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N;
     TmpBuf tb(ctx, (21 * N + 2 + 28) * (size_t)B * sizeof(double));
@@ -1786,20 +1800,13 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
     if (!ctx || !x0 || !xf || !xs || !us || !T || !p || !y || B < 1) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
-    if (int rc = time_rows_ok(ctx, B)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = solve_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wx, xs, sizeof(double) * 14 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wu, us, sizeof(double) * 7 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_wT, T, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = solve_dispatch(ctx, B, ctx->d_x0, ctx->d_xf, ctx->d_wx, ctx->d_wu, ctx->d_wT, ctx->d_sx, ctx->d_su,
-                                ctx->d_sT, nullptr, st, 1))
-        return rc;
+    if (int rc = upload_problems(ctx, B, x0, xf, xs, us, T, st)) return rc;
+    SolveCall c = staged_call(ctx, B, true, st);
+    c.info = nullptr; c.only_qp = 1;
+    if (int rc = solve_dispatch(ctx, c)) return rc;
     HIPCHK(ctx, hipMemcpyAsync(p, ctx->ws.p, sizeof(double) * ctx->n * B, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(y, ctx->ws.y, sizeof(double) * ctx->mn * B, hipMemcpyDeviceToHost, st));
     if (iters) HIPCHK(ctx, hipMemcpyAsync(iters, ctx->ws.qpit, sizeof(int) * B, hipMemcpyDeviceToHost, st));
@@ -1811,7 +1818,7 @@ extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const dou
 // leaf kernels
 extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const double *qd, const double *qdd, double *tau) {
     if (!ctx || n < 1 || !q || !qd || !qdd || !tau) return MPCMP_EINVAL;
-    if (int rc = payload_rows_ok(ctx, n)) return rc;
+    if (int rc = rows_ok(ctx, n, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TmpBuf tb(ctx, 28 * (size_t)n * sizeof(double));
     double *dq = tb.get<double>(7 * (size_t)n), *dv = tb.get<double>(7 * (size_t)n), *da = tb.get<double>(7 * (size_t)n), *dt = tb.get<double>(7 * (size_t)n);
@@ -1831,7 +1838,7 @@ extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const do
 
 extern "C" int mpcmp_eval_constraints_batch(mpcmp_ctx *ctx, int n, const double *x, const double *u, double *g, double *G) {
     if (!ctx || n < 1 || !x || !u || !g || !G) return MPCMP_EINVAL;
-    if (int rc = payload_rows_ok(ctx, n)) return rc;
+    if (int rc = rows_ok(ctx, n, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TmpBuf tb(ctx, (14 + 7 + 8 + 176) * (size_t)n * sizeof(double));
     double *dx = tb.get<double>(14 * (size_t)n), *du = tb.get<double>(7 * (size_t)n), *dg = tb.get<double>(8 * (size_t)n), *dG = tb.get<double>(176 * (size_t)n);
@@ -1857,7 +1864,7 @@ extern "C" int mpcmp_sample_batch_device(mpcmp_ctx *ctx, int B, const double *d_
                                          int n_pts, double *d_out, void *hip_stream) {
     if (!ctx || B < 1 || n_pts < 1 || !d_sx || !d_su || !d_sT || !d_out) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long total = (long)B * (n_pts + 1);
     int ms;
@@ -1870,7 +1877,7 @@ extern "C" int mpcmp_sample_batch_device(mpcmp_ctx *ctx, int B, const double *d_
 
 extern "C" int mpcmp_sample_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_pts, double *out) {
     if (!ctx || B < 1 || n_pts < 1 || !sx || !su || !sT || !out) return MPCMP_EINVAL;
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t N = ctx->N, np = (size_t)B * (n_pts + 1) * 29;
     TmpBuf tb(ctx, (21 * N * B + B + np) * sizeof(double));
@@ -1892,7 +1899,7 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
                                       int n_pts, double *out) {
     if (!ctx || B < 1 || n_pts < 1 || !sx || !su || !sT || !xf || !out) return MPCMP_EINVAL;
     SINGLE_ARM_ONLY(ctx);
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     // the kernel keeps the n_pts+1 samples of one trajectory (28 doubles each) in LDS: 160 KB per workgroup on gfx950
     if (sizeof(double) * 28 * (size_t)(n_pts + 1) > 150 * 1024) { ctx->err = "mpcmp_traj_stats_batch: n_pts must be <= 684 (the samples of one trajectory are held in LDS)"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1997,16 +2004,11 @@ extern "C" int mpcmp_set_obstacles(mpcmp_ctx *ctx, int n_sets, int n_obs, const 
 extern "C" int mpcmp_set_obstacles_device(mpcmp_ctx *ctx, int n_sets, int n_obs, const mpcmp_obstacle *d_obs, void *hip_stream) {
     if (int rc = obstacles_check(ctx, n_sets, n_obs, d_obs)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n_sets > 0 && n_obs > 0) {
-        // after the caller's work on its stream (which writes d_obs) and the context's own, before the context's later work; the caller's later
-        // work (a clearance check on that stream) waits for the copy
-        hipStream_t cs = (hipStream_t)hip_stream;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_clr_obs, d_obs, sizeof(mpcmp_obstacle) * n_sets * n_obs, hipMemcpyDeviceToDevice, ctx->stream));
-        HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
-        HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
-    }
+    if (n_sets > 0 && n_obs > 0)      // (the caller's later work: a clearance check on its stream, which waits for the copy)
+        if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_clr_obs, d_obs, sizeof(mpcmp_obstacle) * n_sets * n_obs, hipMemcpyDeviceToDevice, st));
+                return MPCMP_OK;
+            })) return rc;
     ctx->clr_sets = n_obs > 0 ? n_sets : 0; ctx->clr_nobs = n_sets > 0 ? n_obs : 0;
     return MPCMP_OK;
 }
@@ -2121,7 +2123,7 @@ static int pose_targets_check(mpcmp_ctx *ctx, int B, int arm, const double *R, c
 extern "C" int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_R, const double *d_p, const double *d_twist,
                                                int S, const double *d_seeds, const double *d_q_ref, double *d_xf, mpcmp_ik_info *d_info, void *hip_stream) {
     if (int rc = pose_targets_check(ctx, B, arm, d_R, d_p, S, d_seeds, d_xf)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     IkBounds bd;
     for (int j = 0; j < 7; j++) { bd.lq[j] = ctx->cfg.lbx[j]; bd.uq[j] = ctx->cfg.ubx[j]; bd.lv[j] = ctx->cfg.lbx[7 + j]; bd.uv[j] = ctx->cfg.ubx[7 + j]; }
@@ -2137,7 +2139,7 @@ extern "C" int mpcmp_pose_targets_batch_device(mpcmp_ctx *ctx, int B, int arm, c
 extern "C" int mpcmp_pose_targets_batch(mpcmp_ctx *ctx, int B, int arm, const double *R, const double *p, const double *twist,
                                         int S, const double *seeds, const double *q_ref, double *xf, mpcmp_ik_info *info) {
     if (int rc = pose_targets_check(ctx, B, arm, R, p, S, seeds, xf)) return rc;
-    if (int rc = bound_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
     const size_t nb = B, nx = ctx->nx;
     const struct { const double *v; size_t n; } in[5] = {{R, 9 * nb}, {p, 3 * nb}, {twist, 6 * nb}, {seeds, 7 * nb * S}, {q_ref, 7 * nb}};
     for (const auto &a : in)
@@ -2196,7 +2198,7 @@ extern "C" int mpcmp_reset_multipliers(mpcmp_ctx *ctx) {
 extern "C" int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const double *xf) {
     if (!ctx || !x0 || !xf || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
-    if (int rc = payload_rows_ok(ctx, B)) return rc;
+    if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     if (ctx->bnd_rows > 0) { ctx->err = "mpcmp_rh_init: the receding-horizon driver does not read bound rows (clear them: mpcmp_set_bounds(ctx, 0, NULL))"; return MPCMP_EINVAL; }
     if (ctx->tw_rows > 0) { ctx->err = "mpcmp_rh_init: the receding-horizon driver does not read final-time rows (clear them: mpcmp_set_time_windows(ctx, 0, NULL, NULL))"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2205,16 +2207,15 @@ extern "C" int mpcmp_rh_init(mpcmp_ctx *ctx, int B, const double *x0, const doub
     HIPCHK(ctx, hipMemsetAsync(ctx->ws.status, 0, sizeof(*ctx->ws.status) * ctx->max_batch, st));
     HIPCHK(ctx, hipMemsetAsync(ctx->d_retired, 0, sizeof(int) * ctx->max_batch, st));                       // nobody has arrived
     HIPCHK(ctx, hipMemsetAsync(ctx->d_rh_count, 0, 2 * sizeof(unsigned long long), st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_x0, x0, sizeof(double) * ctx->nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_xf, xf, sizeof(double) * ctx->nx * B, hipMemcpyHostToDevice, st));
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));
     ctx->rh_B = B; ctx->rh_first = true;
-    if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
-    if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
+    drop_rh_graph(ctx);
     return MPCMP_OK;
 }
 
-static int rh_enqueue_step(mpcmp_ctx *ctx, double dt, bool first, hipStream_t st) {
+// capturing: st is being captured into the step graph
+static int rh_enqueue_step(mpcmp_ctx *ctx, double dt, bool first, hipStream_t st, bool capturing) {
     const int B = ctx->rh_B;
     // The driver's start guess, every step, from every instance's current state: the jerk-limited time-synchronised trajectory the reference takes from
     // Ruckig for solve_trajectory(true) (motionPlanner.cpp:146-175), with the velocity / acceleration limits of the configuration and the jerk
@@ -2228,11 +2229,11 @@ static int rh_enqueue_step(mpcmp_ctx *ctx, double dt, bool first, hipStream_t st
     if (int rc = warm_start_jerk_device(ctx, B, ctx->d_x0, ctx->d_xf, nullptr, nullptr, nullptr, nullptr, jm, ctx->d_wx, ctx->d_wu, ctx->d_wT, st,
                                         first ? nullptr : ctx->ws.status, MPCMP_ST_NO_GUESS))
         return rc;
-    const double *wx = first ? ctx->d_wx : ctx->d_sx, *wu = first ? ctx->d_wu : ctx->d_su, *wT = first ? ctx->d_wT : ctx->d_sT;
-    ctx->rh_step = true;           // the driver's defaults of the start flags (run_config) and the retired instances (WS.retired)
-    const int rc = solve_dispatch(ctx, B, ctx->d_x0, ctx->d_xf, wx, wu, wT, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, st, 0, first ? 0 : 1);
-    ctx->rh_step = false;
-    if (rc) return rc;
+    SolveCall c = staged_call(ctx, B, true, st);
+    if (!first) { c.wx = ctx->d_sx; c.wu = ctx->d_su; c.wT = ctx->d_sT; c.reguess = 1; }
+    c.rh_step = true;              // the driver's defaults of the start flags (run_config) and the retired instances (WS::retired)
+    c.capturing = capturing;
+    if (int rc = solve_dispatch(ctx, c)) return rc;
     hipLaunchKernelGGL(k_advance, dim3((B + 255) / 256), dim3(256), 0, st, ctx->nseg, ctx->nx, B, dt, ctx->cfg.eps_target, ctx->d_sx, ctx->d_sT,
                        ctx->ws.status, ctx->d_xf, ctx->d_x0, ctx->d_retired, ctx->d_info, ctx->d_rh_count);
     HIPCHK(ctx, hipGetLastError());
@@ -2245,18 +2246,15 @@ extern "C" int mpcmp_rh_run(mpcmp_ctx *ctx, int steps, double dt, int use_graph)
     hipStream_t st = ctx->stream;
     int done = 0;
     if (ctx->rh_first) {                       // first solve: built-in initialiser, not part of the graph
-        if (int rc = rh_enqueue_step(ctx, dt, true, st)) return rc;
+        if (int rc = rh_enqueue_step(ctx, dt, true, st, false)) return rc;
         ctx->rh_first = false; done = 1;
     }
     if (use_graph && steps - done > 0) {
         if (!ctx->rh_exec || ctx->rh_dt != dt) {
-            if (ctx->rh_exec) { (void)hipGraphExecDestroy(ctx->rh_exec); ctx->rh_exec = nullptr; }
-            if (ctx->rh_graph) { (void)hipGraphDestroy(ctx->rh_graph); ctx->rh_graph = nullptr; }
-            ctx->capturing = true;
+            drop_rh_graph(ctx);
             HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const int rc = rh_enqueue_step(ctx, dt, false, st);
+            const int rc = rh_enqueue_step(ctx, dt, false, st, true);
             hipError_t e = hipStreamEndCapture(st, &ctx->rh_graph);
-            ctx->capturing = false;
             if (rc) return rc;
             HIPCHK(ctx, e);
             HIPCHK(ctx, hipGraphInstantiate(&ctx->rh_exec, ctx->rh_graph, nullptr, nullptr, 0));
@@ -2265,7 +2263,7 @@ extern "C" int mpcmp_rh_run(mpcmp_ctx *ctx, int steps, double dt, int use_graph)
         for (; done < steps; done++) HIPCHK(ctx, hipGraphLaunch(ctx->rh_exec, st));
     } else {
         for (; done < steps; done++)
-            if (int rc = rh_enqueue_step(ctx, dt, false, st)) return rc;
+            if (int rc = rh_enqueue_step(ctx, dt, false, st, false)) return rc;
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
@@ -2322,27 +2320,16 @@ extern "C" int mpcmp_rh_update(mpcmp_ctx *ctx, int n, const int *idx, const doub
 extern "C" int mpcmp_rh_update_device(mpcmp_ctx *ctx, int n, const int *d_idx, const double *d_x, const double *d_xf, int flags, void *hip_stream) {
     if (int rc = rh_update_check(ctx, n, d_idx, d_x, d_xf, flags)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // after the caller's work on its stream (which writes the inputs), before the next step on ctx->stream; the caller's later work waits for the
-    // update's reads of its buffers
-    hipStream_t cs = (hipStream_t)hip_stream;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[0], cs));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upd[0], 0));
-    if (int rc = rh_update_enqueue(ctx, n, d_idx, d_x, d_xf, flags, ctx->stream)) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_upd[1], ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->ev_upd[1], 0));
-    return MPCMP_OK;
+    return with_caller_stream(ctx, hip_stream, [&](hipStream_t st) { return rh_update_enqueue(ctx, n, d_idx, d_x, d_xf, flags, st); });
 }
 
 extern "C" int mpcmp_rh_get(mpcmp_ctx *ctx, double *x0_now, double *sx, double *su, double *sT, mpcmp_info *info) {
     if (!ctx || ctx->rh_B < 1) return MPCMP_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t B = ctx->rh_B, N = ctx->N;
+    const size_t B = ctx->rh_B;
     hipStream_t st = ctx->stream;
     if (x0_now) HIPCHK(ctx, hipMemcpyAsync(x0_now, ctx->d_x0, sizeof(double) * ctx->nx * B, hipMemcpyDeviceToHost, st));
-    if (sx) HIPCHK(ctx, hipMemcpyAsync(sx, ctx->d_sx, sizeof(double) * ctx->nx * N * B, hipMemcpyDeviceToHost, st));
-    if (su) HIPCHK(ctx, hipMemcpyAsync(su, ctx->d_su, sizeof(double) * ctx->nu * N * B, hipMemcpyDeviceToHost, st));
-    if (sT) HIPCHK(ctx, hipMemcpyAsync(sT, ctx->d_sT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, ctx->d_info, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    if (int rc = download_trajectories(ctx, B, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }
@@ -2389,8 +2376,7 @@ extern "C" int mpcmp_kernel_timing(mpcmp_ctx *ctx, int reset, const char **name,
     }
     ctx->ev_used = 0;
     ctx->timing = true;            // event recording starts with the first call (bench.py calls it once before the timed region)
-    // (the loop kernel KSel picks: MPCMP_FORCE_V1 sends num_seg 2 and 4 to the generic k_qp)
-    if (name) *name = (ctx->nseg == 6 && ctx->narm == 1 && ctx->qp19 == 5) ? "k_qp5" : ctx->nseg >= 6 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 3 ? "k_qp3" : (ctx->nseg == 4 && ctx->qp13 == 4 ? "k_qp4" : ((ctx->nseg == 2 || ctx->nseg == 4) && !ctx->force_v1 ? "k_qp2" : "k_qp")));
+    if (name) *name = ctx->loop_kernel;
     if (ms_total) *ms_total = ctx->qp_ms;
     if (launches) *launches = ctx->qp_launches;
     if (reset) { ctx->qp_ms = 0.0; ctx->qp_launches = 0; }
