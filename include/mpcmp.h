@@ -464,6 +464,83 @@ int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sol_T, const m
 int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sol_T, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
                                     const int *d_group, int n_groups, int *d_chosen, void *hip_stream);
 
+/* ---- via-point routes: plan, join, sample and check multi-leg moves ----
+ * A route is x0 -> via_0 -> .. -> via_{M-1} -> xf, passed without stopping.  With the joint state (q, qd) fixed at a via, the legs on either side are
+ * independent minimum-time OCPs: a batch of B routes with M >= 0 vias is a batch of L = B (M + 1) ordinary problems, and LEG SLOT l = b (M + 1) + m
+ * is leg m of route b.  The row tables (payloads, final-time windows, bounds) and the per-problem obstacle sets keep their one rule, row l applies to
+ * batch slot l: for routes the batch slot is the leg slot, so a route under its own limits sets its row M + 1 times.  No solve kernel changes.
+ * L > max_batch: MPCMP_EINVAL, nothing written.  All arithmetic is FP64 and every sum runs sequentially in leg order: a route's records do not depend
+ * on the batch around it and are bitwise reproducible.  A context that never calls one of these entry points behaves bit for bit as before.
+ * Points and velocities (nq = 7 narm): P_0 = q(x0[b]), P_i = via[b][i-1], P_{M+1} = q(xf[b]); V_0 = qd(x0[b]), V_{M+1} = qd(xf[b]); leg m runs from
+ * (P_m, V_m) to (P_{m+1}, V_{m+1}).  V_1 .. V_M are via_qd when it is given (copied bit for bit), otherwise the CHORD RULE: with a = P_i - P_{i-1},
+ * b = P_{i+1} - P_i, per column j
+ *   vlim_j = min(ubx[7 + j], -lbx[7 + j]),  alim_j = min(ubu[j], -lbu[j])     of the bound row of the leg slot that STARTS at the via, or of the
+ *                                                                              configuration without rows (per-arm tables: every arm's 7 columns)
+ *   d_j = 0.5 (a_j + b_j)  if a_j b_j > 0 and vlim_j > 0 and alim_j > 0,  else 0   (a joint that reverses or rests at the via; a locked joint)
+ *   s   = min over the j with d_j != 0 of  min(vlim_j, sqrt(2 alim_j min(|a_j|, |b_j|))) / |d_j|
+ *   V_i = speed_b s d,  each entry then held to |V_j| <= vlim_j (against the rounding of the product);  V_i = 0 if every d_j is 0, or if s is
+ *         infinite (every moving joint without limits: nothing to scale to)
+ * The rule keeps the direction of the tangent; no joint passes faster than its limit, or faster than the speed it could reach over the shorter
+ * neighbouring chord at its acceleration limit.  With M == 0 the one leg is (x0, xf) unchanged. */
+/* the chord rule on the host (no GPU needed; the function the kernel runs): p_prev, p_via, p_next, v [7 narm]; speed in [0, 1] */
+int mpcmp_route_via_velocity(const double *p_prev, const double *p_via, const double *p_next, const mpcmp_bounds *row, int narm, double speed,
+                             double *v);
+/* x0, xf [B][14 narm]; via [B][M][7 narm] (NULL with M == 0); via_qd [B][M][7 narm] or NULL; speed [B] or NULL (= 1).  leg_x0, leg_xf [L][14 narm];
+ * via_qd_out [B][M][7 narm] may be NULL.  The host-pointer variant returns MPCMP_EINVAL, writing nothing, for B < 1, M < 0, L > max_batch, a required
+ * pointer NULL, a value that is not finite, a speed outside [0, 1], fewer bound rows than leg slots; the device variant does not read its inputs on
+ * the host.  Both return MPCMP_EINVAL after mpcmp_rh_init. */
+int mpcmp_route_legs(mpcmp_ctx *ctx, int B, int M, const double *x0, const double *via, const double *via_qd, const double *speed, const double *xf,
+                     double *leg_x0, double *leg_xf, double *via_qd_out);
+int mpcmp_route_legs_device(mpcmp_ctx *ctx, int B, int M, const double *d_x0, const double *d_via, const double *d_via_qd, const double *d_speed,
+                            const double *d_xf, double *d_leg_x0, double *d_leg_xf, double *d_via_qd_out, void *hip_stream);
+/* Join: the legs' outputs sol_x [B][M+1][N][14 narm], sol_u [B][M+1][N][7 narm], sol_T [L], info [L] and optionally clr [L] (with route_clr [B];
+ * both NULL otherwise) as one record per route, in the types mpcmp_select_clear_batch[_device] takes.
+ *   route_T [B], route_info [B]: T = the sum of the legs' sol_T, m = 0 .. M; viol_l1, defect_inf, path_viol_inf, term_err_inf and sqp_iters maxima
+ *     over the legs, last_alpha the minimum (a NaN stays); qp_iters_total and qp_capped sums; status the OR of the legs' bits.
+ *   seam [B]: state_jump_inf = the largest |last node of leg m - node 0 of leg m + 1| over the vias and the columns of sol_x, acc_jump_inf the same
+ *     over sol_u (both 0 with M == 0); leg_longest = the leg with the largest T, ties to the lowest; leg_first_bad = the lowest leg whose status has a
+ *     bit of mpcmp_select_clear_batch's inadmissible set, -1 if none.  ACCELERATIONS ARE NOT CONTINUOUS AT A VIA: position and velocity are fixed
+ *     there, the acceleration is each leg's own, and acc_jump_inf says by how much they differ (a tracking controller sees a torque step there).
+ *   route_clr [B]: d_min = the minimum over the legs that have a pair, ties to the lowest leg, sphere and other from that leg, t_min = that leg's
+ *     t_min + the sum of the earlier legs' T; t_first from the lowest leg that has one, shifted the same way; n_hit the sum (a junction sample belongs
+ *     to both legs and is counted in both); status the OR.  If any leg has MPCMP_CLR_NAN: d_min = NaN, t_min = t_first = -1, sphere = -1, other = 0,
+ *     n_hit = 0, status still the OR.  If no leg has a pair, the "no pair" record of mpcmp_clearance.
+ * One thread per route.  MPCMP_EINVAL, writing nothing: B < 1, M < 0, L > max_batch, a required pointer NULL, exactly one of clr / route_clr given. */
+typedef struct {
+    double state_jump_inf;
+    double acc_jump_inf;
+    int    leg_longest;
+    int    leg_first_bad;
+} mpcmp_route_seam;
+int mpcmp_route_join(mpcmp_ctx *ctx, int B, int M, const double *sol_x, const double *sol_u, const double *sol_T, const mpcmp_info *info,
+                     const mpcmp_clearance *clr, double *route_T, mpcmp_info *route_info, mpcmp_route_seam *seam, mpcmp_clearance *route_clr);
+int mpcmp_route_join_device(mpcmp_ctx *ctx, int B, int M, const double *d_sol_x, const double *d_sol_u, const double *d_sol_T, const mpcmp_info *d_info,
+                            const mpcmp_clearance *d_clr, double *d_route_T, mpcmp_info *d_route_info, mpcmp_route_seam *d_seam,
+                            mpcmp_clearance *d_route_clr, void *hip_stream);
+/* Solve, in this order: 1. the leg builder into context scratch (allocated by the first call, never afterwards); 2. the start guess of the legs:
+ * mpcmp_warm_start_jerk_batch_device on the leg states when jmax [7] (a HOST pointer in both variants) is given, the built-in initialiser when it is
+ * NULL (two-arm contexts need jmax); 3. ONE ordinary solve of the L legs with the rows in force: the leg outputs are bit for bit those of
+ * mpcmp_solve_batch[_device] on (leg_x0, leg_xf) with that start guess; 4. the join.  Outputs: the legs' sol_x, sol_u, sol_T [L] and info [L] (may be
+ * NULL), route_T, route_info, seam [B], via_qd_out (may be NULL).  Both arm layouts, every num_seg of the context.  The device variant makes no host
+ * round trip and is ordered on hip_stream; the scratch belongs to the context: enqueue route solves of one context on one stream at a time.
+ * MPCMP_EINVAL, writing nothing: as mpcmp_route_legs, fewer rows of any table than leg slots, and after mpcmp_rh_init (as the row setters). */
+int mpcmp_solve_route_batch(mpcmp_ctx *ctx, int B, int M, const double *x0, const double *via, const double *via_qd, const double *speed,
+                            const double *xf, const double *jmax, double *sol_x, double *sol_u, double *sol_T, mpcmp_info *info,
+                            double *route_T, mpcmp_info *route_info, mpcmp_route_seam *seam, double *via_qd_out);
+int mpcmp_solve_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_x0, const double *d_via, const double *d_via_qd, const double *d_speed,
+                                   const double *d_xf, const double *jmax, double *d_sol_x, double *d_sol_u, double *d_sol_T, mpcmp_info *d_info,
+                                   double *d_route_T, mpcmp_info *d_route_info, mpcmp_route_seam *d_seam, double *d_via_qd_out, void *hip_stream);
+/* Sampling on a uniform clock across the junctions (single-arm contexts, as mpcmp_sample_batch): out [B][n_pts+1][29] = route time, q, qd, qdd, tau.
+ * R = the sequential sum of the legs' T, E_m its prefix sum after leg m (E_-1 = 0).  Sample i has t = (double)i / n_pts * R; its leg is the smallest m
+ * with t < E_m, M if there is none; its normalised time is clamp((t - E_{m-1}) / T_m, 0, 1) (0 where the quotient is no number); sample n_pts is leg
+ * M at exactly 1.  A junction sample belongs to the LATER leg at normalised time 0.  The row is the one mpcmp_sample_batch gives for that leg there
+ * (one device function: the same Lagrange interpolation, RNEA with the payload row of the leg slot).  A route with a leg T that is not finite gets
+ * NaN rows.  mpcmp_route_locate is the leg / normalised-time rule on the host (no GPU needed; the function the kernel runs). */
+int mpcmp_route_locate(int n_legs, const double *leg_T, double t, int *leg, double *tau);
+int mpcmp_sample_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sol_x, const double *sol_u, const double *sol_T, int n_pts, double *out);
+int mpcmp_sample_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sol_x, const double *d_sol_u, const double *d_sol_T, int n_pts,
+                                    double *d_out, void *hip_stream);
+
 /* ---- receding-horizon driver (BASELINE.json config #5) ---- */
 /* B instances; every step = re-solve warm-started from the previous solution with the reference's re-guess rule
  * (head := current state, tail := target; motionPlanner.cpp:199-207), then the current state advances along the

@@ -430,6 +430,34 @@ class MotionPlanner {
         chk(mpcmp_sample_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, NP, out.data()));
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
     }
+    // extension beyond the reference's members: the move current_state -> vias[0] -> .. -> target_state, passed without stopping (mpcmp.h, "via-point
+    // routes").  vias: M joint configurations; the velocities at the vias follow the chord rule at `speed` in [0, 1].  The legs start from the
+    // jerk-limited guess with the limits of `input`.  Afterwards last_info is the record of the whole route (T = its duration), route_seam the
+    // record of its junctions (accelerations are not continuous at a via), route_leg_T the legs' durations; get_route_trajectory samples it.
+    mpcmp_route_seam route_seam{};
+    std::vector<double> route_leg_T;
+    void solve_route(const std::vector<Vec7> &vias, double speed = 0.5) {
+        const int M = (int)vias.size(), L = M + 1;
+        std::vector<double> via((size_t)7 * M + 1);
+        for (int i = 0; i < M; i++) for (int j = 0; j < 7; j++) via[(size_t)7 * i + j] = vias[i](j);
+        route_x_.assign((size_t)14 * N_ * L, 0.0); route_u_.assign((size_t)7 * N_ * L, 0.0); route_leg_T.assign(L, 0.0);
+        double T = 0.0;
+        use_payload(L);
+        chk(mpcmp_solve_route_batch(ctx_, 1, M, current_state.data(), M ? via.data() : nullptr, nullptr, &speed, target_state.data(), input.max_jerk.data(),
+                                    route_x_.data(), route_u_.data(), route_leg_T.data(), nullptr, &T, &last_info, &route_seam, nullptr));
+    }
+    // the route variant of get_MPC_trajectory: NP + 1 samples on a uniform clock across the junctions (mpcmp_sample_route_batch)
+    template <const int NP>
+    void get_route_trajectory(mpcmp_shim::Mat<1, NP + 1> &time, mpcmp_shim::Mat<7, NP + 1> &position_trajectory,
+                              mpcmp_shim::Mat<7, NP + 1> &velocity_trajectory, mpcmp_shim::Mat<7, NP + 1> &acceleration_trajectory,
+                              mpcmp_shim::Mat<7, NP + 1> &torque_trajectory) {
+        if (route_leg_T.empty()) throw std::runtime_error("get_route_trajectory: no route solved yet (solve_route)");
+        const int L = (int)route_leg_T.size();
+        std::vector<double> out((size_t)(NP + 1) * 29);
+        use_payload(L);
+        chk(mpcmp_sample_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), NP, out.data()));
+        unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
+    }
     // motionPlanner.hpp:73-96 — the jerk-limited trajectory of the last solve_trajectory(true) sampled uniformly, torques by
     // RNEA (motionPlanner.hpp:92); after a solve from another guess: that guess, resampled like the MPC solution
     template <const int NP>
@@ -543,7 +571,7 @@ class MotionPlanner {
     friend struct mpcmp_shim::Otg;
     mpcmp_ctx *ctx_ = nullptr;
     int N_ = 0, max_batch_ = 0;
-    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_;
+    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_;
     double sol_T_ = 0, warm_T_ = 0, guess_T_ = 0;
     bool guess_is_profile_ = false;                 // the last guess came from the jerk-limited generator
     double guess_x0_[14] = {0}, guess_xf_[14] = {0}, guess_a0_[7] = {0}, guess_aT_[7] = {0};      // states and boundary accelerations of the last jerk-limited guess

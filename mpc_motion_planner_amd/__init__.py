@@ -13,7 +13,8 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    default_model, forward_velocities, inverse_kinematic, inverse_velocities, lib, library_path,
                    model_add_payload, model_from_urdf, models_from_urdf, num_nodes, payload, time_nodes, tool_jacobian,
                    SPHERE_DTYPE, OBSTACLE_DTYPE, CLEARANCE_DTYPE, OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE, CLR_HIT, CLR_NAN,
-                   spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins)
+                   spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
+                   ROUTE_SEAM_DTYPE, route_via_velocity, route_locate)
 from .planner import BatchMotionPlanner, Solver
 
 __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED", "STATUS_OUTSIDE_TOL", "STATUS_T_OUT_OF_BOX", "STATUS_ARRIVED", "STATUS_HARD", "RH_RESTART",
@@ -24,4 +25,5 @@ __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED",
            "inverse_velocities", "tool_jacobian", "arm_models", "DUAL_BASES", "Payload", "payload", "model_add_payload",
            "SPHERE_DTYPE", "OBSTACLE_DTYPE", "CLEARANCE_DTYPE", "OBS_SPHERE", "OBS_CAPSULE", "OBS_BOX", "OBS_HALFSPACE", "CLR_HIT", "CLR_NAN",
            "spheres", "obstacle", "link_spheres", "clearance_config",
-           "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins"]
+           "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",
+           "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate"]

@@ -67,6 +67,9 @@ MAX_SPHERES, MAX_OBSTACLES = 64, 256
 # one row of mpcmp_set_bounds[_device] (mpcmp_bounds, include/mpcmp.h): the six bound tables of Config, in its order
 BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7), ("ubu", "f8", 7), ("lbg", "f8", 8), ("ubg", "f8", 8)])
 
+# the seam record of a joined route (mpcmp_route_seam, include/mpcmp.h)
+ROUTE_SEAM_DTYPE = np.dtype([("state_jump_inf", "f8"), ("acc_jump_inf", "f8"), ("leg_longest", "i4"), ("leg_first_bad", "i4")])
+
 # every symbol include/mpcmp.h declares (the CPU test suite checks the library exports all of them)
 SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_urdf", "mpcmp_default_limits", "mpcmp_default_config",
            "mpcmp_set_margins", "mpcmp_set_min_height", "mpcmp_num_nodes", "mpcmp_time_nodes", "mpcmp_version",
@@ -85,7 +88,10 @@ SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_ur
            "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device",
            "mpcmp_link_spheres", "mpcmp_clearance_config", "mpcmp_set_robot_spheres", "mpcmp_set_obstacles", "mpcmp_set_obstacles_device",
            "mpcmp_clearance_batch", "mpcmp_clearance_batch_device", "mpcmp_select_clear_batch", "mpcmp_select_clear_batch_device",
-           "mpcmp_bounds_from_config", "mpcmp_bounds_from_margins", "mpcmp_set_bounds", "mpcmp_set_bounds_device"]
+           "mpcmp_bounds_from_config", "mpcmp_bounds_from_margins", "mpcmp_set_bounds", "mpcmp_set_bounds_device",
+           "mpcmp_route_via_velocity", "mpcmp_route_locate", "mpcmp_route_legs", "mpcmp_route_legs_device", "mpcmp_route_join",
+           "mpcmp_route_join_device", "mpcmp_solve_route_batch", "mpcmp_solve_route_batch_device", "mpcmp_sample_route_batch",
+           "mpcmp_sample_route_batch_device"]
 
 # prototypes of the final-time entry points (include/mpcmp.h): the argument kinds, "i" = int, "p" = pointer
 PROTOTYPES = {
@@ -114,6 +120,19 @@ BOUNDS_PROTOTYPES = {
     "mpcmp_bounds_from_margins": "dddddp",
     "mpcmp_set_bounds": "pip",
     "mpcmp_set_bounds_device": "pipp",
+}
+# prototypes of the via-point routes
+ROUTE_PROTOTYPES = {
+    "mpcmp_route_via_velocity": "ppppidp",
+    "mpcmp_route_locate": "ipdpp",
+    "mpcmp_route_legs": "pii" + "p" * 8,
+    "mpcmp_route_legs_device": "pii" + "p" * 9,
+    "mpcmp_route_join": "pii" + "p" * 9,
+    "mpcmp_route_join_device": "pii" + "p" * 10,
+    "mpcmp_solve_route_batch": "pii" + "p" * 14,
+    "mpcmp_solve_route_batch_device": "pii" + "p" * 15,
+    "mpcmp_sample_route_batch": "pii" + "ppp" + "ip",
+    "mpcmp_sample_route_batch_device": "pii" + "ppp" + "ipp",
 }
 _KINDS = {"i": C.c_int, "p": C.c_void_p, "d": C.c_double}
 
@@ -180,7 +199,7 @@ def lib():
         for name, kinds in PROTOTYPES.items():
             getattr(L, name).argtypes = [C.c_int if k == "i" else C.c_void_p for k in kinds]
             getattr(L, name).restype = C.c_int
-        for name, kinds in list(CLEARANCE_PROTOTYPES.items()) + list(BOUNDS_PROTOTYPES.items()):
+        for name, kinds in list(CLEARANCE_PROTOTYPES.items()) + list(BOUNDS_PROTOTYPES.items()) + list(ROUTE_PROTOTYPES.items()):
             getattr(L, name).argtypes = [_KINDS[k] for k in kinds]
             getattr(L, name).restype = C.c_int
         _lib = L
@@ -367,6 +386,25 @@ def bounds_from_margins(margin_position=1.0, margin_velocity=1.0, margin_acceler
     check(lib().mpcmp_bounds_from_margins(float(margin_position), float(margin_velocity), float(margin_acceleration), float(margin_torque),
                                           float(min_height), out.ctypes.data))
     return out
+
+
+def route_via_velocity(p_prev, p_via, p_next, row, narm=1, speed=1.0):
+    """mpcmp_route_via_velocity: the chord rule's pass-through velocity [7 narm] at p_via between p_prev and p_next, within the limits of the
+    BOUNDS_DTYPE record `row` (host, no GPU)"""
+    a, b, c = [f64(v).reshape(7 * narm) for v in (p_prev, p_via, p_next)]
+    row = np.ascontiguousarray(row).reshape(())
+    if row.dtype != BOUNDS_DTYPE:
+        raise ValueError("row must be one BOUNDS_DTYPE record")
+    v = np.zeros(7 * narm)
+    check(lib().mpcmp_route_via_velocity(a.ctypes.data, b.ctypes.data, c.ctypes.data, row.ctypes.data, int(narm), float(speed), v.ctypes.data))
+    return v
+
+
+def route_locate(leg_T, t):
+    """mpcmp_route_locate: (leg, normalised time) of the route time t on the legs of durations leg_T (host, no GPU)"""
+    T = f64(leg_T).reshape(-1); leg, tau = C.c_int(0), C.c_double(0)
+    check(lib().mpcmp_route_locate(T.shape[0], T.ctypes.data, float(t), C.addressof(leg), C.addressof(tau)))
+    return leg.value, tau.value
 
 
 def num_nodes(num_seg):

@@ -31,6 +31,7 @@
 #include "payload.hpp"
 #include "time_sync.hpp"
 #include "clearance.hpp"
+#include "route.hpp"
 
 #ifdef MPCMP_SPLIT_N25
 // the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
@@ -96,6 +97,12 @@ struct mpcmp_ctx {
     mpcmp_clearance *d_sel_clr = nullptr;
     double *d_sel_T = nullptr;
     mpcmp_info *d_sel_info = nullptr;
+    // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
+    // start guess, the legs' records when the caller wants none, and the host variant's staging of its inputs and of the route records
+    double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;
+    mpcmp_info *d_rt_info = nullptr, *d_rt_rinfo = nullptr;
+    double *d_rt_in0 = nullptr, *d_rt_inf = nullptr, *d_rt_via = nullptr, *d_rt_vqd = nullptr, *d_rt_speed = nullptr, *d_rt_vout = nullptr, *d_rt_T = nullptr;
+    mpcmp_route_seam *d_rt_seam = nullptr;
     int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
     uint32_t *d_terms = nullptr;
     WS ws{};
@@ -2105,6 +2112,249 @@ extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT,
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, select_clear_launch(B, ctx->d_sel_T, ctx->d_sel_info, ctx->d_sel_clr, ctx->d_sel_group, n_groups, ctx->d_sel_key, ctx->d_sel_chosen, st));
     HIPCHK(ctx, hipMemcpyAsync(chosen, ctx->d_sel_chosen, sizeof(int) * n_groups, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// via-point routes (route.hpp, route.hip): B routes with M vias = L = B (M + 1) leg slots
+// the checks every route entry point shares; *L = the number of leg slots
+static int route_check(mpcmp_ctx *ctx, const char *who, int B, int M, int *L) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    if (ctx->rh_B > 0) { ctx->err = std::string(who) + ": not available after mpcmp_rh_init (the receding-horizon driver plans single moves)"; return MPCMP_EINVAL; }
+    if (B < 1 || M < 0) { ctx->err = std::string(who) + ": B >= 1 and M >= 0 required"; return MPCMP_EINVAL; }
+    const long long l = (long long)B * ((long long)M + 1);
+    if (l > ctx->max_batch) {
+        ctx->err = std::string(who) + ": " + std::to_string(l) + " leg slots (B (M + 1)) exceed the context capacity (" + std::to_string(ctx->max_batch) + ")";
+        return MPCMP_EINVAL;
+    }
+    *L = (int)l;
+    return MPCMP_OK;
+}
+// the host-pointer variants' look at their values: finite states and vias, speed in [0, 1]
+static int route_values_ok(mpcmp_ctx *ctx, const char *who, int B, int M, const double *x0, const double *via, const double *via_qd, const double *speed,
+                           const double *xf) {
+    const size_t nx = ctx->nx, nv = (size_t)B * M * (nx / 2);
+    auto finite = [](const double *p, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; };
+    if (!finite(x0, nx * B) || !finite(xf, nx * B) || (M > 0 && !finite(via, nv)) || (M > 0 && via_qd && !finite(via_qd, nv))) {
+        ctx->err = std::string(who) + ": x0, xf, via and via_qd must be finite"; return MPCMP_EINVAL;
+    }
+    if (speed)
+        for (int b = 0; b < B; b++)
+            if (!(speed[b] >= 0.0 && speed[b] <= 1.0)) { ctx->err = std::string(who) + ": speed[" + std::to_string(b) + "] must lie in [0, 1]"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+static int route_legs_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_x0, const double *d_via, const double *d_vqd, const double *d_speed,
+                              const double *d_xf, double *d_l0, double *d_lf, double *d_vout, hipStream_t st) {
+    mpcmp_bounds row;
+    mpcmp_bounds_from_config(&ctx->cfg, &row);
+    HIPCHK(ctx, route_legs_launch(B, M, ctx->narm, d_x0, d_via, d_vqd, d_speed, d_xf, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, row, d_l0, d_lf, d_vout, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_route_legs_device(mpcmp_ctx *ctx, int B, int M, const double *d_x0, const double *d_via, const double *d_vqd, const double *d_speed,
+                                       const double *d_xf, double *d_l0, double *d_lf, double *d_vout, void *hip_stream) {
+    int L;
+    if (int rc = route_check(ctx, "mpcmp_route_legs", B, M, &L)) return rc;
+    if (!d_x0 || !d_xf || !d_l0 || !d_lf || (M > 0 && !d_via)) { ctx->err = "mpcmp_route_legs: x0, xf, leg_x0, leg_xf (and via with M > 0) are required"; return MPCMP_EINVAL; }
+    if (int rc = rows_ok(ctx, L, BOUND_ROWS)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return route_legs_enqueue(ctx, B, M, d_x0, d_via, d_vqd, d_speed, d_xf, d_l0, d_lf, d_vout, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_route_legs(mpcmp_ctx *ctx, int B, int M, const double *x0, const double *via, const double *via_qd, const double *speed,
+                                const double *xf, double *leg_x0, double *leg_xf, double *via_qd_out) {
+    int L;
+    if (int rc = route_check(ctx, "mpcmp_route_legs", B, M, &L)) return rc;
+    if (!x0 || !xf || !leg_x0 || !leg_xf || (M > 0 && !via)) { ctx->err = "mpcmp_route_legs: x0, xf, leg_x0, leg_xf (and via with M > 0) are required"; return MPCMP_EINVAL; }
+    if (int rc = route_values_ok(ctx, "mpcmp_route_legs", B, M, x0, via, via_qd, speed, xf)) return rc;
+    if (int rc = rows_ok(ctx, L, BOUND_ROWS)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nx = ctx->nx, nv = (size_t)B * M * (nx / 2);
+    TmpBuf tb(ctx, (2 * nx * B + 3 * nv + B + 2 * nx * L) * sizeof(double));
+    double *d0 = tb.get<double>(nx * B), *df = tb.get<double>(nx * B), *dv = tb.get<double>(nv + 1), *dq = tb.get<double>(nv + 1), *ds = tb.get<double>(B),
+           *dl0 = tb.get<double>(nx * L), *dlf = tb.get<double>(nx * L), *dvo = tb.get<double>(nv + 1);
+    if (!dvo) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(d0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(df, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    if (M > 0) HIPCHK(ctx, hipMemcpyAsync(dv, via, sizeof(double) * nv, hipMemcpyHostToDevice, st));
+    if (M > 0 && via_qd) HIPCHK(ctx, hipMemcpyAsync(dq, via_qd, sizeof(double) * nv, hipMemcpyHostToDevice, st));
+    if (speed) HIPCHK(ctx, hipMemcpyAsync(ds, speed, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    if (int rc = route_legs_enqueue(ctx, B, M, d0, dv, (M > 0 && via_qd) ? dq : nullptr, speed ? ds : nullptr, df, dl0, dlf, dvo, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(leg_x0, dl0, sizeof(double) * nx * L, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(leg_xf, dlf, sizeof(double) * nx * L, hipMemcpyDeviceToHost, st));
+    if (via_qd_out && M > 0) HIPCHK(ctx, hipMemcpyAsync(via_qd_out, dvo, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+static int route_join_check(mpcmp_ctx *ctx, int B, int M, const void *sx, const void *su, const void *sT, const void *info, const void *clr, const void *rT,
+                            const void *rinfo, const void *seam, const void *rclr, int *L) {
+    if (int rc = route_check(ctx, "mpcmp_route_join", B, M, L)) return rc;
+    if (!sx || !su || !sT || !info || !rT || !rinfo || !seam || ((clr != nullptr) != (rclr != nullptr))) {
+        ctx->err = "mpcmp_route_join: sol_x, sol_u, sol_T, info, route_T, route_info and seam are required; clr and route_clr both or neither"; return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_route_join_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, const mpcmp_info *d_info,
+                                       const mpcmp_clearance *d_clr, double *d_rT, mpcmp_info *d_rinfo, mpcmp_route_seam *d_seam, mpcmp_clearance *d_rclr,
+                                       void *hip_stream) {
+    int L;
+    if (int rc = route_join_check(ctx, B, M, d_sx, d_su, d_sT, d_info, d_clr, d_rT, d_rinfo, d_seam, d_rclr, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, route_join_launch(B, M, ctx->N, ctx->narm, d_sx, d_su, d_sT, d_info, d_clr, d_rT, d_rinfo, d_seam, d_rclr, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_route_join(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, const mpcmp_info *info,
+                                const mpcmp_clearance *clr, double *rT, mpcmp_info *rinfo, mpcmp_route_seam *seam, mpcmp_clearance *rclr) {
+    int L;
+    if (int rc = route_join_check(ctx, B, M, sx, su, sT, info, clr, rT, rinfo, seam, rclr, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+    TmpBuf tb(ctx, ((nx + nu) * N * L + L + B) * sizeof(double) + (sizeof(mpcmp_info) + sizeof(mpcmp_clearance)) * ((size_t)L + B) + sizeof(mpcmp_route_seam) * B);
+    double *dx = tb.get<double>(nx * N * L), *du = tb.get<double>(nu * N * L), *dT = tb.get<double>(L), *drT = tb.get<double>(B);
+    mpcmp_info *di = tb.get<mpcmp_info>(L), *dri = tb.get<mpcmp_info>(B);
+    mpcmp_clearance *dc = tb.get<mpcmp_clearance>(L), *drc = tb.get<mpcmp_clearance>(B);
+    mpcmp_route_seam *ds = tb.get<mpcmp_route_seam>(B);
+    if (!ds) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx * N * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * nu * N * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(di, info, sizeof(mpcmp_info) * L, hipMemcpyHostToDevice, st));
+    if (clr) HIPCHK(ctx, hipMemcpyAsync(dc, clr, sizeof(mpcmp_clearance) * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, route_join_launch(B, M, ctx->N, ctx->narm, dx, du, dT, di, clr ? dc : nullptr, drT, dri, ds, clr ? drc : nullptr, st));
+    HIPCHK(ctx, hipMemcpyAsync(rT, drT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(rinfo, dri, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(seam, ds, sizeof(mpcmp_route_seam) * B, hipMemcpyDeviceToHost, st));
+    if (clr) HIPCHK(ctx, hipMemcpyAsync(rclr, drc, sizeof(mpcmp_clearance) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+// everything a route solve is refused for, and its scratch (first call only)
+static int route_solve_check(mpcmp_ctx *ctx, int B, int M, const void *x0, const void *via, const void *xf, const double *jmax, const void *sx, const void *su,
+                             const void *sT, const void *rT, const void *rinfo, const void *seam, int *L) {
+    if (int rc = route_check(ctx, "mpcmp_solve_route_batch", B, M, L)) return rc;
+    if (!x0 || !xf || (M > 0 && !via) || !sx || !su || !sT || !rT || !rinfo || !seam) {
+        ctx->err = "mpcmp_solve_route_batch: x0, xf (and via with M > 0), sol_x, sol_u, sol_T, route_T, route_info and seam are required"; return MPCMP_EINVAL;
+    }
+    if (int rc = solve_rows_ok(ctx, *L)) return rc;
+    if (ctx->narm == 2 && !jmax) { ctx->err = "mpcmp_solve_route_batch: multi-arm solves need the jerk-limited start guess (jmax)"; return MPCMP_EINVAL; }
+    if (jmax) { JerkLimits lim; if (int rc = jerk_limits(ctx, nullptr, nullptr, jmax, lim)) return rc; }
+    if (!ctx->d_rt_x0) {              // first use
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t Mx = ctx->max_batch, N = ctx->N, nx = ctx->nx, nu = ctx->nu;
+        if (int rc = dalloc(ctx, &ctx->d_rt_xf, Mx * nx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_wx, Mx * nx * N)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_wu, Mx * nu * N)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_wT, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_info, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_rinfo, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_in0, Mx * nx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_inf, Mx * nx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_via, Mx * nu)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_vqd, Mx * nu)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_speed, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_vout, Mx * nu)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_T, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_seam, Mx)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_rt_x0, Mx * nx)) return rc;      // (last: the mark of a complete scratch)
+    }
+    return MPCMP_OK;
+}
+
+// leg builder, start guess, one solve of the L legs, join: all on st, no host round trip
+static int route_solve_enqueue(mpcmp_ctx *ctx, int B, int M, int L, const double *d_x0, const double *d_via, const double *d_vqd, const double *d_speed,
+                               const double *d_xf, const double *jmax, double *d_sx, double *d_su, double *d_sT, mpcmp_info *d_info, double *d_rT,
+                               mpcmp_info *d_rinfo, mpcmp_route_seam *d_seam, double *d_vout, hipStream_t st) {
+    if (int rc = route_legs_enqueue(ctx, B, M, d_x0, d_via, d_vqd, d_speed, d_xf, ctx->d_rt_x0, ctx->d_rt_xf, d_vout, st)) return rc;
+    SolveCall c;
+    c.B = L; c.x0 = ctx->d_rt_x0; c.xf = ctx->d_rt_xf;
+    if (jmax) {
+        if (int rc = mpcmp_warm_start_jerk_batch_device(ctx, L, ctx->d_rt_x0, ctx->d_rt_xf, jmax, ctx->d_rt_wx, ctx->d_rt_wu, ctx->d_rt_wT, st)) return rc;
+        c.wx = ctx->d_rt_wx; c.wu = ctx->d_rt_wu; c.wT = ctx->d_rt_wT;
+    }
+    c.sx = d_sx; c.su = d_su; c.sT = d_sT; c.info = d_info ? d_info : ctx->d_rt_info; c.stream = st;
+    if (int rc = solve_dispatch(ctx, c)) return rc;
+    HIPCHK(ctx, route_join_launch(B, M, ctx->N, ctx->narm, d_sx, d_su, d_sT, c.info, nullptr, d_rT, d_rinfo, d_seam, nullptr, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_solve_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_x0, const double *d_via, const double *d_vqd, const double *d_speed,
+                                              const double *d_xf, const double *jmax, double *d_sx, double *d_su, double *d_sT, mpcmp_info *d_info,
+                                              double *d_rT, mpcmp_info *d_rinfo, mpcmp_route_seam *d_seam, double *d_vout, void *hip_stream) {
+    int L;
+    if (int rc = route_solve_check(ctx, B, M, d_x0, d_via, d_xf, jmax, d_sx, d_su, d_sT, d_rT, d_rinfo, d_seam, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return route_solve_enqueue(ctx, B, M, L, d_x0, d_via, d_vqd, d_speed, d_xf, jmax, d_sx, d_su, d_sT, d_info, d_rT, d_rinfo, d_seam, d_vout,
+                               (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_solve_route_batch(mpcmp_ctx *ctx, int B, int M, const double *x0, const double *via, const double *via_qd, const double *speed,
+                                       const double *xf, const double *jmax, double *sx, double *su, double *sT, mpcmp_info *info, double *rT,
+                                       mpcmp_info *rinfo, mpcmp_route_seam *seam, double *via_qd_out) {
+    int L;
+    if (int rc = route_check(ctx, "mpcmp_solve_route_batch", B, M, &L)) return rc;
+    if (!x0 || !xf || (M > 0 && !via)) { ctx->err = "mpcmp_solve_route_batch: x0, xf (and via with M > 0) are required"; return MPCMP_EINVAL; }
+    if (int rc = route_values_ok(ctx, "mpcmp_solve_route_batch", B, M, x0, via, via_qd, speed, xf)) return rc;
+    if (int rc = route_solve_check(ctx, B, M, x0, via, xf, jmax, sx, su, sT, rT, rinfo, seam, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nx = ctx->nx, nv = (size_t)B * M * (nx / 2);
+    const bool vq = M > 0 && via_qd;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_in0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_inf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
+    if (M > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_via, via, sizeof(double) * nv, hipMemcpyHostToDevice, st));
+    if (vq) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_vqd, via_qd, sizeof(double) * nv, hipMemcpyHostToDevice, st));
+    if (speed) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_speed, speed, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    if (int rc = route_solve_enqueue(ctx, B, M, L, ctx->d_rt_in0, ctx->d_rt_via, vq ? ctx->d_rt_vqd : nullptr, speed ? ctx->d_rt_speed : nullptr, ctx->d_rt_inf,
+                                     jmax, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, ctx->d_rt_T, ctx->d_rt_rinfo, ctx->d_rt_seam, ctx->d_rt_vout, st))
+        return rc;
+    if (int rc = download_trajectories(ctx, L, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(rT, ctx->d_rt_T, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(rinfo, ctx->d_rt_rinfo, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(seam, ctx->d_rt_seam, sizeof(mpcmp_route_seam) * B, hipMemcpyDeviceToHost, st));
+    if (via_qd_out && M > 0) HIPCHK(ctx, hipMemcpyAsync(via_qd_out, ctx->d_rt_vout, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return MPCMP_OK;
+}
+
+static int route_sample_check(mpcmp_ctx *ctx, int B, int M, const void *sx, const void *su, const void *sT, int n_pts, const void *out, int *L) {
+    if (int rc = route_check(ctx, "mpcmp_sample_route_batch", B, M, L)) return rc;
+    if (n_pts < 1 || !sx || !su || !sT || !out) { ctx->err = "mpcmp_sample_route_batch: n_pts >= 1 and all pointers required"; return MPCMP_EINVAL; }
+    SINGLE_ARM_ONLY(ctx);
+    return rows_ok(ctx, *L, PAYLOAD_ROWS);
+}
+
+extern "C" int mpcmp_sample_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_pts,
+                                               double *d_out, void *hip_stream) {
+    int L;
+    if (int rc = route_sample_check(ctx, B, M, d_sx, d_su, d_sT, n_pts, d_out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, route_sample_launch(md, ms, ctx->nseg, B, M, n_pts, d_sx, d_su, d_sT, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sample_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_pts, double *out) {
+    int L;
+    if (int rc = route_sample_check(ctx, B, M, sx, su, sT, n_pts, out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = ctx->N, np = (size_t)B * (n_pts + 1) * 29;
+    TmpBuf tb(ctx, (21 * N * L + L + np) * sizeof(double));
+    double *dx = tb.get<double>(14 * N * L), *du = tb.get<double>(7 * N * L), *dT = tb.get<double>(L), *dout = tb.get<double>(np);
+    if (!dout) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * 14 * N * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * L, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * L, hipMemcpyHostToDevice, st));
+    if (int rc = mpcmp_sample_route_batch_device(ctx, B, M, dx, du, dT, n_pts, dout, st)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * np, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return MPCMP_OK;
 }

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "rbd_device.hpp"
+#include "sample_device.hpp"
 #include "structure.hpp"
 
 namespace mpcmp {
@@ -1126,38 +1127,10 @@ __global__ __launch_bounds__(128) void k_sample(const mpcmp_model *mdl, int mstr
     const int b = (int)(gid / (n_pts + 1)), ip = (int)(gid % (n_pts + 1));
     mdl += (size_t)b * mstride;
     const int N = 3 * nseg + 1;
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
     const double t = (double)ip / n_pts;
-    int s = (int)floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    double Lg[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    const double *X = sx + (size_t)b * 14 * N, *U = su + (size_t)b * 7 * N;
-    double q[7], v[7], a[7], tau[7], sc[14];
-#pragma unroll
-    for (int r = 0; r < 7; r++) {
-        q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            q[r] += Lg[j] * X[14 * (3 * s + j) + r];
-            v[r] += Lg[j] * X[14 * (3 * s + j) + 7 + r];
-            a[r] += Lg[j] * U[7 * (3 * s + j) + r];
-        }
-        sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
-    }
-    rnea_dir<false>(mdl, sc, v, a, 0, 0, tau, nullptr);
     double *o = out + (size_t)gid * 29;
+    sample_row(mdl, nseg, sx + (size_t)b * 14 * N, su + (size_t)b * 7 * N, t, o);
     o[0] = t * sT[b];
-#pragma unroll
-    for (int r = 0; r < 7; r++) { o[1 + r] = q[r]; o[8 + r] = v[r]; o[15 + r] = a[r]; o[22 + r] = tau[r]; }
 }
 
 

@@ -260,6 +260,102 @@ class Solver:
         check(lib().mpcmp_select_clear_batch_device(self._ctx, int(B), vp(sol_T), vp(info), vp(clr), vp(group), int(n_groups), vp(chosen),
                                                     vp(stream or None)), self._ctx)
 
+    # -- via-point routes: B routes with M vias = B (M + 1) leg slots (include/mpcmp.h, "via-point routes")
+    @staticmethod
+    def repeat(rows, M):
+        """one row per route -> one row per leg slot: every row M + 1 times (a route under its own payload, window or limits sets its row for each
+        of its legs); works on the arrays set_payloads / set_time_windows take and on BOUNDS_DTYPE / OBSTACLE_DTYPE tables"""
+        return np.ascontiguousarray(np.repeat(np.asarray(rows), int(M) + 1, axis=0))
+
+    def _route_in(self, x0, via, via_qd, speed, xf):
+        x0, xf = self._states(x0, xf); B = x0.shape[0]; nq = self.nu
+        via = np.zeros((B, 0, nq)) if via is None else f64(via)
+        if via.ndim != 3 or via.shape[0] != B or via.shape[2] != nq:
+            raise ValueError("via must be [B][M][%d] with B = %d, got %s" % (nq, B, via.shape))
+        M = via.shape[1]
+        if via_qd is not None:
+            via_qd = f64(via_qd)
+            if via_qd.shape != via.shape:
+                raise ValueError("via_qd must have the shape of via %s, got %s" % (via.shape, via_qd.shape))
+        if speed is not None:
+            speed = f64(np.broadcast_to(np.asarray(speed, dtype=np.float64), (B,)))
+        return x0, via, via_qd, speed, xf, B, M
+
+    @staticmethod
+    def _p(a):
+        return None if a is None or a.size == 0 else a.ctypes.data
+
+    def route_legs(self, x0, via, xf, via_qd=None, speed=None):
+        """mpcmp_route_legs: (leg_x0 [B (M+1)][nx], leg_xf, via_qd [B][M][7 narm]); via_qd None = the chord rule at `speed` (None = 1)"""
+        x0, via, via_qd, speed, xf, B, M = self._route_in(x0, via, via_qd, speed, xf)
+        L = B * (M + 1)
+        l0, lf, vo = np.zeros((L, self.nx)), np.zeros((L, self.nx)), np.zeros_like(via)
+        check(lib().mpcmp_route_legs(self._ctx, B, M, self._p(x0), self._p(via), self._p(via_qd), self._p(speed), self._p(xf), l0.ctypes.data,
+                                     lf.ctypes.data, self._p(vo)), self._ctx)
+        return l0, lf, vo
+
+    def route_legs_device(self, B, M, x0, via, xf, leg_x0, leg_xf, via_qd=0, speed=0, via_qd_out=0, stream=0):
+        check(lib().mpcmp_route_legs_device(self._ctx, int(B), int(M), x0, via or None, via_qd or None, speed or None, xf, leg_x0, leg_xf,
+                                            via_qd_out or None, stream or None), self._ctx)
+
+    def solve_route(self, x0, via, xf, via_qd=None, speed=None, jmax=None):
+        """mpcmp_solve_route_batch: a dict with the legs' sol_x [B][M+1][N][nx], sol_u, sol_T [B][M+1], info [B][M+1] and the routes' route_T [B],
+        route_info [B] (INFO_DTYPE), seam [B] (ROUTE_SEAM_DTYPE), via_qd [B][M][7 narm].  jmax [7]: the legs start from the jerk-limited guess;
+        None: from the built-in initialiser"""
+        x0, via, via_qd, speed, xf, B, M = self._route_in(x0, via, via_qd, speed, xf)
+        jm = None if jmax is None else f64(jmax).reshape(7)
+        sx, su, sT = np.zeros((B, M + 1, self.N, self.nx)), np.zeros((B, M + 1, self.N, self.nu)), np.zeros((B, M + 1))
+        info, rinfo = np.zeros((B, M + 1), dtype=capi.INFO_DTYPE), np.zeros(B, dtype=capi.INFO_DTYPE)
+        rT, seam, vo = np.zeros(B), np.zeros(B, dtype=capi.ROUTE_SEAM_DTYPE), np.zeros_like(via)
+        check(lib().mpcmp_solve_route_batch(self._ctx, B, M, self._p(x0), self._p(via), self._p(via_qd), self._p(speed), self._p(xf), self._p(jm),
+                                            sx.ctypes.data, su.ctypes.data, sT.ctypes.data, info.ctypes.data, rT.ctypes.data, rinfo.ctypes.data,
+                                            seam.ctypes.data, self._p(vo)), self._ctx)
+        return dict(sol_x=sx, sol_u=su, sol_T=sT, info=info, route_T=rT, route_info=rinfo, seam=seam, via_qd=vo)
+
+    def solve_route_device(self, B, M, x0, via, xf, sol_x, sol_u, sol_T, route_T, route_info, seam, info=0, via_qd=0, speed=0, jmax=None, via_qd_out=0,
+                           stream=0):
+        jm = None if jmax is None else f64(jmax).reshape(7)
+        check(lib().mpcmp_solve_route_batch_device(self._ctx, int(B), int(M), x0, via or None, via_qd or None, speed or None, xf, self._p(jm), sol_x,
+                                                   sol_u, sol_T, info or None, route_T, route_info, seam, via_qd_out or None, stream or None), self._ctx)
+
+    def _route_traj(self, sx, su, sT):
+        sx, su, sT = f64(sx), f64(su), f64(sT)
+        if sT.ndim != 2 or sx.shape != sT.shape + (self.N, self.nx) or su.shape != sT.shape + (self.N, self.nu):
+            raise ValueError("route trajectories must be [B][M+1][%d][%d], [B][M+1][%d][%d], [B][M+1]; got %s, %s, %s"
+                             % (self.N, self.nx, self.N, self.nu, sx.shape, su.shape, sT.shape))
+        return sx, su, sT, sT.shape[0], sT.shape[1] - 1
+
+    def route_join(self, sx, su, sT, info, clr=None):
+        """mpcmp_route_join: (route_T [B], route_info [B], seam [B]) and, with the legs' clearance records clr [B][M+1], route_clr [B]"""
+        sx, su, sT, B, M = self._route_traj(sx, su, sT)
+        info = np.ascontiguousarray(info)
+        if info.dtype != capi.INFO_DTYPE or info.shape != sT.shape:
+            raise ValueError("info must be INFO_DTYPE [B][M+1]")
+        rclr = None
+        if clr is not None:
+            clr = np.ascontiguousarray(clr)
+            if clr.dtype != capi.CLEARANCE_DTYPE or clr.shape != sT.shape:
+                raise ValueError("clr must be CLEARANCE_DTYPE [B][M+1]")
+            rclr = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
+        rT, rinfo, seam = np.zeros(B), np.zeros(B, dtype=capi.INFO_DTYPE), np.zeros(B, dtype=capi.ROUTE_SEAM_DTYPE)
+        check(lib().mpcmp_route_join(self._ctx, B, M, sx.ctypes.data, su.ctypes.data, sT.ctypes.data, info.ctypes.data, self._p(clr), rT.ctypes.data,
+                                     rinfo.ctypes.data, seam.ctypes.data, self._p(rclr)), self._ctx)
+        return (rT, rinfo, seam) if clr is None else (rT, rinfo, seam, rclr)
+
+    def route_join_device(self, B, M, sol_x, sol_u, sol_T, info, route_T, route_info, seam, clr=0, route_clr=0, stream=0):
+        check(lib().mpcmp_route_join_device(self._ctx, int(B), int(M), sol_x, sol_u, sol_T, info, clr or None, route_T, route_info, seam,
+                                            route_clr or None, stream or None), self._ctx)
+
+    def sample_route(self, sx, su, sT, n_pts=200):
+        """mpcmp_sample_route_batch: out [B][n_pts+1][29] = route time, q, qd, qdd, tau on a uniform clock across the junctions"""
+        sx, su, sT, B, M = self._route_traj(sx, su, sT)
+        out = np.zeros((B, n_pts + 1, 29))
+        check(lib().mpcmp_sample_route_batch(self._ctx, B, M, sx.ctypes.data, su.ctypes.data, sT.ctypes.data, int(n_pts), out.ctypes.data), self._ctx)
+        return out
+
+    def sample_route_device(self, B, M, sol_x, sol_u, sol_T, n_pts, out, stream=0):
+        check(lib().mpcmp_sample_route_batch_device(self._ctx, int(B), int(M), sol_x, sol_u, sol_T, int(n_pts), out, stream or None), self._ctx)
+
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
         x0, xf = f64(x0), f64(xf)
@@ -507,6 +603,8 @@ class BatchMotionPlanner:
         self._sol = None
         self._rk = None
         self._payload = None
+        self._via = None
+        self._route = None
 
     # motionPlanner.cpp:56-90
     def set_constraint_margins(self, margin_position, margin_velocity, margin_acceleration, margin_torque, margin_jerk):
@@ -587,8 +685,25 @@ class BatchMotionPlanner:
         self._solver.set_obstacles(obstacles)
 
     def check_clearance(self, n_pts=200, margin=0.0, self_gap=0):
-        """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions"""
+        """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions; of routes: the legs' records joined per route"""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            clr = self._solver.clearance(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin, self_gap)
+            return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
         return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
+
+    # extension beyond the reference's members: a move through via points (include/mpcmp.h, "via-point routes")
+    def set_via_points(self, via, via_velocity=None, speed=0.5):
+        """via [B][M][7] (or [M][7] for every problem): the next solve_trajectory plans x0 -> via_0 -> .. -> xf without stopping, and
+        get_MPC_trajectory samples the route.  via_velocity [B][M][7]: the joint velocities at the vias; None: the chord rule at `speed` in [0, 1].
+        via None: back to direct moves.  Payloads, windows and obstacle sets given per problem apply to every leg of its route; with per-problem
+        obstacle SETS, repeat each set M + 1 times (Solver.repeat)."""
+        if via is None:
+            self._via = self._route = None
+            return
+        via = f64(via)
+        self._via = (via if via.ndim == 3 else via[None], None if via_velocity is None else f64(via_velocity).reshape(-1, via.shape[-2], 7), speed)
 
     # motionPlanner.cpp:177-208
     def solve_trajectory(self, use_builtin_warm_start=True):
@@ -597,6 +712,9 @@ class BatchMotionPlanner:
         if getattr(self, "_twin", None) is not None:
             self._solver.set_time_windows(np.broadcast_to(self._twin[0], (B,)), np.broadcast_to(self._twin[1], (B,)))
         x0 = np.broadcast_to(self.current_state, (B, 14)); xf = np.broadcast_to(self.target_state, (B, 14))
+        if self._via is not None:
+            return self._solve_route(B, x0, xf, use_builtin_warm_start)
+        self._route = None
         if use_builtin_warm_start:      # what the reference gets from Ruckig (warm_start_RK, motionPlanner.cpp:146-175)
             self._rk = (np.array(x0), np.array(xf))
             warm = self._solver.warm_start_jerk(x0, xf, self.margin_jerk_ * self.limits["jmax"])     # motionPlanner.cpp:86-88
@@ -610,7 +728,26 @@ class BatchMotionPlanner:
         self.info = info
         return info
 
+    def _solve_route(self, B, x0, xf, jerk_start):
+        via, vqd, speed = self._via
+        M = via.shape[1]; rep = self._solver.repeat
+        via = np.broadcast_to(via, (B, M, 7)); vqd = None if vqd is None else np.broadcast_to(vqd, (B, M, 7))
+        if self._payload is not None:           # rows are per leg slot: every route's row M + 1 times
+            m, c, I = self._payload
+            self._solver.set_payloads(rep(np.broadcast_to(m, (B,)), M), None if c is None else rep(np.broadcast_to(c, (B, 3)), M),
+                                      None if I is None else rep(np.broadcast_to(I, (B, 3, 3)), M))
+        if getattr(self, "_twin", None) is not None:
+            self._solver.set_time_windows(rep(np.broadcast_to(self._twin[0], (B,)), M), rep(np.broadcast_to(self._twin[1], (B,)), M))
+        r = self._solver.solve_route(x0, via, xf, vqd, speed, self.margin_jerk_ * self.limits["jmax"] if jerk_start else None)
+        self._route = r
+        self._sol = self._warm = None           # (the re-guess rule is that of a single move)
+        self.info = r["route_info"]
+        return self.info
+
     def solution(self):
+        """(sol_x, sol_u, sol_T) of the last solve; of routes: the legs' [B][M+1][..] arrays"""
+        if self._route is not None:
+            return self._route["sol_x"], self._route["sol_u"], self._route["sol_T"]
         return self._sol
 
     # motionPlanner.hpp:118-128 / 130-142
@@ -637,5 +774,8 @@ class BatchMotionPlanner:
 
     # motionPlanner.hpp:99-116
     def get_MPC_trajectory(self, n_pts=200):
-        out = self._solver.sample(*self._sol, n_pts=n_pts)
+        if self._route is not None:
+            out = self._solver.sample_route(self._route["sol_x"], self._route["sol_u"], self._route["sol_T"], n_pts=n_pts)
+        else:
+            out = self._solver.sample(*self._sol, n_pts=n_pts)
         return out[..., 0], out[..., 1:8], out[..., 8:15], out[..., 15:22], out[..., 22:29]
