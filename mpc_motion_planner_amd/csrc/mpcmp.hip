@@ -2,6 +2,7 @@
 // Host logic only orchestrates HIP launches; there is NO CPU fallback: without a HIP device every compute
 // entry point fails with MPCMP_ENODEVICE.
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -77,14 +78,14 @@ struct mpcmp_ctx {
     // tables of cfg for every problem
     mpcmp_bounds *d_bnd = nullptr;
     int bnd_rows = 0;
-    // the synchronised solve's buffers (mpcmp_solve_batch_synced*), [max_batch] each, allocated by its first call: group ids (host staging), group
-    // keys, member counts and times, the pass-2 mask (WS::retired of pass 2), the pass-1 status words, rows, T_new and stretched start guess
-    int *d_sg_group = nullptr, *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
+    // the synchronised solve's buffers (mpcmp_solve_batch_synced*), [max_batch] each, allocated by its first call: group keys, member counts and
+    // times, the pass-2 mask (WS::retired of pass 2), the pass-1 status words, rows, T_new and stretched start guess
+    int *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
     unsigned long long *d_sg_key = nullptr;
     double *d_sg_T = nullptr, *d_sg_rows = nullptr, *d_sg_Tn = nullptr, *d_sg_wx = nullptr, *d_sg_wu = nullptr, *d_sg_wT = nullptr;
     // clearance checks (mpcmp_clearance_batch*): the sphere tables of the arms (host copies; d_clr_sph [128] holds them arm-major, allocated by
-    // mpcmp_create), the obstacle sets d_clr_obs [clr_sets][clr_nobs] (allocated and grown by mpcmp_set_obstacles*), the selection's scratch
-    // (keys / staging, [max_batch], allocated by its first call).  Read by no other entry point
+    // mpcmp_create), the obstacle sets d_clr_obs [clr_sets][clr_nobs] (allocated and grown by mpcmp_set_obstacles*), the selection's keys
+    // ([max_batch], allocated by its first call).  Read by no other entry point
     mpcmp_sphere clr_sph[2][CLR_MAX_SPH];
     int clr_nsph[2] = {0, 0};
     ClrSphere *d_clr_sph = nullptr;
@@ -93,16 +94,10 @@ struct mpcmp_ctx {
     int clr_sets = 0, clr_nobs = 0;
     bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
     unsigned long long *d_sel_key = nullptr;
-    int *d_sel_group = nullptr, *d_sel_chosen = nullptr;
-    mpcmp_clearance *d_sel_clr = nullptr;
-    double *d_sel_T = nullptr;
-    mpcmp_info *d_sel_info = nullptr;
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
-    // start guess, the legs' records when the caller wants none, and the host variant's staging of its inputs and of the route records
+    // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;
-    mpcmp_info *d_rt_info = nullptr, *d_rt_rinfo = nullptr;
-    double *d_rt_in0 = nullptr, *d_rt_inf = nullptr, *d_rt_via = nullptr, *d_rt_vqd = nullptr, *d_rt_speed = nullptr, *d_rt_vout = nullptr, *d_rt_T = nullptr;
-    mpcmp_route_seam *d_rt_seam = nullptr;
+    mpcmp_info *d_rt_info = nullptr;
     int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
     uint32_t *d_terms = nullptr;
     WS ws{};
@@ -132,7 +127,7 @@ struct mpcmp_ctx {
     double qp_ms = 0.0;
     int qp_launches = 0;
     bool timing = false;             // off until mpcmp_kernel_timing is first called: a plain solve records no events
-    // growable device scratch of the host-buffer leaf entry points (no hipMalloc per call once it is large enough)
+    // growable device scratch of the host-pointer entry points (Stage: no hipMalloc per call once it is large enough)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
     // receding-horizon state (mpcmp_rh_*)
@@ -1452,30 +1447,57 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     return MPCMP_OK;
 }
 
-// Device scratch of the host-buffer leaf entry points, owned by the context and only ever grown: after the first call of a
-// given size these entry points do not allocate (a control loop calls get_MPC_point / get_RK_point every tick).
-struct TmpBuf {
-    mpcmp_ctx *ctx;
-    size_t off = 0;
-    bool ok = true;
-    TmpBuf(mpcmp_ctx *c, size_t total_bytes) : ctx(c) {
-        total_bytes += 256 * 16;                       // alignment slack for up to 16 sub-buffers
-        if (total_bytes > c->scratch_bytes) {
-            if (c->scratch) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-            void *q = nullptr;
-            const size_t want = total_bytes < (1u << 20) ? (1u << 20) : total_bytes;
-            if (hipMalloc(&q, want) != hipSuccess) { ok = false; return; }
-            c->scratch = q; c->scratch_bytes = want;
+// Device staging of the host-pointer entry points, in the context's scratch: owned by the context and only ever grown, so that after the first call
+// of a given size these entry points do not allocate (a control loop calls get_MPC_point / get_RK_point every tick).
+// An entry point DECLARES every device array it needs, each with the variable that will hold its device pointer, an element count and what happens to
+// it: in() is copied from a host pointer by upload(), out() is copied to one by finish(), inout() both.  upload() adds up the aligned sizes, grows the
+// scratch at most once and only then fills the variables in, so no pointer exists that a growth could leave dangling.  A NULL host pointer is an array
+// the caller did not give: its device pointer stays NULL, and nothing is reserved or copied for it.
+struct Stage {
+    explicit Stage(mpcmp_ctx *c) : ctx(c) {}
+    template <typename T> void in(T **dev, const T *host, size_t count) { *dev = nullptr; add(dev, host, nullptr, count * sizeof(T)); }
+    template <typename T> void out(T **dev, T *host, size_t count) { *dev = nullptr; add(dev, nullptr, host, count * sizeof(T)); }
+    template <typename T> void inout(T **dev, T *host, size_t count) { *dev = nullptr; add(dev, host, host, count * sizeof(T)); }
+    // after the last declaration, before the launch: the scratch, the device pointers, and every input copy on ctx->stream
+    int upload() {
+        size_t total = 0;
+        for (int i = 0; i < n; i++) total += aligned(items[i].bytes);
+        if (total > ctx->scratch_bytes) {
+            if (ctx->scratch) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
+            const size_t want = total < (1u << 20) ? (1u << 20) : total;
+            if (hipMalloc(&ctx->scratch, want) != hipSuccess) { ctx->scratch = nullptr; ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
+            ctx->scratch_bytes = want;
         }
+        char *p = static_cast<char *>(ctx->scratch);
+        for (int i = 0; i < n; i++) {
+            items[i].dev = p;
+            std::memcpy(items[i].var, &p, sizeof p);      // (the variables are pointers of several types: no cast of one to the other's address)
+            p += aligned(items[i].bytes);
+        }
+        for (int i = 0; i < n; i++)
+            if (items[i].src) HIPCHK(ctx, hipMemcpyAsync(items[i].dev, items[i].src, items[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+        return MPCMP_OK;
     }
-    template <typename T> T *get(size_t count) {
-        if (!ok) return nullptr;
-        off = (off + 255) / 256 * 256;
-        T *r = reinterpret_cast<T *>(static_cast<char *>(ctx->scratch) + off);
-        off += count * sizeof(T);
-        if (off > ctx->scratch_bytes) { ok = false; return nullptr; }
-        return r;
+    // after the launch: every output copy on ctx->stream, and the wait for it
+    int finish() {
+        for (int i = 0; i < n; i++)
+            if (items[i].dst) HIPCHK(ctx, hipMemcpyAsync(items[i].dst, items[i].dev, items[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        return MPCMP_OK;
     }
+
+private:
+    struct Item { void *var, *dev; const void *src; void *dst; size_t bytes; };
+    static constexpr int MAX_ITEMS = 12;
+    static size_t aligned(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    void add(void *var, const void *src, void *dst, size_t bytes) {
+        if (!src && !dst) return;
+        assert(n < MAX_ITEMS);
+        items[n++] = {var, nullptr, src, dst, bytes};
+    }
+    mpcmp_ctx *ctx;
+    Item items[MAX_ITEMS];
+    int n = 0;
 };
 
 // ---- time scaling and the time-synchronised solve (time_sync.hpp) ----
@@ -1497,24 +1519,14 @@ extern "C" int mpcmp_time_scale_batch(mpcmp_ctx *ctx, int B, const double *x0, c
                                       const double *Tn, double *ox, double *ou, double *oT) {
     if (!ctx || B < 1 || !x0 || !xf || !sx || !su || !sT || !Tn || !ox || !ou || !oT) return MPCMP_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
-    TmpBuf tb(ctx, ((2 * nx + 2 * (nx + nu) * N + 3) * (size_t)B) * sizeof(double));
-    double *d0 = tb.get<double>(nx * B), *d1 = tb.get<double>(nx * B), *dx = tb.get<double>(nx * N * B), *du = tb.get<double>(nu * N * B),
-           *dT = tb.get<double>(B), *dn = tb.get<double>(B), *qx = tb.get<double>(nx * N * B), *qu = tb.get<double>(nu * N * B), *qT = tb.get<double>(B);
-    if (!qT) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d1, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * nu * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dn, Tn, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = time_scale_enqueue(ctx, B, d0, d1, dx, du, dT, dn, nullptr, qx, qu, qT, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ox, qx, sizeof(double) * nx * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ou, qu, sizeof(double) * nu * N * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(oT, qT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    const size_t nb = B, nx = ctx->nx * nb, nxN = nx * ctx->N, nuN = ctx->nu * nb * ctx->N;
+    Stage sg(ctx);
+    double *d0, *d1, *dx, *du, *dT, *dn, *qx, *qu, *qT;
+    sg.in(&d0, x0, nx); sg.in(&d1, xf, nx); sg.in(&dx, sx, nxN); sg.in(&du, su, nuN); sg.in(&dT, sT, nb); sg.in(&dn, Tn, nb);
+    sg.out(&qx, ox, nxN); sg.out(&qu, ou, nuN); sg.out(&qT, oT, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = time_scale_enqueue(ctx, B, d0, d1, dx, du, dT, dn, nullptr, qx, qu, qT, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, const double *wu, const double *wT) {
@@ -1524,9 +1536,8 @@ static int synced_check(mpcmp_ctx *ctx, int B, int n_groups, const double *wx, c
     if (int rc = warm_all_or_none(ctx, wx, wu, wT)) return rc;
     if (int rc = solve_rows_ok(ctx, B)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_sg_group) {            // first use
+    if (!ctx->d_sg_count) {            // first use
         const size_t M = ctx->max_batch, N = ctx->N;
-        if (int rc = dalloc(ctx, &ctx->d_sg_group, M)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_sg_count, M)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_sg_skip, M)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_sg_status, M)) return rc;
@@ -1588,13 +1599,15 @@ extern "C" int mpcmp_solve_batch_synced(mpcmp_ctx *ctx, int B, const double *x0,
             ctx->err = "mpcmp_solve_batch_synced: group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
         }
     hipStream_t st = ctx->stream;
+    Stage sg(ctx);
+    int *dg;
+    sg.in(&dg, group, B);
     if (int rc = upload_problems(ctx, B, x0, xf, wx, wu, wT, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sg_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
-    if (int rc = synced_enqueue(ctx, staged_call(ctx, B, wx != nullptr, st), ctx->d_sg_group, n_groups, ctx->d_sg_T)) return rc;
+    if (int rc = sg.upload()) return rc;
+    if (int rc = synced_enqueue(ctx, staged_call(ctx, B, wx != nullptr, st), dg, n_groups, ctx->d_sg_T)) return rc;
     if (int rc = download_trajectories(ctx, B, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
     if (group_T && n_groups > 0) HIPCHK(ctx, hipMemcpyAsync(group_T, ctx->d_sg_T, sizeof(double) * n_groups, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 // ---- jerk-limited, time-synchronised warm start / comparison trajectory (stands in for Ruckig) ----
@@ -1669,33 +1682,22 @@ static int check_boundary_acc(mpcmp_ctx *ctx, int B, const double *x0, const dou
     return MPCMP_OK;
 }
 
-// host [B][7] boundary accelerations (either may be NULL) staged next to the states; returns the device pointers (or NULL)
-static int stage_acc(mpcmp_ctx *ctx, TmpBuf &tb, int B, const double *acc0, const double *accT, hipStream_t st, const double **d0, const double **dT) {
-    *d0 = *dT = nullptr;
-    if (!acc0 && !accT) return MPCMP_OK;
-    if (ctx->narm != 1) { ctx->err = "boundary accelerations: single-arm contexts only"; return MPCMP_EINVAL; }
-    double *buf = tb.get<double>(14 * (size_t)B);
-    if (!buf) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    if (acc0) { HIPCHK(ctx, hipMemcpyAsync(buf, acc0, sizeof(double) * 7 * B, hipMemcpyHostToDevice, st)); *d0 = buf; }
-    if (accT) { HIPCHK(ctx, hipMemcpyAsync(buf + 7 * (size_t)B, accT, sizeof(double) * 7 * B, hipMemcpyHostToDevice, st)); *dT = buf + 7 * (size_t)B; }
-    return MPCMP_OK;
-}
-
 extern "C" int mpcmp_warm_start_jerk_lim_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *acc0, const double *accT,
                                                const double *vmax, const double *amax, const double *jmax, double *wx, double *wu, double *wT) {
     if (!ctx || !x0 || !xf || !jmax || !wx || !wu || !wT || B < 1) return MPCMP_EINVAL;
     if (B > ctx->max_batch) return MPCMP_ETOOBIG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
-    TmpBuf tb(ctx, (acc0 || accT) ? 14 * (size_t)B * sizeof(double) : 0);
-    const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
-    if (int rc = stage_acc(ctx, tb, B, acc0, accT, st, &da0, &daT)) return rc;
+    if ((acc0 || accT) && ctx->narm != 1) { ctx->err = "boundary accelerations: single-arm contexts only"; return MPCMP_EINVAL; }
+    hipStream_t st = ctx->stream;
+    Stage sg(ctx);
+    double *da0, *daT;
+    sg.in(&da0, acc0, 7 * (size_t)B); sg.in(&daT, accT, 7 * (size_t)B);
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
+    if (int rc = sg.upload()) return rc;
     if (int rc = warm_start_jerk_device(ctx, B, ctx->d_x0, ctx->d_xf, da0, daT, vmax, amax, jmax, ctx->d_wx, ctx->d_wu, ctx->d_wT, st)) return rc;
     if (int rc = download_trajectories(ctx, B, ctx->d_wx, ctx->d_wu, ctx->d_wT, wx, wu, wT, nullptr, st)) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_warm_start_jerk_acc_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *acc0, const double *accT,
@@ -1715,21 +1717,17 @@ extern "C" int mpcmp_jerk_trajectory_lim_batch(mpcmp_ctx *ctx, int B, const doub
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JerkLimits lim;
     if (int rc = jerk_limits(ctx, vmax, amax, jmax, lim)) return rc;
-    const size_t cnt = (size_t)B * (n_pts + 1) * 22;
-    TmpBuf tb(ctx, (cnt + 14 * (size_t)B) * sizeof(double));
-    double *dout = tb.get<double>(cnt);
-    if (!dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
-    const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
-    if (int rc = stage_acc(ctx, tb, B, acc0, accT, st, &da0, &daT)) return rc;
+    hipStream_t st = ctx->stream;
+    Stage sg(ctx);
+    double *da0, *daT, *dout;
+    sg.in(&da0, acc0, 7 * (size_t)B); sg.in(&daT, accT, 7 * (size_t)B); sg.out(&dout, out, (size_t)B * (n_pts + 1) * 22);
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
+    if (int rc = sg.upload()) return rc;
     hipLaunchKernelGGL(k_jerk_traj, dim3(B), dim3(64), 0, st, lim, ctx->d_x0, ctx->d_xf, da0, daT, n_pts, dout, ctx->d_wT);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
     if (T_out) HIPCHK(ctx, hipMemcpyAsync(T_out, ctx->d_wT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_jerk_trajectory_acc_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *acc0, const double *accT,
@@ -1750,21 +1748,17 @@ extern "C" int mpcmp_jerk_point_lim_batch(mpcmp_ctx *ctx, int B, const double *x
     HIPCHK(ctx, hipSetDevice(ctx->device));
     JerkLimits lim;
     if (int rc = jerk_limits(ctx, vmax, amax, jmax, lim)) return rc;
-    TmpBuf tb(ctx, (29 + 14) * (size_t)B * sizeof(double));
-    double *dt = tb.get<double>(B), *dout = tb.get<double>(28 * (size_t)B);
-    if (!dt || !dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(dt, time, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    const double *da0, *daT;
     if (int rc = check_boundary_acc(ctx, B, x0, xf, acc0, accT, vmax, jmax)) return rc;
-    if (int rc = stage_acc(ctx, tb, B, acc0, accT, st, &da0, &daT)) return rc;
+    hipStream_t st = ctx->stream;
+    Stage sg(ctx);
+    double *dt, *da0, *daT, *dout;
+    sg.in(&dt, time, B); sg.in(&da0, acc0, 7 * (size_t)B); sg.in(&daT, accT, 7 * (size_t)B); sg.out(&dout, out, 28 * (size_t)B);
+    if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
+    if (int rc = sg.upload()) return rc;
     hipLaunchKernelGGL(k_jerk_point, dim3(B), dim3(64), 0, st, ctx->d_model, lim, ctx->d_x0, ctx->d_xf, da0, daT, dt, dout, ctx->d_wT);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 28 * B, hipMemcpyDeviceToHost, st));
     if (T_out) HIPCHK(ctx, hipMemcpyAsync(T_out, ctx->d_wT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_jerk_point_acc_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *acc0, const double *accT,
@@ -1783,23 +1777,16 @@ extern "C" int mpcmp_mpc_point_batch(mpcmp_ctx *ctx, int B, const double *sx, co
     SINGLE_ARM_ONLY(ctx);
     if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N;
-    TmpBuf tb(ctx, (21 * N + 2 + 28) * (size_t)B * sizeof(double));
-    double *dx = tb.get<double>(14 * N * B), *du = tb.get<double>(7 * N * B), *dT = tb.get<double>(B), *dt = tb.get<double>(B),
-           *dout = tb.get<double>(28 * (size_t)B);
-    if (!dx || !du || !dT || !dt || !dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * 14 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dt, time, sizeof(double) * B, hipMemcpyHostToDevice, st));
+    const size_t nb = B, NB = ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dt, *dout;
+    sg.in(&dx, sx, 14 * NB); sg.in(&du, su, 7 * NB); sg.in(&dT, sT, nb); sg.in(&dt, time, nb); sg.out(&dout, out, 28 * nb);
+    if (int rc = sg.upload()) return rc;
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    hipLaunchKernelGGL(k_mpc_point, dim3((B + 63) / 64), dim3(64), 0, st, md, ms, ctx->nseg, B, dx, du, dT, dt, dout);
+    hipLaunchKernelGGL(k_mpc_point, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, md, ms, ctx->nseg, B, dx, du, dT, dt, dout);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 28 * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_qp_batch(mpcmp_ctx *ctx, int B, const double *x0, const double *xf, const double *xs,
@@ -1827,44 +1814,36 @@ extern "C" int mpcmp_rnea_batch(mpcmp_ctx *ctx, int n, const double *q, const do
     if (!ctx || n < 1 || !q || !qd || !qdd || !tau) return MPCMP_EINVAL;
     if (int rc = rows_ok(ctx, n, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    TmpBuf tb(ctx, 28 * (size_t)n * sizeof(double));
-    double *dq = tb.get<double>(7 * (size_t)n), *dv = tb.get<double>(7 * (size_t)n), *da = tb.get<double>(7 * (size_t)n), *dt = tb.get<double>(7 * (size_t)n);
-    if (!dq || !dv || !da || !dt) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dq, q, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dv, qd, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(da, qdd, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
+    const size_t n7 = 7 * (size_t)n;
+    Stage sg(ctx);
+    double *dq, *dv, *da, *dt;
+    sg.in(&dq, q, n7); sg.in(&dv, qd, n7); sg.in(&da, qdd, n7); sg.out(&dt, tau, n7);
+    if (int rc = sg.upload()) return rc;
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    hipLaunchKernelGGL(k_rnea_batch, dim3((n + 63) / 64), dim3(64), 0, st, md, ms, n, dq, dv, da, dt);
+    hipLaunchKernelGGL(k_rnea_batch, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, md, ms, n, dq, dv, da, dt);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(tau, dt, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_eval_constraints_batch(mpcmp_ctx *ctx, int n, const double *x, const double *u, double *g, double *G) {
     if (!ctx || n < 1 || !x || !u || !g || !G) return MPCMP_EINVAL;
     if (int rc = rows_ok(ctx, n, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    TmpBuf tb(ctx, (14 + 7 + 8 + 176) * (size_t)n * sizeof(double));
-    double *dx = tb.get<double>(14 * (size_t)n), *du = tb.get<double>(7 * (size_t)n), *dg = tb.get<double>(8 * (size_t)n), *dG = tb.get<double>(176 * (size_t)n);
-    if (!dx || !du || !dg || !dG) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, x, sizeof(double) * 14 * n, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, u, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st));
+    const size_t np = n;
+    Stage sg(ctx);
+    double *dx, *du, *dg, *dG;
+    sg.in(&dx, x, 14 * np); sg.in(&du, u, 7 * np); sg.out(&dg, g, 8 * np); sg.out(&dG, G, 176 * np);
+    if (int rc = sg.upload()) return rc;
     constexpr int NS = 4;
     const size_t l = EvalLds<NS>::size * sizeof(double);
     if (int rc = set_lds(ctx, k_eval_constraints<NS>, l)) return rc;
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
     const int per = ms ? 1 : Dim<NS>::N;           // points per workgroup: one with per-point models (k_eval_constraints)
-    hipLaunchKernelGGL(k_eval_constraints<NS>, dim3((n + per - 1) / per), dim3(Dim<NS>::NT), l, st, ctx->cfg, md, ms, n, dx, du, dg, dG);
+    hipLaunchKernelGGL(k_eval_constraints<NS>, dim3((n + per - 1) / per), dim3(Dim<NS>::NT), l, ctx->stream, ctx->cfg, md, ms, n, dx, du, dg, dG);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(g, dg, sizeof(double) * 8 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(G, dG, sizeof(double) * 176 * n, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_sample_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT,
@@ -1886,18 +1865,13 @@ extern "C" int mpcmp_sample_batch(mpcmp_ctx *ctx, int B, const double *sx, const
     if (!ctx || B < 1 || n_pts < 1 || !sx || !su || !sT || !out) return MPCMP_EINVAL;
     if (int rc = rows_ok(ctx, B, PAYLOAD_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, np = (size_t)B * (n_pts + 1) * 29;
-    TmpBuf tb(ctx, (21 * N * B + B + np) * sizeof(double));
-    double *dx = tb.get<double>(14 * N * B), *du = tb.get<double>(7 * N * B), *dT = tb.get<double>(B), *dout = tb.get<double>(np);
-    if (!dx || !du || !dT || !dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * 14 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = mpcmp_sample_batch_device(ctx, B, dx, du, dT, n_pts, dout, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    const size_t nb = B, NB = ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dout;
+    sg.in(&dx, sx, 14 * NB); sg.in(&du, su, 7 * NB); sg.in(&dT, sT, nb); sg.out(&dout, out, nb * (n_pts + 1) * 29);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_sample_batch_device(ctx, B, dx, du, dT, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 
@@ -1910,29 +1884,21 @@ extern "C" int mpcmp_traj_stats_batch(mpcmp_ctx *ctx, int B, const double *sx, c
     // the kernel keeps the n_pts+1 samples of one trajectory (28 doubles each) in LDS: 160 KB per workgroup on gfx950
     if (sizeof(double) * 28 * (size_t)(n_pts + 1) > 150 * 1024) { ctx->err = "mpcmp_traj_stats_batch: n_pts must be <= 684 (the samples of one trajectory are held in LDS)"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N;
-    TmpBuf tb(ctx, (21 * N * B + B + 14 * (size_t)B + 7 + 74 * (size_t)B) * sizeof(double));
-    double *dx = tb.get<double>(14 * N * B), *du = tb.get<double>(7 * N * B), *dT = tb.get<double>(B), *df = tb.get<double>(14 * (size_t)B),
-           *dj = tb.get<double>(7), *dout = tb.get<double>(74 * (size_t)B);
-    if (!dx || !du || !dT || !df || !dj || !dout) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
     double jerk[7], j10[7];
     mpcmp_default_limits(nullptr, nullptr, nullptr, nullptr, jerk, nullptr);
     for (int r = 0; r < 7; r++) j10[r] = 10.0 * jerk[r];                     // benchmark.cpp:128
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * 14 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(df, xf, sizeof(double) * 14 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dj, j10, sizeof j10, hipMemcpyHostToDevice, st));
+    const size_t nb = B, NB = ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *df, *dj, *dout;
+    sg.in(&dx, sx, 14 * NB); sg.in(&du, su, 7 * NB); sg.in(&dT, sT, nb); sg.in(&df, xf, 14 * nb); sg.in(&dj, j10, 7); sg.out(&dout, out, 74 * nb);
+    if (int rc = sg.upload()) return rc;
     const size_t lds = sizeof(double) * 28 * (size_t)(n_pts + 1);
     if (int rc = set_lds(ctx, k_traj_stats, lds)) return rc;
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, st, md, ms, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
+    hipLaunchKernelGGL(k_traj_stats, dim3(B), dim3(256), lds, ctx->stream, md, ms, ctx->nseg, n_pts, dx, du, dT, df, 1.7, 2.5, dj, dout);   // pandaWrapper.hpp:37-38
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * 74 * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2054,18 +2020,13 @@ extern "C" int mpcmp_clearance_batch(mpcmp_ctx *ctx, int B, const double *sx, co
                                      mpcmp_clearance *out) {
     if (int rc = clearance_check(ctx, B, sx, sT, n_pts, margin, self_gap, out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t nx = (size_t)ctx->nx * ctx->N * B;
-    TmpBuf tb(ctx, (nx + B) * sizeof(double) + sizeof(mpcmp_clearance) * (size_t)B);
-    double *dx = tb.get<double>(nx), *dT = tb.get<double>(B);
-    mpcmp_clearance *dout = tb.get<mpcmp_clearance>(B);
-    if (!dx || !dT || !dout) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = clearance_enqueue(ctx, B, dx, dT, n_pts, margin, self_gap, dout, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(mpcmp_clearance) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    Stage sg(ctx);
+    double *dx, *dT;
+    mpcmp_clearance *dout;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = clearance_enqueue(ctx, B, dx, dT, n_pts, margin, self_gap, dout, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 static int select_check(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group, int n_groups,
@@ -2077,13 +2038,7 @@ static int select_check(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_inf
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (!ctx->d_sel_key) {            // first use
         HIPCHK(ctx, hipSetDevice(ctx->device));
-        const size_t M = ctx->max_batch;
-        if (int rc = dalloc(ctx, &ctx->d_sel_key, M)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_sel_group, M)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_sel_chosen, M)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_sel_clr, M)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_sel_T, M)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_sel_info, M)) return rc;
+        if (int rc = dalloc(ctx, &ctx->d_sel_key, (size_t)ctx->max_batch)) return rc;
     }
     return MPCMP_OK;
 }
@@ -2105,15 +2060,15 @@ extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT,
         }
     if (n_groups == 0) return MPCMP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_T, sT, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_info, info, sizeof(mpcmp_info) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_clr, clr, sizeof(mpcmp_clearance) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_sel_group, group, sizeof(int) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, select_clear_launch(B, ctx->d_sel_T, ctx->d_sel_info, ctx->d_sel_clr, ctx->d_sel_group, n_groups, ctx->d_sel_key, ctx->d_sel_chosen, st));
-    HIPCHK(ctx, hipMemcpyAsync(chosen, ctx->d_sel_chosen, sizeof(int) * n_groups, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    Stage sg(ctx);
+    double *dT;
+    mpcmp_info *di;
+    mpcmp_clearance *dc;
+    int *dg, *dch;
+    sg.in(&dT, sT, B); sg.in(&di, info, B); sg.in(&dc, clr, B); sg.in(&dg, group, B); sg.out(&dch, chosen, n_groups);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, select_clear_launch(B, dT, di, dc, dg, n_groups, ctx->d_sel_key, dch, ctx->stream));
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2171,22 +2126,13 @@ extern "C" int mpcmp_route_legs(mpcmp_ctx *ctx, int B, int M, const double *x0, 
     if (int rc = rows_ok(ctx, L, BOUND_ROWS)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nx = ctx->nx, nv = (size_t)B * M * (nx / 2);
-    TmpBuf tb(ctx, (2 * nx * B + 3 * nv + B + 2 * nx * L) * sizeof(double));
-    double *d0 = tb.get<double>(nx * B), *df = tb.get<double>(nx * B), *dv = tb.get<double>(nv + 1), *dq = tb.get<double>(nv + 1), *ds = tb.get<double>(B),
-           *dl0 = tb.get<double>(nx * L), *dlf = tb.get<double>(nx * L), *dvo = tb.get<double>(nv + 1);
-    if (!dvo) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(d0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(df, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    if (M > 0) HIPCHK(ctx, hipMemcpyAsync(dv, via, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    if (M > 0 && via_qd) HIPCHK(ctx, hipMemcpyAsync(dq, via_qd, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    if (speed) HIPCHK(ctx, hipMemcpyAsync(ds, speed, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = route_legs_enqueue(ctx, B, M, d0, dv, (M > 0 && via_qd) ? dq : nullptr, speed ? ds : nullptr, df, dl0, dlf, dvo, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(leg_x0, dl0, sizeof(double) * nx * L, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(leg_xf, dlf, sizeof(double) * nx * L, hipMemcpyDeviceToHost, st));
-    if (via_qd_out && M > 0) HIPCHK(ctx, hipMemcpyAsync(via_qd_out, dvo, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    Stage sg(ctx);
+    double *d0, *df, *dv, *dq, *ds, *dl0, *dlf, *dvo;
+    sg.in(&d0, x0, nx * B); sg.in(&df, xf, nx * B); sg.in(&dv, M > 0 ? via : nullptr, nv); sg.in(&dq, M > 0 ? via_qd : nullptr, nv); sg.in(&ds, speed, B);
+    sg.out(&dl0, leg_x0, nx * L); sg.out(&dlf, leg_xf, nx * L); sg.out(&dvo, M > 0 ? via_qd_out : nullptr, nv);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = route_legs_enqueue(ctx, B, M, d0, dv, dq, ds, df, dl0, dlf, dvo, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 static int route_join_check(mpcmp_ctx *ctx, int B, int M, const void *sx, const void *su, const void *sT, const void *info, const void *clr, const void *rT,
@@ -2213,26 +2159,17 @@ extern "C" int mpcmp_route_join(mpcmp_ctx *ctx, int B, int M, const double *sx, 
     int L;
     if (int rc = route_join_check(ctx, B, M, sx, su, sT, info, clr, rT, rinfo, seam, rclr, &L)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, nx = ctx->nx, nu = ctx->nu;
-    TmpBuf tb(ctx, ((nx + nu) * N * L + L + B) * sizeof(double) + (sizeof(mpcmp_info) + sizeof(mpcmp_clearance)) * ((size_t)L + B) + sizeof(mpcmp_route_seam) * B);
-    double *dx = tb.get<double>(nx * N * L), *du = tb.get<double>(nu * N * L), *dT = tb.get<double>(L), *drT = tb.get<double>(B);
-    mpcmp_info *di = tb.get<mpcmp_info>(L), *dri = tb.get<mpcmp_info>(B);
-    mpcmp_clearance *dc = tb.get<mpcmp_clearance>(L), *drc = tb.get<mpcmp_clearance>(B);
-    mpcmp_route_seam *ds = tb.get<mpcmp_route_seam>(B);
-    if (!ds) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * nx * N * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * nu * N * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(di, info, sizeof(mpcmp_info) * L, hipMemcpyHostToDevice, st));
-    if (clr) HIPCHK(ctx, hipMemcpyAsync(dc, clr, sizeof(mpcmp_clearance) * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, route_join_launch(B, M, ctx->N, ctx->narm, dx, du, dT, di, clr ? dc : nullptr, drT, dri, ds, clr ? drc : nullptr, st));
-    HIPCHK(ctx, hipMemcpyAsync(rT, drT, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(rinfo, dri, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(seam, ds, sizeof(mpcmp_route_seam) * B, hipMemcpyDeviceToHost, st));
-    if (clr) HIPCHK(ctx, hipMemcpyAsync(rclr, drc, sizeof(mpcmp_clearance) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    const size_t NL = (size_t)ctx->N * L;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *drT;
+    mpcmp_info *di, *dri;
+    mpcmp_clearance *dc, *drc;         // (clr and rclr: both given or neither, route_join_check)
+    mpcmp_route_seam *ds;
+    sg.in(&dx, sx, ctx->nx * NL); sg.in(&du, su, ctx->nu * NL); sg.in(&dT, sT, L); sg.in(&di, info, L); sg.in(&dc, clr, L);
+    sg.out(&drT, rT, B); sg.out(&dri, rinfo, B); sg.out(&ds, seam, B); sg.out(&drc, rclr, B);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, route_join_launch(B, M, ctx->N, ctx->narm, dx, du, dT, di, dc, drT, dri, ds, drc, ctx->stream));
+    return sg.finish();
 }
 
 // everything a route solve is refused for, and its scratch (first call only)
@@ -2253,15 +2190,6 @@ static int route_solve_check(mpcmp_ctx *ctx, int B, int M, const void *x0, const
         if (int rc = dalloc(ctx, &ctx->d_rt_wu, Mx * nu * N)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_rt_wT, Mx)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_rt_info, Mx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_rinfo, Mx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_in0, Mx * nx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_inf, Mx * nx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_via, Mx * nu)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_vqd, Mx * nu)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_speed, Mx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_vout, Mx * nu)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_T, Mx)) return rc;
-        if (int rc = dalloc(ctx, &ctx->d_rt_seam, Mx)) return rc;
         if (int rc = dalloc(ctx, &ctx->d_rt_x0, Mx * nx)) return rc;      // (last: the mark of a complete scratch)
     }
     return MPCMP_OK;
@@ -2304,23 +2232,17 @@ extern "C" int mpcmp_solve_route_batch(mpcmp_ctx *ctx, int B, int M, const doubl
     if (int rc = route_solve_check(ctx, B, M, x0, via, xf, jmax, sx, su, sT, rT, rinfo, seam, &L)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nx = ctx->nx, nv = (size_t)B * M * (nx / 2);
-    const bool vq = M > 0 && via_qd;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_in0, x0, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_inf, xf, sizeof(double) * nx * B, hipMemcpyHostToDevice, st));
-    if (M > 0) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_via, via, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    if (vq) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_vqd, via_qd, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    if (speed) HIPCHK(ctx, hipMemcpyAsync(ctx->d_rt_speed, speed, sizeof(double) * B, hipMemcpyHostToDevice, st));
-    if (int rc = route_solve_enqueue(ctx, B, M, L, ctx->d_rt_in0, ctx->d_rt_via, vq ? ctx->d_rt_vqd : nullptr, speed ? ctx->d_rt_speed : nullptr, ctx->d_rt_inf,
-                                     jmax, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, ctx->d_rt_T, ctx->d_rt_rinfo, ctx->d_rt_seam, ctx->d_rt_vout, st))
-        return rc;
+    Stage sg(ctx);
+    double *d0, *df, *dv, *dq, *ds, *drT, *dvo;
+    mpcmp_info *dri;
+    mpcmp_route_seam *dsm;
+    sg.in(&d0, x0, nx * B); sg.in(&df, xf, nx * B); sg.in(&dv, M > 0 ? via : nullptr, nv); sg.in(&dq, M > 0 ? via_qd : nullptr, nv); sg.in(&ds, speed, B);
+    sg.out(&drT, rT, B); sg.out(&dri, rinfo, B); sg.out(&dsm, seam, B); sg.out(&dvo, M > 0 ? via_qd_out : nullptr, nv);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = route_solve_enqueue(ctx, B, M, L, d0, dv, dq, ds, df, jmax, ctx->d_sx, ctx->d_su, ctx->d_sT, ctx->d_info, drT, dri, dsm, dvo, st)) return rc;
     if (int rc = download_trajectories(ctx, L, ctx->d_sx, ctx->d_su, ctx->d_sT, sx, su, sT, info, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(rT, ctx->d_rt_T, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(rinfo, ctx->d_rt_rinfo, sizeof(mpcmp_info) * B, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(seam, ctx->d_rt_seam, sizeof(mpcmp_route_seam) * B, hipMemcpyDeviceToHost, st));
-    if (via_qd_out && M > 0) HIPCHK(ctx, hipMemcpyAsync(via_qd_out, ctx->d_rt_vout, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    return sg.finish();
 }
 
 static int route_sample_check(mpcmp_ctx *ctx, int B, int M, const void *sx, const void *su, const void *sT, int n_pts, const void *out, int *L) {
@@ -2345,18 +2267,13 @@ extern "C" int mpcmp_sample_route_batch(mpcmp_ctx *ctx, int B, int M, const doub
     int L;
     if (int rc = route_sample_check(ctx, B, M, sx, su, sT, n_pts, out, &L)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t N = ctx->N, np = (size_t)B * (n_pts + 1) * 29;
-    TmpBuf tb(ctx, (21 * N * L + L + np) * sizeof(double));
-    double *dx = tb.get<double>(14 * N * L), *du = tb.get<double>(7 * N * L), *dT = tb.get<double>(L), *dout = tb.get<double>(np);
-    if (!dout) { ctx->err = "device scratch allocation failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dx, sx, sizeof(double) * 14 * N * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(du, su, sizeof(double) * 7 * N * L, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dT, sT, sizeof(double) * L, hipMemcpyHostToDevice, st));
-    if (int rc = mpcmp_sample_route_batch_device(ctx, B, M, dx, du, dT, n_pts, dout, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, dout, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    const size_t NL = (size_t)ctx->N * L;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dout;
+    sg.in(&dx, sx, 14 * NL); sg.in(&du, su, 7 * NL); sg.in(&dT, sT, L); sg.out(&dout, out, (size_t)B * (n_pts + 1) * 29);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_sample_route_batch_device(ctx, B, M, dx, du, dT, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2413,23 +2330,15 @@ extern "C" int mpcmp_pose_targets_batch(mpcmp_ctx *ctx, int B, int arm, const do
         }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    TmpBuf tb(ctx, (9 + 3 + 6 + 7 * (size_t)S + 7 + nx) * nb * sizeof(double) + nb * sizeof(mpcmp_ik_info));
-    double *dR = tb.get<double>(9 * nb), *dp_ = tb.get<double>(3 * nb), *dtw = twist ? tb.get<double>(6 * nb) : nullptr,
-           *dsd = tb.get<double>(7 * nb * S), *dqr = q_ref ? tb.get<double>(7 * nb) : nullptr, *dxf = tb.get<double>(nx * nb);
-    mpcmp_ik_info *dinfo = info ? tb.get<mpcmp_ik_info>(nb) : nullptr;
-    if (!tb.ok) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(dR, R, sizeof(double) * 9 * nb, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dp_, p, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, st));
-    if (dtw) HIPCHK(ctx, hipMemcpyAsync(dtw, twist, sizeof(double) * 6 * nb, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dsd, seeds, sizeof(double) * 7 * nb * S, hipMemcpyHostToDevice, st));
-    if (dqr) HIPCHK(ctx, hipMemcpyAsync(dqr, q_ref, sizeof(double) * 7 * nb, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(dxf, xf, sizeof(double) * nx * nb, hipMemcpyHostToDevice, st));     // the other arm's columns come back as they were
-    if (int rc = mpcmp_pose_targets_batch_device(ctx, B, arm, dR, dp_, dtw, S, dsd, dqr, dxf, dinfo, st)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(xf, dxf, sizeof(double) * nx * nb, hipMemcpyDeviceToHost, st));
-    if (info) HIPCHK(ctx, hipMemcpyAsync(info, dinfo, sizeof(mpcmp_ik_info) * nb, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    Stage sg(ctx);
+    double *dR, *dp_, *dtw, *dsd, *dqr, *dxf;
+    mpcmp_ik_info *dinfo;
+    sg.in(&dR, R, 9 * nb); sg.in(&dp_, p, 3 * nb); sg.in(&dtw, twist, 6 * nb); sg.in(&dsd, seeds, 7 * nb * S); sg.in(&dqr, q_ref, 7 * nb);
+    sg.inout(&dxf, xf, nx * nb);       // the other arm's columns come back as they were
+    sg.out(&dinfo, info, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_pose_targets_batch_device(ctx, B, arm, dR, dp_, dtw, S, dsd, dqr, dxf, dinfo, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2554,17 +2463,13 @@ extern "C" int mpcmp_rh_update(mpcmp_ctx *ctx, int n, const int *idx, const doub
             for (size_t k = 0; k < n * nx; k++)
                 if (!std::isfinite(v[k])) { ctx->err = "mpcmp_rh_update: a state or target value is not finite"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    TmpBuf tb(ctx, (size_t)n * sizeof(int) + 2 * n * nx * sizeof(double));
-    int *di = idx ? tb.get<int>(n) : nullptr;
-    double *dx = x ? tb.get<double>(n * nx) : nullptr, *dxf = xf ? tb.get<double>(n * nx) : nullptr;
-    if (!tb.ok) { ctx->err = "hipMalloc failed"; return MPCMP_ERUNTIME; }
-    hipStream_t st = ctx->stream;
-    if (di) HIPCHK(ctx, hipMemcpyAsync(di, idx, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    if (dx) HIPCHK(ctx, hipMemcpyAsync(dx, x, sizeof(double) * n * nx, hipMemcpyHostToDevice, st));
-    if (dxf) HIPCHK(ctx, hipMemcpyAsync(dxf, xf, sizeof(double) * n * nx, hipMemcpyHostToDevice, st));
-    if (int rc = rh_update_enqueue(ctx, n, di, dx, dxf, flags, st)) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return MPCMP_OK;
+    Stage sg(ctx);
+    int *di;
+    double *dx, *dxf;
+    sg.in(&di, idx, n); sg.in(&dx, x, n * nx); sg.in(&dxf, xf, n * nx);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = rh_update_enqueue(ctx, n, di, dx, dxf, flags, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 extern "C" int mpcmp_rh_update_device(mpcmp_ctx *ctx, int n, const int *d_idx, const double *d_x, const double *d_xf, int flags, void *hip_stream) {

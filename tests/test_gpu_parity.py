@@ -670,3 +670,47 @@ def test_jerk_limited_warm_start_vs_oracle_and_stored_ruckig(M, golden_dir):
     for b in range(4):
         xs, us, Tb, oi = o.solve(ocfg, x0[b], xf[b], wx[b], wu[b], wT[b])
         assert abs(sT[b] - Tb) <= 1e-6 * abs(Tb) and np.abs(sx[b] - xs).max() <= 1e-6 and info["qp_iters_total"][b] == oi.qp_iters_total
+
+
+def test_host_staging_across_a_scratch_growth_and_optional_arrays(M):
+    """the host-pointer entry points stage their arrays in one device scratch of the context that grows when a call needs more than it holds (1 MiB at
+    first): results before, during and after a growth, and every combination of optional arrays, all bit for bit (same kernels, same inputs; no solve)"""
+    import torch
+    from mpc_motion_planner_amd import scenarios
+    cfg, _ = _cfgs(M, 4, 1)
+    B = 2
+    s = M.Solver(cfg, 8)
+    jmax = MARGINS[4] * M.default_limits()["jmax"]
+    x0, xf = scenarios.make_batch(B, stream_offset=900)
+    wx, wu, wT = s.warm_start_jerk(x0, xf, jmax)
+    rng = np.random.default_rng(11)
+    q, v, a = rng.uniform(-2, 2, (3, 7)), rng.uniform(-2, 2, (3, 7)), rng.uniform(-10, 10, (3, 7))
+    # 1. inside the first allocation
+    tau1, smp1 = s.rnea(q, v, a), s.sample(wx, wu, wT, n_pts=8)
+    assert np.all(np.isfinite(tau1)) and np.all(np.isfinite(smp1)) and np.abs(tau1).max() > 0.0
+    # 2. the output alone (2 x 3001 x 29 doubles = 1.39 MB) is larger than the first allocation: the scratch grows in this call
+    big = s.sample(wx, wu, wT, n_pts=3000)
+    tx, tu, tT = (torch.from_numpy(np.ascontiguousarray(w)).to("cuda") for w in (wx, wu, wT))
+    tout = torch.zeros(B, 3001, 29, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    s.sample_device(B, tx.data_ptr(), tu.data_ptr(), tT.data_ptr(), 3000, tout.data_ptr())
+    torch.cuda.synchronize()
+    assert big.shape == (B, 3001, 29) and np.array_equal(big, tout.cpu().numpy())
+    # 3. after the growth
+    assert np.array_equal(s.rnea(q, v, a), tau1) and np.array_equal(s.sample(wx, wu, wT, n_pts=8), smp1)
+    # 4. optional inputs of rh_update: rh_get shows the states (the targets are not among its outputs); a row is written only where x is given
+    s.rh_init(x0, xf)
+    xa, xb = x0 + 0.01, x0 - 0.02
+    s.rh_update([1], x=xa[1:])
+    assert np.array_equal(s.rh_get()[0], np.stack([x0[0], xa[1]]))
+    s.rh_update([0], xf=xf[1:])
+    assert np.array_equal(s.rh_get()[0], np.stack([x0[0], xa[1]]))
+    s.rh_update(x=xb, xf=xf[::-1])
+    assert np.array_equal(s.rh_get()[0], xb)
+    # 5. optional inputs of jerk_point: a boundary acceleration that is not given is zero
+    x0s, xfs = x0.copy(), xf.copy(); x0s[:, 7:] *= 0.6; xfs[:, 7:] *= 0.6
+    acc, z, t = rng.uniform(-0.8, 0.8, (B, 7)) * MARGINS[2] * M.default_limits()["amax"], np.zeros((B, 7)), 0.4 * wT
+    for only, full in ((dict(acc0=acc), dict(acc0=acc, accT=z)), (dict(accT=acc), dict(acc0=z, accT=acc))):
+        p1, T1 = s.jerk_point(x0s, xfs, jmax, t, **only)
+        p2, T2 = s.jerk_point(x0s, xfs, jmax, t, **full)
+        assert np.array_equal(p1, p2) and np.array_equal(T1, T2) and np.all(np.isfinite(p1))
