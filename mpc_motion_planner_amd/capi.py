@@ -70,71 +70,60 @@ BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7),
 # the seam record of a joined route (mpcmp_route_seam, include/mpcmp.h)
 ROUTE_SEAM_DTYPE = np.dtype([("state_jump_inf", "f8"), ("acc_jump_inf", "f8"), ("leg_longest", "i4"), ("leg_first_bad", "i4")])
 
-# every symbol include/mpcmp.h declares (the CPU test suite checks the library exports all of them)
-SYMBOLS = ["mpcmp_default_model", "mpcmp_model_from_urdf", "mpcmp_models_from_urdf", "mpcmp_default_limits", "mpcmp_default_config",
-           "mpcmp_set_margins", "mpcmp_set_min_height", "mpcmp_num_nodes", "mpcmp_time_nodes", "mpcmp_version",
-           "mpcmp_create", "mpcmp_create_multi", "mpcmp_destroy", "mpcmp_set_config", "mpcmp_last_error", "mpcmp_solve_batch",
-           "mpcmp_solve_batch_device", "mpcmp_warm_start_batch", "mpcmp_rnea_batch",
-           "mpcmp_eval_constraints_batch", "mpcmp_qp_batch", "mpcmp_sample_batch", "mpcmp_sample_batch_device",
-           "mpcmp_kernel_timing", "mpcmp_debug_stamps", "mpcmp_rh_init", "mpcmp_rh_run", "mpcmp_rh_get", "mpcmp_traj_stats_batch",
-           "mpcmp_tool_jacobian", "mpcmp_forward_velocities", "mpcmp_inverse_velocities", "mpcmp_inverse_kinematics",
-           "mpcmp_warm_start_jerk_batch", "mpcmp_warm_start_jerk_batch_device", "mpcmp_jerk_trajectory_batch",
-           "mpcmp_jerk_point_batch", "mpcmp_mpc_point_batch", "mpcmp_debug_fetch",
-           "mpcmp_warm_start_jerk_acc_batch", "mpcmp_warm_start_jerk_acc_batch_device", "mpcmp_jerk_trajectory_acc_batch", "mpcmp_jerk_point_acc_batch",
-           "mpcmp_warm_start_jerk_lim_batch", "mpcmp_jerk_trajectory_lim_batch", "mpcmp_jerk_point_lim_batch", "mpcmp_reset_multipliers", "mpcmp_rh_stats",
-           "mpcmp_rh_update", "mpcmp_rh_update_device", "mpcmp_pose_targets_batch", "mpcmp_pose_targets_batch_device",
-           "mpcmp_model_add_payload", "mpcmp_set_payloads", "mpcmp_set_payloads_device",
-           "mpcmp_set_time_windows", "mpcmp_set_time_windows_device", "mpcmp_time_scale_batch", "mpcmp_time_scale_batch_device",
-           "mpcmp_solve_batch_synced", "mpcmp_solve_batch_synced_device",
-           "mpcmp_link_spheres", "mpcmp_clearance_config", "mpcmp_set_robot_spheres", "mpcmp_set_obstacles", "mpcmp_set_obstacles_device",
-           "mpcmp_clearance_batch", "mpcmp_clearance_batch_device", "mpcmp_select_clear_batch", "mpcmp_select_clear_batch_device",
-           "mpcmp_bounds_from_config", "mpcmp_bounds_from_margins", "mpcmp_set_bounds", "mpcmp_set_bounds_device",
-           "mpcmp_route_via_velocity", "mpcmp_route_locate", "mpcmp_route_legs", "mpcmp_route_legs_device", "mpcmp_route_join",
-           "mpcmp_route_join_device", "mpcmp_solve_route_batch", "mpcmp_solve_route_batch_device", "mpcmp_sample_route_batch",
-           "mpcmp_sample_route_batch_device"]
-
-# prototypes of the final-time entry points (include/mpcmp.h): the argument kinds, "i" = int, "p" = pointer
-PROTOTYPES = {
-    "mpcmp_set_time_windows": "pi" + "p" * 2,
-    "mpcmp_set_time_windows_device": "pi" + "p" * 3,
-    "mpcmp_time_scale_batch": "pi" + "p" * 9,
-    "mpcmp_time_scale_batch_device": "pi" + "p" * 10,
-    "mpcmp_solve_batch_synced": "pi" + "p" * 6 + "i" + "p" * 5,
-    "mpcmp_solve_batch_synced_device": "pi" + "p" * 6 + "i" + "p" * 6,
+# The whole C ABI, every function include/mpcmp.h declares in the header's order: name -> the kinds of its arguments, "p" = any pointer (a context,
+# a struct, an array, a hipStream_t as void *), "i" = int, "d" = double, "l" = long.  lib() declares exactly this to ctypes, so a 64-bit address
+# passed as a plain Python integer arrives whole; the CPU test suite checks the table against the header and the library's exports.
+ABI = {
+    "mpcmp_reset_multipliers": "p",
+    # configuration helpers
+    "mpcmp_default_model": "p", "mpcmp_model_add_payload": "ppp", "mpcmp_model_from_urdf": "pp", "mpcmp_models_from_urdf": "pipp",
+    "mpcmp_default_limits": "pppppp", "mpcmp_default_config": "pii", "mpcmp_set_margins": "pdddd", "mpcmp_set_min_height": "pd",
+    "mpcmp_num_nodes": "i", "mpcmp_time_nodes": "ip", "mpcmp_version": "",
+    # context
+    "mpcmp_create": "ppiip", "mpcmp_create_multi": "ppiiip", "mpcmp_destroy": "p", "mpcmp_set_config": "pp", "mpcmp_last_error": "p",
+    # per-problem payloads
+    "mpcmp_set_payloads": "pip", "mpcmp_set_payloads_device": "pipp",
+    # the hot path
+    "mpcmp_solve_batch": "pi" + "p" * 9, "mpcmp_solve_batch_device": "pi" + "p" * 10, "mpcmp_warm_start_batch": "pippppp",
+    # per-problem final-time windows and bounds
+    "mpcmp_set_time_windows": "pipp", "mpcmp_set_time_windows_device": "pippp",
+    "mpcmp_bounds_from_config": "pp", "mpcmp_bounds_from_margins": "dddddp", "mpcmp_set_bounds": "pip", "mpcmp_set_bounds_device": "pipp",
+    # time scaling, time-synchronised solve
+    "mpcmp_time_scale_batch": "pi" + "p" * 9, "mpcmp_time_scale_batch_device": "pi" + "p" * 10,
+    "mpcmp_solve_batch_synced": "pi" + "p" * 6 + "i" + "p" * 5, "mpcmp_solve_batch_synced_device": "pi" + "p" * 6 + "i" + "p" * 6,
+    # leaf kernels, resampling
+    "mpcmp_rnea_batch": "pipppp", "mpcmp_eval_constraints_batch": "pipppp", "mpcmp_qp_batch": "pi" + "p" * 8,
+    "mpcmp_sample_batch": "pipppip", "mpcmp_sample_batch_device": "pipppipp",
+    # jerk-limited warm start
+    "mpcmp_warm_start_jerk_batch": "pipppppp", "mpcmp_warm_start_jerk_batch_device": "pippppppp",
+    "mpcmp_jerk_trajectory_batch": "pipppipp", "mpcmp_jerk_point_batch": "pipppppp",
+    "mpcmp_warm_start_jerk_acc_batch": "pi" + "p" * 8, "mpcmp_warm_start_jerk_acc_batch_device": "pi" + "p" * 9,
+    "mpcmp_jerk_trajectory_acc_batch": "pipppppipp", "mpcmp_jerk_point_acc_batch": "pi" + "p" * 8,
+    "mpcmp_warm_start_jerk_lim_batch": "pi" + "p" * 10, "mpcmp_jerk_trajectory_lim_batch": "pi" + "p" * 7 + "ipp",
+    "mpcmp_jerk_point_lim_batch": "pi" + "p" * 10, "mpcmp_mpc_point_batch": "pippppp",
+    # scenario helpers of the robot wrapper
+    "mpcmp_tool_jacobian": "ppppp", "mpcmp_forward_velocities": "pppp", "mpcmp_inverse_velocities": "ppppp", "mpcmp_inverse_kinematics": "pppppp",
+    # batched tool-pose targets, trajectory checks
+    "mpcmp_pose_targets_batch": "piipppipppp", "mpcmp_pose_targets_batch_device": "piipppippppp", "mpcmp_traj_stats_batch": "pippppip",
+    # clearance
+    "mpcmp_link_spheres": "pddipp", "mpcmp_clearance_config": "pippipipppp", "mpcmp_set_robot_spheres": "piip",
+    "mpcmp_set_obstacles": "piip", "mpcmp_set_obstacles_device": "piipp",
+    "mpcmp_clearance_batch": "pippidip", "mpcmp_clearance_batch_device": "pippidipp",
+    "mpcmp_select_clear_batch": "pippppip", "mpcmp_select_clear_batch_device": "pippppipp",
+    # via-point routes
+    "mpcmp_route_via_velocity": "ppppidp", "mpcmp_route_legs": "pii" + "p" * 8, "mpcmp_route_legs_device": "pii" + "p" * 9,
+    "mpcmp_route_join": "pii" + "p" * 9, "mpcmp_route_join_device": "pii" + "p" * 10,
+    "mpcmp_solve_route_batch": "pii" + "p" * 14, "mpcmp_solve_route_batch_device": "pii" + "p" * 15,
+    "mpcmp_route_locate": "ipdpp", "mpcmp_sample_route_batch": "piipppip", "mpcmp_sample_route_batch_device": "piipppipp",
+    # receding-horizon driver
+    "mpcmp_rh_init": "pipp", "mpcmp_rh_run": "pidi", "mpcmp_rh_get": "pppppp", "mpcmp_rh_stats": "ppp",
+    "mpcmp_rh_update": "pipppi", "mpcmp_rh_update_device": "pipppip",
+    # measurement hooks, diagnostics
+    "mpcmp_kernel_timing": "pippp", "mpcmp_debug_fetch": "pipl", "mpcmp_debug_stamps": "pip",
 }
-# prototypes of the clearance entry points, with "d" = double
-CLEARANCE_PROTOTYPES = {
-    "mpcmp_link_spheres": "pddipp",
-    "mpcmp_clearance_config": "pippipippp" + "p",
-    "mpcmp_set_robot_spheres": "piip",
-    "mpcmp_set_obstacles": "piip",
-    "mpcmp_set_obstacles_device": "piipp",
-    "mpcmp_clearance_batch": "pippidip",
-    "mpcmp_clearance_batch_device": "pippidipp",
-    "mpcmp_select_clear_batch": "pippppip",
-    "mpcmp_select_clear_batch_device": "pippppipp",
-}
-# prototypes of the per-problem bounds (kept apart from PROTOTYPES, whose entries are int / pointer only)
-BOUNDS_PROTOTYPES = {
-    "mpcmp_bounds_from_config": "pp",
-    "mpcmp_bounds_from_margins": "dddddp",
-    "mpcmp_set_bounds": "pip",
-    "mpcmp_set_bounds_device": "pipp",
-}
-# prototypes of the via-point routes
-ROUTE_PROTOTYPES = {
-    "mpcmp_route_via_velocity": "ppppidp",
-    "mpcmp_route_locate": "ipdpp",
-    "mpcmp_route_legs": "pii" + "p" * 8,
-    "mpcmp_route_legs_device": "pii" + "p" * 9,
-    "mpcmp_route_join": "pii" + "p" * 9,
-    "mpcmp_route_join_device": "pii" + "p" * 10,
-    "mpcmp_solve_route_batch": "pii" + "p" * 14,
-    "mpcmp_solve_route_batch_device": "pii" + "p" * 15,
-    "mpcmp_sample_route_batch": "pii" + "ppp" + "ip",
-    "mpcmp_sample_route_batch_device": "pii" + "ppp" + "ipp",
-}
-_KINDS = {"i": C.c_int, "p": C.c_void_p, "d": C.c_double}
+_KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
+_RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
+SYMBOLS = list(ABI)
 
 
 def library_path():
@@ -187,21 +176,10 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        L.mpcmp_version.restype = C.c_char_p
-        L.mpcmp_last_error.restype = C.c_char_p
-        L.mpcmp_last_error.argtypes = [C.c_void_p]
-        L.mpcmp_rh_update.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
-        L.mpcmp_rh_update_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.mpcmp_pose_targets_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
-        L.mpcmp_pose_targets_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 5
-        L.mpcmp_set_payloads.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.mpcmp_set_payloads_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        for name, kinds in PROTOTYPES.items():
-            getattr(L, name).argtypes = [C.c_int if k == "i" else C.c_void_p for k in kinds]
-            getattr(L, name).restype = C.c_int
-        for name, kinds in list(CLEARANCE_PROTOTYPES.items()) + list(BOUNDS_PROTOTYPES.items()) + list(ROUTE_PROTOTYPES.items()):
-            getattr(L, name).argtypes = [_KINDS[k] for k in kinds]
-            getattr(L, name).restype = C.c_int
+        for name, kinds in ABI.items():
+            f = getattr(L, name)
+            f.argtypes = [_KINDS[k] for k in kinds]
+            f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
         _lib = L
     return _lib
 
@@ -212,8 +190,9 @@ def check(rc, ctx=None):
         raise MpcmpError(rc, (msg or b"").decode())
 
 
-def dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
+def host(a):
+    """the address of a host array for a pointer argument; None (NULL) for None and for an array without elements"""
+    return a.ctypes.data if a is not None and a.size else None
 
 
 def f64(a):
@@ -286,7 +265,7 @@ def _records(a, dtype, what):
 def link_spheres(model, radius, spacing, max_spheres=MAX_SPHERES):
     """mpcmp_link_spheres: a SKELETON sphere model from the joint origins alone (not a fitted hull), SPHERE_DTYPE [n]"""
     out = np.zeros(max(int(max_spheres), 1), dtype=SPHERE_DTYPE); n = C.c_int(0)
-    check(lib().mpcmp_link_spheres(C.addressof(model), float(radius), float(spacing), int(max_spheres), out.ctypes.data, C.addressof(n)))
+    check(lib().mpcmp_link_spheres(C.byref(model), float(radius), float(spacing), int(max_spheres), host(out), C.byref(n)))
     return out[:n.value].copy()
 
 
@@ -305,9 +284,8 @@ def clearance_config(models, spheres_per_arm, obstacles, q, self_gap=0):
     obs = np.zeros(0, dtype=OBSTACLE_DTYPE) if obstacles is None else _records(obstacles, OBSTACLE_DTYPE, "obstacle").reshape(-1)
     q = f64(q).reshape(7 * narm)
     d, sp, ot = C.c_double(0), C.c_int(0), C.c_int(0)
-    check(lib().mpcmp_clearance_config(C.addressof(arr), narm, cnt.ctypes.data, tab.ctypes.data if tab.shape[0] else None, obs.shape[0],
-                                       obs.ctypes.data if obs.shape[0] else None, int(self_gap), q.ctypes.data, C.addressof(d), C.addressof(sp),
-                                       C.addressof(ot)))
+    check(lib().mpcmp_clearance_config(arr, narm, host(cnt), host(tab), obs.shape[0], host(obs), int(self_gap), host(q), C.byref(d), C.byref(sp),
+                                       C.byref(ot)))
     return d.value, sp.value, ot.value
 
 
@@ -330,21 +308,21 @@ def models_from_urdf(path, max_chains=8):
 def tool_jacobian(model, q):
     """World-aligned 6x7 tool-frame Jacobian [linear; angular], tool position and rotation."""
     q = f64(q); J = np.zeros((6, 7)); p = np.zeros(3); R = np.zeros((3, 3))
-    check(lib().mpcmp_tool_jacobian(C.byref(model), dp(q), dp(J), dp(p), dp(R)))
+    check(lib().mpcmp_tool_jacobian(C.byref(model), host(q), host(J), host(p), host(R)))
     return J, p, R
 
 
 def forward_velocities(model, q, qd):
     """PandaWrapper::forward_velocities: task velocity [linear(3); angular(3)] of the tool frame."""
     q, qd = f64(q), f64(qd); out = np.zeros(6)
-    check(lib().mpcmp_forward_velocities(C.byref(model), dp(q), dp(qd), dp(out)))
+    check(lib().mpcmp_forward_velocities(C.byref(model), host(q), host(qd), host(out)))
     return out
 
 
 def inverse_velocities(model, q, linear_velocity, angular_velocity):
     """PandaWrapper::inverse_velocities: damped (1e-5) pseudo-inverse map from task to joint velocity."""
     q, lin, ang = f64(q), f64(linear_velocity), f64(angular_velocity); out = np.zeros(7)
-    check(lib().mpcmp_inverse_velocities(C.byref(model), dp(q), dp(lin), dp(ang), dp(out)))
+    check(lib().mpcmp_inverse_velocities(C.byref(model), host(q), host(lin), host(ang), host(out)))
     return out
 
 
@@ -352,7 +330,7 @@ def inverse_kinematic(model, orientation, position, q_init=None):
     """PandaWrapper::inverse_kinematic: returns (q, converged, iterations); the start configuration is explicit."""
     R, p = f64(orientation), f64(position); q = np.zeros(7); it = C.c_int(0)
     qi = f64(q_init) if q_init is not None else None
-    rc = lib().mpcmp_inverse_kinematics(C.byref(model), dp(R), dp(p), dp(qi), dp(q), C.byref(it))
+    rc = lib().mpcmp_inverse_kinematics(C.byref(model), host(R), host(p), host(qi), host(q), C.byref(it))
     if rc not in (0, 1):
         check(rc)
     return q, rc == 0, it.value
@@ -360,14 +338,14 @@ def inverse_kinematic(model, orientation, position, q_init=None):
 
 def default_limits():
     out = [np.zeros(7) for _ in range(6)]
-    check(lib().mpcmp_default_limits(*[dp(o) for o in out]))
+    check(lib().mpcmp_default_limits(*[host(o) for o in out]))
     return dict(zip(["qmin", "qmax", "vmax", "amax", "jmax", "taumax"], out))
 
 
 def default_config(num_seg=4, sqp_iters=20, margins=None, **kw):
     c = Config(); check(lib().mpcmp_default_config(C.byref(c), int(num_seg), int(sqp_iters)))
     if margins is not None:
-        check(lib().mpcmp_set_margins(C.byref(c), *[C.c_double(x) for x in margins[:4]]))
+        check(lib().mpcmp_set_margins(C.byref(c), *[float(x) for x in margins[:4]]))
     for k, v in kw.items():
         setattr(c, k, v)
     return c
@@ -376,7 +354,7 @@ def default_config(num_seg=4, sqp_iters=20, margins=None, **kw):
 def bounds_from_config(cfg):
     """mpcmp_bounds_from_config: the six bound tables of a Config as one BOUNDS_DTYPE record (bit for bit)"""
     out = np.zeros((), dtype=BOUNDS_DTYPE)
-    check(lib().mpcmp_bounds_from_config(C.addressof(cfg), out.ctypes.data))
+    check(lib().mpcmp_bounds_from_config(C.byref(cfg), host(out)))
     return out
 
 
@@ -384,7 +362,7 @@ def bounds_from_margins(margin_position=1.0, margin_velocity=1.0, margin_acceler
     """mpcmp_bounds_from_margins: the tables of default_config + mpcmp_set_margins + mpcmp_set_min_height as one BOUNDS_DTYPE record"""
     out = np.zeros((), dtype=BOUNDS_DTYPE)
     check(lib().mpcmp_bounds_from_margins(float(margin_position), float(margin_velocity), float(margin_acceleration), float(margin_torque),
-                                          float(min_height), out.ctypes.data))
+                                          float(min_height), host(out)))
     return out
 
 
@@ -396,14 +374,14 @@ def route_via_velocity(p_prev, p_via, p_next, row, narm=1, speed=1.0):
     if row.dtype != BOUNDS_DTYPE:
         raise ValueError("row must be one BOUNDS_DTYPE record")
     v = np.zeros(7 * narm)
-    check(lib().mpcmp_route_via_velocity(a.ctypes.data, b.ctypes.data, c.ctypes.data, row.ctypes.data, int(narm), float(speed), v.ctypes.data))
+    check(lib().mpcmp_route_via_velocity(host(a), host(b), host(c), host(row), int(narm), float(speed), host(v)))
     return v
 
 
 def route_locate(leg_T, t):
     """mpcmp_route_locate: (leg, normalised time) of the route time t on the legs of durations leg_T (host, no GPU)"""
     T = f64(leg_T).reshape(-1); leg, tau = C.c_int(0), C.c_double(0)
-    check(lib().mpcmp_route_locate(T.shape[0], T.ctypes.data, float(t), C.addressof(leg), C.addressof(tau)))
+    check(lib().mpcmp_route_locate(T.shape[0], host(T), float(t), C.byref(leg), C.byref(tau)))
     return leg.value, tau.value
 
 
@@ -412,4 +390,4 @@ def num_nodes(num_seg):
 
 
 def time_nodes(num_seg):
-    t = np.zeros(3 * num_seg + 1); check(lib().mpcmp_time_nodes(int(num_seg), dp(t))); return t
+    t = np.zeros(3 * num_seg + 1); check(lib().mpcmp_time_nodes(int(num_seg), host(t))); return t

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import check, dp, f64, lib
+from .capi import check, f64, host, lib
 
 
 class Solver:
@@ -79,7 +79,7 @@ class Solver:
     def set_payloads(self, mass, com=None, inertia=None):
         """row i applies to problem i of every later call that evaluates dynamics (include/mpcmp.h, mpcmp_set_payloads); see payload_table"""
         t = self.payload_table(mass, com, inertia)
-        check(lib().mpcmp_set_payloads(self._ctx, t.shape[0], t.ctypes.data_as(C.c_void_p)), self._ctx)
+        check(lib().mpcmp_set_payloads(self._ctx, t.shape[0], host(t)), self._ctx)
         self.payload_rows = t.shape[0]
 
     def clear_payloads(self):
@@ -89,7 +89,7 @@ class Solver:
 
     def set_payloads_device(self, n, ptr, stream=0):
         """n rows of narm mpcmp_payload records (104 bytes each) at the device pointer ptr, ordered on `stream` (values not checked)"""
-        check(lib().mpcmp_set_payloads_device(self._ctx, int(n), C.c_void_p(ptr or None), C.c_void_p(stream or None)), self._ctx)
+        check(lib().mpcmp_set_payloads_device(self._ctx, int(n), ptr or None, stream or None), self._ctx)
         self.payload_rows = int(n)
 
     # -- per-problem final-time windows, time scaling, time-synchronised solves (include/mpcmp.h)
@@ -98,7 +98,7 @@ class Solver:
         lbT, ubT = f64(lbT).reshape(-1), f64(ubT).reshape(-1)
         if lbT.shape != ubT.shape or lbT.shape[0] < 1:
             raise ValueError("lbT and ubT must be [n] arrays of one length, got %s and %s" % (lbT.shape, ubT.shape))
-        check(lib().mpcmp_set_time_windows(self._ctx, lbT.shape[0], dp(lbT), dp(ubT)), self._ctx)
+        check(lib().mpcmp_set_time_windows(self._ctx, lbT.shape[0], host(lbT), host(ubT)), self._ctx)
         self.time_window_rows = lbT.shape[0]
 
     def clear_time_windows(self):
@@ -108,8 +108,7 @@ class Solver:
 
     def set_time_windows_device(self, n, p_lb, p_ub, stream=0):
         """n rows from the device pointers p_lb / p_ub (doubles), ordered on `stream` (values not checked)"""
-        vp = C.c_void_p
-        check(lib().mpcmp_set_time_windows_device(self._ctx, int(n), vp(p_lb or None), vp(p_ub or None), vp(stream or None)), self._ctx)
+        check(lib().mpcmp_set_time_windows_device(self._ctx, int(n), p_lb or None, p_ub or None, stream or None), self._ctx)
         self.time_window_rows = int(n)
 
     # -- per-problem bounds (include/mpcmp.h, mpcmp_set_bounds)
@@ -148,6 +147,7 @@ class Solver:
         rows = np.ascontiguousarray(rows).reshape(-1)
         if rows.dtype != capi.BOUNDS_DTYPE:
             raise ValueError("rows must be an array of BOUNDS_DTYPE records")
+        # (the plain address, not host(): n == 0 with NULL is the clear, and an empty table stays the error it is)
         check(lib().mpcmp_set_bounds(self._ctx, rows.shape[0], rows.ctypes.data), self._ctx)
         self.bound_rows = rows.shape[0]
 
@@ -169,13 +169,13 @@ class Solver:
         if x0.shape[0] != B:
             raise ValueError("states are for %d problems, trajectories for %d" % (x0.shape[0], B))
         ox, ou, oT = np.zeros_like(sx), np.zeros_like(su), np.zeros(B)
-        check(lib().mpcmp_time_scale_batch(self._ctx, B, dp(x0), dp(xf), dp(sx), dp(su), dp(sT), dp(T_new), dp(ox), dp(ou), dp(oT)), self._ctx)
+        check(lib().mpcmp_time_scale_batch(self._ctx, B, host(x0), host(xf), host(sx), host(su), host(sT), host(T_new), host(ox), host(ou), host(oT)),
+                                           self._ctx)
         return ox, ou, oT
 
     def time_scale_device(self, B, x0, xf, sx, su, sT, T_new, ox, ou, oT, stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_time_scale_batch_device(self._ctx, int(B), vp(x0), vp(xf), vp(sx), vp(su), vp(sT), vp(T_new), vp(ox), vp(ou), vp(oT),
-                                                  vp(stream or None)), self._ctx)
+        check(lib().mpcmp_time_scale_batch_device(self._ctx, int(B), x0 or None, xf or None, sx or None, su or None, sT or None, T_new or None,
+                                                  ox or None, ou or None, oT or None, stream or None), self._ctx)
 
     def solve_synced(self, x0, xf, group, warm=None, n_groups=None):
         """mpcmp_solve_batch_synced: the members of each group (group[i] in [0, n_groups); -1 = on its own) that solved cleanly end at their group's
@@ -194,21 +194,20 @@ class Solver:
         sx, su, sT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
         info = np.zeros(B, dtype=capi.INFO_DTYPE)
         gT = np.zeros(max(n_groups, 1))
-        check(lib().mpcmp_solve_batch_synced(self._ctx, B, dp(x0), dp(xf), dp(wx), dp(wu), dp(wT), group.ctypes.data_as(C.c_void_p), n_groups,
-                                             dp(sx), dp(su), dp(sT), info.ctypes.data_as(C.c_void_p), dp(gT)), self._ctx)
+        check(lib().mpcmp_solve_batch_synced(self._ctx, B, host(x0), host(xf), host(wx), host(wu), host(wT), host(group), n_groups,
+                                             host(sx), host(su), host(sT), host(info), host(gT)), self._ctx)
         return sx, su, sT, info, gT[:n_groups]
 
     def solve_synced_device(self, B, x0, xf, group, n_groups, sol_x, sol_u, sol_T, info=0, group_T=0, warm=(0, 0, 0), stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_solve_batch_synced_device(self._ctx, int(B), vp(x0), vp(xf), vp(warm[0] or None), vp(warm[1] or None), vp(warm[2] or None),
-                                                    vp(group), int(n_groups), vp(sol_x), vp(sol_u), vp(sol_T), vp(info or None), vp(group_T or None),
-                                                    vp(stream or None)), self._ctx)
+        check(lib().mpcmp_solve_batch_synced_device(self._ctx, int(B), x0 or None, xf or None, warm[0] or None, warm[1] or None, warm[2] or None,
+                                                    group or None, int(n_groups), sol_x or None, sol_u or None, sol_T or None, info or None,
+                                                    group_T or None, stream or None), self._ctx)
 
     # -- clearance checks: robot spheres against obstacles and against the other arm (include/mpcmp.h)
     def set_robot_spheres(self, spheres, arm=0):
         """sphere table of one arm: capi.SPHERE_DTYPE [n], n <= 64 (capi.link_spheres, capi.spheres); None or an empty table clears it"""
         t = np.zeros(0, dtype=capi.SPHERE_DTYPE) if spheres is None else capi._records(spheres, capi.SPHERE_DTYPE, "sphere").reshape(-1)
-        check(lib().mpcmp_set_robot_spheres(self._ctx, int(arm), t.shape[0], t.ctypes.data if t.shape[0] else None), self._ctx)
+        check(lib().mpcmp_set_robot_spheres(self._ctx, int(arm), t.shape[0], host(t)), self._ctx)
 
     def set_obstacles(self, obstacles):
         """obstacles: capi.OBSTACLE_DTYPE [n_obs] (one world for every problem) or [n_sets][n_obs] (set i for problem i)"""
@@ -217,14 +216,14 @@ class Solver:
             t = t[None, :]
         if t.ndim != 2:
             raise ValueError("obstacles must be [n_obs] or [n_sets][n_obs], got %s" % (t.shape,))
-        check(lib().mpcmp_set_obstacles(self._ctx, t.shape[0], t.shape[1], t.ctypes.data if t.size else None), self._ctx)
+        check(lib().mpcmp_set_obstacles(self._ctx, t.shape[0], t.shape[1], host(t)), self._ctx)
 
     def clear_obstacles(self):
         check(lib().mpcmp_set_obstacles(self._ctx, 0, 0, None), self._ctx)
 
     def set_obstacles_device(self, n_sets, n_obs, ptr, stream=0):
         """[n_sets][n_obs] mpcmp_obstacle records (64 bytes each) at the device pointer ptr, ordered on `stream` (values not checked)"""
-        check(lib().mpcmp_set_obstacles_device(self._ctx, int(n_sets), int(n_obs), C.c_void_p(ptr or None), C.c_void_p(stream or None)), self._ctx)
+        check(lib().mpcmp_set_obstacles_device(self._ctx, int(n_sets), int(n_obs), ptr or None, stream or None), self._ctx)
 
     def clearance(self, sx, sT, n_pts=200, margin=0.0, self_gap=0):
         """mpcmp_clearance_batch: capi.CLEARANCE_DTYPE [B] for the trajectories sx [B][N][nx], sT [B] at n_pts + 1 uniform samples"""
@@ -232,13 +231,12 @@ class Solver:
         if sx.shape != (B, self.N, self.nx):
             raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
         out = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
-        check(lib().mpcmp_clearance_batch(self._ctx, B, sx.ctypes.data, sT.ctypes.data, int(n_pts), float(margin), int(self_gap), out.ctypes.data), self._ctx)
+        check(lib().mpcmp_clearance_batch(self._ctx, B, host(sx), host(sT), int(n_pts), float(margin), int(self_gap), host(out)), self._ctx)
         return out
 
     def clearance_device(self, B, sol_x, sol_T, n_pts, margin, self_gap, out, stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_clearance_batch_device(self._ctx, int(B), vp(sol_x), vp(sol_T), int(n_pts), float(margin), int(self_gap), vp(out),
-                                                 vp(stream or None)), self._ctx)
+        check(lib().mpcmp_clearance_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_pts), float(margin), int(self_gap),
+                                                 out or None, stream or None), self._ctx)
 
     def select_clear(self, sT, info, clr, group, n_groups=None):
         """mpcmp_select_clear_batch: per group the admissible member (clean solve status, clearance status 0) with the smallest final time,
@@ -251,14 +249,12 @@ class Solver:
         if n_groups is None:
             n_groups = max(int(group.max()) + 1, 0)
         chosen = np.full(max(int(n_groups), 1), -1, dtype=np.int32)
-        check(lib().mpcmp_select_clear_batch(self._ctx, B, sT.ctypes.data, info.ctypes.data, clr.ctypes.data, group.ctypes.data, int(n_groups),
-                                             chosen.ctypes.data), self._ctx)
+        check(lib().mpcmp_select_clear_batch(self._ctx, B, host(sT), host(info), host(clr), host(group), int(n_groups), host(chosen)), self._ctx)
         return chosen[:n_groups]
 
     def select_clear_device(self, B, sol_T, info, clr, group, n_groups, chosen, stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_select_clear_batch_device(self._ctx, int(B), vp(sol_T), vp(info), vp(clr), vp(group), int(n_groups), vp(chosen),
-                                                    vp(stream or None)), self._ctx)
+        check(lib().mpcmp_select_clear_batch_device(self._ctx, int(B), sol_T or None, info or None, clr or None, group or None, int(n_groups),
+                                                    chosen or None, stream or None), self._ctx)
 
     # -- via-point routes: B routes with M vias = B (M + 1) leg slots (include/mpcmp.h, "via-point routes")
     @staticmethod
@@ -281,22 +277,18 @@ class Solver:
             speed = f64(np.broadcast_to(np.asarray(speed, dtype=np.float64), (B,)))
         return x0, via, via_qd, speed, xf, B, M
 
-    @staticmethod
-    def _p(a):
-        return None if a is None or a.size == 0 else a.ctypes.data
-
     def route_legs(self, x0, via, xf, via_qd=None, speed=None):
         """mpcmp_route_legs: (leg_x0 [B (M+1)][nx], leg_xf, via_qd [B][M][7 narm]); via_qd None = the chord rule at `speed` (None = 1)"""
         x0, via, via_qd, speed, xf, B, M = self._route_in(x0, via, via_qd, speed, xf)
         L = B * (M + 1)
         l0, lf, vo = np.zeros((L, self.nx)), np.zeros((L, self.nx)), np.zeros_like(via)
-        check(lib().mpcmp_route_legs(self._ctx, B, M, self._p(x0), self._p(via), self._p(via_qd), self._p(speed), self._p(xf), l0.ctypes.data,
-                                     lf.ctypes.data, self._p(vo)), self._ctx)
+        check(lib().mpcmp_route_legs(self._ctx, B, M, host(x0), host(via), host(via_qd), host(speed), host(xf), host(l0), host(lf), host(vo)),
+                                     self._ctx)
         return l0, lf, vo
 
     def route_legs_device(self, B, M, x0, via, xf, leg_x0, leg_xf, via_qd=0, speed=0, via_qd_out=0, stream=0):
-        check(lib().mpcmp_route_legs_device(self._ctx, int(B), int(M), x0, via or None, via_qd or None, speed or None, xf, leg_x0, leg_xf,
-                                            via_qd_out or None, stream or None), self._ctx)
+        check(lib().mpcmp_route_legs_device(self._ctx, int(B), int(M), x0 or None, via or None, via_qd or None, speed or None, xf or None,
+                                            leg_x0 or None, leg_xf or None, via_qd_out or None, stream or None), self._ctx)
 
     def solve_route(self, x0, via, xf, via_qd=None, speed=None, jmax=None):
         """mpcmp_solve_route_batch: a dict with the legs' sol_x [B][M+1][N][nx], sol_u, sol_T [B][M+1], info [B][M+1] and the routes' route_T [B],
@@ -307,16 +299,16 @@ class Solver:
         sx, su, sT = np.zeros((B, M + 1, self.N, self.nx)), np.zeros((B, M + 1, self.N, self.nu)), np.zeros((B, M + 1))
         info, rinfo = np.zeros((B, M + 1), dtype=capi.INFO_DTYPE), np.zeros(B, dtype=capi.INFO_DTYPE)
         rT, seam, vo = np.zeros(B), np.zeros(B, dtype=capi.ROUTE_SEAM_DTYPE), np.zeros_like(via)
-        check(lib().mpcmp_solve_route_batch(self._ctx, B, M, self._p(x0), self._p(via), self._p(via_qd), self._p(speed), self._p(xf), self._p(jm),
-                                            sx.ctypes.data, su.ctypes.data, sT.ctypes.data, info.ctypes.data, rT.ctypes.data, rinfo.ctypes.data,
-                                            seam.ctypes.data, self._p(vo)), self._ctx)
+        check(lib().mpcmp_solve_route_batch(self._ctx, B, M, host(x0), host(via), host(via_qd), host(speed), host(xf), host(jm),
+                                            host(sx), host(su), host(sT), host(info), host(rT), host(rinfo), host(seam), host(vo)), self._ctx)
         return dict(sol_x=sx, sol_u=su, sol_T=sT, info=info, route_T=rT, route_info=rinfo, seam=seam, via_qd=vo)
 
     def solve_route_device(self, B, M, x0, via, xf, sol_x, sol_u, sol_T, route_T, route_info, seam, info=0, via_qd=0, speed=0, jmax=None, via_qd_out=0,
                            stream=0):
         jm = None if jmax is None else f64(jmax).reshape(7)
-        check(lib().mpcmp_solve_route_batch_device(self._ctx, int(B), int(M), x0, via or None, via_qd or None, speed or None, xf, self._p(jm), sol_x,
-                                                   sol_u, sol_T, info or None, route_T, route_info, seam, via_qd_out or None, stream or None), self._ctx)
+        check(lib().mpcmp_solve_route_batch_device(self._ctx, int(B), int(M), x0 or None, via or None, via_qd or None, speed or None, xf or None,
+                                                   host(jm), sol_x or None, sol_u or None, sol_T or None, info or None, route_T or None,
+                                                   route_info or None, seam or None, via_qd_out or None, stream or None), self._ctx)
 
     def _route_traj(self, sx, su, sT):
         sx, su, sT = f64(sx), f64(su), f64(sT)
@@ -338,23 +330,24 @@ class Solver:
                 raise ValueError("clr must be CLEARANCE_DTYPE [B][M+1]")
             rclr = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
         rT, rinfo, seam = np.zeros(B), np.zeros(B, dtype=capi.INFO_DTYPE), np.zeros(B, dtype=capi.ROUTE_SEAM_DTYPE)
-        check(lib().mpcmp_route_join(self._ctx, B, M, sx.ctypes.data, su.ctypes.data, sT.ctypes.data, info.ctypes.data, self._p(clr), rT.ctypes.data,
-                                     rinfo.ctypes.data, seam.ctypes.data, self._p(rclr)), self._ctx)
+        check(lib().mpcmp_route_join(self._ctx, B, M, host(sx), host(su), host(sT), host(info), host(clr), host(rT), host(rinfo), host(seam),
+                                     host(rclr)), self._ctx)
         return (rT, rinfo, seam) if clr is None else (rT, rinfo, seam, rclr)
 
     def route_join_device(self, B, M, sol_x, sol_u, sol_T, info, route_T, route_info, seam, clr=0, route_clr=0, stream=0):
-        check(lib().mpcmp_route_join_device(self._ctx, int(B), int(M), sol_x, sol_u, sol_T, info, clr or None, route_T, route_info, seam,
-                                            route_clr or None, stream or None), self._ctx)
+        check(lib().mpcmp_route_join_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, info or None, clr or None,
+                                            route_T or None, route_info or None, seam or None, route_clr or None, stream or None), self._ctx)
 
     def sample_route(self, sx, su, sT, n_pts=200):
         """mpcmp_sample_route_batch: out [B][n_pts+1][29] = route time, q, qd, qdd, tau on a uniform clock across the junctions"""
         sx, su, sT, B, M = self._route_traj(sx, su, sT)
         out = np.zeros((B, n_pts + 1, 29))
-        check(lib().mpcmp_sample_route_batch(self._ctx, B, M, sx.ctypes.data, su.ctypes.data, sT.ctypes.data, int(n_pts), out.ctypes.data), self._ctx)
+        check(lib().mpcmp_sample_route_batch(self._ctx, B, M, host(sx), host(su), host(sT), int(n_pts), host(out)), self._ctx)
         return out
 
     def sample_route_device(self, B, M, sol_x, sol_u, sol_T, n_pts, out, stream=0):
-        check(lib().mpcmp_sample_route_batch_device(self._ctx, int(B), int(M), sol_x, sol_u, sol_T, int(n_pts), out, stream or None), self._ctx)
+        check(lib().mpcmp_sample_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_pts), out or None,
+                                                    stream or None), self._ctx)
 
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
@@ -381,21 +374,19 @@ class Solver:
                 raise ValueError("warm start is for %d problems, states for %d" % (wT.shape[0], B))
         sx, su, sT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
         info = np.zeros(B, dtype=capi.INFO_DTYPE)
-        check(lib().mpcmp_solve_batch(self._ctx, B, dp(x0), dp(xf), dp(wx), dp(wu), dp(wT), dp(sx), dp(su), dp(sT),
-                                      info.ctypes.data_as(C.c_void_p)), self._ctx)
+        check(lib().mpcmp_solve_batch(self._ctx, B, host(x0), host(xf), host(wx), host(wu), host(wT), host(sx), host(su), host(sT), host(info)),
+                                      self._ctx)
         return sx, su, sT, info
 
     # -- hot path, device-resident buffers (raw pointers, e.g. torch tensors' data_ptr())
     def solve_device(self, B, x0, xf, sol_x, sol_u, sol_T, info=0, warm=(0, 0, 0), stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_solve_batch_device(self._ctx, int(B), vp(x0), vp(xf), vp(warm[0] or None), vp(warm[1] or None),
-                                             vp(warm[2] or None), vp(sol_x), vp(sol_u), vp(sol_T), vp(info or None),
-                                             vp(stream or None)), self._ctx)
+        check(lib().mpcmp_solve_batch_device(self._ctx, int(B), x0 or None, xf or None, warm[0] or None, warm[1] or None, warm[2] or None,
+                                             sol_x or None, sol_u or None, sol_T or None, info or None, stream or None), self._ctx)
 
     def warm_start(self, x0, xf):
         x0, xf = self._states(x0, xf); B = x0.shape[0]
         wx, wu, wT = np.zeros((B, self.N, 14)), np.zeros((B, self.N, 7)), np.zeros(B)
-        check(lib().mpcmp_warm_start_batch(self._ctx, B, dp(x0), dp(xf), dp(wx), dp(wu), dp(wT)), self._ctx)
+        check(lib().mpcmp_warm_start_batch(self._ctx, B, host(x0), host(xf), host(wx), host(wu), host(wT)), self._ctx)
         return wx, wu, wT
 
     def _acc(self, a, B):
@@ -412,24 +403,23 @@ class Solver:
         (x0, xf), jmax = self._states(x0, xf), f64(jmax).reshape(7); B = x0.shape[0]
         wx, wu, wT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
         a0, aT = self._acc(acc0, B), self._acc(accT, B)
-        check(lib().mpcmp_warm_start_jerk_lim_batch(self._ctx, B, dp(x0), dp(xf), dp(a0), dp(aT), dp(self._lim(vmax)), dp(self._lim(amax)), dp(jmax),
-                                                    dp(wx), dp(wu), dp(wT)), self._ctx)
+        check(lib().mpcmp_warm_start_jerk_lim_batch(self._ctx, B, host(x0), host(xf), host(a0), host(aT), host(self._lim(vmax)),
+                                                    host(self._lim(amax)), host(jmax), host(wx), host(wu), host(wT)), self._ctx)
         return wx, wu, wT
 
     def warm_start_jerk_device(self, B, x0, xf, jmax, warm_x, warm_u, warm_T, stream=0):
         """Device-pointer form: writes the warm start where solve_device(..., warm=(warm_x, warm_u, warm_T)) reads it."""
-        vp = C.c_void_p
         jmax = f64(jmax)
-        check(lib().mpcmp_warm_start_jerk_batch_device(self._ctx, int(B), vp(x0), vp(xf), dp(jmax), vp(warm_x), vp(warm_u), vp(warm_T),
-                                                       vp(stream or None)), self._ctx)
+        check(lib().mpcmp_warm_start_jerk_batch_device(self._ctx, int(B), x0 or None, xf or None, host(jmax), warm_x or None, warm_u or None,
+                                                       warm_T or None, stream or None), self._ctx)
 
     def jerk_trajectory(self, x0, xf, jmax, n_pts=200, acc0=None, accT=None, vmax=None, amax=None):
         """The same trajectory sampled uniformly: out [B][n_pts+1][22] = t, q, qd, qdd, and the durations [B]."""
         (x0, xf), jmax = self._states(x0, xf), f64(jmax).reshape(7); B = x0.shape[0]
         out, T = np.zeros((B, n_pts + 1, 22)), np.zeros(B)
         a0, aT = self._acc(acc0, B), self._acc(accT, B)
-        check(lib().mpcmp_jerk_trajectory_lim_batch(self._ctx, B, dp(x0), dp(xf), dp(a0), dp(aT), dp(self._lim(vmax)), dp(self._lim(amax)), dp(jmax),
-                                                    int(n_pts), dp(out), dp(T)), self._ctx)
+        check(lib().mpcmp_jerk_trajectory_lim_batch(self._ctx, B, host(x0), host(xf), host(a0), host(aT), host(self._lim(vmax)),
+                                                    host(self._lim(amax)), host(jmax), int(n_pts), host(out), host(T)), self._ctx)
         return out, T
 
     def jerk_point(self, x0, xf, jmax, time, acc0=None, accT=None, vmax=None, amax=None):
@@ -438,8 +428,8 @@ class Solver:
         time = f64(np.broadcast_to(np.asarray(time, dtype=np.float64), (B,)))
         out, T = np.zeros((B, 28)), np.zeros(B)
         a0, aT = self._acc(acc0, B), self._acc(accT, B)
-        check(lib().mpcmp_jerk_point_lim_batch(self._ctx, B, dp(x0), dp(xf), dp(a0), dp(aT), dp(self._lim(vmax)), dp(self._lim(amax)), dp(jmax),
-                                               dp(time), dp(out), dp(T)), self._ctx)
+        check(lib().mpcmp_jerk_point_lim_batch(self._ctx, B, host(x0), host(xf), host(a0), host(aT), host(self._lim(vmax)), host(self._lim(amax)),
+                                               host(jmax), host(time), host(out), host(T)), self._ctx)
         return out, T
 
     def mpc_point(self, sx, su, sT, time):
@@ -447,18 +437,18 @@ class Solver:
         sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
         time = f64(np.broadcast_to(np.asarray(time, dtype=np.float64), (B,)))
         out = np.zeros((B, 28))
-        check(lib().mpcmp_mpc_point_batch(self._ctx, B, dp(sx), dp(su), dp(sT), dp(time), dp(out)), self._ctx)
+        check(lib().mpcmp_mpc_point_batch(self._ctx, B, host(sx), host(su), host(sT), host(time), host(out)), self._ctx)
         return out
 
     def rnea(self, q, qd, qdd):
         q, qd, qdd = f64(q), f64(qd), f64(qdd); tau = np.zeros_like(q)
-        check(lib().mpcmp_rnea_batch(self._ctx, q.shape[0], dp(q), dp(qd), dp(qdd), dp(tau)), self._ctx)
+        check(lib().mpcmp_rnea_batch(self._ctx, q.shape[0], host(q), host(qd), host(qdd), host(tau)), self._ctx)
         return tau
 
     def eval_constraints(self, x, u):
         x, u = f64(x), f64(u); nn = x.shape[0]
         g, G = np.zeros((nn, 8)), np.zeros((nn, 8, 22))
-        check(lib().mpcmp_eval_constraints_batch(self._ctx, nn, dp(x), dp(u), dp(g), dp(G)), self._ctx)
+        check(lib().mpcmp_eval_constraints_batch(self._ctx, nn, host(x), host(u), host(g), host(G)), self._ctx)
         return g, G
 
     def qp(self, x0, xf, xs, us, T):
@@ -467,27 +457,25 @@ class Solver:
         if T.shape[0] != B:
             raise ValueError("linearisation point is for %d problems, states for %d" % (T.shape[0], B))
         p, y = np.zeros((B, self.n)), np.zeros((B, self.m + self.n)); it = np.zeros(B, dtype=np.int32)
-        check(lib().mpcmp_qp_batch(self._ctx, B, dp(x0), dp(xf), dp(xs), dp(us), dp(T), dp(p), dp(y),
-                                   it.ctypes.data_as(C.c_void_p)), self._ctx)
+        check(lib().mpcmp_qp_batch(self._ctx, B, host(x0), host(xf), host(xs), host(us), host(T), host(p), host(y), host(it)), self._ctx)
         return p, y, it
 
     def sample(self, sx, su, sT, n_pts=200):
         sx, su, sT = self._traj(sx, su, sT); B = sx.shape[0]
         out = np.zeros((B, n_pts + 1, 29))
-        check(lib().mpcmp_sample_batch(self._ctx, B, dp(sx), dp(su), dp(sT), int(n_pts), dp(out)), self._ctx)
+        check(lib().mpcmp_sample_batch(self._ctx, B, host(sx), host(su), host(sT), int(n_pts), host(out)), self._ctx)
         return out
 
     def sample_device(self, B, sol_x, sol_u, sol_T, n_pts, out, stream=0):
-        vp = C.c_void_p
-        check(lib().mpcmp_sample_batch_device(self._ctx, int(B), vp(sol_x), vp(sol_u), vp(sol_T), int(n_pts), vp(out),
-                                              vp(stream or None)), self._ctx)
+        check(lib().mpcmp_sample_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_pts), out or None,
+                                              stream or None), self._ctx)
 
     def traj_stats(self, sx, su, sT, xf, n_pts=200):
         (sx, su, sT), xf = self._traj(sx, su, sT), f64(xf); B = sx.shape[0]
         if xf.shape != (B, 14):
             raise ValueError("xf must be [B][14]")
         out = np.zeros((B, 74))
-        check(lib().mpcmp_traj_stats_batch(self._ctx, B, dp(sx), dp(su), dp(sT), dp(xf), int(n_pts), dp(out)), self._ctx)
+        check(lib().mpcmp_traj_stats_batch(self._ctx, B, host(sx), host(su), host(sT), host(xf), int(n_pts), host(out)), self._ctx)
         return out
 
     def reset_multipliers(self):
@@ -498,16 +486,16 @@ class Solver:
     def rh_init(self, x0, xf):
         x0, xf = self._states(x0, xf)
         self._rh_B = x0.shape[0]
-        check(lib().mpcmp_rh_init(self._ctx, self._rh_B, dp(x0), dp(xf)), self._ctx)
+        check(lib().mpcmp_rh_init(self._ctx, self._rh_B, host(x0), host(xf)), self._ctx)
 
     def rh_run(self, steps, dt, use_graph=True):
-        check(lib().mpcmp_rh_run(self._ctx, int(steps), C.c_double(dt), int(bool(use_graph))), self._ctx)
+        check(lib().mpcmp_rh_run(self._ctx, int(steps), float(dt), int(bool(use_graph))), self._ctx)
 
     def rh_get(self):
         B = self._rh_B
         x0 = np.zeros((B, self.nx)); sx, su, sT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
         info = np.zeros(B, dtype=capi.INFO_DTYPE)
-        check(lib().mpcmp_rh_get(self._ctx, dp(x0), dp(sx), dp(su), dp(sT), info.ctypes.data_as(C.c_void_p)), self._ctx)
+        check(lib().mpcmp_rh_get(self._ctx, host(x0), host(sx), host(su), host(sT), host(info)), self._ctx)
         return x0, sx, su, sT, info
 
     def rh_stats(self):
@@ -526,15 +514,13 @@ class Solver:
         if len(set(rows)) > 1:
             raise ValueError("idx, x and xf must list the same number of instances, got %s" % rows)
         n = rows[0] if rows else getattr(self, "_rh_B", 0)
-        ip = idx.ctypes.data_as(C.POINTER(C.c_int)) if idx is not None else None
-        check(lib().mpcmp_rh_update(self._ctx, int(n), ip, dp(x), dp(xf), capi.RH_RESTART if restart else 0), self._ctx)
+        check(lib().mpcmp_rh_update(self._ctx, int(n), host(idx), host(x), host(xf), capi.RH_RESTART if restart else 0), self._ctx)
 
     def rh_update_device(self, n, idx, x, xf, restart=False, stream=0):
         """rh_update with raw device pointers (idx: int32 [n], x / xf: double [n][nx]; 0 = NULL), ordered after the work on `stream`
         (mpcmp_rh_update_device: indices and values are not checked)"""
-        vp = C.c_void_p
-        check(lib().mpcmp_rh_update_device(self._ctx, int(n), vp(idx or None), vp(x or None), vp(xf or None), capi.RH_RESTART if restart else 0,
-                                           vp(stream or None)), self._ctx)
+        check(lib().mpcmp_rh_update_device(self._ctx, int(n), idx or None, x or None, xf or None, capi.RH_RESTART if restart else 0,
+                                           stream or None), self._ctx)
 
     def pose_targets(self, R, p, seeds, q_ref=None, twist=None, arm=0, xf=None):
         """Joint-space targets from tool poses: multi-start DLS inverse kinematics on the GPU (mpcmp_pose_targets_batch, include/mpcmp.h).
@@ -555,23 +541,20 @@ class Solver:
         elif not (isinstance(xf, np.ndarray) and xf.dtype == np.float64 and xf.flags.c_contiguous and xf.shape == (B, self.nx)):
             raise ValueError("xf must be a C-contiguous float64 array of shape (%d, %d)" % (B, self.nx))
         info = np.zeros(B, dtype=capi.IK_INFO_DTYPE)
-        vp = C.c_void_p
-        check(lib().mpcmp_pose_targets_batch(self._ctx, int(B), int(arm), vp(R.ctypes.data), vp(p.ctypes.data),
-                                             vp(twist.ctypes.data if twist is not None else None), int(S), vp(seeds.ctypes.data),
-                                             vp(q_ref.ctypes.data if q_ref is not None else None), vp(xf.ctypes.data), vp(info.ctypes.data)), self._ctx)
+        check(lib().mpcmp_pose_targets_batch(self._ctx, int(B), int(arm), host(R), host(p), host(twist), int(S), host(seeds), host(q_ref), host(xf),
+                                             host(info)), self._ctx)
         return xf, info
 
     def pose_targets_device(self, B, arm, R, p, twist, S, seeds, q_ref, xf, info, stream=0):
         """pose_targets with raw device pointers (0 = NULL for twist, q_ref and info), ordered on `stream`; values are not checked
         (mpcmp_pose_targets_batch_device)"""
-        vp = C.c_void_p
-        check(lib().mpcmp_pose_targets_batch_device(self._ctx, int(B), int(arm), vp(R), vp(p), vp(twist or None), int(S), vp(seeds),
-                                                    vp(q_ref or None), vp(xf), vp(info or None), vp(stream or None)), self._ctx)
+        check(lib().mpcmp_pose_targets_batch_device(self._ctx, int(B), int(arm), R or None, p or None, twist or None, int(S), seeds or None,
+                                                    q_ref or None, xf or None, info or None, stream or None), self._ctx)
 
     def debug_fetch(self, which, count):
         """diagnostics: first `count` doubles of a workspace array (0 z, 1 lambda, 2 c_eq, 3 g, 4 p, 5 y), device layout"""
         out = np.zeros(int(count))
-        check(lib().mpcmp_debug_fetch(self._ctx, int(which), dp(out), C.c_long(int(count))), self._ctx)
+        check(lib().mpcmp_debug_fetch(self._ctx, int(which), host(out), int(count)), self._ctx)
         return out
 
     def kernel_timing(self, reset=False):
@@ -610,13 +593,13 @@ class BatchMotionPlanner:
     def set_constraint_margins(self, margin_position, margin_velocity, margin_acceleration, margin_torque, margin_jerk):
         self.margin_position_, self.margin_velocity_ = margin_position, margin_velocity
         self.margin_acceleration_, self.margin_torque_, self.margin_jerk_ = margin_acceleration, margin_torque, margin_jerk
-        check(lib().mpcmp_set_margins(C.byref(self.cfg), C.c_double(margin_position), C.c_double(margin_velocity),
-                                      C.c_double(margin_acceleration), C.c_double(margin_torque)))
+        check(lib().mpcmp_set_margins(C.byref(self.cfg), float(margin_position), float(margin_velocity), float(margin_acceleration),
+                                      float(margin_torque)))
         self._solver.set_config(self.cfg)
 
     # motionPlanner.cpp:92-100
     def set_min_height(self, min_height):
-        check(lib().mpcmp_set_min_height(C.byref(self.cfg), C.c_double(min_height)))
+        check(lib().mpcmp_set_min_height(C.byref(self.cfg), float(min_height)))
         self._solver.set_config(self.cfg)
 
     # motionPlanner.cpp:27-39 / 41-54

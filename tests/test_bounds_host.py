@@ -1,5 +1,5 @@
 """Per-problem bounds, the part that needs no GPU (mpcmp_bounds, mpcmp_bounds_from_config, mpcmp_bounds_from_margins and the declarations of
-mpcmp_set_bounds[_device]; include/mpcmp.h): exported symbols, header declarations and prototypes, the size of a row, and the two host helpers
+mpcmp_set_bounds[_device]; include/mpcmp.h): exported symbols and header declarations (prototypes: tests/test_capi_host.py), the size of a row, and the two host helpers
 bit for bit against the configuration helpers they restate.  (The setters' error paths need a context: tests/test_gpu_bounds.py.)"""
 import ctypes as C
 import os
@@ -35,20 +35,6 @@ def test_library_exports_and_header_declares_the_four_symbols(M):
         assert name in capi.SYMBOLS
         assert hasattr(L, name), name
         assert re.search(r"\bint\s+%s\s*\(" % name, text), name
-
-
-def test_prototypes_match_the_header(M):
-    from mpc_motion_planner_amd import capi
-    text = re.sub(r"/\*.*?\*/", " ", _header(), flags=re.S)
-    kinds_of = {C.c_int: "i", C.c_void_p: "p", C.c_double: "d"}
-    for name in NEW:
-        args = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, text).group(1)
-        kinds = ""
-        for a in args.split(","):
-            a = a.strip()
-            kinds += "p" if "*" in a else ("i" if re.match(r"int\s+\w+$", a) else ("d" if re.match(r"double\s+\w+$", a) else "?"))
-        assert kinds == capi.BOUNDS_PROTOTYPES[name], (name, kinds)
-        assert "".join(kinds_of[t] for t in getattr(M.lib(), name).argtypes) == kinds, name
 
 
 def test_row_is_464_bytes_in_c_and_in_numpy(M, tmp_path):
@@ -92,7 +78,6 @@ def test_bounds_from_config_is_the_six_tables_bit_for_bit(M):
 def test_bounds_from_margins_is_default_config_plus_margins_plus_height(M, mg):
     cfg = M.default_config(6, 2)
     M.capi.check(M.lib().mpcmp_set_margins(C.byref(cfg), *[C.c_double(x) for x in mg[:4]]))
-    M.lib().mpcmp_set_min_height.argtypes = [C.c_void_p, C.c_double]
     M.capi.check(M.lib().mpcmp_set_min_height(C.addressof(cfg), mg[4]))
     row = M.bounds_from_margins(*mg)
     assert row.tobytes() == _tables(cfg)

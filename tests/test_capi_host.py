@@ -31,6 +31,38 @@ def test_library_exports_every_declared_symbol(M):
     assert M.lib().mpcmp_version().startswith(b"mpcmp")
 
 
+def _declarations():
+    """every function include/mpcmp.h declares, in its order: (name, return type, argument kinds); an argument that is none of pointer, int,
+    double, long gets the kind "?" """
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "mpcmp.h")).read(), flags=re.S)
+    out = []
+    for ret, name, args in re.findall(r"\b(int|const\s+char\s*\*)\s*(mpcmp_\w+)\s*\(([^)]*)\)\s*;", hdr):
+        kinds = ""
+        for a in [" ".join(a.split()) for a in args.split(",")]:
+            if a != "void":
+                kinds += "p" if "*" in a else {"int": "i", "double": "d", "long": "l"}.get(a.split(" ")[0] if re.fullmatch(r"\w+ \w+", a) else "", "?")
+        out.append((name, "int" if ret == "int" else "text", kinds))
+    return out
+
+
+def test_abi_table_matches_the_header_and_the_library(M):
+    """capi.ABI, the one table lib() declares to ctypes, against the header: the same functions in the same order, for each the exact argument
+    kinds, and on the loaded library the exact argtypes and restype"""
+    from mpc_motion_planner_amd import capi
+    decl = _declarations()
+    assert len(decl) == 84 and [d[0] for d in decl] == capi.SYMBOLS == list(capi.ABI)
+    ctype = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
+    for name, ret, kinds in decl:
+        assert "?" not in kinds, (name, kinds)
+        assert kinds == capi.ABI[name], (name, kinds, capi.ABI[name])
+        f = getattr(M.lib(), name)
+        assert f.argtypes == [ctype[k] for k in kinds], name
+        assert f.restype is (C.c_char_p if ret == "text" else C.c_int), name
+    assert [d[0] for d in decl if d[1] == "text"] == ["mpcmp_version", "mpcmp_last_error"]
+    # the kinds the table had to learn beside int and pointer are in use
+    assert capi.ABI["mpcmp_rh_run"] == "pidi" and capi.ABI["mpcmp_debug_fetch"] == "pipl" and capi.ABI["mpcmp_set_min_height"] == "pd"
+
+
 def test_struct_layouts_match_header(M, tmp_path):
     assert C.sizeof(M.Info) == 64 and M.INFO_DTYPE.itemsize == 64
     assert C.sizeof(M.Config) == C.sizeof(o.Config) and C.sizeof(M.Model) == C.sizeof(o.Model)

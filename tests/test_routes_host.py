@@ -1,8 +1,7 @@
 """CPU-side checks of the via-point routes (include/mpcmp.h, "via-point routes"): the chord rule and the leg / normalised-time rule against NumPy
-restatements written here, the argument checks that need no device, the record layouts and the prototypes."""
+restatements written here, the argument checks that need no device and the record layouts (the prototypes: tests/test_capi_host.py)."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -180,20 +179,6 @@ def test_struct_layouts_match_the_header(M, tmp_path):
     d = capi.ROUTE_SEAM_DTYPE
     assert sz == [d.itemsize] + [d.fields[n][1] for n in ("state_jump_inf", "acc_jump_inf", "leg_longest", "leg_first_bad")] + \
         [capi.INFO_DTYPE.itemsize, capi.CLEARANCE_DTYPE.itemsize], sz
-
-
-def test_capi_prototypes_match_the_header(M):
-    """the argument kinds of capi.ROUTE_PROTOTYPES against the declarations of include/mpcmp.h"""
-    from mpc_motion_planner_amd import capi
-    hdr = open(os.path.join(ROOT, "include", "mpcmp.h")).read()
-    assert set(capi.ROUTE_PROTOTYPES) <= set(capi.SYMBOLS)
-    for name, kinds in capi.ROUTE_PROTOTYPES.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", hdr)
-        assert m, name
-        args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-        got = "".join("p" if "*" in a else ("d" if a.startswith("double") else "i") for a in args)
-        assert got == kinds, (name, got, kinds)
-        assert hasattr(M.lib(), name)
 
 
 def test_repeat_gives_one_row_per_leg_slot(M):
