@@ -46,7 +46,10 @@ typedef struct {
     double p[7][3];    /* joint origin in the parent joint frame                                     */
     double mass[7];
     double com[7][3];  /* COM of the lumped body in its joint frame                                  */
-    double I[7][9];    /* rotational inertia about the COM                                           */
+    double I[7][9];    /* rotational inertia about the COM, in the joint frame, row-major.  All nine entries are read:
+                        * I w is the row-major 3 x 3 product in every kernel (and in oracle/rbd.c).  A rigid body's tensor is
+                        * symmetric; an asymmetric array is used as it stands, not symmetrised
+                        * (tests/test_gpu_general_robot.py::test_inertia_is_read_row_by_row_vs_oracle)         */
     double tool[3];    /* frame "panda_tool" in the joint-7 frame (height constraint, robot_ocp.hpp:52,91) */
     double link8[3];   /* frame "panda_link8" in the joint-7 frame                                    */
     double gravity[3];
