@@ -120,6 +120,13 @@ int main() {
                         c.d_min, c.t_min, c.sphere, c.other, c.n_hit, c.status);
             planner.set_obstacles(nullptr, 0);
         }
+        {   // the limits between the nodes of the same plan, under the reference benchmark's tool speed limits
+            mpcmp_limits_spec spec = {};
+            spec.tool_lin_max = 1.7; spec.tool_ang_max = 2.5;
+            const mpcmp_limits l = planner.check_limits(200, &spec);
+            std::printf("\"lim_stretch\": %.17g, \"lim_excess_qd\": %.17g, \"lim_channel_qd\": %d, \"lim_n_viol\": %d, \"lim_status\": %d, ",
+                        l.stretch, l.excess[MPCMP_LIM_QD], l.channel[MPCMP_LIM_QD], l.n_viol, l.status);
+        }
         // robot.data look-alike (examples/benchmark.cpp:108-110)
         pinocchio::forwardKinematics(planner.robot.model, planner.robot.data, qT);
         pinocchio::updateFramePlacement(planner.robot.model, planner.robot.data, planner.robot.frame_id);

@@ -213,7 +213,8 @@ int mpcmp_set_time_windows_device(mpcmp_ctx *ctx, int n, const double *d_lbT, co
  * mpcmp_pose_targets_batch[_device]: with rows set, rules 2, 3 and 5 (wrap, qualify, MPCMP_IK_QD_OUT_OF_BOUNDS) use problem i's position and velocity
  * rows, so that a target generated for a problem lies inside the box the problem is then solved in.
  * Not read by: the jerk-limited generators (the *_lim_* entry points take caller limits), the leaf calls, sampling, mpcmp_traj_stats_batch, the
- * clearance checks.  The receding-horizon driver does not read the rows either (its start guess comes from the generator with limits by value, and
+ * clearance checks.  mpcmp_limits_batch[_device] (mpcmp_limits.h) checks problem i's interpolant under row i.
+ * The receding-horizon driver does not read the rows either (its start guess comes from the generator with limits by value, and
  * a captured step holds kernel arguments): with rows set mpcmp_rh_init returns MPCMP_EINVAL, and after mpcmp_rh_init both setters do.
  * A call with more problems than rows returns MPCMP_EINVAL and writes nothing.  n == 0 with rows == NULL clears the rows: outputs then are bit for
  * bit those of a context that never set any.  The table (max_batch x 464 B) is allocated by the first setter call, never in a solve.
@@ -237,6 +238,7 @@ int mpcmp_set_bounds_device(mpcmp_ctx *ctx, int n, const mpcmp_bounds *d_rows, v
  *   nodes 1 .. N-2:  ox[k][c] = sx[k][c]                   for c <  7 narm (joint positions)
  *                    ox[k][c] = sx[k][c] * s               for c >= 7 narm (joint velocities)
  *   node 0: ox[0] = x0[b];  node N-1: ox[N-1] = xf[b]     (the re-guess rule, motionPlanner.cpp:199-207: a stretch is exact only between states at rest)
+ *                    (mpcmp_limits_batch's `stretch` is the factor of T that makes the kinematic limits hold between the nodes: exact under the same condition)
  *   every node:      ou[k][j] = su[k][j] * (s * s)
  *   oT[b] = T_new[b]
  * Layouts as mpcmp_solve_batch (x [B][N][14 narm], u [B][N][7 narm]); both arm layouts.  The outputs may be the inputs (ox == sx, ou == su,
@@ -466,6 +468,11 @@ int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sol_T, const m
                              int n_groups, int *chosen);
 int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sol_T, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
                                     const int *d_group, int n_groups, int *d_chosen, void *hip_stream);
+
+/* ---- limits between the nodes: excess per group, the stretch that cures it, and the selection that reads it ----
+ * The checker of the limits themselves, beside the clearance checker: records, constants and entry points are declared in mpcmp_limits.h, which
+ * needs the types above and is part of this interface. */
+#include "mpcmp_limits.h"
 
 /* ---- via-point routes: plan, join, sample and check multi-leg moves ----
  * A route is x0 -> via_0 -> .. -> via_{M-1} -> xf, passed without stopping.  With the joint state (q, qd) fixed at a via, the legs on either side are

@@ -331,6 +331,13 @@ class MotionPlanner {
         chk(mpcmp_clearance_batch(ctx_, 1, sol_x_.data(), &sol_T_, n_pts, margin, self_gap, &r));
         return r;
     }
+    // limit record of the last solution BETWEEN its nodes, at n_pts + 1 uniform samples (include/mpcmp_limits.h): excess per group under the bounds
+    // the plan was solved with, and the stretch of T that makes the kinematic groups hold.  spec NULL: tol 0, no tool speed limits
+    mpcmp_limits check_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr) {
+        mpcmp_limits r;
+        chk(mpcmp_limits_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, n_pts, spec, &r));
+        return r;
+    }
 
     // one draw in [-1,1) of the planner's seeded stream: what `Matrix<...>::Random()` coefficients are in the reference's examples
     double random_unit() { return uniform(); }

@@ -14,7 +14,8 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    model_add_payload, model_from_urdf, models_from_urdf, num_nodes, payload, time_nodes, tool_jacobian,
                    SPHERE_DTYPE, OBSTACLE_DTYPE, CLEARANCE_DTYPE, OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE, CLR_HIT, CLR_NAN,
                    spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
-                   ROUTE_SEAM_DTYPE, route_via_velocity, route_locate)
+                   ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
+                   LIMITS_SPEC_DTYPE, LIMITS_DTYPE, LIM_GROUPS, LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG, LIM_NAN, limits_spec, limits_config)
 from .planner import BatchMotionPlanner, Solver
 
 __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED", "STATUS_OUTSIDE_TOL", "STATUS_T_OUT_OF_BOX", "STATUS_ARRIVED", "STATUS_HARD", "RH_RESTART",
@@ -26,4 +27,5 @@ __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED",
            "SPHERE_DTYPE", "OBSTACLE_DTYPE", "CLEARANCE_DTYPE", "OBS_SPHERE", "OBS_CAPSULE", "OBS_BOX", "OBS_HALFSPACE", "CLR_HIT", "CLR_NAN",
            "spheres", "obstacle", "link_spheres", "clearance_config",
            "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",
-           "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate"]
+           "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate",
+           "LIMITS_SPEC_DTYPE", "LIMITS_DTYPE", "LIM_GROUPS", "LIM_Q", "LIM_QD", "LIM_QDD", "LIM_TAU", "LIM_HEIGHT", "LIM_TOOL_LIN", "LIM_TOOL_ANG", "LIM_NAN", "limits_spec", "limits_config"]

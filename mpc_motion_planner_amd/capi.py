@@ -64,6 +64,14 @@ OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE = 0, 1, 2, 3
 CLR_HIT, CLR_NAN = 1, 2
 MAX_SPHERES, MAX_OBSTACLES = 64, 256
 
+# records of the between-node limit checks (mpcmp_limits_spec, mpcmp_limits; include/mpcmp.h): 72 and 168 bytes
+LIMITS_SPEC_DTYPE = np.dtype([("tol", "f8", 7), ("tool_lin_max", "f8"), ("tool_ang_max", "f8")])
+LIMITS_DTYPE = np.dtype([("excess", "f8", 7), ("t_at", "f8", 7), ("stretch", "f8"), ("t_first", "f8"), ("channel", "i4", 7), ("n_viol", "i4"),
+                         ("status", "i4"), ("pad", "i4")])
+LIM_GROUPS = 7
+LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG = range(7)
+LIM_NAN = 128       # status bit of mpcmp_limits: a non-finite sample value (bit g: group g over its tolerance)
+
 # one row of mpcmp_set_bounds[_device] (mpcmp_bounds, include/mpcmp.h): the six bound tables of Config, in its order
 BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7), ("ubu", "f8", 7), ("lbg", "f8", 8), ("ubg", "f8", 8)])
 
@@ -121,6 +129,12 @@ ABI = {
     # measurement hooks, diagnostics
     "mpcmp_kernel_timing": "pippp", "mpcmp_debug_fetch": "pipl", "mpcmp_debug_stamps": "pip",
 }
+# ... and every function include/mpcmp_limits.h declares (the between-node limit checker; mpcmp.h includes that header), in its order: the same
+# rules, checked the same way by the CPU test suite
+ABI_LIMITS = {
+    "mpcmp_limits_batch": "pipppipp", "mpcmp_limits_batch_device": "pipppippp", "mpcmp_limits_config": "pi" + "p" * 8,
+    "mpcmp_select_checked_batch": "pippppipip", "mpcmp_select_checked_batch_device": "pippppipipp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -131,11 +145,12 @@ def library_path():
 
 
 def build_dependencies():
-    """every file the library is built from, taken from the directory itself: csrc/*.hip, csrc/*.hpp, csrc/Makefile and include/mpcmp.h"""
+    """every file the library is built from, taken from the directories themselves: csrc/*.hip, csrc/*.hpp, csrc/Makefile and the C headers
+    include/mpcmp*.h (mpcmp.h and what it includes; the C++ shim is a .hpp the library does not read)"""
     import glob
     src = os.path.join(_HERE, "csrc")
     deps = sorted(glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.hpp")))
-    return deps + [os.path.join(src, "Makefile"), os.path.join(os.path.dirname(_HERE), "include", "mpcmp.h")]
+    return deps + [os.path.join(src, "Makefile")] + sorted(glob.glob(os.path.join(os.path.dirname(_HERE), "include", "mpcmp*.h")))
 
 
 def build_library(force=False):
@@ -176,7 +191,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in ABI.items():
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -287,6 +302,36 @@ def clearance_config(models, spheres_per_arm, obstacles, q, self_gap=0):
     check(lib().mpcmp_clearance_config(arr, narm, host(cnt), host(tab), obs.shape[0], host(obs), int(self_gap), host(q), C.byref(d), C.byref(sp),
                                        C.byref(ot)))
     return d.value, sp.value, ot.value
+
+
+def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+    """one LIMITS_SPEC_DTYPE record: tol a scalar or [7] (default 0), the tool speed maxima (default +inf: no such limit)"""
+    t = np.zeros((), dtype=LIMITS_SPEC_DTYPE)
+    t["tol"] = 0.0 if tol is None else np.broadcast_to(f64(tol), (7,))
+    t["tool_lin_max"] = tool_lin_max; t["tool_ang_max"] = tool_ang_max
+    return t
+
+
+def limits_config(models, row, q, qd, qdd, spec=None):
+    """mpcmp_limits_config: ONE configuration q, qd, qdd [7 narm] on the host under the BOUNDS_DTYPE record `row` and the LIMITS_SPEC_DTYPE record
+    `spec` (None: tol 0, no tool limits).  models: a Model or a sequence of them.  Returns (excess [7], channel [7], ratios [4] = r_v, r_a, r_lin,
+    r_ang)."""
+    if isinstance(models, Model):
+        models = [models]
+    narm = len(models)
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    row = np.ascontiguousarray(row).reshape(())
+    if row.dtype != BOUNDS_DTYPE:
+        raise ValueError("row must be one BOUNDS_DTYPE record")
+    if spec is not None:
+        spec = np.ascontiguousarray(spec).reshape(())
+        if spec.dtype != LIMITS_SPEC_DTYPE:
+            raise ValueError("spec must be one LIMITS_SPEC_DTYPE record")
+    q, qd, qdd = [f64(v).reshape(7 * narm) for v in (q, qd, qdd)]
+    ex, ch, r = np.zeros(7), np.zeros(7, dtype=np.int32), np.zeros(4)
+    check(lib().mpcmp_limits_config(arr, narm, host(row), None if spec is None else spec.ctypes.data, host(q), host(qd), host(qdd), host(ex),
+                                    host(ch), host(r)))
+    return ex, ch, r
 
 
 def model_from_urdf(path):

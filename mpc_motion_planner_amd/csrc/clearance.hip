@@ -197,24 +197,27 @@ __global__ __launch_bounds__(CLR_NT) void k_clearance(const mpcmp_model *__restr
     }
 }
 
-// ---- choice of the fastest admissible member of each group (mpcmp_select_clear_batch) ----
-__device__ __forceinline__ bool sel_admissible(int i, const int *group, int n_groups, const mpcmp_info *info, const mpcmp_clearance *clr) {
+// ---- choice of the fastest admissible member of each group (mpcmp_select_clear_batch, mpcmp_select_checked_batch) ----
+// clr and lim may each be null: that test is then skipped.  lim_bad = lim_mask | MPCMP_LIM_NAN
+__device__ __forceinline__ bool sel_admissible(int i, const int *group, int n_groups, const mpcmp_info *info, const mpcmp_clearance *clr,
+                                               const mpcmp_limits *lim, int lim_bad) {
     const int g = group[i];
     const int bad = MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_OUTSIDE_TOL | MPCMP_STATUS_T_OUT_OF_BOX;
-    return g >= 0 && g < n_groups && (info[i].status & bad) == 0 && clr[i].status == 0;
+    return g >= 0 && g < n_groups && (info[i].status & bad) == 0 && (!clr || clr[i].status == 0) && (!lim || (lim[i].status & lim_bad) == 0);
 }
 // keys [n_groups] preset to all ones: the smallest ordered key of the admissible members' final times (an integer minimum: order-independent)
-__global__ __launch_bounds__(256) void k_select_tmin(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
-                                                     int n_groups, unsigned long long *keys) {
+__global__ __launch_bounds__(256) void k_select_tmin(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
+                                                     const mpcmp_limits *lim, int lim_bad, const int *group, int n_groups, unsigned long long *keys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B || !sel_admissible(i, group, n_groups, info, clr)) return;
+    if (i >= B || !sel_admissible(i, group, n_groups, info, clr, lim, lim_bad)) return;
     atomicMin(keys + group[i], clr_tkey(sT[i]));
 }
 // chosen [n_groups] preset to 0x7F7F7F7F: the lowest index among the members that hold the group's key
-__global__ __launch_bounds__(256) void k_select_index(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
-                                                      int n_groups, const unsigned long long *keys, int *chosen) {
+__global__ __launch_bounds__(256) void k_select_index(int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
+                                                      const mpcmp_limits *lim, int lim_bad, const int *group, int n_groups,
+                                                      const unsigned long long *keys, int *chosen) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B || !sel_admissible(i, group, n_groups, info, clr)) return;
+    if (i >= B || !sel_admissible(i, group, n_groups, info, clr, lim, lim_bad)) return;
     if (clr_tkey(sT[i]) == keys[group[i]]) atomicMin(chosen + group[i], i);
 }
 __global__ __launch_bounds__(256) void k_select_finish(int n_groups, int *chosen) {
@@ -242,16 +245,17 @@ hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const
     return hipGetLastError();
 }
 
-hipError_t select_clear_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const int *d_group, int n_groups,
-                               unsigned long long *d_keys, int *d_chosen, hipStream_t st) {
+hipError_t select_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const mpcmp_limits *d_lim, int lim_mask,
+                         const int *d_group, int n_groups, unsigned long long *d_keys, int *d_chosen, hipStream_t st) {
+    const int lim_bad = lim_mask | MPCMP_LIM_NAN;
     if (n_groups < 1) return hipSuccess;
     hipError_t e = hipMemsetAsync(d_keys, 0xFF, sizeof(unsigned long long) * n_groups, st);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_chosen, 0x7F, sizeof(int) * n_groups, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_select_tmin, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_group, n_groups, d_keys);
-    hipLaunchKernelGGL(k_select_index, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_group, n_groups,
-                       (const unsigned long long *)d_keys, d_chosen);
+    hipLaunchKernelGGL(k_select_tmin, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_lim, lim_bad, d_group, n_groups, d_keys);
+    hipLaunchKernelGGL(k_select_index, dim3((B + 255) / 256), dim3(256), 0, st, B, d_sT, d_info, d_clr, d_lim, lim_bad, d_group,
+                       n_groups, (const unsigned long long *)d_keys, d_chosen);
     hipLaunchKernelGGL(k_select_finish, dim3((n_groups + 255) / 256), dim3(256), 0, st, n_groups, d_chosen);
     return hipGetLastError();
 }

@@ -98,8 +98,9 @@ struct ClrTables {
 hipError_t clearance_prepare();     // the kernel's dynamic-LDS ceiling; called by a context's first check
 hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
                             mpcmp_clearance *d_out, hipStream_t st);
-// keys [n_groups] scratch; chosen [n_groups]
-hipError_t select_clear_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const int *d_group, int n_groups,
-                               unsigned long long *d_keys, int *d_chosen, hipStream_t st);
+// keys [n_groups] scratch; chosen [n_groups].  d_clr and d_lim may each be NULL (that test is skipped); lim_mask: the bits of mpcmp_limits.status that
+// make a member inadmissible (MPCMP_LIM_NAN always does)
+hipError_t select_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const mpcmp_limits *d_lim, int lim_mask,
+                         const int *d_group, int n_groups, unsigned long long *d_keys, int *d_chosen, hipStream_t st);
 
 }  // namespace mpcmp

@@ -32,6 +32,7 @@
 #include "payload.hpp"
 #include "time_sync.hpp"
 #include "clearance.hpp"
+#include "limits.hpp"
 #include "route.hpp"
 
 #ifdef MPCMP_SPLIT_N25
@@ -2029,11 +2030,12 @@ extern "C" int mpcmp_clearance_batch(mpcmp_ctx *ctx, int B, const double *sx, co
     return sg.finish();
 }
 
-static int select_check(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group, int n_groups,
-                        const int *chosen) {
-    if (!ctx) { g_err = "mpcmp_select_clear_batch: no context"; return MPCMP_EINVAL; }
-    if (B < 1 || n_groups < 0 || n_groups > ctx->max_batch || !sT || !info || !clr || !group || (n_groups > 0 && !chosen)) {
-        ctx->err = "mpcmp_select_clear_batch: B >= 1, n_groups in [0, max_batch] and all pointers required"; return MPCMP_EINVAL;
+// `who`: the entry point's name; clr is required by mpcmp_select_clear_batch only
+static int select_check(mpcmp_ctx *ctx, const char *who, bool need_clr, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
+                        const int *group, int n_groups, const int *chosen) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_groups < 0 || n_groups > ctx->max_batch || !sT || !info || (need_clr && !clr) || !group || (n_groups > 0 && !chosen)) {
+        ctx->err = std::string(who) + ": B >= 1, n_groups in [0, max_batch] and all pointers required"; return MPCMP_EINVAL;
     }
     if (B > ctx->max_batch) { ctx->err = "batch exceeds the context capacity"; return MPCMP_ETOOBIG; }
     if (!ctx->d_sel_key) {            // first use
@@ -2043,20 +2045,20 @@ static int select_check(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_inf
     return MPCMP_OK;
 }
 
-extern "C" int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
-                                               const int *d_group, int n_groups, int *d_chosen, void *hip_stream) {
-    if (int rc = select_check(ctx, B, d_sT, d_info, d_clr, d_group, n_groups, d_chosen)) return rc;
+static int select_device(mpcmp_ctx *ctx, const char *who, bool need_clr, int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
+                         const mpcmp_limits *d_lim, int lim_mask, const int *d_group, int n_groups, int *d_chosen, void *hip_stream) {
+    if (int rc = select_check(ctx, who, need_clr, B, d_sT, d_info, d_clr, d_group, n_groups, d_chosen)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, select_clear_launch(B, d_sT, d_info, d_clr, d_group, n_groups, ctx->d_sel_key, d_chosen, (hipStream_t)hip_stream));
+    HIPCHK(ctx, select_launch(B, d_sT, d_info, d_clr, d_lim, lim_mask, d_group, n_groups, ctx->d_sel_key, d_chosen, (hipStream_t)hip_stream));
     return MPCMP_OK;
 }
 
-extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
-                                        int n_groups, int *chosen) {
-    if (int rc = select_check(ctx, B, sT, info, clr, group, n_groups, chosen)) return rc;
+static int select_host(mpcmp_ctx *ctx, const char *who, bool need_clr, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
+                       const mpcmp_limits *lim, int lim_mask, const int *group, int n_groups, int *chosen) {
+    if (int rc = select_check(ctx, who, need_clr, B, sT, info, clr, group, n_groups, chosen)) return rc;
     for (int i = 0; i < B; i++)
         if (group[i] < -1 || group[i] >= n_groups) {
-            ctx->err = "mpcmp_select_clear_batch: group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
+            ctx->err = std::string(who) + ": group[" + std::to_string(i) + "] must be -1 or in [0, n_groups)"; return MPCMP_EINVAL;
         }
     if (n_groups == 0) return MPCMP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2064,11 +2066,78 @@ extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT,
     double *dT;
     mpcmp_info *di;
     mpcmp_clearance *dc;
+    mpcmp_limits *dl;
     int *dg, *dch;
-    sg.in(&dT, sT, B); sg.in(&di, info, B); sg.in(&dc, clr, B); sg.in(&dg, group, B); sg.out(&dch, chosen, n_groups);
+    sg.in(&dT, sT, B); sg.in(&di, info, B); sg.in(&dc, clr, B); sg.in(&dl, lim, B); sg.in(&dg, group, B); sg.out(&dch, chosen, n_groups);
     if (int rc = sg.upload()) return rc;
-    HIPCHK(ctx, select_clear_launch(B, dT, di, dc, dg, n_groups, ctx->d_sel_key, dch, ctx->stream));
+    HIPCHK(ctx, select_launch(B, dT, di, dc, dl, lim_mask, dg, n_groups, ctx->d_sel_key, dch, ctx->stream));
     return sg.finish();
+}
+
+extern "C" int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
+                                               const int *d_group, int n_groups, int *d_chosen, void *hip_stream) {
+    return select_device(ctx, "mpcmp_select_clear_batch", true, B, d_sT, d_info, d_clr, nullptr, 0, d_group, n_groups, d_chosen, hip_stream);
+}
+
+extern "C" int mpcmp_select_clear_batch(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr, const int *group,
+                                        int n_groups, int *chosen) {
+    return select_host(ctx, "mpcmp_select_clear_batch", true, B, sT, info, clr, nullptr, 0, group, n_groups, chosen);
+}
+
+// ------------------------------------------------------------------------------------------------
+// limits between the nodes (limits.hpp; the kernel is in limits.hip)
+static int limits_check(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_pts, const mpcmp_limits_spec *spec,
+                        const mpcmp_limits *out) {
+    if (!ctx) { g_err = "mpcmp_limits_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch || n_pts < 1 || n_pts > LIM_MAX_PTS || !sx || !su || !sT || !out) {
+        ctx->err = "mpcmp_limits_batch: B in [1, max_batch], 1 <= n_pts <= 4096 and all pointers (but spec) required"; return MPCMP_EINVAL;
+    }
+    if (spec && !lim_spec_ok(*spec)) { ctx->err = "mpcmp_limits_batch: finite tolerances and tool maxima >= 0 (+inf: none) required"; return MPCMP_EINVAL; }
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
+    return rows_ok(ctx, B, PAYLOAD_ROWS);
+}
+
+static int limits_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_pts, const mpcmp_limits_spec *spec,
+                          mpcmp_limits *d_out, hipStream_t st) {
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, limits_launch(md, ms, ctx->narm, ctx->nseg, B, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
+                              spec ? *spec : lim_default_spec(), d_out, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_limits_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_pts,
+                                         const mpcmp_limits_spec *spec, mpcmp_limits *d_out, void *hip_stream) {
+    if (int rc = limits_check(ctx, B, d_sx, d_su, d_sT, n_pts, spec, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return limits_enqueue(ctx, B, d_sx, d_su, d_sT, n_pts, spec, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_limits_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_pts,
+                                  const mpcmp_limits_spec *spec, mpcmp_limits *out) {
+    if (int rc = limits_check(ctx, B, sx, su, sT, n_pts, spec, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t NB = (size_t)ctx->N * B;
+    Stage sg(ctx);
+    double *dx, *du, *dT;
+    mpcmp_limits *dout;
+    sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, B); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = limits_enqueue(ctx, B, dx, du, dT, n_pts, spec, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+extern "C" int mpcmp_select_checked_batch_device(mpcmp_ctx *ctx, int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr,
+                                                 const mpcmp_limits *d_lim, int lim_mask, const int *d_group, int n_groups, int *d_chosen,
+                                                 void *hip_stream) {
+    return select_device(ctx, "mpcmp_select_checked_batch", false, B, d_sT, d_info, d_clr, d_lim, lim_mask, d_group, n_groups, d_chosen, hip_stream);
+}
+
+extern "C" int mpcmp_select_checked_batch(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
+                                          const mpcmp_limits *lim, int lim_mask, const int *group, int n_groups, int *chosen) {
+    return select_host(ctx, "mpcmp_select_checked_batch", false, B, sT, info, clr, lim, lim_mask, group, n_groups, chosen);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -256,6 +256,45 @@ class Solver:
         check(lib().mpcmp_select_clear_batch_device(self._ctx, int(B), sol_T or None, info or None, clr or None, group or None, int(n_groups),
                                                     chosen or None, stream or None), self._ctx)
 
+    # -- limits between the nodes (include/mpcmp.h, "limits between the nodes")
+    def limits(self, sx, su, sT, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """mpcmp_limits_batch: capi.LIMITS_DTYPE [B] for the trajectories sx, su, sT at n_pts + 1 uniform samples, under the bound rows (or the
+        configuration's tables) and payload rows in force.  tol: None (a NULL spec when the tool maxima are infinite too), a scalar or [7]"""
+        sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
+        spec = None if tol is None and np.isposinf(tool_lin_max) and np.isposinf(tool_ang_max) else capi.limits_spec(tol, tool_lin_max, tool_ang_max)
+        out = np.zeros(B, dtype=capi.LIMITS_DTYPE)
+        check(lib().mpcmp_limits_batch(self._ctx, B, host(sx), host(su), host(sT), int(n_pts), None if spec is None else spec.ctypes.data,
+                                       host(out)), self._ctx)
+        return out
+
+    def limits_device(self, B, sol_x, sol_u, sol_T, n_pts, out, spec=None, stream=0):
+        """spec: a capi.LIMITS_SPEC_DTYPE record on the HOST (capi.limits_spec) or None; everything else raw device pointers"""
+        check(lib().mpcmp_limits_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_pts),
+                                              None if spec is None else np.ascontiguousarray(spec).ctypes.data, out or None, stream or None), self._ctx)
+
+    def select_checked(self, sT, info, group, clr=None, lim=None, lim_mask=0x7F, n_groups=None):
+        """mpcmp_select_checked_batch: select_clear with an optional clearance test (clr None: none) and an optional limits test (a member whose
+        lim status has a bit of lim_mask, or LIM_NAN, is inadmissible).  n_groups defaults to max(group) + 1"""
+        sT = f64(sT).reshape(-1); B = sT.shape[0]
+        info = np.ascontiguousarray(info)
+        clr = None if clr is None else np.ascontiguousarray(clr)
+        lim = None if lim is None else np.ascontiguousarray(lim)
+        group = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if info.dtype != capi.INFO_DTYPE or info.shape != (B,) or group.shape != (B,) or \
+                (clr is not None and (clr.dtype != capi.CLEARANCE_DTYPE or clr.shape != (B,))) or \
+                (lim is not None and (lim.dtype != capi.LIMITS_DTYPE or lim.shape != (B,))):
+            raise ValueError("info (INFO_DTYPE), clr (CLEARANCE_DTYPE or None), lim (LIMITS_DTYPE or None) and group must be [B] = [%d]" % B)
+        if n_groups is None:
+            n_groups = max(int(group.max()) + 1, 0)
+        chosen = np.full(max(int(n_groups), 1), -1, dtype=np.int32)
+        check(lib().mpcmp_select_checked_batch(self._ctx, B, host(sT), host(info), host(clr), host(lim), int(lim_mask), host(group), int(n_groups),
+                                               host(chosen)), self._ctx)
+        return chosen[:n_groups]
+
+    def select_checked_device(self, B, sol_T, info, clr, lim, lim_mask, group, n_groups, chosen, stream=0):
+        check(lib().mpcmp_select_checked_batch_device(self._ctx, int(B), sol_T or None, info or None, clr or None, lim or None, int(lim_mask),
+                                                      group or None, int(n_groups), chosen or None, stream or None), self._ctx)
+
     # -- via-point routes: B routes with M vias = B (M + 1) leg slots (include/mpcmp.h, "via-point routes")
     @staticmethod
     def repeat(rows, M):
@@ -675,6 +714,17 @@ class BatchMotionPlanner:
             clr = self._solver.clearance(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin, self_gap)
             return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
         return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
+
+    def check_limits(self, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """limit records (capi.LIMITS_DTYPE) of the last solve_trajectory's solutions between their nodes, [B]; of routes: one record per leg,
+        [B][M + 1] (times are leg times)"""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            lim = self._solver.limits(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_u"].reshape(L, self._solver.N, 7), r["sol_T"].reshape(L),
+                                      n_pts, tol, tool_lin_max, tool_ang_max)
+            return lim.reshape(r["sol_T"].shape)
+        return self._solver.limits(self._sol[0], self._sol[1], self._sol[2], n_pts, tol, tool_lin_max, tool_ang_max)
 
     # extension beyond the reference's members: a move through via points (include/mpcmp.h, "via-point routes")
     def set_via_points(self, via, via_velocity=None, speed=0.5):
