@@ -145,11 +145,11 @@ def library_path():
 
 
 def build_dependencies():
-    """every file the library is built from, taken from the directories themselves: csrc/*.hip, csrc/*.hpp, csrc/Makefile and the C headers
+    """every file the library is built from, taken from the directories themselves: csrc/*.hip, csrc/*.cpp, csrc/*.hpp, csrc/Makefile and the C headers
     include/mpcmp*.h (mpcmp.h and what it includes; the C++ shim is a .hpp the library does not read)"""
     import glob
     src = os.path.join(_HERE, "csrc")
-    deps = sorted(glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.hpp")))
+    deps = sorted(glob.glob(os.path.join(src, "*.hip")) + glob.glob(os.path.join(src, "*.cpp")) + glob.glob(os.path.join(src, "*.hpp")))
     return deps + [os.path.join(src, "Makefile")] + sorted(glob.glob(os.path.join(os.path.dirname(_HERE), "include", "mpcmp*.h")))
 
 

@@ -1,6 +1,6 @@
 // clearance.hip — batched clearance checks (include/mpcmp.h, "clearance"): robot spheres against obstacles and against the other arm, over the
 // uniform samples of B trajectories; the choice of the fastest clear member of a group; and the host helpers that need no context.
-// A translation unit of its own, so that the register-bound QP kernels of mpcmp.hip compile exactly as before.
+// A translation unit of its own, so that the register-bound QP kernels of solver.hip compile exactly as before.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>

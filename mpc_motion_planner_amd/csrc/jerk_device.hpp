@@ -14,9 +14,11 @@
 //
 // One 64-thread workgroup (one wave) per problem: lanes 0..6 find the minimum-time profile of one joint each, the wave then
 // re-plans the faster joints to the common duration one after the other (64 scan points at a time), then all lanes sample.
+// At the end: the two kernels that make a multi-arm start guess of it (k_split_states, k_warm_merge).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rbd_device.hpp"
+#include "solver_types.hpp"
 
 namespace mpcmp {
 
@@ -286,6 +288,41 @@ __global__ __launch_bounds__(64) void k_jerk_point(const mpcmp_model *mdl, JerkL
         for (int j = 0; j < 7; j++) { o[j] = pt[j]; o[7 + j] = v[j]; o[14 + j] = a[j]; o[21 + j] = tau[j]; }
         if (Tout) Tout[b] = T;
     }
+}
+
+// warm start of a multi-arm OCP from the single-arm generator (k_warm_jerk run on B*NARM arm problems): the common duration
+// is the slowest arm's and a faster arm's trajectory is played back uniformly slower (q(t) = q_a(s t), qd = s qd_a,
+// qdd = s^2 qdd_a with s = T_a / T <= 1: every limit still holds); exact end states (motionPlanner.cpp:202-203).
+// in: ax [B*NARM][N][14], au [B*NARM][N][7], aT [B*NARM]  (arm problem index = b*NARM + a);  out: ABI layout.
+template <int NARM>
+__global__ __launch_bounds__(256) void k_warm_merge(int N, int B, const double *ax, const double *au, const double *aT, const double *x0,
+                                                    const double *xf, double *wx, double *wu, double *wT) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double T = 0.0;
+    for (int a = 0; a < NARM; a++) T = fmax(T, aT[b * NARM + a]);
+    for (int t = tid; t < N * 21 * NARM; t += blockDim.x) {
+        const int a = t / (N * 21), w = t % (N * 21), k = w / 21, c = w % 21;
+        const double s = aT[b * NARM + a] / T;
+        const size_t ap = (size_t)b * NARM + a;
+        if (c < 14) {
+            double val = ax[(ap * N + k) * 14 + c] * (c < 7 ? 1.0 : s);
+            if (k == 0) val = x0[(size_t)b * 14 * NARM + ext_x<NARM>(a, c)];
+            if (k == N - 1) val = xf[(size_t)b * 14 * NARM + ext_x<NARM>(a, c)];
+            wx[((size_t)b * N + k) * 14 * NARM + ext_x<NARM>(a, c)] = val;
+        } else {
+            wu[((size_t)b * N + k) * 7 * NARM + 7 * a + (c - 14)] = au[(ap * N + k) * 7 + (c - 14)] * (s * s);
+        }
+    }
+    if (tid == 0) wT[b] = T;
+}
+
+// split external states [B][14 NARM] into per-arm states [B*NARM][14] (input of k_warm_jerk)
+template <int NARM>
+__global__ void k_split_states(int B, const double *xe, double *xa) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * NARM * 14) return;
+    const int b = i / (NARM * 14), a = (i / 14) % NARM, r = i % 14;
+    xa[i] = xe[(size_t)b * 14 * NARM + ext_x<NARM>(a, r)];
 }
 
 }  // namespace mpcmp

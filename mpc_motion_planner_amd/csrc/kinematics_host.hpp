@@ -5,11 +5,16 @@
 // batched multi-start IK kernel (ik_device.hpp) runs this source, one DLS step at a time, so host and device share one
 // implementation.  The batched solve never calls them.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include "../../include/mpcmp.h"
 
+// (model_host.cpp is plain C++: it reads this file without the HIP runtime's header)
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define MPCMP_HD __host__ __device__ inline
+#else
+#define MPCMP_HD inline
+#endif
 
 namespace mpcmp_host {
 

@@ -1,6 +1,6 @@
 // limits.hip — the between-node limit checker (include/mpcmp.h, "limits between the nodes"): per trajectory the excess of every group over its
 // bounds at the uniform samples of the interpolant, the stretch that cures the kinematic groups, and the host helper that needs no context.
-// A translation unit of its own, so that the register-bound QP kernels of mpcmp.hip compile exactly as before.
+// A translation unit of its own, so that the register-bound QP kernels of solver.hip compile exactly as before.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "limits.hpp"

@@ -1,0 +1,489 @@
+// model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
+// configuration, a bound row and a payload must satisfy, and the single-problem kinematics of the reference's robot wrapper.  Plain C++: no HIP
+// header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
+// (examples/urdf_selftest.cpp).
+#include <array>
+#include <cctype>
+#include <cmath>
+#include <cstddef>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <functional>
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../include/mpcmp.h"
+#include "model_host.hpp"
+#include "kinematics_host.hpp"
+#include "payload.hpp"
+
+using namespace mpcmp;
+
+thread_local std::string mpcmp::g_err;
+
+// ------------------------------------------------------------------------------------------------
+// configuration helpers (host only)
+extern "C" const char *mpcmp_version(void) { return "mpcmp 0.1 (gfx950)"; }
+
+extern "C" int mpcmp_num_nodes(int num_seg) { return 3 * num_seg + 1; }
+
+extern "C" int mpcmp_time_nodes(int num_seg, double *tau) {
+    if (num_seg < 1 || !tau) return MPCMP_EINVAL;
+    static const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
+    for (int s = 0; s < num_seg; s++)
+        for (int j = 0; j < 4; j++) tau[3 * s + j] = (s + 0.5 * (xi[j] + 1.0)) / num_seg;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_default_limits(double *qmin, double *qmax, double *vmax, double *amax, double *jmax,
+                                    double *taumax) {
+    // Franka Emika limits as tabulated by the reference, robot_utils/pandaWrapper.hpp:29-34
+    static const double t[6][7] = {{-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973},
+                                   {2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973},
+                                   {2.1750, 2.1750, 2.1750, 2.1750, 2.6100, 2.6100, 2.6100},
+                                   {15.0, 7.5, 10.0, 12.5, 15.0, 20.0, 20.0},
+                                   {7500, 3750, 5000, 6250, 7500, 10000, 10000},
+                                   {87, 87, 87, 87, 12, 12, 12}};
+    double *o[6] = {qmin, qmax, vmax, amax, jmax, taumax};
+    for (int k = 0; k < 6; k++)
+        if (o[k]) std::memcpy(o[k], t[k], sizeof t[k]);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_min_height(mpcmp_config *c, double min_height) {
+    if (!c) return MPCMP_EINVAL;
+    c->lbg[7] = min_height;
+    c->ubg[7] = INFINITY;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_margins(mpcmp_config *c, double mp, double mv, double ma, double mt) {
+    if (!c) return MPCMP_EINVAL;
+    double qmin[7], qmax[7], vmax[7], amax[7], tmax[7];
+    mpcmp_default_limits(qmin, qmax, vmax, amax, nullptr, tmax);
+    for (int j = 0; j < 7; j++) {
+        const double s = (1.0 - mp) * (qmax[j] - qmin[j]) / 2.0;   // motionPlanner.cpp:66
+        c->lbx[j] = qmin[j] + s; c->ubx[j] = qmax[j] - s;
+        c->lbx[7 + j] = -mv * vmax[j]; c->ubx[7 + j] = mv * vmax[j];
+        c->lbu[j] = -ma * amax[j]; c->ubu[j] = ma * amax[j];
+        c->lbg[j] = -mt * tmax[j]; c->ubg[j] = mt * tmax[j];
+    }
+    c->lbT = 0.0; c->ubT = 10.0;                                  // motionPlanner.cpp:77-78
+    return mpcmp_set_min_height(c, 0.05);                         // pandaWrapper.hpp:40
+}
+
+extern "C" int mpcmp_default_config(mpcmp_config *c, int num_seg, int sqp_iters) {
+    if (!c || num_seg < 1) return MPCMP_EINVAL;
+    std::memset(c, 0, sizeof *c);
+    c->num_seg = num_seg; c->sqp_iters = sqp_iters;
+    c->qp_iters = 700; c->ls_iters = 10; c->check_every = 25; c->quirk_dtau_dT = 1;
+    c->eps_abs = 1e-3; c->eps_rel = 1e-3;
+    c->rho = 0.02; c->sigma = 1e-6; c->alpha = 1.4; c->rho_eq_scale = 1e3;      // fitted to the reference's stored solve: tools/polympc_param_fit.py
+    c->ls_eta = 0.25; c->ls_tau = 0.5; c->hess_reg = 1e-3; c->eps_target = 1e-2;
+    return mpcmp_set_margins(c, 1.0, 1.0, 1.0, 1.0);              // motionPlanner.cpp:24
+}
+
+// per-problem bounds: a row is the six tables of the configuration, which lie there in the row's order without a gap
+static_assert(sizeof(mpcmp_bounds) == 58 * sizeof(double), "mpcmp_bounds: 58 doubles");
+static_assert(offsetof(mpcmp_config, ubg) + sizeof(double[8]) - offsetof(mpcmp_config, lbx) == sizeof(mpcmp_bounds) &&
+              offsetof(mpcmp_config, ubx) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubx) &&
+              offsetof(mpcmp_config, lbu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbu) &&
+              offsetof(mpcmp_config, ubu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubu) &&
+              offsetof(mpcmp_config, lbg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbg) &&
+              offsetof(mpcmp_config, ubg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubg),
+              "mpcmp_bounds has the layout of the six tables of mpcmp_config");
+extern "C" int mpcmp_bounds_from_config(const mpcmp_config *c, mpcmp_bounds *out) {
+    if (!c || !out) return MPCMP_EINVAL;
+    std::memcpy(out, c->lbx, sizeof *out);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_bounds_from_margins(double mp, double mv, double ma, double mt, double min_height, mpcmp_bounds *out) {
+    if (!out) return MPCMP_EINVAL;
+    mpcmp_config c;
+    if (int rc = mpcmp_default_config(&c, 4, 1)) return rc;      // (the tables do not depend on num_seg or sqp_iters)
+    if (int rc = mpcmp_set_margins(&c, mp, mv, ma, mt)) return rc;
+    if (int rc = mpcmp_set_min_height(&c, min_height)) return rc;
+    return mpcmp_bounds_from_config(&c, out);
+}
+
+static void rpy_to_R(const double rpy[3], double R[9]) {
+    const double cr = std::cos(rpy[0]), sr = std::sin(rpy[0]), cp = std::cos(rpy[1]), sp = std::sin(rpy[1]),
+                 cy = std::cos(rpy[2]), sy = std::sin(rpy[2]);
+    // R = Rz(yaw) Ry(pitch) Rx(roll)
+    R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
+    R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
+    R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
+}
+
+// ---- scenario helpers (host): robot_utils/pandaWrapper.cpp:14-107 ----
+extern "C" int mpcmp_tool_jacobian(const mpcmp_model *model, const double *q, double *J, double *p, double *R) {
+    if (!model || !q || !J) return MPCMP_EINVAL;
+    double pp[3], RR[9];
+    mpcmp_host::tool_jacobian(*model, q, J, pp, RR);
+    if (p) for (int k = 0; k < 3; k++) p[k] = pp[k];
+    if (R) for (int k = 0; k < 9; k++) R[k] = RR[k];
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_forward_velocities(const mpcmp_model *model, const double *q, const double *qd, double *out) {
+    if (!model || !q || !qd || !out) return MPCMP_EINVAL;
+    double J[42], p[3], R[9];
+    mpcmp_host::tool_jacobian(*model, q, J, p, R);
+    for (int r = 0; r < 6; r++) { double s = 0; for (int k = 0; k < 7; k++) s += J[r * 7 + k] * qd[k]; out[r] = s; }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_inverse_velocities(const mpcmp_model *model, const double *q, const double *lin, const double *ang, double *qd) {
+    if (!model || !q || !lin || !ang || !qd) return MPCMP_EINVAL;
+    const double b[6] = {lin[0], lin[1], lin[2], ang[0], ang[1], ang[2]};
+    return mpcmp_host::inverse_velocities(*model, q, b, qd) ? MPCMP_OK : MPCMP_ERUNTIME;
+}
+
+// the loop of PandaWrapper::inverse_kinematic around the DLS step the batched kernel shares (kinematics_host.hpp)
+extern "C" int mpcmp_inverse_kinematics(const mpcmp_model *model, const double *Rdes, const double *pdes, const double *q_init,
+                                        double *q, int *iters) {
+    if (!model || !Rdes || !pdes || !q) return MPCMP_EINVAL;
+    for (int k = 0; k < 7; k++) q[k] = q_init ? q_init[k] : 0.0;
+    for (int it = 0;; it++) {
+        double en;
+        const int r = mpcmp_host::ik_dls_step(*model, Rdes, pdes, q, it, &en);
+        if (iters) *iters = it;
+        if (r == mpcmp_host::IK_CONVERGED) return MPCMP_OK;
+        if (r == mpcmp_host::IK_CAPPED) return 1;
+        if (r == mpcmp_host::IK_NOT_PD) return MPCMP_ERUNTIME;
+    }
+}
+
+extern "C" int mpcmp_default_model(mpcmp_model *m) {
+    if (!m) return MPCMP_EINVAL;
+    // Kinematic / inertial parameters of the Panda arm (robot_utils/panda-model/panda_arm.urdf)
+    static const double rpy[7][3] = {{0, 0, 0}, {-1.57079632679, 0, 0}, {1.57079632679, 0, 0}, {1.57079632679, 0, 0},
+                                     {-1.57079632679, 0, 0}, {1.57079632679, 0, 0}, {1.57079632679, 0, 0}};
+    static const double xyz[7][3] = {{0, 0, 0.333}, {0, 0, 0}, {0, -0.316, 0}, {0.0825, 0, 0},
+                                     {-0.0825, 0.384, 0}, {0, 0, 0}, {0.088, 0, 0}};
+    static const double mass[7] = {4.970684, 0.646926, 3.228604, 3.587895, 1.225946, 1.666555, 0.735522};
+    static const double com[7][3] = {{3.875e-03, 2.081e-03, -0.1750}, {-3.141e-03, -2.872e-02, 3.495e-03},
+                                     {2.7518e-02, 3.9252e-02, -6.6502e-02}, {-5.317e-02, 1.04419e-01, 2.7454e-02},
+                                     {-1.1953e-02, 4.1065e-02, -3.8437e-02}, {6.0149e-02, -1.4117e-02, -1.0517e-02},
+                                     {1.0517e-02, -4.252e-03, 6.1597e-02}};
+    static const double in6[7][6] = {{7.0337e-01, -1.3900e-04, 6.7720e-03, 7.0661e-01, 1.9169e-02, 9.1170e-03},
+                                     {7.9620e-03, -3.9250e-03, 1.0254e-02, 2.8110e-02, 7.0400e-04, 2.5995e-02},
+                                     {3.7242e-02, -4.7610e-03, -1.1396e-02, 3.6155e-02, -1.2805e-02, 1.0830e-02},
+                                     {2.5853e-02, 7.7960e-03, -1.3320e-03, 1.9552e-02, 8.6410e-03, 2.8323e-02},
+                                     {3.5549e-02, -2.1170e-03, -4.0370e-03, 2.9474e-02, 2.2900e-04, 8.6270e-03},
+                                     {1.9640e-03, 1.0900e-04, -1.1580e-03, 4.3540e-03, 3.4100e-04, 5.4330e-03},
+                                     {1.2516e-02, -4.2800e-04, -1.1960e-03, 1.0027e-02, -7.4100e-04, 4.8150e-03}};
+    std::memset(m, 0, sizeof *m);
+    for (int i = 0; i < 7; i++) {
+        rpy_to_R(rpy[i], m->R0[i]);
+        std::memcpy(m->p[i], xyz[i], sizeof xyz[i]);
+        m->mass[i] = mass[i];
+        std::memcpy(m->com[i], com[i], sizeof com[i]);
+        const double *I = in6[i];
+        const double F[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
+        std::memcpy(m->I[i], F, sizeof F);
+    }
+    m->link8[2] = 0.107;
+    m->tool[2] = 0.107 + 0.15;
+    m->gravity[2] = -9.81;
+    // fixed children of link7: link8 (m=0, I=1e-3 Id) and panda_tool (m=1, I=1e-3 Id) are lumped into body 7
+    const double mk[3] = {mass[6], 0.0, 1.0};
+    const double ck[3][3] = {{com[6][0], com[6][1], com[6][2]}, {0, 0, 0.107}, {0, 0, 0.257}};
+    double Ik[3][9];
+    std::memcpy(Ik[0], m->I[6], sizeof Ik[0]);
+    for (int k = 1; k < 3; k++) { std::memset(Ik[k], 0, sizeof Ik[k]); Ik[k][0] = Ik[k][4] = Ik[k][8] = 1e-3; }
+    lump_last_body(m, 3, mk, ck, Ik);
+    return MPCMP_OK;
+}
+
+// ---- URDF reader: any number of serial 7-joint chains on one base (robot_utils/pandaWrapper.cpp:3-12 takes any URDF) --------
+// What the kernels need of a robot is, per chain, seven revolute joints about the z axis of their own frame, the placement of
+// each joint in its parent joint's frame, one rigid body per joint frame and the two named frames behind the last joint.  A URDF
+// is brought into that form here: fixed joints (before, between and behind the revolute joints, rotated or not) are folded into
+// the next joint's placement and their links lumped into the body of the joint frame they hang on; a chain's base placement is
+// folded into its first joint; rotated inertial frames rotate the inertia tensor; a joint axis other than +z is absorbed by a
+// constant rotation of the child frame.
+namespace {
+struct UrdfLink { double mass = 0, com[3] = {0, 0, 0}, I[9] = {0}, irpy[3] = {0, 0, 0}; bool has_inertial = false; };
+struct UrdfJoint { std::string name, type, parent, child; double xyz[3] = {0, 0, 0}, rpy[3] = {0, 0, 0}, axis[3] = {0, 0, 1}; };
+struct Xf { double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}; };       // rigid transform, parent <- child
+
+static std::string attr(const std::string &tag, const std::string &key) {
+    size_t p = 0;
+    while ((p = tag.find(key + "=", p)) != std::string::npos) {
+        if (p > 0 && (isalnum((unsigned char)tag[p - 1]) || tag[p - 1] == '_')) { p += key.size(); continue; }
+        const size_t q0 = p + key.size() + 1;
+        const char quote = tag[q0];
+        const size_t q1 = tag.find(quote, q0 + 1);
+        return tag.substr(q0 + 1, q1 - q0 - 1);
+    }
+    return "";
+}
+static void parse3(const std::string &s, double *o) {
+    if (s.empty()) return;
+    std::istringstream is(s);
+    is >> o[0] >> o[1] >> o[2];
+}
+static bool is_identity(const double *R) {
+    return R[0] == 1 && R[4] == 1 && R[8] == 1 && R[1] == 0 && R[2] == 0 && R[3] == 0 && R[5] == 0 && R[6] == 0 && R[7] == 0;
+}
+static void matmul3(const double *A, const double *B, double *Cm) {
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Cm[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+}
+// (identity factors are skipped, so that a URDF without rotated fixed joints gives bit-for-bit the numbers it holds)
+static Xf compose(const Xf &a, const Xf &b) {
+    Xf o;
+    if (is_identity(a.R)) { std::memcpy(o.R, b.R, sizeof o.R); for (int d = 0; d < 3; d++) o.t[d] = a.t[d] + b.t[d]; }
+    else {
+        if (is_identity(b.R)) std::memcpy(o.R, a.R, sizeof o.R); else matmul3(a.R, b.R, o.R);
+        for (int d = 0; d < 3; d++) o.t[d] = a.t[d] + (a.R[3 * d] * b.t[0] + a.R[3 * d + 1] * b.t[1] + a.R[3 * d + 2] * b.t[2]);
+    }
+    return o;
+}
+static void rotate_inertia(const double *R, const double *I, double *o) {          // R I R^T
+    if (is_identity(R)) { std::memcpy(o, I, 9 * sizeof(double)); return; }
+    double RI[9], Rt[9];
+    matmul3(R, I, RI);
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * c + r];
+    matmul3(RI, Rt, o);
+}
+// rotation that takes +z to the (normalised) axis a
+static bool axis_rotation(const double *a_in, double *R) {
+    const double n = std::sqrt(a_in[0] * a_in[0] + a_in[1] * a_in[1] + a_in[2] * a_in[2]);
+    if (!(n > 0)) return false;
+    const double a[3] = {a_in[0] / n, a_in[1] / n, a_in[2] / n};
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (a[0] == 0 && a[1] == 0 && a[2] == 1) { std::memcpy(R, I3, sizeof I3); return true; }
+    if (a[0] == 0 && a[1] == 0 && a[2] == -1) { const double F[9] = {1, 0, 0, 0, -1, 0, 0, 0, -1}; std::memcpy(R, F, sizeof F); return true; }
+    // Rodrigues: axis v = z x a, sin = |v|, cos = a_z
+    const double v[3] = {-a[1], a[0], 0.0}, c = a[2], k = 1.0 / (1.0 + c);
+    const double V[9] = {0, -v[2], v[1], v[2], 0, -v[0], -v[1], v[0], 0};
+    double V2[9];
+    matmul3(V, V, V2);
+    for (int i = 0; i < 9; i++) R[i] = I3[i] + V[i] + k * V2[i];
+    return true;
+}
+struct BodyAcc { std::vector<double> m; std::vector<std::array<double, 3>> c; std::vector<std::array<double, 9>> I; };
+struct ChainAcc {
+    std::string first_joint;
+    std::vector<Xf> placement;                      // joint i in joint i - 1 (the first: in the base / world frame)
+    std::vector<BodyAcc> bodies;                    // per joint frame
+    std::vector<std::vector<std::array<double, 3>>> frames;     // fixed descendants of each joint frame (origins, in order of discovery)
+};
+// same arithmetic, in the same order, as lump_last_body for three bodies
+static void lump(const BodyAcc &b, double &M, double *c, double *It) {
+    const size_t n = b.m.size();
+    M = b.m[0];
+    for (size_t k = 1; k < n; k++) M = M + b.m[k];
+    c[0] = c[1] = c[2] = 0;
+    for (size_t k = 0; k < n; k++) for (int d = 0; d < 3; d++) c[d] += b.m[k] * b.c[k][d];
+    for (int d = 0; d < 3; d++) c[d] /= M;
+    for (int i = 0; i < 9; i++) It[i] = 0;
+    for (size_t k = 0; k < n; k++) {
+        const double d[3] = {b.c[k][0] - c[0], b.c[k][1] - c[1], b.c[k][2] - c[2]};
+        const double d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        for (int r = 0; r < 3; r++) for (int s2 = 0; s2 < 3; s2++)
+            It[3 * r + s2] += b.I[k][3 * r + s2] + b.m[k] * ((r == s2 ? d2 : 0.0) - d[r] * d[s2]);
+    }
+}
+}  // namespace
+
+extern "C" int mpcmp_models_from_urdf(const char *path, int max_chains, mpcmp_model *models, int *n_chains) {
+    if (!path || !models || !n_chains || max_chains < 1) return MPCMP_EINVAL;
+    *n_chains = 0;
+    std::ifstream f(path);
+    if (!f) { g_err = std::string("cannot open URDF ") + path; return MPCMP_EINVAL; }
+    std::stringstream ss; ss << f.rdbuf();
+    const std::string xml = ss.str();
+    std::map<std::string, UrdfLink> links;
+    std::vector<std::string> link_order;
+    std::vector<UrdfJoint> joints;
+    size_t pos = 0;
+    std::string cur_link; UrdfJoint cur_joint; bool in_link = false, in_joint = false, in_inertial = false;
+    while ((pos = xml.find('<', pos)) != std::string::npos) {
+        if (xml.compare(pos, 4, "<!--") == 0) { const size_t e = xml.find("-->", pos); if (e == std::string::npos) break; pos = e + 3; continue; }
+        const size_t end = xml.find('>', pos);
+        if (end == std::string::npos) break;
+        const std::string tag = xml.substr(pos + 1, end - pos - 1);
+        pos = end + 1;
+        if (tag.empty() || tag[0] == '?' || tag[0] == '!') continue;
+        std::istringstream ts(tag); std::string name; ts >> name;
+        if (!name.empty() && name.back() == '/') name.pop_back();
+        if (name == "link") { cur_link = attr(tag, "name"); if (!links.count(cur_link)) link_order.push_back(cur_link); links[cur_link]; in_link = tag.back() != '/'; }
+        else if (name == "/link") in_link = false;
+        else if (name == "joint" && tag.find("type=") != std::string::npos) {
+            cur_joint = UrdfJoint(); cur_joint.type = attr(tag, "type"); cur_joint.name = attr(tag, "name"); in_joint = true;
+        } else if (name == "/joint") { if (in_joint) joints.push_back(cur_joint); in_joint = false; }
+        else if (name == "inertial") in_inertial = true;
+        else if (name == "/inertial") in_inertial = false;
+        else if (name == "origin") {
+            if (in_joint) { parse3(attr(tag, "xyz"), cur_joint.xyz); parse3(attr(tag, "rpy"), cur_joint.rpy); }
+            else if (in_link && in_inertial) { parse3(attr(tag, "xyz"), links[cur_link].com); parse3(attr(tag, "rpy"), links[cur_link].irpy); }
+        } else if (name == "mass" && in_link && in_inertial) { links[cur_link].mass = atof(attr(tag, "value").c_str()); links[cur_link].has_inertial = true; }
+        else if (name == "inertia" && in_link && in_inertial) {
+            UrdfLink &L = links[cur_link];
+            const double xx = atof(attr(tag, "ixx").c_str()), xy = atof(attr(tag, "ixy").c_str()), xz = atof(attr(tag, "ixz").c_str()),
+                         yy = atof(attr(tag, "iyy").c_str()), yz = atof(attr(tag, "iyz").c_str()), zz = atof(attr(tag, "izz").c_str());
+            const double F[9] = {xx, xy, xz, xy, yy, yz, xz, yz, zz};
+            std::memcpy(L.I, F, sizeof F);
+        } else if (name == "parent" && in_joint) cur_joint.parent = attr(tag, "link");
+        else if (name == "child" && in_joint) cur_joint.child = attr(tag, "link");
+        else if (name == "axis" && in_joint) parse3(attr(tag, "xyz"), cur_joint.axis);
+    }
+    if (links.empty()) { g_err = "URDF holds no links"; return MPCMP_EINVAL; }
+    // the kinematic tree
+    std::map<std::string, std::vector<const UrdfJoint *>> kids;
+    std::map<std::string, int> is_child;
+    for (auto &j : joints) {
+        if (!links.count(j.parent) || !links.count(j.child)) { g_err = "joint " + j.name + " names an unknown link"; return MPCMP_EINVAL; }
+        kids[j.parent].push_back(&j);
+        if (is_child[j.child]++) { g_err = "link " + j.child + " has two parent joints"; return MPCMP_EINVAL; }
+    }
+    std::string root;
+    for (auto &ln : link_order) if (!is_child.count(ln)) { if (!root.empty()) { g_err = "URDF has more than one root link"; return MPCMP_EINVAL; } root = ln; }
+    if (root.empty()) { g_err = "URDF has no root link (cycle)"; return MPCMP_EINVAL; }
+    std::vector<ChainAcc> chains;
+    std::string err;
+    // depth first in file order; C: link frame in the current model frame (the world before a chain starts, then the joint frame)
+    std::function<bool(const std::string &, const Xf &, int, int)> visit = [&](const std::string &ln, const Xf &C, int ci, int ji) -> bool {
+        const UrdfLink &L = links[ln];
+        if (ci >= 0) {
+            ChainAcc &ch = chains[ci];
+            if (L.has_inertial) {
+                double Rin[9], Il[9], If[9];
+                rpy_to_R(L.irpy, Rin);
+                rotate_inertia(Rin, L.I, Il);          // inertial frame -> link axes
+                rotate_inertia(C.R, Il, If);           // link axes -> joint frame axes
+                Xf com; std::memcpy(com.t, L.com, sizeof L.com);
+                const Xf cj = compose(C, com);
+                ch.bodies[ji].m.push_back(L.mass);
+                ch.bodies[ji].c.push_back({cj.t[0], cj.t[1], cj.t[2]});
+                std::array<double, 9> Ia; std::memcpy(Ia.data(), If, sizeof If);
+                ch.bodies[ji].I.push_back(Ia);
+            }
+        }
+        int revolute_kids = 0;
+        for (const UrdfJoint *j : kids[ln]) {
+            Xf T; rpy_to_R(j->rpy, T.R); std::memcpy(T.t, j->xyz, sizeof j->xyz);
+            if (j->type == "fixed") {
+                const Xf Cc = compose(C, T);
+                if (ci >= 0) chains[ci].frames[ji].push_back({Cc.t[0], Cc.t[1], Cc.t[2]});
+                if (!visit(j->child, Cc, ci, ji)) return false;
+            } else if (j->type == "revolute" || j->type == "continuous") {
+                if (ci >= 0 && ++revolute_kids > 1) { err = "link " + ln + " carries two revolute joints: not a serial chain"; return false; }
+                Xf Ra;
+                if (!axis_rotation(j->axis, Ra.R)) { err = "joint " + j->name + " has a zero axis"; return false; }
+                int c2 = ci;
+                if (c2 < 0) { chains.emplace_back(); c2 = (int)chains.size() - 1; chains[c2].first_joint = j->name; }
+                else if (ji != (int)chains[c2].placement.size() - 1) { err = "joint " + j->name + " branches off the chain starting at " + chains[c2].first_joint; return false; }
+                ChainAcc &ch = chains[c2];
+                ch.placement.push_back(compose(compose(C, T), Ra));
+                ch.bodies.emplace_back(); ch.frames.emplace_back();
+                Xf Cn;                                  // child link frame in the new joint frame: the inverse of the axis rotation
+                for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Cn.R[3 * r + c] = Ra.R[3 * c + r];
+                if (!visit(j->child, Cn, c2, (int)ch.placement.size() - 1)) return false;
+            } else { err = "joint " + j->name + ": type '" + j->type + "' is not supported (fixed, revolute, continuous)"; return false; }
+        }
+        return true;
+    };
+    // (a chain must run through consecutive joint frames: the recursion above passes the frame index down, so a revolute joint
+    //  found below joint frame ji of chain ci extends that chain only if ji is its last frame)
+    if (!visit(root, Xf(), -1, -1)) { g_err = err; return MPCMP_EINVAL; }
+    if (chains.empty()) { g_err = "URDF holds no revolute joint"; return MPCMP_EINVAL; }
+    if ((int)chains.size() > max_chains) { g_err = "URDF holds more chains than the caller has room for"; return MPCMP_ETOOBIG; }
+    for (size_t ci = 0; ci < chains.size(); ci++) {
+        const ChainAcc &ch = chains[ci];
+        if (ch.placement.size() != 7) {
+            g_err = "the chain starting at joint " + ch.first_joint + " has " + std::to_string(ch.placement.size()) + " revolute joints; the kernels are built for 7";
+            return MPCMP_EINVAL;
+        }
+        mpcmp_model *m = models + ci;
+        std::memset(m, 0, sizeof *m);
+        for (int i = 0; i < 7; i++) {
+            std::memcpy(m->R0[i], ch.placement[i].R, sizeof m->R0[i]);
+            std::memcpy(m->p[i], ch.placement[i].t, sizeof m->p[i]);
+            const BodyAcc &b = ch.bodies[i];
+            if (b.m.empty()) continue;                                   // (a massless joint frame)
+            if (b.m.size() == 1) { m->mass[i] = b.m[0]; std::memcpy(m->com[i], b.c[0].data(), sizeof m->com[i]); std::memcpy(m->I[i], b.I[0].data(), sizeof m->I[i]); }
+            else lump(b, m->mass[i], m->com[i], m->I[i]);
+        }
+        // the two named frames of the reference behind the last joint (panda_link8, panda_tool: panda_arm.urdf:134-153): the first
+        // and the last fixed descendant of joint frame 7
+        const auto &fr = ch.frames[6];
+        if (!fr.empty()) { std::memcpy(m->link8, fr.front().data(), sizeof m->link8); std::memcpy(m->tool, fr.back().data(), sizeof m->tool); }
+        m->gravity[2] = -9.81;
+    }
+    *n_chains = (int)chains.size();
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_model_from_urdf(const char *path, mpcmp_model *m) {
+    if (!path || !m) return MPCMP_EINVAL;
+    mpcmp_model tmp[8];
+    int n = 0;
+    const int rc = mpcmp_models_from_urdf(path, 8, tmp, &n);
+    if (rc != MPCMP_OK) return rc;
+    if (n != 1) { g_err = "URDF holds " + std::to_string(n) + " chains: use mpcmp_models_from_urdf / mpcmp_create_multi"; return MPCMP_EINVAL; }
+    *m = tmp[0];
+    return MPCMP_OK;
+}
+
+// the rule of the six bound tables (of the configuration, and of every row of mpcmp_set_bounds): infinite ends are allowed (a row or box switched
+// off); NaN, lb > ub and an empty box (lb = +inf or ub = -inf) are not.  A general row narrower than 1e-4 takes rho_eq (oracle/ocp.c: u - l < 1e-4);
+// the assembly of k_qp and k_qp2 (num_seg 1, 2, 4) gives every general row the plain rho, so its factor would not be the matrix its iteration uses:
+// such rows are supported from num_seg 6 on (k_qp3, k_qp5)
+int mpcmp::validate_boxes(const mpcmp_bounds *t, std::string &err) {
+    auto box_ok = [](double lb, double ub) { return lb <= ub && lb < INFINITY && ub > -INFINITY; };
+    for (int i = 0; i < 14; i++) if (!box_ok(t->lbx[i], t->ubx[i])) { err = "lbx[" + std::to_string(i) + "] <= ubx[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 7; i++) if (!box_ok(t->lbu[i], t->ubu[i])) { err = "lbu[" + std::to_string(i) + "] <= ubu[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    for (int i = 0; i < 8; i++) if (!box_ok(t->lbg[i], t->ubg[i])) { err = "lbg[" + std::to_string(i) + "] <= ubg[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+int mpcmp::validate_general_rows(const mpcmp_bounds *t, int num_seg, std::string &err) {
+    if (num_seg <= 4)
+        for (int i = 0; i < 8; i++)
+            if (t->ubg[i] - t->lbg[i] < 1e-4) { err = "num_seg 1, 2 and 4: ubg[" + std::to_string(i) + "] - lbg[" + std::to_string(i) + "] must be >= 1e-4 (narrower general rows need num_seg 6 or 8)"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
+int mpcmp::validate(const mpcmp_config *c, std::string &err) {
+    if (c->num_seg != 1 && c->num_seg != 2 && c->num_seg != 4 && c->num_seg != 6 && c->num_seg != 8) { err = "num_seg must be 1, 2, 4, 6 or 8 on the HIP backend"; return MPCMP_EINVAL; }
+    if (c->sqp_iters < 1 || c->qp_iters < 1 || c->check_every < 1) { err = "iteration counts must be >= 1"; return MPCMP_EINVAL; }
+    if (c->ls_iters < 2 || c->ls_iters > 10) { err = "ls_iters must be in [2,10]"; return MPCMP_EINVAL; }
+    if (!(c->rho > 0) || !(c->sigma > 0) || !(c->alpha > 0 && c->alpha < 2)) { err = "rho, sigma > 0 and 0 < alpha < 2 required"; return MPCMP_EINVAL; }
+    if (c->qp_warm_start < -1 || c->qp_warm_start > 1 || c->carry_multipliers < -1 || c->carry_multipliers > 1) { err = "qp_warm_start and carry_multipliers are -1, 0 or 1"; return MPCMP_EINVAL; }
+    // (written as !(x >= 0) and the like, so that a NaN fails every test)
+    if (!(c->eps_abs >= 0) || !(c->eps_rel >= 0) || !(c->eps_target >= 0) || !(c->hess_reg >= 0)) { err = "eps_abs, eps_rel, eps_target and hess_reg must be >= 0"; return MPCMP_EINVAL; }
+    if (!(c->rho_eq_scale > 0)) { err = "rho_eq_scale must be > 0"; return MPCMP_EINVAL; }
+    if (!(c->ls_eta > 0 && c->ls_eta < 1) || !(c->ls_tau > 0 && c->ls_tau < 1)) { err = "ls_eta and ls_tau must lie in (0, 1)"; return MPCMP_EINVAL; }
+    if (c->quirk_dtau_dT != 0 && c->quirk_dtau_dT != 1) { err = "quirk_dtau_dT is 0 or 1"; return MPCMP_EINVAL; }
+    mpcmp_bounds t;
+    mpcmp_bounds_from_config(c, &t);
+    if (int rc = validate_boxes(&t, err)) return rc;
+    if (!(c->lbT <= c->ubT && c->lbT < INFINITY && c->ubT > -INFINITY)) { err = "lbT <= ubT required (no NaN, no empty box)"; return MPCMP_EINVAL; }
+    if (int rc = validate_general_rows(&t, c->num_seg, err)) return rc;
+    return MPCMP_OK;
+}
+
+// per-problem payloads (payload.hpp: the lumping, shared by the host and k_lump_payloads)
+int mpcmp::check_payload(const mpcmp_payload *p, std::string &err) {
+    if (!(p->mass >= 0.0) || !std::isfinite(p->mass)) { err = "payload mass must be finite and >= 0"; return MPCMP_EINVAL; }
+    for (int d = 0; d < 3; d++) if (!std::isfinite(p->com[d])) { err = "payload com must be finite"; return MPCMP_EINVAL; }
+    for (int q = 0; q < 9; q++) if (!std::isfinite(p->I[q])) { err = "payload inertia must be finite"; return MPCMP_EINVAL; }
+    for (int r = 0; r < 3; r++) {
+        if (p->I[4 * r] < 0.0) { err = "payload inertia: negative diagonal entry"; return MPCMP_EINVAL; }
+        for (int c = r + 1; c < 3; c++) if (p->I[3 * r + c] != p->I[3 * c + r]) { err = "payload inertia must be symmetric"; return MPCMP_EINVAL; }
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_model_add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out) {
+    if (!m || !p || !out) return MPCMP_EINVAL;
+    if (int rc = check_payload(p, g_err)) return rc;
+    add_payload(m, p, out);
+    return MPCMP_OK;
+}

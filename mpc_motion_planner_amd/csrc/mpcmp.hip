@@ -1,32 +1,22 @@
 // mpcmp.hip — C-ABI entry points (include/mpcmp.h) of the MI355X-native batched min-time MPC solver.
 // Host logic only orchestrates HIP launches; there is NO CPU fallback: without a HIP device every compute
 // entry point fails with MPCMP_ENODEVICE.
+// The kernels of the SQP chain and their launch code are solver.hip's (reached through solver.hpp), the entry points that touch no device are
+// model_host.cpp's; this unit holds the context's life cycle, the argument checks and staging of every entry point, and the leaf kernels.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <sstream>
 #include <string>
 #include <vector>
-#include <algorithm>
-#include <array>
-#include <functional>
-#include <map>
 
 #include "../../include/mpcmp.h"
-#include "solver_kernels.hpp"
-#include "qp_kernel_v2.hpp"
-#include "qp_kernel_v3.hpp"
-#ifdef MPCMP_WITH_QP4      /* the measured two-OCPs-per-CU alternative for N = 13 (does not pay): tools/experiments/, built only on request (-DMPCMP_WITH_QP4 -Itools/experiments) */
-#include "qp_kernel_v4.hpp"
-#endif
-#include "qp_kernel_v5.hpp"
-#include "multi_kernels.hpp"
-#include "kinematics_host.hpp"
+#include "context.hpp"
+#include "solver.hpp"
+#include "leaf_kernels.hpp"
 #include "jerk_device.hpp"
 #include "ik_device.hpp"
 #include "payload.hpp"
@@ -35,172 +25,7 @@
 #include "limits.hpp"
 #include "route.hpp"
 
-#ifdef MPCMP_SPLIT_N25
-// the N = 25 kernels live in qp3_n25.hip (built with another scheduler strategy: see there)
-namespace mpcmp {
-extern template __global__ void k_qp3f<8, 1>(mpcmp_config, WS, const Qp3Pat *, Xch, int, double *);
-extern template __global__ void k_qp3f<8, 2>(mpcmp_config, WS, const Qp3Pat *, Xch, int, double *);
-extern template __global__ void k_qp3<8, 1>(mpcmp_config, WS, const Qp3Pat *, Xch, int, const double *);
-extern template __global__ void k_qp3<8, 2>(mpcmp_config, WS, const Qp3Pat *, Xch, int, const double *);
-}  // namespace mpcmp
-#endif
-
-#ifdef MPCMP_SPLIT_N19
-// the N = 19 one-arm pair lives in qp5_n19.hip (its own scheduler strategy: see there)
-namespace mpcmp {
-extern template __global__ void k_qp3f<6, 1, 5>(mpcmp_config, WS, const Qp3Pat *, Xch, int, double *);
-extern template __global__ void k_qp5<6>(mpcmp_config, WS, const Qp3Pat *, Xch, int, const double *);
-}  // namespace mpcmp
-#endif
-
 using namespace mpcmp;
-
-struct mpcmp_ctx {
-    mpcmp_config cfg;
-    int device = 0, max_batch = 0, nseg = 0, narm = 1;
-    int N = 0, n = 0, meq = 0, m = 0, mn = 0;      // of the whole OCP (all arms): n = 21 N narm + 1, meq = 14 (N-1) narm, m = meq + 8 N narm
-    int nx = 14, nu = 7;                           // state / control entries per node: 14 narm, 7 narm
-    std::string err;
-    hipStream_t stream = nullptr;
-    hipStream_t stream_x[3] = {nullptr, nullptr, nullptr};   // further parts of a large solve (see solve_impl)
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-    // device buffers
-    mpcmp_model *d_model = nullptr;   // [narm]
-    mpcmp_model model;             // host copy: passed by value to the kernels that run the rigid-body recursions
-    // per-problem payloads (mpcmp_set_payloads): d_pmodel [max_batch][narm] = the context's models with row b's payloads lumped in, written by
-    // k_lump_payloads from d_pay [max_batch][narm]; both allocated by the first mpcmp_set_payloads.  pay_rows = 0: every problem reads d_model
-    mpcmp_model *d_pmodel = nullptr;
-    mpcmp_payload *d_pay = nullptr;
-    int pay_rows = 0;
-    // per-problem final-time windows (mpcmp_set_time_windows): d_tbox [max_batch][2] = (lbT, ubT), allocated by the first call; tw_rows = 0: cfg.lbT / ubT
-    double *d_tbox = nullptr;
-    int tw_rows = 0;
-    // per-problem bounds (mpcmp_set_bounds): d_bnd [max_batch] rows of the six bound tables, allocated by the first setter call; bnd_rows = 0: the
-    // tables of cfg for every problem
-    mpcmp_bounds *d_bnd = nullptr;
-    int bnd_rows = 0;
-    // the synchronised solve's buffers (mpcmp_solve_batch_synced*), [max_batch] each, allocated by its first call: group keys, member counts and
-    // times, the pass-2 mask (WS::retired of pass 2), the pass-1 status words, rows, T_new and stretched start guess
-    int *d_sg_count = nullptr, *d_sg_skip = nullptr, *d_sg_status = nullptr;
-    unsigned long long *d_sg_key = nullptr;
-    double *d_sg_T = nullptr, *d_sg_rows = nullptr, *d_sg_Tn = nullptr, *d_sg_wx = nullptr, *d_sg_wu = nullptr, *d_sg_wT = nullptr;
-    // clearance checks (mpcmp_clearance_batch*): the sphere tables of the arms (host copies; d_clr_sph [128] holds them arm-major, allocated by
-    // mpcmp_create), the obstacle sets d_clr_obs [clr_sets][clr_nobs] (allocated and grown by mpcmp_set_obstacles*), the selection's keys
-    // ([max_batch], allocated by its first call).  Read by no other entry point
-    mpcmp_sphere clr_sph[2][CLR_MAX_SPH];
-    int clr_nsph[2] = {0, 0};
-    ClrSphere *d_clr_sph = nullptr;
-    mpcmp_obstacle *d_clr_obs = nullptr;
-    size_t clr_obs_cap = 0;
-    int clr_sets = 0, clr_nobs = 0;
-    bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
-    unsigned long long *d_sel_key = nullptr;
-    // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
-    // start guess, and the legs' records when the caller wants none
-    double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;
-    mpcmp_info *d_rt_info = nullptr;
-    int *d_ext_of_int = nullptr, *d_entry_ptr = nullptr;
-    uint32_t *d_terms = nullptr;
-    WS ws{};
-    std::vector<void *> allocs;
-    // host-API staging (device side)
-    double *d_x0 = nullptr, *d_xf = nullptr, *d_wx = nullptr, *d_wu = nullptr, *d_wT = nullptr;
-    double *d_sx = nullptr, *d_su = nullptr, *d_sT = nullptr;
-    double *d_ax0 = nullptr, *d_axf = nullptr, *d_awx = nullptr, *d_awu = nullptr, *d_awT = nullptr;   // multi-arm warm start staging
-    mpcmp_info *d_info = nullptr;
-    uint32_t *d_stream = nullptr;
-    Qp2Streams streams{};
-    Qp3Pat *d_pat = nullptr;       // sparse K_JC pattern of k_qp3 (num_seg 6, 8), device copy
-    double *d_fac = nullptr;       // factor workspace of k_qp3f -> k_qp3: [max_batch][narm][Qp3::FAC]
-    Xch xch{nullptr};              // arm-to-arm exchange slots (multi-arm contexts)
-    // num_seg 4: second set of structure tables (structure3.hpp order, T bordered out) for the E-free QP kernels (k_qp3f + k_qp4 / k_qp3)
-    int *d3_ext_of_int = nullptr, *d3_entry_ptr = nullptr;
-    uint32_t *d3_terms = nullptr;
-    uint32_t *d_lane4 = nullptr;   // lane-constant table of k_qp4 (qp4_build_lanes)
-    int qp13 = 2;                  // QP kernel of num_seg 4: 2 = k_qp2, 3 = k_qp3f + k_qp3, 4 = k_qp3f + k_qp4 (env MPCMP_QP13)
-    int qp19 = 5;                  // QP kernel of num_seg 6, one arm: 5 = k_qp3f<6, 1, 5> + k_qp5 (factor resident in registers), 3 = k_qp3f + k_qp3 (env MPCMP_QP19)
-    // timing of the dominant kernel (k_qp)
-    struct EvPair { hipEvent_t e[2]; };
-    std::vector<EvPair> ev;          // at most MAX_EV pairs are ever created; launches beyond that are not timed until the
-    size_t ev_used = 0;              // pairs have been folded by mpcmp_kernel_timing
-    static constexpr size_t MAX_EV = 4096;
-    const char *loop_kernel = "";    // its name: KSel::loop_kernel_name, set with the kernels' LDS limits (prepare_kernels)
-    double qp_ms = 0.0;
-    int qp_launches = 0;
-    bool timing = false;             // off until mpcmp_kernel_timing is first called: a plain solve records no events
-    // growable device scratch of the host-pointer entry points (Stage: no hipMalloc per call once it is large enough)
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    // receding-horizon state (mpcmp_rh_*)
-    int rh_B = 0;
-    size_t lam_count = 0;          // doubles in ws.lam (max_batch x (m + n))
-    bool rh_first = true;
-    hipGraph_t rh_graph = nullptr;
-    hipGraphExec_t rh_exec = nullptr;
-    double rh_dt = 0.0;
-    int *d_retired = nullptr;                    // [max_batch] arrived instances of the receding-horizon loop (k_advance); not re-solved
-    unsigned long long *d_rh_count = nullptr;    // [2] re-solves executed, instances retired now (since mpcmp_rh_init)
-    hipEvent_t ev_upd[2] = {nullptr, nullptr};   // with_caller_stream: the caller's stream -> ctx->stream, and back
-    // diagnostics read from the environment ONCE PER CONTEXT, in mpcmp_create (never process-global state)
-    bool force_v1 = false, single_stream = false, debug_occ = false;
-    int parts_env = 0;                           // MPCMP_STREAMS: parts of a large batch (0 = automatic, see solve_impl)
-};
-
-// the sizes of one problem (all arms): the context's buffers are allocated with them (create_impl) and sliced by them (split)
-struct Dims { int N, n, meq, m, mn; };
-static constexpr Dims dims_of(int nseg, int narm) {
-    const int N = 3 * nseg + 1, n = 21 * N * narm + 1, meq = 14 * (N - 1) * narm, m = meq + 8 * N * narm;
-    return {N, n, meq, m, m + n};
-}
-// ... and that they are the sizes the kernels index with, for every instantiated discretisation
-template <int NSEG>
-static constexpr bool dims_match() { constexpr Dims d = dims_of(NSEG, 1); using D = Dim<NSEG>; return d.N == D::N && d.n == D::n && d.meq == D::meq && d.m == D::m && d.mn == D::mn; }
-template <int NSEG, int NARM>
-static constexpr bool dims_match_m() { constexpr Dims d = dims_of(NSEG, NARM); using D = DimM<NSEG, NARM>; return d.N == D::N && d.n == D::n && d.meq == NARM * D::meq && d.m == D::m && d.mn == D::mn; }
-static_assert(dims_match<1>() && dims_match<2>() && dims_match<4>() && dims_match<6>(), "Dim<NSEG> and the context's strides differ");
-static_assert(dims_match_m<8, 1>() && dims_match_m<6, 2>() && dims_match_m<8, 2>(), "DimM<NSEG, NARM> and the context's strides differ");
-
-// One solve as the launch code sees it: B problems, device pointers, the stream it is enqueued on, and everything that makes it differ from a plain
-// mpcmp_solve_batch_device.  A call is built where the solve is asked for and passed down by reference: the context holds no mode of a solve in flight
-struct SolveCall {
-    int B = 0;
-    const double *x0 = nullptr, *xf = nullptr;                      // [B][nx]
-    const double *wx = nullptr, *wu = nullptr, *wT = nullptr;       // start guess: all three or none (the built-in initialiser)
-    double *sx = nullptr, *su = nullptr, *sT = nullptr;
-    mpcmp_info *info = nullptr;
-    hipStream_t stream = nullptr;
-    int only_qp = 0, reguess = 0;
-    bool rh_step = false;              // a step of the receding-horizon driver: its defaults of the start flags, its retired instances, no per-problem time / bound rows
-    const double *tw_rows = nullptr;   // final-time rows that override the context's (the second pass of a synchronised solve)
-    const int *skip = nullptr;         // problems that are not re-solved (the second pass of a synchronised solve)
-    bool capturing = false;            // the stream is being captured into a graph: no timing events
-};
-
-// the configuration the kernels of a solve see: the two start flags resolved to 0 / 1.  0 = the library default (off for mpcmp_solve_batch, ON for
-// the receding-horizon driver), 1 = on, -1 = off everywhere (include/mpcmp.h)
-static mpcmp_config run_config(const mpcmp_ctx *ctx, const SolveCall &c) {
-    mpcmp_config cfg = ctx->cfg;
-    cfg.qp_warm_start = c.rh_step ? (cfg.qp_warm_start >= 0) : (cfg.qp_warm_start > 0);
-    cfg.carry_multipliers = c.rh_step ? (cfg.carry_multipliers >= 0) : (cfg.carry_multipliers > 0);
-    return cfg;
-}
-
-static thread_local std::string g_err;
-
-// the models the dynamics of a call read: the context's [narm], or the per-problem copies [rows][narm] (problem b, arm a: base + b * stride + a)
-static const mpcmp_model *run_models(const mpcmp_ctx *ctx, int *stride) {
-    *stride = ctx->pay_rows > 0 ? ctx->narm : 0;
-    return ctx->pay_rows > 0 ? ctx->d_pmodel : ctx->d_model;
-}
-// the final-time rows a solve reads (WS::tbox): the call's own, the context's, or none (cfg.lbT / ubT; always none for the receding-horizon driver)
-static const double *run_rows(const mpcmp_ctx *ctx, const SolveCall &c) {
-    if (c.tw_rows) return c.tw_rows;
-    return (ctx->tw_rows > 0 && !c.rh_step) ? ctx->d_tbox : nullptr;
-}
-// the bound rows a solve reads (WS::bnd): the context's, or none (the tables of cfg; always none for the receding-horizon driver)
-static const mpcmp_bounds *run_bounds(const mpcmp_ctx *ctx, const SolveCall &c) { return (ctx->bnd_rows > 0 && !c.rh_step) ? ctx->d_bnd : nullptr; }
-// the problems a solve leaves alone (WS::retired): the arrived instances of the receding-horizon loop, or the call's own mask
-static const int *run_retired(const mpcmp_ctx *ctx, const SolveCall &c) { return c.rh_step ? ctx->d_retired : c.skip; }
 
 // the three per-problem row tables of a context: where the count of rows in force lies, and the words of their messages
 struct RowTable { int mpcmp_ctx::*rows; const char *what, *setter, *usage; bool refused_in_loop; };
@@ -226,474 +51,8 @@ static int warm_all_or_none(mpcmp_ctx *ctx, const double *wx, const double *wu, 
     return MPCMP_OK;
 }
 
-#define HIPCHK(ctx, call)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            std::ostringstream os_;                                                           \
-            os_ << #call << " failed: " << hipGetErrorString(e_) << " (" << __FILE__ << ":" << __LINE__ << ")"; \
-            if (ctx) (ctx)->err = os_.str();                                                  \
-            g_err = os_.str();                                                                \
-            return MPCMP_ERUNTIME;                                                            \
-        }                                                                                     \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// configuration helpers (host only)
-extern "C" const char *mpcmp_version(void) { return "mpcmp 0.1 (gfx950)"; }
-
-extern "C" int mpcmp_num_nodes(int num_seg) { return 3 * num_seg + 1; }
-
-extern "C" int mpcmp_time_nodes(int num_seg, double *tau) {
-    if (num_seg < 1 || !tau) return MPCMP_EINVAL;
-    static const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    for (int s = 0; s < num_seg; s++)
-        for (int j = 0; j < 4; j++) tau[3 * s + j] = (s + 0.5 * (xi[j] + 1.0)) / num_seg;
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_default_limits(double *qmin, double *qmax, double *vmax, double *amax, double *jmax,
-                                    double *taumax) {
-    // Franka Emika limits as tabulated by the reference, robot_utils/pandaWrapper.hpp:29-34
-    static const double t[6][7] = {{-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973},
-                                   {2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973},
-                                   {2.1750, 2.1750, 2.1750, 2.1750, 2.6100, 2.6100, 2.6100},
-                                   {15.0, 7.5, 10.0, 12.5, 15.0, 20.0, 20.0},
-                                   {7500, 3750, 5000, 6250, 7500, 10000, 10000},
-                                   {87, 87, 87, 87, 12, 12, 12}};
-    double *o[6] = {qmin, qmax, vmax, amax, jmax, taumax};
-    for (int k = 0; k < 6; k++)
-        if (o[k]) std::memcpy(o[k], t[k], sizeof t[k]);
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_set_min_height(mpcmp_config *c, double min_height) {
-    if (!c) return MPCMP_EINVAL;
-    c->lbg[7] = min_height;
-    c->ubg[7] = INFINITY;
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_set_margins(mpcmp_config *c, double mp, double mv, double ma, double mt) {
-    if (!c) return MPCMP_EINVAL;
-    double qmin[7], qmax[7], vmax[7], amax[7], tmax[7];
-    mpcmp_default_limits(qmin, qmax, vmax, amax, nullptr, tmax);
-    for (int j = 0; j < 7; j++) {
-        const double s = (1.0 - mp) * (qmax[j] - qmin[j]) / 2.0;   // motionPlanner.cpp:66
-        c->lbx[j] = qmin[j] + s; c->ubx[j] = qmax[j] - s;
-        c->lbx[7 + j] = -mv * vmax[j]; c->ubx[7 + j] = mv * vmax[j];
-        c->lbu[j] = -ma * amax[j]; c->ubu[j] = ma * amax[j];
-        c->lbg[j] = -mt * tmax[j]; c->ubg[j] = mt * tmax[j];
-    }
-    c->lbT = 0.0; c->ubT = 10.0;                                  // motionPlanner.cpp:77-78
-    return mpcmp_set_min_height(c, 0.05);                         // pandaWrapper.hpp:40
-}
-
-extern "C" int mpcmp_default_config(mpcmp_config *c, int num_seg, int sqp_iters) {
-    if (!c || num_seg < 1) return MPCMP_EINVAL;
-    std::memset(c, 0, sizeof *c);
-    c->num_seg = num_seg; c->sqp_iters = sqp_iters;
-    c->qp_iters = 700; c->ls_iters = 10; c->check_every = 25; c->quirk_dtau_dT = 1;
-    c->eps_abs = 1e-3; c->eps_rel = 1e-3;
-    c->rho = 0.02; c->sigma = 1e-6; c->alpha = 1.4; c->rho_eq_scale = 1e3;      // fitted to the reference's stored solve: tools/polympc_param_fit.py
-    c->ls_eta = 0.25; c->ls_tau = 0.5; c->hess_reg = 1e-3; c->eps_target = 1e-2;
-    return mpcmp_set_margins(c, 1.0, 1.0, 1.0, 1.0);              // motionPlanner.cpp:24
-}
-
-// per-problem bounds: a row is the six tables of the configuration, which lie there in the row's order without a gap
-static_assert(sizeof(mpcmp_bounds) == 58 * sizeof(double), "mpcmp_bounds: 58 doubles");
-static_assert(offsetof(mpcmp_config, ubg) + sizeof(double[8]) - offsetof(mpcmp_config, lbx) == sizeof(mpcmp_bounds) &&
-              offsetof(mpcmp_config, ubx) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubx) &&
-              offsetof(mpcmp_config, lbu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbu) &&
-              offsetof(mpcmp_config, ubu) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubu) &&
-              offsetof(mpcmp_config, lbg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, lbg) &&
-              offsetof(mpcmp_config, ubg) - offsetof(mpcmp_config, lbx) == offsetof(mpcmp_bounds, ubg),
-              "mpcmp_bounds has the layout of the six tables of mpcmp_config");
-extern "C" int mpcmp_bounds_from_config(const mpcmp_config *c, mpcmp_bounds *out) {
-    if (!c || !out) return MPCMP_EINVAL;
-    std::memcpy(out, c->lbx, sizeof *out);
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_bounds_from_margins(double mp, double mv, double ma, double mt, double min_height, mpcmp_bounds *out) {
-    if (!out) return MPCMP_EINVAL;
-    mpcmp_config c;
-    if (int rc = mpcmp_default_config(&c, 4, 1)) return rc;      // (the tables do not depend on num_seg or sqp_iters)
-    if (int rc = mpcmp_set_margins(&c, mp, mv, ma, mt)) return rc;
-    if (int rc = mpcmp_set_min_height(&c, min_height)) return rc;
-    return mpcmp_bounds_from_config(&c, out);
-}
-
-static void rpy_to_R(const double rpy[3], double R[9]) {
-    const double cr = std::cos(rpy[0]), sr = std::sin(rpy[0]), cp = std::cos(rpy[1]), sp = std::sin(rpy[1]),
-                 cy = std::cos(rpy[2]), sy = std::sin(rpy[2]);
-    // R = Rz(yaw) Ry(pitch) Rx(roll)
-    R[0] = cy * cp; R[1] = cy * sp * sr - sy * cr; R[2] = cy * sp * cr + sy * sr;
-    R[3] = sy * cp; R[4] = sy * sp * sr + cy * cr; R[5] = sy * sp * cr - cy * sr;
-    R[6] = -sp;     R[7] = cp * sr;                R[8] = cp * cr;
-}
-
-// ---- scenario helpers (host): robot_utils/pandaWrapper.cpp:14-107 ----
-extern "C" int mpcmp_tool_jacobian(const mpcmp_model *model, const double *q, double *J, double *p, double *R) {
-    if (!model || !q || !J) return MPCMP_EINVAL;
-    double pp[3], RR[9];
-    mpcmp_host::tool_jacobian(*model, q, J, pp, RR);
-    if (p) for (int k = 0; k < 3; k++) p[k] = pp[k];
-    if (R) for (int k = 0; k < 9; k++) R[k] = RR[k];
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_forward_velocities(const mpcmp_model *model, const double *q, const double *qd, double *out) {
-    if (!model || !q || !qd || !out) return MPCMP_EINVAL;
-    double J[42], p[3], R[9];
-    mpcmp_host::tool_jacobian(*model, q, J, p, R);
-    for (int r = 0; r < 6; r++) { double s = 0; for (int k = 0; k < 7; k++) s += J[r * 7 + k] * qd[k]; out[r] = s; }
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_inverse_velocities(const mpcmp_model *model, const double *q, const double *lin, const double *ang, double *qd) {
-    if (!model || !q || !lin || !ang || !qd) return MPCMP_EINVAL;
-    const double b[6] = {lin[0], lin[1], lin[2], ang[0], ang[1], ang[2]};
-    return mpcmp_host::inverse_velocities(*model, q, b, qd) ? MPCMP_OK : MPCMP_ERUNTIME;
-}
-
-// the loop of PandaWrapper::inverse_kinematic around the DLS step the batched kernel shares (kinematics_host.hpp)
-extern "C" int mpcmp_inverse_kinematics(const mpcmp_model *model, const double *Rdes, const double *pdes, const double *q_init,
-                                        double *q, int *iters) {
-    if (!model || !Rdes || !pdes || !q) return MPCMP_EINVAL;
-    for (int k = 0; k < 7; k++) q[k] = q_init ? q_init[k] : 0.0;
-    for (int it = 0;; it++) {
-        double en;
-        const int r = mpcmp_host::ik_dls_step(*model, Rdes, pdes, q, it, &en);
-        if (iters) *iters = it;
-        if (r == mpcmp_host::IK_CONVERGED) return MPCMP_OK;
-        if (r == mpcmp_host::IK_CAPPED) return 1;
-        if (r == mpcmp_host::IK_NOT_PD) return MPCMP_ERUNTIME;
-    }
-}
-
-extern "C" int mpcmp_default_model(mpcmp_model *m) {
-    if (!m) return MPCMP_EINVAL;
-    // Kinematic / inertial parameters of the Panda arm (robot_utils/panda-model/panda_arm.urdf)
-    static const double rpy[7][3] = {{0, 0, 0}, {-1.57079632679, 0, 0}, {1.57079632679, 0, 0}, {1.57079632679, 0, 0},
-                                     {-1.57079632679, 0, 0}, {1.57079632679, 0, 0}, {1.57079632679, 0, 0}};
-    static const double xyz[7][3] = {{0, 0, 0.333}, {0, 0, 0}, {0, -0.316, 0}, {0.0825, 0, 0},
-                                     {-0.0825, 0.384, 0}, {0, 0, 0}, {0.088, 0, 0}};
-    static const double mass[7] = {4.970684, 0.646926, 3.228604, 3.587895, 1.225946, 1.666555, 0.735522};
-    static const double com[7][3] = {{3.875e-03, 2.081e-03, -0.1750}, {-3.141e-03, -2.872e-02, 3.495e-03},
-                                     {2.7518e-02, 3.9252e-02, -6.6502e-02}, {-5.317e-02, 1.04419e-01, 2.7454e-02},
-                                     {-1.1953e-02, 4.1065e-02, -3.8437e-02}, {6.0149e-02, -1.4117e-02, -1.0517e-02},
-                                     {1.0517e-02, -4.252e-03, 6.1597e-02}};
-    static const double in6[7][6] = {{7.0337e-01, -1.3900e-04, 6.7720e-03, 7.0661e-01, 1.9169e-02, 9.1170e-03},
-                                     {7.9620e-03, -3.9250e-03, 1.0254e-02, 2.8110e-02, 7.0400e-04, 2.5995e-02},
-                                     {3.7242e-02, -4.7610e-03, -1.1396e-02, 3.6155e-02, -1.2805e-02, 1.0830e-02},
-                                     {2.5853e-02, 7.7960e-03, -1.3320e-03, 1.9552e-02, 8.6410e-03, 2.8323e-02},
-                                     {3.5549e-02, -2.1170e-03, -4.0370e-03, 2.9474e-02, 2.2900e-04, 8.6270e-03},
-                                     {1.9640e-03, 1.0900e-04, -1.1580e-03, 4.3540e-03, 3.4100e-04, 5.4330e-03},
-                                     {1.2516e-02, -4.2800e-04, -1.1960e-03, 1.0027e-02, -7.4100e-04, 4.8150e-03}};
-    std::memset(m, 0, sizeof *m);
-    for (int i = 0; i < 7; i++) {
-        rpy_to_R(rpy[i], m->R0[i]);
-        std::memcpy(m->p[i], xyz[i], sizeof xyz[i]);
-        m->mass[i] = mass[i];
-        std::memcpy(m->com[i], com[i], sizeof com[i]);
-        const double *I = in6[i];
-        const double F[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
-        std::memcpy(m->I[i], F, sizeof F);
-    }
-    m->link8[2] = 0.107;
-    m->tool[2] = 0.107 + 0.15;
-    m->gravity[2] = -9.81;
-    // fixed children of link7: link8 (m=0, I=1e-3 Id) and panda_tool (m=1, I=1e-3 Id) are lumped into body 7
-    const double mk[3] = {mass[6], 0.0, 1.0};
-    const double ck[3][3] = {{com[6][0], com[6][1], com[6][2]}, {0, 0, 0.107}, {0, 0, 0.257}};
-    double Ik[3][9];
-    std::memcpy(Ik[0], m->I[6], sizeof Ik[0]);
-    for (int k = 1; k < 3; k++) { std::memset(Ik[k], 0, sizeof Ik[k]); Ik[k][0] = Ik[k][4] = Ik[k][8] = 1e-3; }
-    lump_last_body(m, 3, mk, ck, Ik);
-    return MPCMP_OK;
-}
-
-// ---- URDF reader: any number of serial 7-joint chains on one base (robot_utils/pandaWrapper.cpp:3-12 takes any URDF) --------
-// What the kernels need of a robot is, per chain, seven revolute joints about the z axis of their own frame, the placement of
-// each joint in its parent joint's frame, one rigid body per joint frame and the two named frames behind the last joint.  A URDF
-// is brought into that form here: fixed joints (before, between and behind the revolute joints, rotated or not) are folded into
-// the next joint's placement and their links lumped into the body of the joint frame they hang on; a chain's base placement is
-// folded into its first joint; rotated inertial frames rotate the inertia tensor; a joint axis other than +z is absorbed by a
-// constant rotation of the child frame.
-namespace {
-struct UrdfLink { double mass = 0, com[3] = {0, 0, 0}, I[9] = {0}, irpy[3] = {0, 0, 0}; bool has_inertial = false; };
-struct UrdfJoint { std::string name, type, parent, child; double xyz[3] = {0, 0, 0}, rpy[3] = {0, 0, 0}, axis[3] = {0, 0, 1}; };
-struct Xf { double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}; };       // rigid transform, parent <- child
-
-static std::string attr(const std::string &tag, const std::string &key) {
-    size_t p = 0;
-    while ((p = tag.find(key + "=", p)) != std::string::npos) {
-        if (p > 0 && (isalnum((unsigned char)tag[p - 1]) || tag[p - 1] == '_')) { p += key.size(); continue; }
-        const size_t q0 = p + key.size() + 1;
-        const char quote = tag[q0];
-        const size_t q1 = tag.find(quote, q0 + 1);
-        return tag.substr(q0 + 1, q1 - q0 - 1);
-    }
-    return "";
-}
-static void parse3(const std::string &s, double *o) {
-    if (s.empty()) return;
-    std::istringstream is(s);
-    is >> o[0] >> o[1] >> o[2];
-}
-static bool is_identity(const double *R) {
-    return R[0] == 1 && R[4] == 1 && R[8] == 1 && R[1] == 0 && R[2] == 0 && R[3] == 0 && R[5] == 0 && R[6] == 0 && R[7] == 0;
-}
-static void matmul3(const double *A, const double *B, double *Cm) {
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Cm[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
-}
-// (identity factors are skipped, so that a URDF without rotated fixed joints gives bit-for-bit the numbers it holds)
-static Xf compose(const Xf &a, const Xf &b) {
-    Xf o;
-    if (is_identity(a.R)) { std::memcpy(o.R, b.R, sizeof o.R); for (int d = 0; d < 3; d++) o.t[d] = a.t[d] + b.t[d]; }
-    else {
-        if (is_identity(b.R)) std::memcpy(o.R, a.R, sizeof o.R); else matmul3(a.R, b.R, o.R);
-        for (int d = 0; d < 3; d++) o.t[d] = a.t[d] + (a.R[3 * d] * b.t[0] + a.R[3 * d + 1] * b.t[1] + a.R[3 * d + 2] * b.t[2]);
-    }
-    return o;
-}
-static void rotate_inertia(const double *R, const double *I, double *o) {          // R I R^T
-    if (is_identity(R)) { std::memcpy(o, I, 9 * sizeof(double)); return; }
-    double RI[9], Rt[9];
-    matmul3(R, I, RI);
-    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * c + r];
-    matmul3(RI, Rt, o);
-}
-// rotation that takes +z to the (normalised) axis a
-static bool axis_rotation(const double *a_in, double *R) {
-    const double n = std::sqrt(a_in[0] * a_in[0] + a_in[1] * a_in[1] + a_in[2] * a_in[2]);
-    if (!(n > 0)) return false;
-    const double a[3] = {a_in[0] / n, a_in[1] / n, a_in[2] / n};
-    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (a[0] == 0 && a[1] == 0 && a[2] == 1) { std::memcpy(R, I3, sizeof I3); return true; }
-    if (a[0] == 0 && a[1] == 0 && a[2] == -1) { const double F[9] = {1, 0, 0, 0, -1, 0, 0, 0, -1}; std::memcpy(R, F, sizeof F); return true; }
-    // Rodrigues: axis v = z x a, sin = |v|, cos = a_z
-    const double v[3] = {-a[1], a[0], 0.0}, c = a[2], k = 1.0 / (1.0 + c);
-    const double V[9] = {0, -v[2], v[1], v[2], 0, -v[0], -v[1], v[0], 0};
-    double V2[9];
-    matmul3(V, V, V2);
-    for (int i = 0; i < 9; i++) R[i] = I3[i] + V[i] + k * V2[i];
-    return true;
-}
-struct BodyAcc { std::vector<double> m; std::vector<std::array<double, 3>> c; std::vector<std::array<double, 9>> I; };
-struct ChainAcc {
-    std::string first_joint;
-    std::vector<Xf> placement;                      // joint i in joint i - 1 (the first: in the base / world frame)
-    std::vector<BodyAcc> bodies;                    // per joint frame
-    std::vector<std::vector<std::array<double, 3>>> frames;     // fixed descendants of each joint frame (origins, in order of discovery)
-};
-// same arithmetic, in the same order, as lump_last_body for three bodies
-static void lump(const BodyAcc &b, double &M, double *c, double *It) {
-    const size_t n = b.m.size();
-    M = b.m[0];
-    for (size_t k = 1; k < n; k++) M = M + b.m[k];
-    c[0] = c[1] = c[2] = 0;
-    for (size_t k = 0; k < n; k++) for (int d = 0; d < 3; d++) c[d] += b.m[k] * b.c[k][d];
-    for (int d = 0; d < 3; d++) c[d] /= M;
-    for (int i = 0; i < 9; i++) It[i] = 0;
-    for (size_t k = 0; k < n; k++) {
-        const double d[3] = {b.c[k][0] - c[0], b.c[k][1] - c[1], b.c[k][2] - c[2]};
-        const double d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-        for (int r = 0; r < 3; r++) for (int s2 = 0; s2 < 3; s2++)
-            It[3 * r + s2] += b.I[k][3 * r + s2] + b.m[k] * ((r == s2 ? d2 : 0.0) - d[r] * d[s2]);
-    }
-}
-}  // namespace
-
-extern "C" int mpcmp_models_from_urdf(const char *path, int max_chains, mpcmp_model *models, int *n_chains) {
-    if (!path || !models || !n_chains || max_chains < 1) return MPCMP_EINVAL;
-    *n_chains = 0;
-    std::ifstream f(path);
-    if (!f) { g_err = std::string("cannot open URDF ") + path; return MPCMP_EINVAL; }
-    std::stringstream ss; ss << f.rdbuf();
-    const std::string xml = ss.str();
-    std::map<std::string, UrdfLink> links;
-    std::vector<std::string> link_order;
-    std::vector<UrdfJoint> joints;
-    size_t pos = 0;
-    std::string cur_link; UrdfJoint cur_joint; bool in_link = false, in_joint = false, in_inertial = false;
-    while ((pos = xml.find('<', pos)) != std::string::npos) {
-        if (xml.compare(pos, 4, "<!--") == 0) { const size_t e = xml.find("-->", pos); if (e == std::string::npos) break; pos = e + 3; continue; }
-        const size_t end = xml.find('>', pos);
-        if (end == std::string::npos) break;
-        const std::string tag = xml.substr(pos + 1, end - pos - 1);
-        pos = end + 1;
-        if (tag.empty() || tag[0] == '?' || tag[0] == '!') continue;
-        std::istringstream ts(tag); std::string name; ts >> name;
-        if (!name.empty() && name.back() == '/') name.pop_back();
-        if (name == "link") { cur_link = attr(tag, "name"); if (!links.count(cur_link)) link_order.push_back(cur_link); links[cur_link]; in_link = tag.back() != '/'; }
-        else if (name == "/link") in_link = false;
-        else if (name == "joint" && tag.find("type=") != std::string::npos) {
-            cur_joint = UrdfJoint(); cur_joint.type = attr(tag, "type"); cur_joint.name = attr(tag, "name"); in_joint = true;
-        } else if (name == "/joint") { if (in_joint) joints.push_back(cur_joint); in_joint = false; }
-        else if (name == "inertial") in_inertial = true;
-        else if (name == "/inertial") in_inertial = false;
-        else if (name == "origin") {
-            if (in_joint) { parse3(attr(tag, "xyz"), cur_joint.xyz); parse3(attr(tag, "rpy"), cur_joint.rpy); }
-            else if (in_link && in_inertial) { parse3(attr(tag, "xyz"), links[cur_link].com); parse3(attr(tag, "rpy"), links[cur_link].irpy); }
-        } else if (name == "mass" && in_link && in_inertial) { links[cur_link].mass = atof(attr(tag, "value").c_str()); links[cur_link].has_inertial = true; }
-        else if (name == "inertia" && in_link && in_inertial) {
-            UrdfLink &L = links[cur_link];
-            const double xx = atof(attr(tag, "ixx").c_str()), xy = atof(attr(tag, "ixy").c_str()), xz = atof(attr(tag, "ixz").c_str()),
-                         yy = atof(attr(tag, "iyy").c_str()), yz = atof(attr(tag, "iyz").c_str()), zz = atof(attr(tag, "izz").c_str());
-            const double F[9] = {xx, xy, xz, xy, yy, yz, xz, yz, zz};
-            std::memcpy(L.I, F, sizeof F);
-        } else if (name == "parent" && in_joint) cur_joint.parent = attr(tag, "link");
-        else if (name == "child" && in_joint) cur_joint.child = attr(tag, "link");
-        else if (name == "axis" && in_joint) parse3(attr(tag, "xyz"), cur_joint.axis);
-    }
-    if (links.empty()) { g_err = "URDF holds no links"; return MPCMP_EINVAL; }
-    // the kinematic tree
-    std::map<std::string, std::vector<const UrdfJoint *>> kids;
-    std::map<std::string, int> is_child;
-    for (auto &j : joints) {
-        if (!links.count(j.parent) || !links.count(j.child)) { g_err = "joint " + j.name + " names an unknown link"; return MPCMP_EINVAL; }
-        kids[j.parent].push_back(&j);
-        if (is_child[j.child]++) { g_err = "link " + j.child + " has two parent joints"; return MPCMP_EINVAL; }
-    }
-    std::string root;
-    for (auto &ln : link_order) if (!is_child.count(ln)) { if (!root.empty()) { g_err = "URDF has more than one root link"; return MPCMP_EINVAL; } root = ln; }
-    if (root.empty()) { g_err = "URDF has no root link (cycle)"; return MPCMP_EINVAL; }
-    std::vector<ChainAcc> chains;
-    std::string err;
-    // depth first in file order; C: link frame in the current model frame (the world before a chain starts, then the joint frame)
-    std::function<bool(const std::string &, const Xf &, int, int)> visit = [&](const std::string &ln, const Xf &C, int ci, int ji) -> bool {
-        const UrdfLink &L = links[ln];
-        if (ci >= 0) {
-            ChainAcc &ch = chains[ci];
-            if (L.has_inertial) {
-                double Rin[9], Il[9], If[9];
-                rpy_to_R(L.irpy, Rin);
-                rotate_inertia(Rin, L.I, Il);          // inertial frame -> link axes
-                rotate_inertia(C.R, Il, If);           // link axes -> joint frame axes
-                Xf com; std::memcpy(com.t, L.com, sizeof L.com);
-                const Xf cj = compose(C, com);
-                ch.bodies[ji].m.push_back(L.mass);
-                ch.bodies[ji].c.push_back({cj.t[0], cj.t[1], cj.t[2]});
-                std::array<double, 9> Ia; std::memcpy(Ia.data(), If, sizeof If);
-                ch.bodies[ji].I.push_back(Ia);
-            }
-        }
-        int revolute_kids = 0;
-        for (const UrdfJoint *j : kids[ln]) {
-            Xf T; rpy_to_R(j->rpy, T.R); std::memcpy(T.t, j->xyz, sizeof j->xyz);
-            if (j->type == "fixed") {
-                const Xf Cc = compose(C, T);
-                if (ci >= 0) chains[ci].frames[ji].push_back({Cc.t[0], Cc.t[1], Cc.t[2]});
-                if (!visit(j->child, Cc, ci, ji)) return false;
-            } else if (j->type == "revolute" || j->type == "continuous") {
-                if (ci >= 0 && ++revolute_kids > 1) { err = "link " + ln + " carries two revolute joints: not a serial chain"; return false; }
-                Xf Ra;
-                if (!axis_rotation(j->axis, Ra.R)) { err = "joint " + j->name + " has a zero axis"; return false; }
-                int c2 = ci;
-                if (c2 < 0) { chains.emplace_back(); c2 = (int)chains.size() - 1; chains[c2].first_joint = j->name; }
-                else if (ji != (int)chains[c2].placement.size() - 1) { err = "joint " + j->name + " branches off the chain starting at " + chains[c2].first_joint; return false; }
-                ChainAcc &ch = chains[c2];
-                ch.placement.push_back(compose(compose(C, T), Ra));
-                ch.bodies.emplace_back(); ch.frames.emplace_back();
-                Xf Cn;                                  // child link frame in the new joint frame: the inverse of the axis rotation
-                for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Cn.R[3 * r + c] = Ra.R[3 * c + r];
-                if (!visit(j->child, Cn, c2, (int)ch.placement.size() - 1)) return false;
-            } else { err = "joint " + j->name + ": type '" + j->type + "' is not supported (fixed, revolute, continuous)"; return false; }
-        }
-        return true;
-    };
-    // (a chain must run through consecutive joint frames: the recursion above passes the frame index down, so a revolute joint
-    //  found below joint frame ji of chain ci extends that chain only if ji is its last frame)
-    if (!visit(root, Xf(), -1, -1)) { g_err = err; return MPCMP_EINVAL; }
-    if (chains.empty()) { g_err = "URDF holds no revolute joint"; return MPCMP_EINVAL; }
-    if ((int)chains.size() > max_chains) { g_err = "URDF holds more chains than the caller has room for"; return MPCMP_ETOOBIG; }
-    for (size_t ci = 0; ci < chains.size(); ci++) {
-        const ChainAcc &ch = chains[ci];
-        if (ch.placement.size() != 7) {
-            g_err = "the chain starting at joint " + ch.first_joint + " has " + std::to_string(ch.placement.size()) + " revolute joints; the kernels are built for 7";
-            return MPCMP_EINVAL;
-        }
-        mpcmp_model *m = models + ci;
-        std::memset(m, 0, sizeof *m);
-        for (int i = 0; i < 7; i++) {
-            std::memcpy(m->R0[i], ch.placement[i].R, sizeof m->R0[i]);
-            std::memcpy(m->p[i], ch.placement[i].t, sizeof m->p[i]);
-            const BodyAcc &b = ch.bodies[i];
-            if (b.m.empty()) continue;                                   // (a massless joint frame)
-            if (b.m.size() == 1) { m->mass[i] = b.m[0]; std::memcpy(m->com[i], b.c[0].data(), sizeof m->com[i]); std::memcpy(m->I[i], b.I[0].data(), sizeof m->I[i]); }
-            else lump(b, m->mass[i], m->com[i], m->I[i]);
-        }
-        // the two named frames of the reference behind the last joint (panda_link8, panda_tool: panda_arm.urdf:134-153): the first
-        // and the last fixed descendant of joint frame 7
-        const auto &fr = ch.frames[6];
-        if (!fr.empty()) { std::memcpy(m->link8, fr.front().data(), sizeof m->link8); std::memcpy(m->tool, fr.back().data(), sizeof m->tool); }
-        m->gravity[2] = -9.81;
-    }
-    *n_chains = (int)chains.size();
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_model_from_urdf(const char *path, mpcmp_model *m) {
-    if (!path || !m) return MPCMP_EINVAL;
-    mpcmp_model tmp[8];
-    int n = 0;
-    const int rc = mpcmp_models_from_urdf(path, 8, tmp, &n);
-    if (rc != MPCMP_OK) return rc;
-    if (n != 1) { g_err = "URDF holds " + std::to_string(n) + " chains: use mpcmp_models_from_urdf / mpcmp_create_multi"; return MPCMP_EINVAL; }
-    *m = tmp[0];
-    return MPCMP_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // context
-template <typename T>
-static int dalloc(mpcmp_ctx *ctx, T **p, size_t count) {
-    void *q = nullptr;
-    HIPCHK(ctx, hipMalloc(&q, count * sizeof(T)));
-    ctx->allocs.push_back(q);
-    *p = (T *)q;
-    return MPCMP_OK;
-}
-
-// the rule of the six bound tables (of the configuration, and of every row of mpcmp_set_bounds): infinite ends are allowed (a row or box switched
-// off); NaN, lb > ub and an empty box (lb = +inf or ub = -inf) are not.  A general row narrower than 1e-4 takes rho_eq (oracle/ocp.c: u - l < 1e-4);
-// the assembly of k_qp and k_qp2 (num_seg 1, 2, 4) gives every general row the plain rho, so its factor would not be the matrix its iteration uses:
-// such rows are supported from num_seg 6 on (k_qp3, k_qp5)
-static int validate_boxes(const mpcmp_bounds *t, std::string &err) {
-    auto box_ok = [](double lb, double ub) { return lb <= ub && lb < INFINITY && ub > -INFINITY; };
-    for (int i = 0; i < 14; i++) if (!box_ok(t->lbx[i], t->ubx[i])) { err = "lbx[" + std::to_string(i) + "] <= ubx[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    for (int i = 0; i < 7; i++) if (!box_ok(t->lbu[i], t->ubu[i])) { err = "lbu[" + std::to_string(i) + "] <= ubu[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    for (int i = 0; i < 8; i++) if (!box_ok(t->lbg[i], t->ubg[i])) { err = "lbg[" + std::to_string(i) + "] <= ubg[" + std::to_string(i) + "] required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    return MPCMP_OK;
-}
-static int validate_general_rows(const mpcmp_bounds *t, int num_seg, std::string &err) {
-    if (num_seg <= 4)
-        for (int i = 0; i < 8; i++)
-            if (t->ubg[i] - t->lbg[i] < 1e-4) { err = "num_seg 1, 2 and 4: ubg[" + std::to_string(i) + "] - lbg[" + std::to_string(i) + "] must be >= 1e-4 (narrower general rows need num_seg 6 or 8)"; return MPCMP_EINVAL; }
-    return MPCMP_OK;
-}
-
-static int validate(const mpcmp_config *c, std::string &err) {
-    if (c->num_seg != 1 && c->num_seg != 2 && c->num_seg != 4 && c->num_seg != 6 && c->num_seg != 8) { err = "num_seg must be 1, 2, 4, 6 or 8 on the HIP backend"; return MPCMP_EINVAL; }
-    if (c->sqp_iters < 1 || c->qp_iters < 1 || c->check_every < 1) { err = "iteration counts must be >= 1"; return MPCMP_EINVAL; }
-    if (c->ls_iters < 2 || c->ls_iters > 10) { err = "ls_iters must be in [2,10]"; return MPCMP_EINVAL; }
-    if (!(c->rho > 0) || !(c->sigma > 0) || !(c->alpha > 0 && c->alpha < 2)) { err = "rho, sigma > 0 and 0 < alpha < 2 required"; return MPCMP_EINVAL; }
-    if (c->qp_warm_start < -1 || c->qp_warm_start > 1 || c->carry_multipliers < -1 || c->carry_multipliers > 1) { err = "qp_warm_start and carry_multipliers are -1, 0 or 1"; return MPCMP_EINVAL; }
-    // (written as !(x >= 0) and the like, so that a NaN fails every test)
-    if (!(c->eps_abs >= 0) || !(c->eps_rel >= 0) || !(c->eps_target >= 0) || !(c->hess_reg >= 0)) { err = "eps_abs, eps_rel, eps_target and hess_reg must be >= 0"; return MPCMP_EINVAL; }
-    if (!(c->rho_eq_scale > 0)) { err = "rho_eq_scale must be > 0"; return MPCMP_EINVAL; }
-    if (!(c->ls_eta > 0 && c->ls_eta < 1) || !(c->ls_tau > 0 && c->ls_tau < 1)) { err = "ls_eta and ls_tau must lie in (0, 1)"; return MPCMP_EINVAL; }
-    if (c->quirk_dtau_dT != 0 && c->quirk_dtau_dT != 1) { err = "quirk_dtau_dT is 0 or 1"; return MPCMP_EINVAL; }
-    mpcmp_bounds t;
-    mpcmp_bounds_from_config(c, &t);
-    if (int rc = validate_boxes(&t, err)) return rc;
-    if (!(c->lbT <= c->ubT && c->lbT < INFINITY && c->ubT > -INFINITY)) { err = "lbT <= ubT required (no NaN, no empty box)"; return MPCMP_EINVAL; }
-    if (int rc = validate_general_rows(&t, c->num_seg, err)) return rc;
-    return MPCMP_OK;
-}
-
 extern "C" const char *mpcmp_last_error(const mpcmp_ctx *ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
 
 extern "C" int mpcmp_destroy(mpcmp_ctx *ctx) {
@@ -702,7 +61,7 @@ extern "C" int mpcmp_destroy(mpcmp_ctx *ctx) {
     if (ctx->rh_exec) (void)hipGraphExecDestroy(ctx->rh_exec);
     if (ctx->rh_graph) (void)hipGraphDestroy(ctx->rh_graph);
     for (void *p : ctx->allocs) (void)hipFree(p);
-    for (auto &e : ctx->ev) { (void)hipEventDestroy(e.e[0]); (void)hipEventDestroy(e.e[1]); }
+    for (auto &e : ctx->sol.ev) { (void)hipEventDestroy(e.e[0]); (void)hipEventDestroy(e.e[1]); }
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (int k = 0; k < 3; k++) { if (ctx->stream_x[k]) (void)hipStreamDestroy(ctx->stream_x[k]); if (ctx->ev_join[k]) (void)hipEventDestroy(ctx->ev_join[k]); }
@@ -713,7 +72,6 @@ extern "C" int mpcmp_destroy(mpcmp_ctx *ctx) {
 }
 
 static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int narm, int device, int max_batch, mpcmp_ctx **out);
-static int prepare_kernels(mpcmp_ctx *ctx);
 
 extern "C" int mpcmp_create(const mpcmp_config *cfg, const mpcmp_model *model, int device, int max_batch, mpcmp_ctx **out) {
     return create_impl(cfg, model, 1, device, max_batch, out);
@@ -761,62 +119,10 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
     TRY(dalloc(ctx, &ctx->d_model, narm));
     HIPTRY(hipMemcpy(ctx->d_model, mdl, sizeof(mpcmp_model) * narm, hipMemcpyHostToDevice));
     ctx->model = mdl[0];
-    StructureTables tab;
-    // k_qp3 / k_qp4: per-arm tables with T bordered out (structure3.hpp), in ELL form
-    auto build_v3 = [&](int nseg, StructureTables &tb, Qp3Pat &pat) -> bool {
-        Tables3 t3;
-        if (!build_tables3(nseg, t3)) return false;
-        tb.nseg = t3.nseg; tb.ext_of_int = t3.ext_of_int; pat = t3.pat;
-        // term lists in ELL form [term index][entry] (entry stride padded to 64): consecutive threads assemble consecutive entries,
-        // so every load of a term word is one coalesced 256-byte request per wave (the per-entry lists of the CSR form cost a
-        // cache line per 4-byte word, and every workgroup of the launch reads the same table: 0.47 M cycles per factorisation)
-        const int E = (int)t3.entry_ptr.size() - 1, EP = (E + 63) / 64 * 64;
-        // (kappa, the (T, T) entry, has one term per row of A: the kernel sums it by a workgroup reduction instead)
-        const int e_kap = nseg * 1225 + 28 + nseg * 196 + nseg * 98 + 98 + 21 * (3 * nseg + 1);      // Dim3<nseg>::eKap
-        int tmax = 0;
-        for (int e = 0; e < E; e++) if (e != e_kap) tmax = std::max(tmax, t3.entry_ptr[e + 1] - t3.entry_ptr[e]);
-        tb.entry_ptr.assign(EP, 0);
-        tb.terms.assign((size_t)tmax * EP, 0xFFFFFFFFu);
-        // Slots instead of entries: inside each of the two assembly calls' ranges ([0, EA): everything but K_II; [EA, E): K_II) the
-        // entries are sorted by the length of their term lists, longest first, so that the 64 lanes of a wave (consecutive slots)
-        // walk lists of (nearly) equal length.  In entry order a wave executed every step of its longest list for all of its 10 - 13
-        // entries per lane: 140 term evaluations per lane for 32 terms.  tb.entry_ptr[slot] = count | entry << 8.
-        const int EA = e_kap + 1;
-        auto count_of = [&](int e) { return e == e_kap ? 0 : t3.entry_ptr[e + 1] - t3.entry_ptr[e]; };
-        for (int part = 0; part < 2; part++) {
-            const int lo = part ? EA : 0, hi = part ? E : EA;
-            std::vector<int> order(hi - lo);
-            for (int e = lo; e < hi; e++) order[e - lo] = e;
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return count_of(a) > count_of(b); });
-            for (int k = 0; k < hi - lo; k++) {
-                const int slot = lo + k, e = order[k], c = count_of(e);
-                tb.entry_ptr[slot] = c | (e << 8);
-                for (int t = 0; t < c; t++) tb.terms[(size_t)t * EP + slot] = t3.terms[t3.entry_ptr[e] + t];
-            }
-        }
-        return true;
-    };
-    auto fac_doubles = [](int nseg) -> size_t { return nseg == 4 ? std::max<size_t>(Qp3<4>::FAC, Qp4Fac<4>::FAC) : (nseg == 6 ? std::max<size_t>(Qp3<6>::FAC, Qp5Fac<6>::FAC) : Qp3<8>::FAC); };
-    if (cfg->num_seg == 6 && narm == 1) {
-        if (const char *e = std::getenv("MPCMP_QP19")) ctx->qp19 = std::atoi(e);
-        if (ctx->qp19 != 3 && ctx->qp19 != 5) { ctx->err = "MPCMP_QP19 must be 3 (k_qp3) or 5 (k_qp5)"; return fail(MPCMP_EINVAL); }
-    }
-    if (cfg->num_seg >= 6) {
-        Qp3Pat pat;
-        if (!build_v3(cfg->num_seg, tab, pat)) { ctx->err = "internal: structure table generation failed"; return fail(MPCMP_EINVAL); }
-        TRY(dalloc(ctx, &ctx->d_fac, (size_t)max_batch * narm * fac_doubles(cfg->num_seg)));
-        TRY(dalloc(ctx, &ctx->d_pat, 1));
-        HIPTRY(hipMemcpy(ctx->d_pat, &pat, sizeof(Qp3Pat), hipMemcpyHostToDevice));
-    } else if (!build_tables(cfg->num_seg, tab)) { ctx->err = "internal: structure table generation failed"; return fail(MPCMP_EINVAL); }
-    TRY(dalloc(ctx, &ctx->d_ext_of_int, tab.ext_of_int.size()));
-    TRY(dalloc(ctx, &ctx->d_entry_ptr, tab.entry_ptr.size()));
-    TRY(dalloc(ctx, &ctx->d_terms, tab.terms.size()));
-    HIPTRY(hipMemcpy(ctx->d_ext_of_int, tab.ext_of_int.data(), tab.ext_of_int.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(ctx->d_entry_ptr, tab.entry_ptr.data(), tab.entry_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(ctx->d_terms, tab.terms.data(), tab.terms.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TRY(solver_create(ctx));      // (environment knobs, structure and stream tables, factor workspace, LDS limits: solver.hip)
     const size_t B = max_batch, N = ctx->N, n = ctx->n, mn = ctx->mn;
     WS &w = ctx->ws;
-    w.model = ctx->d_model; w.ext_of_int = ctx->d_ext_of_int; w.entry_ptr = ctx->d_entry_ptr; w.terms = ctx->d_terms;
+    w.model = ctx->d_model;
     TRY(dalloc(ctx, &w.z, B * n)); TRY(dalloc(ctx, &w.lam, B * mn)); TRY(dalloc(ctx, &w.ceq, B * ctx->meq));
     HIPTRY(hipMemset(w.lam, 0, sizeof(double) * B * mn));        // (mpcmp_config.carry_multipliers: a fresh context starts every slot from lambda = 0)
     ctx->lam_count = B * mn;
@@ -835,52 +141,8 @@ static int create_impl(const mpcmp_config *cfg, const mpcmp_model *model, int na
         TRY(dalloc(ctx, &ctx->d_ax0, B * nx)); TRY(dalloc(ctx, &ctx->d_axf, B * nx));
         TRY(dalloc(ctx, &ctx->d_awx, B * nx * N)); TRY(dalloc(ctx, &ctx->d_awu, B * nu * N)); TRY(dalloc(ctx, &ctx->d_awT, B * narm));
     }
-    if (cfg->num_seg == 2 || cfg->num_seg == 4) {
-        AsmStreams as;
-        const int GS = cfg->num_seg == 4 ? Qp2<4>::GS : Qp2<2>::GS, RSv = Qp2<4>::RS;
-        if (!build_streams(cfg->num_seg, 1024, Qp2<4>::HS, GS, RSv, as)) { ctx->err = "internal: assembly stream generation failed"; return fail(MPCMP_EINVAL); }
-        TRY(dalloc(ctx, &ctx->d_stream, as.words.size()));
-        HIPTRY(hipMemcpy(ctx->d_stream, as.words.data(), as.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        ctx->streams.words = ctx->d_stream; ctx->streams.npass = as.npass;
-        for (int p = 0; p < 8; p++) { ctx->streams.off[p] = as.off[p]; ctx->streams.W[p] = as.W[p]; }
-        ctx->streams.split_dst = as.split_dst; ctx->streams.split_scr = as.split_scr; ctx->streams.split_n = as.split_n;
-    }
-    if (cfg->num_seg == 4) {
-        if (const char *e = std::getenv("MPCMP_QP13")) ctx->qp13 = std::atoi(e);
-        if (ctx->qp13 != 2 && ctx->qp13 != 3 && ctx->qp13 != 4) { ctx->err = "MPCMP_QP13 must be 2 (k_qp2), 3 (k_qp3) or 4 (k_qp4, experimental: slower than k_qp2)"; return fail(MPCMP_EINVAL); }
-#ifndef MPCMP_WITH_QP4
-        if (ctx->qp13 == 4) { ctx->err = "MPCMP_QP13=4: this library was built without k_qp4 (experimental kernel: rebuild with -DMPCMP_WITH_QP4 -Itools/experiments)"; return fail(MPCMP_EINVAL); }
-#endif
-        if (ctx->qp13 != 2 && std::getenv("MPCMP_FORCE_V1")) { ctx->err = "MPCMP_FORCE_V1 and MPCMP_QP13 != 2 exclude each other"; return fail(MPCMP_EINVAL); }
-        if (ctx->qp13 != 2) {
-            StructureTables t4;
-            Qp3Pat pat;
-            if (!build_v3(4, t4, pat)) { ctx->err = "internal: structure table generation failed"; return fail(MPCMP_EINVAL); }
-            TRY(dalloc(ctx, &ctx->d3_ext_of_int, t4.ext_of_int.size()));
-            TRY(dalloc(ctx, &ctx->d3_entry_ptr, t4.entry_ptr.size()));
-            TRY(dalloc(ctx, &ctx->d3_terms, t4.terms.size()));
-            HIPTRY(hipMemcpy(ctx->d3_ext_of_int, t4.ext_of_int.data(), t4.ext_of_int.size() * sizeof(int), hipMemcpyHostToDevice));
-            HIPTRY(hipMemcpy(ctx->d3_entry_ptr, t4.entry_ptr.data(), t4.entry_ptr.size() * sizeof(int), hipMemcpyHostToDevice));
-            HIPTRY(hipMemcpy(ctx->d3_terms, t4.terms.data(), t4.terms.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            TRY(dalloc(ctx, &ctx->d_fac, (size_t)max_batch * fac_doubles(4)));
-            TRY(dalloc(ctx, &ctx->d_pat, 1));
-            HIPTRY(hipMemcpy(ctx->d_pat, &pat, sizeof(Qp3Pat), hipMemcpyHostToDevice));
-#ifdef MPCMP_WITH_QP4
-            std::vector<uint32_t> lane4((size_t)Qp4<4>::NF * Qp4<4>::NT);
-            qp4_build_lanes<4>(pat, t4.ext_of_int.data(), lane4.data());
-            TRY(dalloc(ctx, &ctx->d_lane4, lane4.size()));
-            HIPTRY(hipMemcpy(ctx->d_lane4, lane4.data(), lane4.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-#endif
-        }
-    }
     TRY(dalloc(ctx, &ctx->d_retired, B)); HIPTRY(hipMemset(ctx->d_retired, 0, sizeof(int) * B));
     TRY(dalloc(ctx, &ctx->d_rh_count, 2)); HIPTRY(hipMemset(ctx->d_rh_count, 0, 2 * sizeof(unsigned long long)));
-    // diagnostics (generic kernel everywhere, stream count, occupancy report): read here, per context
-    ctx->force_v1 = std::getenv("MPCMP_FORCE_V1") != nullptr;
-    ctx->single_stream = std::getenv("MPCMP_SINGLE_STREAM") != nullptr;
-    ctx->debug_occ = std::getenv("MPCMP_DEBUG_OCC") != nullptr;
-    if (const char *e = std::getenv("MPCMP_STREAMS")) ctx->parts_env = std::atoi(e);
-    TRY(prepare_kernels(ctx));
     TRY(dalloc(ctx, &ctx->d_clr_sph, 2 * CLR_MAX_SPH));
 #undef TRY
 #undef HIPTRY
@@ -937,26 +199,6 @@ static int rows_alloc(mpcmp_ctx *ctx, T **p, size_t per_row) {
     if (*p) return MPCMP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return dalloc(ctx, p, per_row * ctx->max_batch);
-}
-
-// ------------------------------------------------------------------------------------------------
-// per-problem payloads (payload.hpp: the lumping, shared by the host and k_lump_payloads)
-static int check_payload(const mpcmp_payload *p, std::string &err) {
-    if (!(p->mass >= 0.0) || !std::isfinite(p->mass)) { err = "payload mass must be finite and >= 0"; return MPCMP_EINVAL; }
-    for (int d = 0; d < 3; d++) if (!std::isfinite(p->com[d])) { err = "payload com must be finite"; return MPCMP_EINVAL; }
-    for (int q = 0; q < 9; q++) if (!std::isfinite(p->I[q])) { err = "payload inertia must be finite"; return MPCMP_EINVAL; }
-    for (int r = 0; r < 3; r++) {
-        if (p->I[4 * r] < 0.0) { err = "payload inertia: negative diagonal entry"; return MPCMP_EINVAL; }
-        for (int c = r + 1; c < 3; c++) if (p->I[3 * r + c] != p->I[3 * c + r]) { err = "payload inertia must be symmetric"; return MPCMP_EINVAL; }
-    }
-    return MPCMP_OK;
-}
-
-extern "C" int mpcmp_model_add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out) {
-    if (!m || !p || !out) return MPCMP_EINVAL;
-    if (int rc = check_payload(p, g_err)) return rc;
-    add_payload(m, p, out);
-    return MPCMP_OK;
 }
 
 // n rows of narm payloads at d_p (device) -> ctx->d_pmodel on stream st; the scalar checks are the caller's
@@ -1078,265 +320,7 @@ extern "C" int mpcmp_set_bounds_device(mpcmp_ctx *ctx, int n, const mpcmp_bounds
     return MPCMP_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// launches
-template <typename K>
-static int set_lds(mpcmp_ctx *ctx, K kern, size_t bytes) {
-    HIPCHK(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return MPCMP_OK;
-}
-
-static hipEvent_t *next_events(mpcmp_ctx *ctx) {
-    if (ctx->ev_used == ctx->ev.size()) {
-        if (ctx->ev.size() >= mpcmp_ctx::MAX_EV) return nullptr;      // bounded: untimed until the caller folds the pairs
-        mpcmp_ctx::EvPair p;
-        if (hipEventCreate(&p.e[0]) != hipSuccess) return nullptr;
-        if (hipEventCreate(&p.e[1]) != hipSuccess) { (void)hipEventDestroy(p.e[0]); return nullptr; }
-        ctx->ev.push_back(p);
-    }
-    return ctx->ev[ctx->ev_used++].e;
-}
-
-// Kernel selection of a single-arm context (compile-time candidates, run-time choice by discretisation and the context's diagnostics)
-template <int NSEG>
-struct KSel {
-    static constexpr bool V2C = (NSEG == 2 || NSEG == 4);      // role-specialised 1024-thread QP kernel
-    static constexpr bool V3T = (NSEG >= 4);                   // k_qp3 instantiated (num_seg 4: diagnostics, MPCMP_QP13=3)
-    static constexpr int N3 = V3T ? NSEG : 6, N2 = V2C ? NSEG : 4, N1 = (NSEG >= 6) ? 1 : NSEG;
-    bool V3C, V4, V2, V5;
-    explicit KSel(const mpcmp_ctx *ctx) {
-        V3C = NSEG >= 6 || (NSEG == 4 && ctx->qp13 == 3);      // k_qp3: T bordered out, E-free interior solve (N = 19, 25)
-        V4 = NSEG == 4 && ctx->qp13 == 4;                       // k_qp3f<4, 1, 4> + k_qp4: two OCPs per CU
-        V2 = V2C && !ctx->force_v1 && !V3C && !V4;
-        V5 = NSEG == 6 && ctx->qp19 == 5;
-    }
-    // the kernel that runs the ADMM loop, by the order of preference of solve_impl's launches
-    const char *loop_kernel_name() const { return V4 ? "k_qp4" : V5 ? "k_qp5" : V3C ? "k_qp3" : V2 ? "k_qp2" : "k_qp"; }
-};
-
-// dynamic-LDS limits of every kernel a context of this discretisation can launch: set ONCE, in mpcmp_create
-template <int NSEG>
-static int prepare_impl(mpcmp_ctx *ctx) {
-    using S = KSel<NSEG>;
-    const S k(ctx);
-    ctx->loop_kernel = k.loop_kernel_name();
-    if (int rc = set_lds(ctx, k_init<NSEG>, InitLds<NSEG>::size * sizeof(double))) return rc;
-    if (int rc = set_lds(ctx, k_step<NSEG>, StepLds<NSEG>::size * sizeof(double))) return rc;
-    if (k.V3C) {
-        if (int rc = set_lds(ctx, k_qp3<S::N3, 1>, Qp3<S::N3>::sizeL * sizeof(double))) return rc;
-        if (int rc = set_lds(ctx, k_qp3f<S::N3, 1>, Qp3<S::N3>::sizeF * sizeof(double))) return rc;
-    }
-    if (k.V5) {
-        if (int rc = set_lds(ctx, k_qp5<6>, Qp5<6>::size5 * sizeof(double))) return rc;
-        if (int rc = set_lds(ctx, k_qp3f<6, 1, 5>, Qp3<6>::sizeF * sizeof(double))) return rc;
-    }
-#ifdef MPCMP_WITH_QP4
-    if (k.V4) {
-        const size_t l_qp4 = Qp4<4>::size * sizeof(double);
-        if (int rc = set_lds(ctx, k_qp4<4>, l_qp4)) return rc;
-        if (int rc = set_lds(ctx, k_qp3f<4, 1, 4>, Qp3<4>::sizeF * sizeof(double))) return rc;
-        if (ctx->debug_occ) {
-            int nb = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_qp4<4>, 384, l_qp4);
-            std::fprintf(stderr, "k_qp4: %zu B of dynamic LDS, %d workgroups per CU\n", l_qp4, nb);
-        }
-    }
-#endif
-    if (k.V2) { if (int rc = set_lds(ctx, k_qp2<S::N2>, Qp2<S::N2>::size * sizeof(double))) return rc; }
-    else if (!k.V3C && !k.V4) { if (int rc = set_lds(ctx, k_qp<S::N1>, QpLds<S::N1>::size * sizeof(double))) return rc; }
-    return MPCMP_OK;
-}
-
-// ---- the parts of a solve ----
-// A large batch is solved as parts on as many streams (why: solve_impl).  A part is a contiguous range of the call's problems with every per-problem
-// pointer of the workspace, the exchange slots, the start guess and the outputs moved to its first problem
-struct Part {
-    int b0, B;
-    hipStream_t stream;
-    WS ws;
-    Xch xch;
-    const double *wx, *wu, *wT;
-    double *sx, *su, *sT;
-    mpcmp_info *info;
-};
-struct Parts {
-    int n = 0;
-    Part p[4];
-    const Part *begin() const { return p; }
-    const Part *end() const { return p + n; }
-};
-
-static Parts split(const mpcmp_ctx *ctx, const SolveCall &c, int nparts) {
-    WS w = ctx->ws;
-    w.x0 = c.x0; w.xf = c.xf;
-    w.model = run_models(ctx, &w.mstride);
-    w.retired = run_retired(ctx, c);
-    w.tbox = run_rows(ctx, c);
-    w.bnd = run_bounds(ctx, c);
-    if (c.rh_step) { w.alt_x = ctx->d_wx; w.alt_u = ctx->d_wu; w.alt_T = ctx->d_wT; }
-    const size_t nx = ctx->nx, nu = ctx->nu, N = ctx->N, n = ctx->n, mn = ctx->mn, meq = ctx->meq, narm = ctx->narm;
-    const hipStream_t streams[4] = {c.stream, ctx->stream_x[0], ctx->stream_x[1], ctx->stream_x[2]};
-    Parts ps;
-    ps.n = nparts;
-    for (int h = 0, acc = 0; h < nparts; h++) {
-        Part &q = ps.p[h];
-        q.b0 = acc; q.B = (c.B - acc + (nparts - h) - 1) / (nparts - h); q.stream = streams[h];
-        acc += q.B;
-        const size_t b0 = (size_t)q.b0;
-        WS v = w;
-        v.x0 += nx * b0; v.xf += nx * b0; v.z += n * b0; v.lam += mn * b0; v.ceq += meq * b0; v.g += 8 * N * narm * b0;
-        v.Gk += 176 * N * narm * b0; v.p += n * b0; v.y += mn * b0; v.qpit += b0; v.perm += b0; v.okey += b0; v.done += h;
-        v.qp_total += b0; v.status += b0; v.alpha += b0; v.dbg += (size_t)MPCMP_DBG_WORDS * b0;
-        v.model += (size_t)v.mstride * b0;      // (the payload row is the problem's index in the whole batch, not in its part)
-        if (v.retired) v.retired += b0;
-        if (v.tbox) v.tbox += 2 * b0;
-        if (v.bnd) v.bnd += b0;
-        if (v.alt_x) { v.alt_x += nx * N * b0; v.alt_u += nu * N * b0; v.alt_T += b0; }
-        q.ws = v;
-        q.xch.buf = ctx->xch.buf ? ctx->xch.buf + (size_t)2 * MPCMP_XCH_STRIDE * b0 : nullptr;
-        q.wx = c.wx ? c.wx + nx * N * b0 : nullptr; q.wu = c.wx ? c.wu + nu * N * b0 : nullptr; q.wT = c.wx ? c.wT + b0 : nullptr;
-        q.sx = c.sx ? c.sx + nx * N * b0 : nullptr; q.su = c.su ? c.su + nu * N * b0 : nullptr;
-        q.sT = c.sT ? c.sT + b0 : nullptr; q.info = c.info ? c.info + b0 : nullptr;
-    }
-    return ps;
-}
-// the further parts' streams start behind the work already on the call's stream (fork) and the call's stream goes on behind them (join); under stream
-// capture the events carry the other streams into the graph
-static int fork_parts(mpcmp_ctx *ctx, const Parts &ps) {
-    if (ps.n > 1) HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ps.p[0].stream));
-    for (int h = 1; h < ps.n; h++) HIPCHK(ctx, hipStreamWaitEvent(ps.p[h].stream, ctx->ev_fork, 0));
-    return MPCMP_OK;
-}
-static int join_parts(mpcmp_ctx *ctx, const Parts &ps) {
-    for (int h = 1; h < ps.n; h++) { HIPCHK(ctx, hipEventRecord(ctx->ev_join[h - 1], ps.p[h].stream)); HIPCHK(ctx, hipStreamWaitEvent(ps.p[0].stream, ctx->ev_join[h - 1], 0)); }
-    return MPCMP_OK;
-}
-
-template <int NSEG>
-static int solve_impl(mpcmp_ctx *ctx, const SolveCall &c) {
-    using D = Dim<NSEG>;
-    using S = KSel<NSEG>;
-    const S ks(ctx);
-    const bool V3C = ks.V3C, V4 = ks.V4, V2 = ks.V2;
-    const mpcmp_config cfg = run_config(ctx, c);
-    const size_t l_init = InitLds<NSEG>::size * sizeof(double), l_qp = QpLds<S::N1>::size * sizeof(double),
-                 l_step = StepLds<NSEG>::size * sizeof(double);
-    const size_t l_qp3 = Qp3<S::N3>::sizeL * sizeof(double), l_qp3f = Qp3<S::N3>::sizeF * sizeof(double);
-#ifdef MPCMP_WITH_QP4
-    const size_t l_qp4 = Qp4<4>::size * sizeof(double);
-#endif
-    const size_t l_qp2 = Qp2<S::N2>::size * sizeof(double);
-    // A large batch is solved as two half-batches on two streams.  Every SQP iteration is a chain of dependent launches
-    // (QP -> order -> step), and a QP launch ends in a tail in which most CUs are idle (its problems run 25..700 ADMM
-    // iterations, four workgroups per CU); with two independent chains in flight the tail of one half is filled by the other
-    // half's next launch.  Replay of the bench workload's iteration counts: -5.8 % makespan.  Results are unaffected (problems
-    // are independent); small batches stay on one stream.
-    const bool dual = !ctx->single_stream && !c.only_qp && c.B >= 512;      // (also under stream capture: see fork_parts)
-    // parts: two; three for the N = 13 kernel from 1024 problems on (round 5, three repeats each: 15.74 - 15.77 k against 15.58 - 15.61 k traj/s on the
-    // headline batch; 512 problems — the receding-horizon step — and N = 19 are faster with two: 135.7 k vs 130.0 k re-solves/s, 67.1 k vs 65.2 k traj/s)
-    const int parts_auto = (NSEG == 4 && V2 && c.B >= 1024) ? 3 : 2;
-    const Parts parts = split(ctx, c, dual ? (ctx->parts_env < 1 ? parts_auto : (ctx->parts_env > 4 ? 4 : ctx->parts_env)) : 1);
-    if (int rc = fork_parts(ctx, parts)) return rc;
-    for (const Part &p : parts)
-        hipLaunchKernelGGL(k_init<NSEG>, dim3(p.B), dim3(D::NT), l_init, p.stream, cfg, p.ws, p.wx, p.wu, p.wT, c.reguess);
-    const int iters = c.only_qp ? 1 : cfg.sqp_iters;
-    for (int it = 0; it < iters; it++) {
-        for (const Part &p : parts) {
-            hipEvent_t *ev = (ctx->timing && !c.capturing) ? next_events(ctx) : nullptr;
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], p.stream));
-#ifdef MPCMP_WITH_QP4
-            if (V4) {
-                WS w3 = p.ws;
-                w3.ext_of_int = ctx->d3_ext_of_int; w3.entry_ptr = ctx->d3_entry_ptr; w3.terms = ctx->d3_terms;
-                double *fh = ctx->d_fac + (size_t)p.b0 * Qp4Fac<4>::FAC;
-                hipLaunchKernelGGL((k_qp3f<4, 1, 4>), dim3(p.B), dim3(1024), Qp3<4>::sizeF * sizeof(double), p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, fh);
-                hipLaunchKernelGGL((k_qp4<4>), dim3(p.B), dim3(384), l_qp4, p.stream, cfg, w3, (const uint32_t *)ctx->d_lane4, p.B, (const double *)fh);
-            }
-#else
-            if (V4) { ctx->err = "k_qp4 not built"; return MPCMP_EINVAL; }
-#endif
-            else if (ks.V5) {
-                double *fh = ctx->d_fac + (size_t)p.b0 * Qp5Fac<6>::FAC;
-                hipLaunchKernelGGL((k_qp3f<6, 1, 5>), dim3(p.B), dim3(1024), Qp3<6>::sizeF * sizeof(double), p.stream, cfg, p.ws, ctx->d_pat, ctx->xch, p.B, fh);
-                hipLaunchKernelGGL((k_qp5<6>), dim3(p.B), dim3(768), Qp5<6>::size5 * sizeof(double), p.stream, cfg, p.ws, ctx->d_pat, ctx->xch, p.B, (const double *)fh);
-            }
-            else if (V3C) {
-                WS w3 = p.ws;
-                if (NSEG == 4) { w3.ext_of_int = ctx->d3_ext_of_int; w3.entry_ptr = ctx->d3_entry_ptr; w3.terms = ctx->d3_terms; }
-                double *fh = ctx->d_fac + (size_t)p.b0 * Qp3<S::N3>::FAC;
-                hipLaunchKernelGGL((k_qp3f<S::N3, 1>), dim3(p.B), dim3(1024), l_qp3f, p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, fh);
-                hipLaunchKernelGGL((k_qp3<S::N3, 1>), dim3(p.B), dim3(512), l_qp3, p.stream, cfg, w3, ctx->d_pat, ctx->xch, p.B, (const double *)fh);
-            }
-            else if (V2) hipLaunchKernelGGL((k_qp2<S::N2>), dim3(p.B), dim3(1024), l_qp2, p.stream, cfg, p.ws, ctx->streams);
-            else hipLaunchKernelGGL((k_qp<S::N1>), dim3(p.B), dim3(Dim<S::N1>::NT), l_qp, p.stream, cfg, p.ws);
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], p.stream));
-            if (c.only_qp) continue;
-            hipLaunchKernelGGL(k_step<NSEG>, dim3(p.B), dim3(D::NT), l_step, p.stream, cfg, p.ws, it == iters - 1 ? 1 : 0, it,
-                               p.sx, p.su, p.sT, p.info);
-        }
-    }
-    if (int rc = join_parts(ctx, parts)) return rc;
-    HIPCHK(ctx, hipGetLastError());
-    return MPCMP_OK;
-}
-
-template <int NSEG, int NARM>
-static int prepare_impl_m(mpcmp_ctx *ctx) {
-    using D = DimM<NSEG, NARM>;
-    const size_t l_m = D::size * sizeof(double);
-    ctx->loop_kernel = "k_qp3";
-    if (int rc = set_lds(ctx, k_init_m<NSEG, NARM>, l_m)) return rc;
-    if (int rc = set_lds(ctx, k_step_m<NSEG, NARM>, l_m)) return rc;
-    if (int rc = set_lds(ctx, k_qp3<NSEG, NARM>, Qp3<NSEG>::sizeL * sizeof(double))) return rc;
-    if (int rc = set_lds(ctx, k_qp3f<NSEG, NARM>, Qp3<NSEG>::sizeF * sizeof(double))) return rc;
-    return MPCMP_OK;
-}
-
-// dynamic-LDS limits of the context's kernels (hipFuncSetAttribute): once per context
-static int prepare_kernels(mpcmp_ctx *ctx) {
-    if (ctx->narm == 2) return ctx->nseg == 6 ? prepare_impl_m<6, 2>(ctx) : prepare_impl_m<8, 2>(ctx);
-    switch (ctx->nseg) {
-        case 1: return prepare_impl<1>(ctx);
-        case 2: return prepare_impl<2>(ctx);
-        case 4: return prepare_impl<4>(ctx);
-        case 6: return prepare_impl<6>(ctx);
-        case 8: return prepare_impl_m<8, 1>(ctx);
-    }
-    return MPCMP_EINVAL;
-}
-
-// N = 25 and multi-arm OCPs: k_init_m -> K x [k_qp3 (one workgroup per arm), k_step_m]
-template <int NSEG, int NARM>
-static int solve_impl_m(mpcmp_ctx *ctx, const SolveCall &c) {
-    using D = DimM<NSEG, NARM>;
-    const mpcmp_config cfg = run_config(ctx, c);
-    const size_t l_m = D::size * sizeof(double), l_qp3 = Qp3<NSEG>::sizeL * sizeof(double), l_qp3f = Qp3<NSEG>::sizeF * sizeof(double);
-    // two parts on two streams once one part alone fills the chip (one CU per arm): see solve_impl
-    const bool dual = !ctx->single_stream && !c.only_qp && c.B * NARM >= 512;
-    const Parts parts = split(ctx, c, dual ? 2 : 1);
-    if (int rc = fork_parts(ctx, parts)) return rc;
-    for (const Part &p : parts)
-        hipLaunchKernelGGL((k_init_m<NSEG, NARM>), dim3(p.B), dim3(D::NT), l_m, p.stream, cfg, p.ws.model, p.ws, p.xch, p.wx, p.wu, p.wT, c.reguess);
-    const int iters = c.only_qp ? 1 : cfg.sqp_iters;
-    for (int it = 0; it < iters; it++) {
-        for (const Part &p : parts) {
-            hipEvent_t *ev = (ctx->timing && !c.capturing) ? next_events(ctx) : nullptr;
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[0], p.stream));
-            const int grid = NARM == 1 ? p.B : ((p.B + 7) / 8) * 16;       // arm workgroups of one OCP are 8 apart (k_qp3)
-            double *fh = ctx->d_fac + (size_t)p.b0 * NARM * Qp3<NSEG>::FAC;
-            hipLaunchKernelGGL((k_qp3f<NSEG, NARM>), dim3(grid), dim3(1024), l_qp3f, p.stream, cfg, p.ws, ctx->d_pat, p.xch, p.B, fh);
-            hipLaunchKernelGGL((k_qp3<NSEG, NARM>), dim3(grid), dim3(512), l_qp3, p.stream, cfg, p.ws, ctx->d_pat, p.xch, p.B, (const double *)fh);
-            if (ev) HIPCHK(ctx, hipEventRecord(ev[1], p.stream));
-            if (c.only_qp) continue;
-            hipLaunchKernelGGL((k_step_m<NSEG, NARM>), dim3(p.B), dim3(D::NT), l_m, p.stream, cfg, p.ws.model, p.ws, p.xch,
-                               it == iters - 1 ? 1 : 0, it, p.sx, p.su, p.sT, p.info);
-        }
-    }
-    if (int rc = join_parts(ctx, parts)) return rc;
-    HIPCHK(ctx, hipGetLastError());
-    return MPCMP_OK;
-}
-
+// the solve of a checked call (the kernels and their launch code: solver.hip)
 static int solve_dispatch(mpcmp_ctx *ctx, const SolveCall &c) {
     if (!ctx) return MPCMP_EINVAL;
     if (c.B < 1) return MPCMP_EINVAL;
@@ -1348,16 +332,8 @@ static int solve_dispatch(mpcmp_ctx *ctx, const SolveCall &c) {
     if (ctx->narm == 2) {
         if (c.only_qp) { ctx->err = "mpcmp_qp_batch is defined for single-arm contexts only"; return MPCMP_EINVAL; }
         if (!c.wx) { ctx->err = "multi-arm solves need a warm start (mpcmp_warm_start_jerk_batch)"; return MPCMP_EINVAL; }
-        return ctx->nseg == 6 ? solve_impl_m<6, 2>(ctx, c) : solve_impl_m<8, 2>(ctx, c);
     }
-    switch (ctx->nseg) {
-        case 1: return solve_impl<1>(ctx, c);
-        case 2: return solve_impl<2>(ctx, c);
-        case 4: return solve_impl<4>(ctx, c);
-        case 6: return solve_impl<6>(ctx, c);
-        case 8: return solve_impl_m<8, 1>(ctx, c);
-    }
-    return MPCMP_EINVAL;
+    return solver_run(ctx, c);
 }
 
 // ---- the host-buffer entry points' staging: the context's d_x0 / d_xf / d_w* in, d_s* / d_info (or another triple) out ----
@@ -1426,17 +402,7 @@ extern "C" int mpcmp_warm_start_batch(mpcmp_ctx *ctx, int B, const double *x0, c
     const size_t N = ctx->N, n = ctx->n;
     hipStream_t st = ctx->stream;
     if (int rc = upload_problems(ctx, B, x0, xf, nullptr, nullptr, nullptr, st)) return rc;
-    // k_init alone: the built-in initialiser writes the iterate z = [xs|us|T]
-    const SolveCall plain;
-    const mpcmp_config save = run_config(ctx, plain);
-    WS w = ctx->ws; w.x0 = ctx->d_x0; w.xf = ctx->d_xf; w.tbox = run_rows(ctx, plain); w.bnd = run_bounds(ctx, plain);
-#define LAUNCH_INIT(NS) { const size_t l = InitLds<NS>::size * sizeof(double); \
-        hipLaunchKernelGGL(k_init<NS>, dim3(B), dim3(Dim<NS>::NT), l, st, save, w, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0); }
-    switch (ctx->nseg) { case 1: LAUNCH_INIT(1) break; case 2: LAUNCH_INIT(2) break; case 4: LAUNCH_INIT(4) break; case 6: LAUNCH_INIT(6) break;
-        case 8: { const size_t l = DimM<8, 1>::size * sizeof(double);
-                  hipLaunchKernelGGL((k_init_m<8, 1>), dim3(B), dim3(512), l, st, save, ctx->d_model, w, ctx->xch, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0); } break; }
-#undef LAUNCH_INIT
-    HIPCHK(ctx, hipGetLastError());
+    if (int rc = solver_init_guess(ctx, B, st)) return rc;      // k_init alone: the built-in initialiser writes the iterate z = [xs|us|T]
     std::vector<double> z((size_t)B * n);
     HIPCHK(ctx, hipMemcpyAsync(z.data(), ctx->ws.z, sizeof(double) * n * B, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
@@ -1631,7 +597,7 @@ static int warm_start_jerk_device(mpcmp_ctx *ctx, int B, const double *d_x0, con
     JerkLimits lim;
     if (int rc = jerk_limits(ctx, vmax, amax, jmax, lim)) return rc;
     if (ctx->narm == 2) {
-        // per-arm generator on B * narm arm problems, then the merge to the common (slowest arm's) duration: multi_kernels.hpp
+        // per-arm generator on B * narm arm problems, then the merge to the common (slowest arm's) duration: jerk_device.hpp
         if (B > ctx->max_batch) return MPCMP_ETOOBIG;
         hipStream_t s2 = (hipStream_t)hip_stream;
         const int cnt = B * 2 * 14;
@@ -1836,14 +802,7 @@ extern "C" int mpcmp_eval_constraints_batch(mpcmp_ctx *ctx, int n, const double 
     double *dx, *du, *dg, *dG;
     sg.in(&dx, x, 14 * np); sg.in(&du, u, 7 * np); sg.out(&dg, g, 8 * np); sg.out(&dG, G, 176 * np);
     if (int rc = sg.upload()) return rc;
-    constexpr int NS = 4;
-    const size_t l = EvalLds<NS>::size * sizeof(double);
-    if (int rc = set_lds(ctx, k_eval_constraints<NS>, l)) return rc;
-    int ms;
-    const mpcmp_model *md = run_models(ctx, &ms);
-    const int per = ms ? 1 : Dim<NS>::N;           // points per workgroup: one with per-point models (k_eval_constraints)
-    hipLaunchKernelGGL(k_eval_constraints<NS>, dim3((n + per - 1) / per), dim3(Dim<NS>::NT), l, ctx->stream, ctx->cfg, md, ms, n, dx, du, dg, dG);
-    HIPCHK(ctx, hipGetLastError());
+    if (int rc = solver_eval_constraints(ctx, n, dx, du, dg, dG)) return rc;
     return sg.finish();
 }
 
@@ -2594,13 +1553,13 @@ extern "C" int mpcmp_kernel_timing(mpcmp_ctx *ctx, int reset, const char **name,
     if (!ctx) return MPCMP_EINVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // fold finished event pairs into the accumulators (caller has synchronised the stream)
-    for (size_t i = 0; i < ctx->ev_used; i++) {
+    for (size_t i = 0; i < ctx->sol.ev_used; i++) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[i].e[0], ctx->ev[i].e[1]) == hipSuccess) { ctx->qp_ms += ms; ctx->qp_launches++; }
+        if (hipEventElapsedTime(&ms, ctx->sol.ev[i].e[0], ctx->sol.ev[i].e[1]) == hipSuccess) { ctx->qp_ms += ms; ctx->qp_launches++; }
     }
-    ctx->ev_used = 0;
+    ctx->sol.ev_used = 0;
     ctx->timing = true;            // event recording starts with the first call (bench.py calls it once before the timed region)
-    if (name) *name = ctx->loop_kernel;
+    if (name) *name = ctx->sol.loop_kernel;
     if (ms_total) *ms_total = ctx->qp_ms;
     if (launches) *launches = ctx->qp_launches;
     if (reset) { ctx->qp_ms = 0.0; ctx->qp_launches = 0; }

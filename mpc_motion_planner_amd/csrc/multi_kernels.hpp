@@ -23,10 +23,6 @@ struct DimM {
     static constexpr int oSct = oScr + scr, oPv = oSct + 9 * N * 14, oX0 = oPv + 9 * N, oRed = oX0 + 2 * 14 * NARM, oBg = oRed + NW * 12 + 8, size = oBg + 16;
 };
 
-// index of component r in [0,14) of arm a in an external state vector [q(7 NARM); qd(7 NARM)]
-template <int NARM>
-__device__ __forceinline__ int ext_x(int a, int r) { return r < 7 ? 7 * a + r : 7 * NARM + 7 * a + (r - 7); }
-
 // variable box of arm variable v (external arm order) — motionPlanner.cpp:33,47,66-79
 template <int NSEG>
 __device__ __forceinline__ void arm_box(const mpcmp_config &c, const Bnd &bd, const double *x0a, const double *xfa, int v, double &lo, double &hi) {
@@ -414,41 +410,6 @@ __global__ __launch_bounds__(512) void k_step_m(mpcmp_config cfg, const mpcmp_mo
         }
     }
     step_tail(ws, lds, tid, NT);      // launch order of the next QP launch (see k_step)
-}
-
-// warm start of a multi-arm OCP from the single-arm generator (k_warm_jerk run on B*NARM arm problems): the common duration
-// is the slowest arm's and a faster arm's trajectory is played back uniformly slower (q(t) = q_a(s t), qd = s qd_a,
-// qdd = s^2 qdd_a with s = T_a / T <= 1: every limit still holds); exact end states (motionPlanner.cpp:202-203).
-// in: ax [B*NARM][N][14], au [B*NARM][N][7], aT [B*NARM]  (arm problem index = b*NARM + a);  out: ABI layout.
-template <int NARM>
-__global__ __launch_bounds__(256) void k_warm_merge(int N, int B, const double *ax, const double *au, const double *aT, const double *x0,
-                                                    const double *xf, double *wx, double *wu, double *wT) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    double T = 0.0;
-    for (int a = 0; a < NARM; a++) T = fmax(T, aT[b * NARM + a]);
-    for (int t = tid; t < N * 21 * NARM; t += blockDim.x) {
-        const int a = t / (N * 21), w = t % (N * 21), k = w / 21, c = w % 21;
-        const double s = aT[b * NARM + a] / T;
-        const size_t ap = (size_t)b * NARM + a;
-        if (c < 14) {
-            double val = ax[(ap * N + k) * 14 + c] * (c < 7 ? 1.0 : s);
-            if (k == 0) val = x0[(size_t)b * 14 * NARM + ext_x<NARM>(a, c)];
-            if (k == N - 1) val = xf[(size_t)b * 14 * NARM + ext_x<NARM>(a, c)];
-            wx[((size_t)b * N + k) * 14 * NARM + ext_x<NARM>(a, c)] = val;
-        } else {
-            wu[((size_t)b * N + k) * 7 * NARM + 7 * a + (c - 14)] = au[(ap * N + k) * 7 + (c - 14)] * (s * s);
-        }
-    }
-    if (tid == 0) wT[b] = T;
-}
-
-// split external states [B][14 NARM] into per-arm states [B*NARM][14] (input of k_warm_jerk)
-template <int NARM>
-__global__ void k_split_states(int B, const double *xe, double *xa) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * NARM * 14) return;
-    const int b = i / (NARM * 14), a = (i / 14) % NARM, r = i % 14;
-    xa[i] = xe[(size_t)b * 14 * NARM + ext_x<NARM>(a, r)];
 }
 
 }  // namespace mpcmp

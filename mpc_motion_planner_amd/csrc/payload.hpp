@@ -4,13 +4,20 @@
 // mpcmp_model_add_payload adds a payload on the host, and k_lump_payloads writes the per-problem models of mpcmp_set_payloads[_device].
 // FP contraction is off inside, so that the host and the device round every operation alike and the two agree bit for bit.
 #pragma once
-#include <hip/hip_runtime.h>
 #include "../../include/mpcmp.h"
+
+// (model_host.cpp is plain C++: it reads the two functions without the HIP runtime's header, and not the kernel)
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define MPCMP_PAYLOAD_HD __host__ __device__ inline
+#else
+#define MPCMP_PAYLOAD_HD inline
+#endif
 
 namespace mpcmp {
 
 // body 7 of m := the nb bodies (masses mk, COMs ck and rotational inertias about their COMs Ik, all in the joint-7 frame) lumped into one
-__host__ __device__ inline void lump_last_body(mpcmp_model *m, int nb, const double *mk, const double (*ck)[3], const double (*Ik)[9]) {
+MPCMP_PAYLOAD_HD void lump_last_body(mpcmp_model *m, int nb, const double *mk, const double (*ck)[3], const double (*Ik)[9]) {
 #pragma clang fp contract(off)
     double M = 0.0, c[3] = {0, 0, 0};
     for (int k = 0; k < nb; k++) M += mk[k];
@@ -29,7 +36,7 @@ __host__ __device__ inline void lump_last_body(mpcmp_model *m, int nb, const dou
 }
 
 // out := m with the payload p added to body 7 (out may alias m).  A payload with mass 0 and I = 0 leaves the model as it is, bit for bit.
-__host__ __device__ inline void add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out) {
+MPCMP_PAYLOAD_HD void add_payload(const mpcmp_model *m, const mpcmp_payload *p, mpcmp_model *out) {
     if (out != m) *out = *m;
     bool zero = p->mass == 0.0;
     for (int q = 0; q < 9; q++) zero = zero && p->I[q] == 0.0;
@@ -41,11 +48,13 @@ __host__ __device__ inline void add_payload(const mpcmp_model *m, const mpcmp_pa
     lump_last_body(out, 2, mk, ck, Ik);
 }
 
+#ifdef __HIPCC__
 // per-problem models of mpcmp_set_payloads[_device]: one thread per (row, arm), out[row][arm] = add_payload(base[arm], p[row][arm])
 __global__ __launch_bounds__(256) void k_lump_payloads(const mpcmp_model *base, int narm, int rows, const mpcmp_payload *p, mpcmp_model *out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * narm) return;
     add_payload(base + i % narm, p + i, out + i);
 }
+#endif
 
 }  // namespace mpcmp

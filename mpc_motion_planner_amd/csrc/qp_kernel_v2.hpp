@@ -997,14 +997,6 @@ __device__ __forceinline__ void qp2_role_b(const Qp2Ctx<NSEG> &c) {
     }
 }
 
-// pass metadata of the assembly streams (structure.hpp: build_streams)
-struct Qp2Streams {
-    const uint32_t *words;
-    int npass;
-    int off[8], W[8];
-    int split_dst, split_scr, split_n;
-};
-
 template <int NSEG>
 __global__ __launch_bounds__(1024) void k_qp2(mpcmp_config cfg, WS ws, Qp2Streams st) {
     using D = Dim<NSEG>;

@@ -22,15 +22,7 @@
 
 namespace mpcmp {
 
-// inter-workgroup exchange between the two arm workgroups of one OCP (NARM = 2): 8-byte data-tagged granules, agent-scope
-// relaxed atomics on both sides (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility": valid
-// form for <= 8-byte hand-offs, placement independent).  Every slot is written once per launch; k_init_m / k_step_m reset the
-// slots of their problem to XCH_EMPTY before the next QP launch.  Every spin is bounded.
-#define MPCMP_XCH_STRIDE 1024
-#define MPCMP_XCH_EMPTY 0x7FF8DEADBEEF0001ull          /* a NaN payload no arithmetic produces */
-struct Xch {
-    unsigned long long *buf;        // [B][2][MPCMP_XCH_STRIDE]
-};
+// the two sides of the arm-to-arm exchange (Xch, solver_types.hpp)
 __device__ __forceinline__ void xch_post(unsigned long long *slot, double v) {
     __hip_atomic_store(slot, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -394,7 +386,7 @@ __device__ __forceinline__ int q3_logical_tid() {
         return lds + L::fKJJ + (e - D::eS); \
     }; \
     /* Assembly of the entries of K_0 in the slots [e0, e1).  Term lists in ELL form over SLOTS (the entries of the range sorted by list \
-       length, longest first: mpcmp.hip): ws.entry_ptr[s] = number of terms | entry << 8, ws.terms[t * EP + s] (0xFFFFFFFF beyond a \
+       length, longest first: solver.hip): ws.entry_ptr[s] = number of terms | entry << 8, ws.terms[t * EP + s] (0xFFFFFFFF beyond a \
        list).  A thread owns up to NE slots and walks their lists together: per step the NE term words are loaded by independent, \
        coalesced requests (one round trip to L2 per step; entry after entry it was ~90 dependent round trips of 2 - 4 k cycles each \
        while every workgroup of the launch reads the same table), and the lanes of a wave hold lists of equal length. */ \

@@ -1,6 +1,6 @@
 // route.hip — via-point routes (include/mpcmp.h, "via-point routes"): the leg builder with the chord rule, the join of the legs' records into one
 // record per route, the sampling of a route on a uniform clock across its junctions, and the host helpers that need no context.
-// A translation unit of its own, so that the register-bound QP kernels of mpcmp.hip compile exactly as before.
+// A translation unit of its own, so that the register-bound QP kernels of solver.hip compile exactly as before.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "route.hpp"

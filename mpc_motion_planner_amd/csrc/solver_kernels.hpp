@@ -15,56 +15,18 @@
 #include "rbd_device.hpp"
 #include "sample_device.hpp"
 #include "structure.hpp"
+#include "solver_types.hpp"
 
 namespace mpcmp {
 
 // cubic Chebyshev-Gauss-Lobatto differentiation matrix on ascending nodes {-1,-1/2,1/2,1}
+// Linkage: k_qp reads the table inside a lambda (term_val), and a lambda in a kernel is implicitly __host__ __device__, so in a unit that instantiates
+// k_qp the compiler counts the table as used by host code and emits it as a global symbol that every kernel of the unit reaches through the GOT;
+// in a unit without k_qp (qp3_n25.hip, qp5_n19.hip) it stays local.  The two forms schedule k_qp2, k_step and k_qp3 differently, and the measured
+// product is the global form: solver.hip instantiates k_qp beside them on purpose (see there)
 static __device__ __constant__ double c_D[16] = {-19.0 / 6, 4.0, -4.0 / 3, 0.5,  -1.0, 1.0 / 3, 1.0, -1.0 / 3,
                                           1.0 / 3, -1.0, -1.0 / 3, 1.0,  -0.5, 4.0 / 3, -4.0, 19.0 / 6};
 
-struct WS {
-    const mpcmp_model *model;
-    const int *ext_of_int;
-    const int *entry_ptr;
-    const uint32_t *terms;
-    const double *x0, *xf;    // [B][14]
-    double *z;                // [B][n]
-    double *lam;              // [B][m+n]
-    double *ceq;              // [B][meq]
-    double *g;                // [B][8N]
-    double *Gk;               // [B][N][8][22]
-    double *p;                // [B][n]
-    double *y;                // [B][m+n]
-    int *qpit;                // [B] iterations of the last QP
-    int *perm;                // [B] launch order of the QP kernel: workgroup g solves problem perm[g] (longest expected first)
-    int *okey;                // [B] ordering key: decayed maximum of the problem's previous QP iteration counts
-    int *done;                // [1] workgroups of the running step launch that have finished (the last one computes the next QP order)
-    int *qp_total;            // [B]
-    int *status;              // [B]
-    double *alpha;            // [B]
-    unsigned long long *dbg;  // [B][MPCMP_DBG_WORDS] phase cycle stamps (diagnostic builds with -DMPCMP_STAMPS only)
-    const int *retired;       // [B] or null: receding-horizon instances that have arrived (k_advance) are not re-solved: every solve kernel returns at once (at N = 25 the QP kernels k_qp3f / k_qp3 still run, results discarded)
-    const double *alt_x, *alt_u, *alt_T;   // or null: the receding-horizon driver's start guess (jerk-limited trajectory from the current state) for an instance
-                                           // that cannot be re-guessed from its previous solve (k_init: reguess && prev_bad); null = the built-in initialiser
-    int mstride;              // models per problem behind `model`: 0 = one model (per arm) for every problem; narm = per-problem models
-                              // (mpcmp_set_payloads): problem b of the launch, arm a reads model + b * mstride + a
-    const double *tbox;       // [B][2] or null: final-time window (lbT, ubT) of problem b (mpcmp_set_time_windows, the second pass of a synchronised
-                              // solve); null = cfg.lbT / cfg.ubT for every problem.  Indexed by the problem (after perm), offset by a part's b0 like retired
-    const mpcmp_bounds *bnd;  // [B] or null: the six bound tables of problem b (mpcmp_set_bounds); null = the configuration's for every problem.  Indexed
-                              // and offset like tbox
-};
-// a retired instance of the receding-horizon loop: the whole workgroup leaves (uniform)
-#define MPCMP_RETIRED(ws_, b_) ((ws_).retired != nullptr && (ws_).retired[b_] != 0)
-
-// ws.status[b] while a solve runs: bits 0..6 = status bits of mpcmp_info (include/mpcmp.h), bits 8..30 = number of QPs that ran out of
-// iterations (every QP kernel adds MPCMP_ST_CAP_ONE then); k_step / k_step_m fold it into the record.  Bit 7 (MPCMP_ST_RESTART) is set between two
-// steps of the receding-horizon driver only (k_rh_update: new target, revival, MPCMP_RH_RESTART) and cleared by k_init / k_init_m with the whole word
-#define MPCMP_ST_CAP_ONE 0x100
-#define MPCMP_ST_RESTART 0x80
-// the solve failed hard or left the box of T: there is no trajectory to follow (k_advance holds the state)
-#define MPCMP_ST_FAILED (MPCMP_STATUS_NAN | MPCMP_STATUS_NOT_PD | MPCMP_STATUS_XCH_DEAD | MPCMP_STATUS_T_OUT_OF_BOX)
-// the slot's previous solve is no start for the next one (neither a re-guess nor carried multipliers): it failed, or the caller asked for a restart
-#define MPCMP_ST_NO_GUESS (MPCMP_ST_FAILED | MPCMP_ST_RESTART)
 // tools/isa_phases.py compiles with -DMPCMP_NOCHECK: the ADMM loops then contain no termination-test block, so that the hot path of every role is the
 // straight-line text between its barriers (diagnostic build: the QPs never converge early)
 #ifdef MPCMP_NOCHECK
@@ -80,7 +42,6 @@ struct WS {
 #else
 #define MPCMP_NO_TEST(cfg, period) ((period) < (cfg).check_every)
 #endif
-#define MPCMP_DBG_WORDS 160   /* 16 workgroup stamps + [16 waves][8] per-wave busy cycles of k_qp2 + 16 stamps of k_step */
 #ifdef MPCMP_STAMPS
 #define STAMP(slot) do { if (tid == 0) { const unsigned long long now_ = clock64(); stamp_acc[slot] += now_ - stamp_t; stamp_t = now_; } } while (0)
 #else
@@ -1070,24 +1031,6 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_step(mpcmp_config cfg, WS ws,
     step_tail(ws, lds, tid, NT);
 }
 
-#ifndef MPCMP_V3_TU     /* (the leaf kernels below are not templates: they belong to the main translation unit only) */
-// ------------------------------------------------------------------------------------------------
-// leaf kernels
-// (mstride: models per point behind mdl — 0, or narm with per-problem payload rows, WS::mstride; point / problem i reads arm 0 of row i.  Every
-//  leaf kernel below that evaluates dynamics takes one)
-__global__ __launch_bounds__(64) void k_rnea_batch(const mpcmp_model *mdl, int mstride, int n, const double *q, const double *v, const double *a,
-                             double *tau) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    mdl += (size_t)i * mstride;
-    double sc[14], vv[7], aa[7], t[7];
-#pragma unroll
-    for (int j = 0; j < 7; j++) { sincos(q[7 * i + j], &sc[2 * j], &sc[2 * j + 1]); vv[j] = v[7 * i + j]; aa[j] = a[7 * i + j]; }
-    rnea_dir<false>(mdl, sc, vv, aa, 0, 0, t, nullptr);
-#pragma unroll
-    for (int j = 0; j < 7; j++) tau[7 * i + j] = t[j];
-}
-
 // evalConstraints AD overload for a list of (x,u): processed in chunks of N "nodes" per workgroup
 template <int NSEG>
 __global__ __launch_bounds__(Dim<NSEG>::NT) void k_eval_constraints(mpcmp_config cfg, const mpcmp_model *mdl, int mstride, int total,
@@ -1117,216 +1060,5 @@ __global__ __launch_bounds__(Dim<NSEG>::NT) void k_eval_constraints(mpcmp_config
 }
 template <int NSEG>
 struct EvalLds { static constexpr int size = Dim<NSEG>::n + LinLds<NSEG>::size + Dim<NSEG>::N * (8 + 176); };
-
-// get_MPC_trajectory<n_pts> (motionPlanner.hpp:99-116): Lagrange interpolation on the segment + RNEA
-__global__ __launch_bounds__(128) void k_sample(const mpcmp_model *mdl, int mstride, int nseg, int B, int n_pts, const double *sx, const double *su,
-                         const double *sT, double *out) {
-    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)B * (n_pts + 1);
-    if (gid >= total) return;
-    const int b = (int)(gid / (n_pts + 1)), ip = (int)(gid % (n_pts + 1));
-    mdl += (size_t)b * mstride;
-    const int N = 3 * nseg + 1;
-    const double t = (double)ip / n_pts;
-    double *o = out + (size_t)gid * 29;
-    sample_row(mdl, nseg, sx + (size_t)b * 14 * N, su + (size_t)b * 7 * N, t, o);
-    o[0] = t * sT[b];
-}
-
-
-// MotionPlanner::get_MPC_point (motionPlanner.hpp:118-128) for one physical time per problem, including the reference's clamp
-// (time >= T: the normalised time becomes T, not 1), plus the RNEA torque.  out [B][28] = q(7), v(7), a(7), tau(7).
-__global__ __launch_bounds__(64) void k_mpc_point(const mpcmp_model *mdl, int mstride, int nseg, int B, const double *sx, const double *su, const double *sT,
-                                                  const double *time, double *out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    mdl += (size_t)b * mstride;
-    const int N = 3 * nseg + 1;
-    const double T = sT[b];
-    const double t = (time[b] < T) ? time[b] / T : T;
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    double Lg[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        double w = 1.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (k != j) w *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = w;
-    }
-    const double *X = sx + (size_t)b * 14 * N, *U = su + (size_t)b * 7 * N;
-    double q[7], v[7], a[7], tau[7], sc[14];
-#pragma unroll
-    for (int r = 0; r < 7; r++) {
-        q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            q[r] += Lg[j] * X[14 * (3 * s + j) + r];
-            v[r] += Lg[j] * X[14 * (3 * s + j) + 7 + r];
-            a[r] += Lg[j] * U[7 * (3 * s + j) + r];
-        }
-        sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
-    }
-    rnea_dir<false>(mdl, sc, v, a, 0, 0, tau, nullptr);
-    double *o = out + (size_t)b * 28;
-#pragma unroll
-    for (int r = 0; r < 7; r++) { o[r] = q[r]; o[7 + r] = v[r]; o[14 + r] = a[r]; o[21 + r] = tau[r]; }
-}
-
-// Receding horizon, one thread per instance: x0 <- MPC solution evaluated at physical time dt (MotionPlanner::get_MPC_point,
-// motionPlanner.hpp:118-128), and ARRIVAL: the reference's loop has no end (the caller decides), and an OCP whose start lies in its
-// terminal box degenerates (T -> lbT = 0).  Rule, the same in the oracle (orc_rh_advance):
-//   * retired already                          -> nothing;
-//   * the solve failed hard or left the box of T -> the state is held (there is no trajectory to follow; the next k_init starts afresh);
-//   * T <= dt: the plan ends within this control period -> the instance follows it to its end (last node) and is retired;
-//   * else the state advances by dt (for dt < T the clamp of get_MPC_point never acts); if the new state lies inside the terminal box
-//     |x - x_target| <= eps_target, the instance is retired as well.
-// A retired instance keeps its state, its last solution and its record (status |= MPCMP_STATUS_ARRIVED) and is not re-solved (MPCMP_RETIRED).
-// count[0] += instances solved in this step (not retired at its start), count[1] += instances retired by this step.
-__global__ __launch_bounds__(256) void k_advance(int nseg, int nx, int B, double dt, double eps_target, const double *sx, const double *sT,
-                                                 const int *status, const double *xf, double *x0, int *retired, mpcmp_info *info,
-                                                 unsigned long long *count) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    if (retired[b]) return;
-    atomicAdd(&count[0], 1ull);
-    if (status[b] & MPCMP_ST_FAILED) return;
-    const int N = 3 * nseg + 1;
-    const double T = sT[b];
-    const double *X = sx + (size_t)b * N * nx;
-    double *xo = x0 + (size_t)b * nx;
-    bool arrive = false;
-    if (T <= dt) {
-        for (int r = 0; r < nx; r++) xo[r] = X[(size_t)(N - 1) * nx + r];
-        arrive = true;
-    } else {
-        const double t = dt / T;
-        const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-        int s = (int)floor(t * nseg);
-        if (s >= nseg) s = nseg - 1;
-        if (s < 0) s = 0;
-        const double xx = 2.0 * (t * nseg - s) - 1.0;
-        double w[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double v = 1.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-            w[j] = v;
-        }
-        double far = 0.0;
-        for (int r = 0; r < nx; r++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc += w[j] * X[(size_t)(3 * s + j) * nx + r];
-            xo[r] = acc;
-            far = fmax(far, fabs(acc - xf[(size_t)b * nx + r]));
-        }
-        arrive = far <= eps_target;
-    }
-    if (arrive) {
-        retired[b] = 1;
-        if (info) info[b].status |= MPCMP_STATUS_ARRIVED;
-        atomicAdd(&count[1], 1ull);
-    }
-}
-
-// Receding horizon, between two steps (mpcmp_rh_update[_device]), one thread per listed instance b = idx[i] (idx null: b = i): the measured state
-// x [n][nx] and / or the target xf [n][nx] (either may be null) overwrite the loop's current state x0 / target xt of b
-// (MotionPlanner::set_current_state / set_target_state, motionPlanner.cpp:27-53).  What the next solve of b starts from:
-//   * live, a state only                -> nothing more: k_init re-guesses from the previous solution with the new head (solve_trajectory(false));
-//   * live, a target or `restart`       -> MPCMP_ST_RESTART: the driver's start guess and zero multipliers (k_init / k_init_m: prev_bad);
-//   * retired (arrived)                 -> revived: retired := 0, MPCMP_STATUS_ARRIVED leaves its record now, count[1] -= 1, and a restart.
-// The revival is an atomic exchange, so that an index listed twice (the device entry point cannot check) is counted once.
-__global__ __launch_bounds__(256) void k_rh_update(int nx, int n, const int *idx, const double *x, const double *xf, int restart,
-                                                   double *x0, double *xt, int *retired, int *status, mpcmp_info *info,
-                                                   unsigned long long *count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int b = idx ? idx[i] : i;
-    if (x) for (int r = 0; r < nx; r++) x0[(size_t)b * nx + r] = x[(size_t)i * nx + r];
-    if (xf) for (int r = 0; r < nx; r++) xt[(size_t)b * nx + r] = xf[(size_t)i * nx + r];
-    bool rs = restart || xf;
-    if (atomicExch(&retired[b], 0) != 0) {
-        atomicAnd(&info[b].status, ~MPCMP_STATUS_ARRIVED);
-        atomicAdd(&count[1], ~0ull);                          // (- 1 modulo 2^64)
-        rs = true;
-    }
-    if (rs) atomicOr(&status[b], MPCMP_ST_RESTART);
-}
-
-
-// Per-trajectory checks of examples/benchmark.cpp:58-160 in one pass: resample at n_pts+1 uniform times (interpolation + RNEA),
-// min / max of the 28 channels, terminal error, and the four pass flags (jerk, linear / angular task velocity, table
-// collision).  One workgroup per trajectory; out [B][74] = mins(28) | maxs(28) | x(T) - x_target (14) | flags (4, 1 = pass).
-__global__ __launch_bounds__(256) void k_traj_stats(const mpcmp_model *mdl, int mstride, int nseg, int n_pts, const double *sx, const double *su,
-                                                    const double *sT, const double *xf, double max_lin, double max_ang,
-                                                    const double *jerk10 /*[7] = 10 x max_jerk*/, double *out) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double *smp = lds;                          // [n_pts+1][28]
-    __shared__ int fl[4];
-    const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1;
-    mdl += (size_t)b * mstride;
-    const double *X = sx + (size_t)b * 14 * N, *U = su + (size_t)b * 7 * N;
-    const double T = sT[b];
-    if (tid < 4) fl[tid] = 1;
-    __syncthreads();
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    for (int ip = tid; ip <= n_pts; ip += blockDim.x) {
-        const double t = (double)ip / n_pts;
-        int s = (int)floor(t * nseg);
-        if (s >= nseg) s = nseg - 1;
-        if (s < 0) s = 0;
-        const double xx = 2.0 * (t * nseg - s) - 1.0;
-        double Lg[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double v = 1.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-            Lg[j] = v;
-        }
-        double q[7], v[7], a[7], tau[7], sc[14];
-#pragma unroll
-        for (int r = 0; r < 7; r++) {
-            q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                q[r] += Lg[j] * X[14 * (3 * s + j) + r];
-                v[r] += Lg[j] * X[14 * (3 * s + j) + 7 + r];
-                a[r] += Lg[j] * U[7 * (3 * s + j) + r];
-            }
-            sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
-        }
-        rnea_dir<false>(mdl, sc, v, a, 0, 0, tau, nullptr);
-        V3 pt, vl, va;
-        fk_task_velocity(mdl, sc, v, &pt, &vl, &va);
-        if (sqrt(vl.x * vl.x + vl.y * vl.y + vl.z * vl.z) > max_lin) fl[1] = 0;     // benchmark.cpp:139-142
-        if (sqrt(va.x * va.x + va.y * va.y + va.z * va.z) > max_ang) fl[2] = 0;     // :143-146
-        if (pt.z < 0.0) fl[3] = 0;                                                  // :149-155
-        double *o = smp + (size_t)ip * 28;
-#pragma unroll
-        for (int r = 0; r < 7; r++) { o[r] = q[r]; o[7 + r] = v[r]; o[14 + r] = a[r]; o[21 + r] = tau[r]; }
-    }
-    __syncthreads();
-    const double dT = T / n_pts;                                                     // time(nPoints)/nPoints, :121
-    for (int ip = 1 + tid; ip <= n_pts; ip += blockDim.x)
-        for (int r = 0; r < 7; r++)
-            if (fabs((smp[(size_t)ip * 28 + 14 + r] - smp[(size_t)(ip - 1) * 28 + 14 + r]) / dT) > jerk10[r]) fl[0] = 0;   // :126-133
-    double *o = out + (size_t)b * 74;
-    if (tid < 28) {
-        double mn = smp[tid], mx = smp[tid];
-        for (int ip = 1; ip <= n_pts; ip++) { const double v = smp[(size_t)ip * 28 + tid]; mn = fmin(mn, v); mx = fmax(mx, v); }
-        o[tid] = mn; o[28 + tid] = mx;
-    }
-    if (tid < 14) o[56 + tid] = smp[(size_t)n_pts * 28 + tid] - xf[(size_t)b * 14 + tid];   // :176-179
-    __syncthreads();
-    if (tid < 4) o[70 + tid] = (double)fl[tid];
-}
-
-#endif  /* MPCMP_V3_TU */
 
 }  // namespace mpcmp

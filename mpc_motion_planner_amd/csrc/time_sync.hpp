@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "solver_kernels.hpp"
+#include "solver_types.hpp"
 
 namespace mpcmp {
 

@@ -303,7 +303,7 @@ def test_every_source_file_is_a_build_dependency(M):
     csrc = os.path.join(ROOT, "mpc_motion_planner_amd", "csrc")
     deps = {os.path.realpath(d) for d in capi.build_dependencies()}
     files = _build_inputs(csrc)
-    assert {"qp3_n25.hip", "qp5_n19.hip", "Makefile", "mpcmp.hip"} <= set(files)
+    assert {"qp3_n25.hip", "qp5_n19.hip", "Makefile", "mpcmp.hip", "solver.hip", "model_host.cpp"} <= set(files)
     missing = [f for f in files if os.path.realpath(os.path.join(csrc, f)) not in deps]
     assert not missing, missing
     assert os.path.realpath(os.path.join(ROOT, "include", "mpcmp.h")) in deps

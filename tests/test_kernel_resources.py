@@ -112,7 +112,7 @@ def _count_ops(asm_path, prefix, op):
 
 def test_qp_kernels_stay_inside_their_register_and_scratch_budgets():
     with tempfile.TemporaryDirectory() as tmp:
-        p_main, d_main = _compile("mpcmp.hip", ["-DMPCMP_SPLIT_N25", "-DMPCMP_SPLIT_N19"], tmp, "main")
+        p_main, d_main = _compile("solver.hip", ["-DMPCMP_SPLIT_N25", "-DMPCMP_SPLIT_N19"], tmp, "main")
         p_n25, d_n25 = _compile("qp3_n25.hip", _strategy("qp3_n25.hip"), tmp, "n25")      # (as csrc/Makefile builds it)
         p_n19, d_n19 = _compile("qp5_n19.hip", _strategy("qp5_n19.hip"), tmp, "n19")
         _, e_main = p_main.communicate(timeout=900)
@@ -124,7 +124,7 @@ def test_qp_kernels_stay_inside_their_register_and_scratch_budgets():
         _check(_resources(e_main), BUDGET_MAIN)
         _check(_resources(e_n25), BUDGET_N25)
         _check(_resources(e_n19), BUDGET_N19)
-        asm = os.path.join(d_main, "mpcmp-hip-amdgcn-amd-amdhsa-gfx950.s")
+        asm = os.path.join(d_main, "solver-hip-amdgcn-amd-amdhsa-gfx950.s")
         asm19 = os.path.join(d_n19, "qp5_n19-hip-amdgcn-amd-amdhsa-gfx950.s")
         for prefix, min_loops in (("_ZN5mpcmp5k_qp2ILi4E", 3), ("_ZN5mpcmp5k_qp5ILi6E", 2)):
             nloops, nscr = _hot_loop_scratch(asm19 if "k_qp5" in prefix else asm, prefix)

@@ -3,7 +3,7 @@
 
     python tools/isa_loops.py [k_qp5|k_qp3|k_qp2|<mangled prefix>] [--all]
 
-Compiles mpc_motion_planner_amd/csrc/mpcmp.hip for gfx950 with the product build's flags and --save-temps into a
+Compiles mpc_motion_planner_amd/csrc/solver.hip for gfx950 with the product build's flags and --save-temps into a
 temporary directory, finds every backward branch of the named kernel and prints, per loop, its length in ISA lines, the
 barriers inside it and the scratch loads / stores inside it.  DESIGN.md's "no scratch in the hot loops" statements are
 this listing (a hot loop = a loop with five barriers: one ADMM iteration of one role).
@@ -22,11 +22,11 @@ KERNELS = {"k_qp5": "_ZN5mpcmp5k_qp5ILi6E", "k_qp3": "_ZN5mpcmp5k_qp3ILi6ELi1E",
 def compile_isa(tmp):
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang",
            "-load-store-opt", "-falign-loops=64", "-DMPCMP_SPLIT_N25", "--save-temps", "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(ROOT, "include"),
-           "-c", "-o", os.path.join(tmp, "m.o"), os.path.join(CSRC, "mpcmp.hip")]
+           "-c", "-o", os.path.join(tmp, "m.o"), os.path.join(CSRC, "solver.hip")]
     r = subprocess.run(cmd, cwd=tmp, capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-4000:])
-    return os.path.join(tmp, "mpcmp-hip-amdgcn-amd-amdhsa-gfx950.s"), r.stderr
+    return os.path.join(tmp, "solver-hip-amdgcn-amd-amdhsa-gfx950.s"), r.stderr
 
 
 def loops(path, prefix, show_all):

@@ -3,7 +3,7 @@
 
     python tools/isa_phases.py [k_qp2|k_qp5|k_qp3_n25] [--raw]
 
-Compiles mpc_motion_planner_amd/csrc/mpcmp.hip for gfx950 with the product flags plus -DMPCMP_NOCHECK (the termination-test
+Compiles mpc_motion_planner_amd/csrc/solver.hip for gfx950 with the product flags plus -DMPCMP_NOCHECK (the termination-test
 block is compiled out, so the hot path of a role is the straight-line text between its workgroup barriers), finds the role
 loops (backward branches whose body holds exactly five s_barrier) and prints, per role and per phase (= the text between two
 barriers, in iteration order A, P1, P2, P3, E), the instructions a WAVE of that role issues:
@@ -33,7 +33,7 @@ LDS_W = {"ds_write_b128": 8, "ds_write_b64": 4, "ds_write_b32": 2, "ds_write2_b6
 
 
 def compile_isa(tmp, extra, n25=False, n19=False):
-    src = "qp3_n25.hip" if n25 else ("qp5_n19.hip" if n19 else "mpcmp.hip")
+    src = "qp3_n25.hip" if n25 else ("qp5_n19.hip" if n19 else "solver.hip")
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang",
            "-load-store-opt", "-falign-loops=64", "-DMPCMP_SPLIT_N25", "-DMPCMP_NOCHECK", "--save-temps", "-I", os.path.join(ROOT, "include"),
            "-c", "-o", os.path.join(tmp, "m.o"), os.path.join(CSRC, src)] + extra

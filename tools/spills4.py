@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Where k_qp4's scratch accesses sit: per loop (backward branch) and per barrier-separated segment.  Diagnostic only.
-usage: spills4.py [asm file]   (default: compiles mpcmp.hip to /tmp/m.s)"""
+usage: spills4.py [asm file]   (default: compiles solver.hip to /tmp/m.s)"""
 import re, subprocess, sys, os, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 asm = sys.argv[1] if len(sys.argv) > 1 else '/tmp/m.s'
 if len(sys.argv) <= 1:
     subprocess.check_call(['/opt/rocm/bin/hipcc', '-O3', '-std=c++17', '--offload-arch=gfx950', '-Xclang', '-target-feature', '-Xclang', '-load-store-opt',
-                           '-DMPCMP_SPLIT_N25', *os.environ.get('EXTRA', '').split(), '-S', '--cuda-device-only', '-o', asm, os.path.join(ROOT, 'mpc_motion_planner_amd/csrc/mpcmp.hip')],
+                           '-DMPCMP_SPLIT_N25', *os.environ.get('EXTRA', '').split(), '-S', '--cuda-device-only', '-o', asm, os.path.join(ROOT, 'mpc_motion_planner_amd/csrc/solver.hip')],
                           stderr=subprocess.DEVNULL)
 s = open(asm).read()
 name = os.environ.get('KNAME', '_ZN5mpcmp5k_qp4ILi4EEEv12mpcmp_configNS_2WSEPKjiPKd')
