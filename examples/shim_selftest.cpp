@@ -127,6 +127,32 @@ int main() {
             std::printf("\"lim_stretch\": %.17g, \"lim_excess_qd\": %.17g, \"lim_channel_qd\": %d, \"lim_n_viol\": %d, \"lim_status\": %d, ",
                         l.stretch, l.excess[MPCMP_LIM_QD], l.channel[MPCMP_LIM_QD], l.n_viol, l.status);
         }
+        {   // extension: a move between states at rest, retimed under the groups a stretch cures: slowed only where it leaves them, so never
+            // slower than the stretch of the limit check (a plan with moving ends keeps their speed and may not be retimable at all)
+            MotionPlanner::Vec7 rest = MotionPlanner::Vec7::Zero();
+            planner.set_current_state(q0, rest);
+            planner.set_target_state(qT, rest);
+            planner.solve_trajectory(true);
+            mpcmp_limits_spec spec = {};
+            spec.tool_lin_max = 1.7; spec.tool_ang_max = 2.5;
+            const mpcmp_limits l = planner.check_limits(200, &spec);
+            mpcmp_retime_spec rs = {};
+            rs.tool_lin_max = 1.7; rs.tool_ang_max = 2.5; rs.rate_max = 1.0;
+            rs.groups = (1 << MPCMP_LIM_QD) | (1 << MPCMP_LIM_QDD) | (1 << MPCMP_LIM_TOOL_LIN) | (1 << MPCMP_LIM_TOOL_ANG);
+            const mpcmp_retime rt = planner.retime(200, &rs);
+            mpcmp_shim::Mat<1, 51> rt_t;
+            mpcmp_shim::Mat<7, 51> rt_q, rt_v, rt_a, rt_tau;
+            planner.get_retimed_trajectory<50>(rt_t, rt_q, rt_v, rt_a, rt_tau);
+            double rt_end = 0.0;
+            mpcmp_shim::Mat<1, 51> pl_t;
+            mpcmp_shim::Mat<7, 51> pl_q, pl_v, pl_a, pl_tau;
+            planner.get_MPC_trajectory<50>(pl_t, pl_q, pl_v, pl_a, pl_tau);      // the retimed plan ends where the plan ends
+            for (int j = 0; j < 7; j++) if (std::fabs(rt_q(j, 50) - pl_q(j, 50)) > rt_end) rt_end = std::fabs(rt_q(j, 50) - pl_q(j, 50));
+            auto fin = [](double x) { return std::isfinite(x) ? x : -1.0; };      // (JSON has no inf / nan: an infeasible plan prints -1)
+            std::printf("\"rt_T_new\": %.17g, \"rt_T\": %.17g, \"rt_stretch\": %.17g, \"rt_rate_min\": %.17g, \"rt_n_slowed\": %d, \"rt_status\": %d, "
+                        "\"rt_t_last\": %.17g, \"rt_end_error\": %.17g, ", fin(rt.T_new), planner.last_info.T, fin(l.stretch), rt.rate_min, rt.n_slowed,
+                        rt.status, fin(rt_t(0, 50)), fin(rt_end));
+        }
         // robot.data look-alike (examples/benchmark.cpp:108-110)
         pinocchio::forwardKinematics(planner.robot.model, planner.robot.data, qT);
         pinocchio::updateFramePlacement(planner.robot.model, planner.robot.data, planner.robot.frame_id);

@@ -338,6 +338,30 @@ class MotionPlanner {
         chk(mpcmp_limits_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, n_pts, spec, &r));
         return r;
     }
+    // the last solution retimed along its own path (include/mpcmp_retime.h): slowed only where it leaves the limits it was solved with, at n_grid + 1
+    // grid points.  spec NULL: no tool speed limits, never faster than the plan, all groups.  The profile is kept for get_retimed_trajectory;
+    // status != 0 (MPCMP_RT_INFEASIBLE, MPCMP_RT_NAN): no retimed plan
+    mpcmp_retime retime(int n_grid = 200, const mpcmp_retime_spec *spec = nullptr) {
+        mpcmp_retime r;
+        retime_prof_.assign((size_t)2 * (n_grid > 0 ? n_grid + 1 : 1), 0.0);
+        retime_grid_ = 0;
+        use_payload(1);
+        chk(mpcmp_retime_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, n_grid, spec, retime_prof_.data(), &r));
+        retime_grid_ = n_grid;
+        return r;
+    }
+    // get_MPC_trajectory on the retimed clock: NP + 1 samples at uniform times in [0, T_new] (mpcmp_sample_retimed_batch); call retime() first.
+    // NaN throughout if the plan could not be retimed
+    template <const int NP>
+    void get_retimed_trajectory(mpcmp_shim::Mat<1, NP + 1> &time, mpcmp_shim::Mat<7, NP + 1> &position_trajectory,
+                                mpcmp_shim::Mat<7, NP + 1> &velocity_trajectory, mpcmp_shim::Mat<7, NP + 1> &acceleration_trajectory,
+                                mpcmp_shim::Mat<7, NP + 1> &torque_trajectory) {
+        if (retime_grid_ < 1) throw std::runtime_error("get_retimed_trajectory: call retime() first");
+        std::vector<double> out((size_t)(NP + 1) * 29);
+        use_payload(1);
+        chk(mpcmp_sample_retimed_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, retime_grid_, retime_prof_.data(), NP, out.data()));
+        unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
+    }
 
     // one draw in [-1,1) of the planner's seeded stream: what `Matrix<...>::Random()` coefficients are in the reference's examples
     double random_unit() { return uniform(); }
@@ -578,7 +602,8 @@ class MotionPlanner {
     friend struct mpcmp_shim::Otg;
     mpcmp_ctx *ctx_ = nullptr;
     int N_ = 0, max_batch_ = 0;
-    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_;
+    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_, retime_prof_;
+    int retime_grid_ = 0;      // n_grid of the profile retime() left, 0: none
     double sol_T_ = 0, warm_T_ = 0, guess_T_ = 0;
     bool guess_is_profile_ = false;                 // the last guess came from the jerk-limited generator
     double guess_x0_[14] = {0}, guess_xf_[14] = {0}, guess_a0_[7] = {0}, guess_aT_[7] = {0};      // states and boundary accelerations of the last jerk-limited guess

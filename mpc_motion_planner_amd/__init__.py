@@ -15,7 +15,8 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    SPHERE_DTYPE, OBSTACLE_DTYPE, CLEARANCE_DTYPE, OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE, CLR_HIT, CLR_NAN,
                    spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
                    ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
-                   LIMITS_SPEC_DTYPE, LIMITS_DTYPE, LIM_GROUPS, LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG, LIM_NAN, limits_spec, limits_config)
+                   LIMITS_SPEC_DTYPE, LIMITS_DTYPE, LIM_GROUPS, LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG, LIM_NAN, limits_spec, limits_config,
+                   RETIME_SPEC_DTYPE, RETIME_DTYPE, RT_INFEASIBLE, RT_NAN, RT_ALL_GROUPS, retime_spec, retime_one)
 from .planner import BatchMotionPlanner, Solver
 
 __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED", "STATUS_OUTSIDE_TOL", "STATUS_T_OUT_OF_BOX", "STATUS_ARRIVED", "STATUS_HARD", "RH_RESTART",
@@ -28,4 +29,5 @@ __all__ = ["STATUS_NAN", "STATUS_NOT_PD", "STATUS_XCH_DEAD", "STATUS_QP_CAPPED",
            "spheres", "obstacle", "link_spheres", "clearance_config",
            "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",
            "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate",
-           "LIMITS_SPEC_DTYPE", "LIMITS_DTYPE", "LIM_GROUPS", "LIM_Q", "LIM_QD", "LIM_QDD", "LIM_TAU", "LIM_HEIGHT", "LIM_TOOL_LIN", "LIM_TOOL_ANG", "LIM_NAN", "limits_spec", "limits_config"]
+           "LIMITS_SPEC_DTYPE", "LIMITS_DTYPE", "LIM_GROUPS", "LIM_Q", "LIM_QD", "LIM_QDD", "LIM_TAU", "LIM_HEIGHT", "LIM_TOOL_LIN", "LIM_TOOL_ANG", "LIM_NAN", "limits_spec", "limits_config",
+           "RETIME_SPEC_DTYPE", "RETIME_DTYPE", "RT_INFEASIBLE", "RT_NAN", "RT_ALL_GROUPS", "retime_spec", "retime_one"]

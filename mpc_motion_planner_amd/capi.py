@@ -72,6 +72,12 @@ LIM_GROUPS = 7
 LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG = range(7)
 LIM_NAN = 128       # status bit of mpcmp_limits: a non-finite sample value (bit g: group g over its tolerance)
 
+# records of retiming (mpcmp_retime_spec, mpcmp_retime; include/mpcmp_retime.h): 32 and 40 bytes
+RETIME_SPEC_DTYPE = np.dtype([("tool_lin_max", "f8"), ("tool_ang_max", "f8"), ("rate_max", "f8"), ("groups", "i4"), ("pad", "i4")])
+RETIME_DTYPE = np.dtype([("T_new", "f8"), ("rate_min", "f8"), ("s_slowest", "f8"), ("k_fail", "i4"), ("n_slowed", "i4"), ("status", "i4"), ("pad", "i4")])
+RT_INFEASIBLE, RT_NAN = 1, 128
+RT_ALL_GROUPS = (1 << LIM_QD) | (1 << LIM_QDD) | (1 << LIM_TAU) | (1 << LIM_TOOL_LIN) | (1 << LIM_TOOL_ANG)
+
 # one row of mpcmp_set_bounds[_device] (mpcmp_bounds, include/mpcmp.h): the six bound tables of Config, in its order
 BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7), ("ubu", "f8", 7), ("lbg", "f8", 8), ("ubg", "f8", 8)])
 
@@ -135,6 +141,11 @@ ABI_LIMITS = {
     "mpcmp_limits_batch": "pipppipp", "mpcmp_limits_batch_device": "pipppippp", "mpcmp_limits_config": "pi" + "p" * 8,
     "mpcmp_select_checked_batch": "pippppipip", "mpcmp_select_checked_batch_device": "pippppipipp",
 }
+# ... and every function include/mpcmp_retime.h declares (retiming of finished plans), in its order
+ABI_RETIME = {
+    "mpcmp_retime_batch": "pipppippp", "mpcmp_retime_batch_device": "pipppipppp", "mpcmp_retime_one": "piippppdipp",
+    "mpcmp_sample_retimed_batch": "pipppipip", "mpcmp_sample_retimed_batch_device": "pipppipipp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -191,7 +202,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -332,6 +343,42 @@ def limits_config(models, row, q, qd, qdd, spec=None):
     check(lib().mpcmp_limits_config(arr, narm, host(row), None if spec is None else spec.ctypes.data, host(q), host(qd), host(qdd), host(ex),
                                     host(ch), host(r)))
     return ex, ch, r
+
+
+def retime_spec(tool_lin_max=np.inf, tool_ang_max=np.inf, rate_max=1.0, groups=RT_ALL_GROUPS):
+    """one RETIME_SPEC_DTYPE record: the tool speed maxima (default +inf: none), the largest rate (default 1: never faster than the plan) and the
+    mask of the groups that take part (bits 1 << LIM_QD, LIM_QDD, LIM_TAU, LIM_TOOL_LIN, LIM_TOOL_ANG)"""
+    t = np.zeros((), dtype=RETIME_SPEC_DTYPE)
+    t["tool_lin_max"] = tool_lin_max; t["tool_ang_max"] = tool_ang_max; t["rate_max"] = rate_max; t["groups"] = groups
+    return t
+
+
+def _retime_spec_arg(spec):
+    if spec is None:
+        return None
+    spec = np.ascontiguousarray(spec).reshape(())
+    if spec.dtype != RETIME_SPEC_DTYPE:
+        raise ValueError("spec must be one RETIME_SPEC_DTYPE record")
+    return spec
+
+
+def retime_one(models, num_seg, row, x, u, T, n_grid=200, spec=None):
+    """mpcmp_retime_one: ONE trajectory x [N][14 narm], u [N][7 narm], T on the host (no context, no GPU) under the BOUNDS_DTYPE record `row` and the
+    RETIME_SPEC_DTYPE record `spec` (None: no tool limits, rate_max 1, all groups).  models: a Model or a sequence of them.  Returns
+    (prof [n_grid + 1][2] = (t_k, x_k), the RETIME_DTYPE record)."""
+    if isinstance(models, Model):
+        models = [models]
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    row = np.ascontiguousarray(row).reshape(())
+    if row.dtype != BOUNDS_DTYPE:
+        raise ValueError("row must be one BOUNDS_DTYPE record")
+    spec = _retime_spec_arg(spec)
+    x, u = f64(x).reshape(N, 14 * narm), f64(u).reshape(N, 7 * narm)
+    prof = np.zeros((max(int(n_grid), 0) + 1, 2)); rec = np.zeros(1, dtype=RETIME_DTYPE)
+    check(lib().mpcmp_retime_one(arr, narm, int(num_seg), host(row), None if spec is None else spec.ctypes.data, host(x), host(u), float(T), int(n_grid),
+                                 host(prof), host(rec)))
+    return prof, rec[0]
 
 
 def model_from_urdf(path):

@@ -23,6 +23,7 @@
 #include "time_sync.hpp"
 #include "clearance.hpp"
 #include "limits.hpp"
+#include "retime.hpp"
 #include "route.hpp"
 
 using namespace mpcmp;
@@ -1097,6 +1098,86 @@ extern "C" int mpcmp_select_checked_batch_device(mpcmp_ctx *ctx, int B, const do
 extern "C" int mpcmp_select_checked_batch(mpcmp_ctx *ctx, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
                                           const mpcmp_limits *lim, int lim_mask, const int *group, int n_groups, int *chosen) {
     return select_host(ctx, "mpcmp_select_checked_batch", false, B, sT, info, clr, lim, lim_mask, group, n_groups, chosen);
+}
+
+// ------------------------------------------------------------------------------------------------
+// retiming (retime.hpp; the kernels are in retime.hip)
+static int retime_check(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const mpcmp_retime_spec *spec,
+                        const double *prof, const mpcmp_retime *out) {
+    if (!ctx) { g_err = "mpcmp_retime_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch || n_grid < 1 || n_grid > RT_MAX_GRID || !sx || !su || !sT || !prof || !out) {
+        ctx->err = "mpcmp_retime_batch: B in [1, max_batch], 1 <= n_grid <= 4096 and all pointers (but spec) required"; return MPCMP_EINVAL;
+    }
+    if (spec && !rt_spec_ok(*spec)) {
+        ctx->err = "mpcmp_retime_batch: tool maxima >= 0 (+inf: none), a finite rate_max > 0 and groups within MPCMP_RT_ALL_GROUPS required"; return MPCMP_EINVAL;
+    }
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
+    return rows_ok(ctx, B, PAYLOAD_ROWS);
+}
+
+static int retime_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid, const mpcmp_retime_spec *spec,
+                          double *d_prof, mpcmp_retime *d_out, hipStream_t st) {
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, retime_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
+                              spec ? *spec : rt_default_spec(), d_prof, d_out, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_retime_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                         const mpcmp_retime_spec *spec, double *d_prof, mpcmp_retime *d_out, void *hip_stream) {
+    if (int rc = retime_check(ctx, B, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return retime_enqueue(ctx, B, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_retime_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid,
+                                  const mpcmp_retime_spec *spec, double *prof, mpcmp_retime *out) {
+    if (int rc = retime_check(ctx, B, sx, su, sT, n_grid, spec, prof, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = B, NB = (size_t)ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof;
+    mpcmp_retime *dout;
+    sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, nb); sg.out(&dprof, prof, nb * (n_grid + 1) * 2); sg.out(&dout, out, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = retime_enqueue(ctx, B, dx, du, dT, n_grid, spec, dprof, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+static int sample_retimed_check(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof, int n_pts,
+                                const double *out) {
+    if (!ctx) { g_err = "mpcmp_sample_retimed_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch || n_grid < 1 || n_grid > RT_MAX_GRID || n_pts < 1 || !sx || !su || !sT || !prof || !out) {
+        ctx->err = "mpcmp_sample_retimed_batch: B in [1, max_batch], 1 <= n_grid <= 4096, n_pts >= 1 and all pointers required"; return MPCMP_EINVAL;
+    }
+    return rows_ok(ctx, B, PAYLOAD_ROWS);
+}
+
+extern "C" int mpcmp_sample_retimed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                                 const double *d_prof, int n_pts, double *d_out, void *hip_stream) {
+    if (int rc = sample_retimed_check(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, sample_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, n_pts, d_sx, d_su, d_sT, d_prof, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sample_retimed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof,
+                                          int n_pts, double *out) {
+    if (int rc = sample_retimed_check(ctx, B, sx, su, sT, n_grid, prof, n_pts, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = B, NB = (size_t)ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof, *dout;
+    sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, nb); sg.in(&dprof, prof, nb * (n_grid + 1) * 2);
+    sg.out(&dout, out, nb * (n_pts + 1) * (1 + 28 * (size_t)ctx->narm));
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_sample_retimed_batch_device(ctx, B, dx, du, dT, n_grid, dprof, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------------------------------------

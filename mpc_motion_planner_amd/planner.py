@@ -272,6 +272,40 @@ class Solver:
         check(lib().mpcmp_limits_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_pts),
                                               None if spec is None else np.ascontiguousarray(spec).ctypes.data, out or None, stream or None), self._ctx)
 
+    # -- retiming (include/mpcmp_retime.h)
+    def retime(self, sx, su, sT, n_grid=200, spec=None):
+        """mpcmp_retime_batch: the time-optimal rate of every plan along its own path under the bound rows (or the configuration's tables), payload
+        rows and the capi.RETIME_SPEC_DTYPE record `spec` (capi.retime_spec; None: no tool limits, never faster than the plan, all groups).
+        Returns (prof [B][n_grid + 1][2] = (t_k, x_k), capi.RETIME_DTYPE [B])"""
+        sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
+        spec = capi._retime_spec_arg(spec)
+        prof = np.zeros((B, max(int(n_grid), 0) + 1, 2)); out = np.zeros(B, dtype=capi.RETIME_DTYPE)
+        check(lib().mpcmp_retime_batch(self._ctx, B, host(sx), host(su), host(sT), int(n_grid), None if spec is None else spec.ctypes.data,
+                                       host(prof), host(out)), self._ctx)
+        return prof, out
+
+    def retime_device(self, B, sol_x, sol_u, sol_T, n_grid, prof, out, spec=None, stream=0):
+        """spec: a capi.RETIME_SPEC_DTYPE record on the HOST (capi.retime_spec) or None; everything else raw device pointers"""
+        check(lib().mpcmp_retime_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_grid),
+                                              None if spec is None else np.ascontiguousarray(spec).ctypes.data, prof or None, out or None,
+                                              stream or None), self._ctx)
+
+    def sample_retimed(self, sx, su, sT, prof, n_pts=200):
+        """mpcmp_sample_retimed_batch: [B][n_pts + 1][1 + 28 narm] = the time i T_new / n_pts, then per arm q, qd, qdd, tau of the plans retimed by
+        `prof` (what retime returned); NaN rows for a problem whose profile is NaN.  One arm or two."""
+        sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
+        prof = f64(prof)
+        if prof.ndim != 3 or prof.shape[0] != B or prof.shape[1] < 2 or prof.shape[2] != 2:
+            raise ValueError("prof must be [B][n_grid + 1][2] = [%d][..][2]" % B)
+        out = np.zeros((B, max(int(n_pts), 0) + 1, 1 + 2 * self.nx))
+        check(lib().mpcmp_sample_retimed_batch(self._ctx, B, host(sx), host(su), host(sT), prof.shape[1] - 1, host(prof), int(n_pts), host(out)),
+              self._ctx)
+        return out
+
+    def sample_retimed_device(self, B, sol_x, sol_u, sol_T, n_grid, prof, n_pts, out, stream=0):
+        check(lib().mpcmp_sample_retimed_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_grid), prof or None,
+                                                      int(n_pts), out or None, stream or None), self._ctx)
+
     def select_checked(self, sT, info, group, clr=None, lim=None, lim_mask=0x7F, n_groups=None):
         """mpcmp_select_checked_batch: select_clear with an optional clearance test (clr None: none) and an optional limits test (a member whose
         lim status has a bit of lim_mask, or LIM_NAN, is inadmissible).  n_groups defaults to max(group) + 1"""
@@ -726,6 +760,24 @@ class BatchMotionPlanner:
             return lim.reshape(r["sol_T"].shape)
         return self._solver.limits(self._sol[0], self._sol[1], self._sol[2], n_pts, tol, tool_lin_max, tool_ang_max)
 
+    def retime(self, n_grid=200, spec=None):
+        """the last solve_trajectory's solutions retimed along their own paths (Solver.retime): (prof [B][n_grid + 1][2], capi.RETIME_DTYPE [B]); of
+        routes: leg by leg, ([B][M + 1][n_grid + 1][2], [B][M + 1]) with leg times.  The profiles are kept for get_retimed_trajectory."""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            prof, rec = self._solver.retime(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_u"].reshape(L, self._solver.N, 7),
+                                            r["sol_T"].reshape(L), n_grid, spec)
+            return prof.reshape(r["sol_T"].shape + prof.shape[1:]), rec.reshape(r["sol_T"].shape)
+        self._retimed = self._solver.retime(self._sol[0], self._sol[1], self._sol[2], n_grid, spec)
+        return self._retimed
+
+    def get_retimed_trajectory(self, n_pts=200):
+        """get_MPC_trajectory on the retimed clock: [B][n_pts + 1][1 + 28 narm] from the profiles of the last retime call (direct moves)"""
+        if self._route is not None or getattr(self, "_retimed", None) is None:
+            raise ValueError("call retime() after solve_trajectory() first (direct moves)")
+        return self._solver.sample_retimed(self._sol[0], self._sol[1], self._sol[2], self._retimed[0], n_pts)
+
     # extension beyond the reference's members: a move through via points (include/mpcmp.h, "via-point routes")
     def set_via_points(self, via, via_velocity=None, speed=0.5):
         """via [B][M][7] (or [M][7] for every problem): the next solve_trajectory plans x0 -> via_0 -> .. -> xf without stopping, and
@@ -755,6 +807,7 @@ class BatchMotionPlanner:
             warm = self._warm
         sx, su, sT, info = self._solver.solve(x0, xf, warm)
         self._sol = (sx, su, sT)
+        self._retimed = None                    # (a profile belongs to the plan it was computed for)
         # re-guess with exact end states (motionPlanner.cpp:199-207)
         gx = sx.copy(); gx[:, 0] = x0; gx[:, -1] = xf
         self._warm = (gx, su.copy(), sT.copy())
