@@ -363,6 +363,28 @@ class MotionPlanner {
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
     }
 
+    // A straight tool line from the current state's posture to the pose (R row-major [9], p [3]) as the plan (include/mpcmp_toolpath.h): it becomes the
+    // last solution, so check_limits, check_clearance, retime, get_retimed_trajectory and get_MPC_trajectory apply to it.  T <= 0: the duration
+    // from the tool-speed maxima of spec (NULL: the defaults).  status & MPCMP_TL_STOPPED: the line met a singularity or left the workspace at
+    // node k_fail, and the nodes from there on are NaN
+    mpcmp_tool_line plan_tool_line(const double *R, const double *p, double T = 0.0, const mpcmp_tool_line_spec *spec = nullptr) {
+        mpcmp_tool_line r;
+        chk(mpcmp_tool_line_batch(ctx_, 1, 0, current_state.data(), R, p, &T, spec, sol_x_.data(), sol_u_.data(), &sol_T_, &r));
+        retime_grid_ = 0;
+        warm_x_ = sol_x_; warm_u_ = sol_u_; warm_T_ = sol_T_; have_warm_ = true;      // (a tool line is a legal start guess of the next solve)
+        for (int k = 0; k < 9; k++) line_R_[k] = R[k];
+        for (int k = 0; k < 3; k++) line_p_[k] = p[k];
+        have_line_ = true;
+        return r;
+    }
+    // how far the interpolant of that plan leaves its line at n_pts + 1 uniform samples; it holds for the retimed plan as well
+    mpcmp_tool_dev check_tool_line(int n_pts = 200, double tol_lin = INFINITY, double tol_ang = INFINITY) {
+        if (!have_line_) throw std::runtime_error("check_tool_line: call plan_tool_line() first");
+        mpcmp_tool_dev r;
+        chk(mpcmp_tool_deviation_batch(ctx_, 1, 0, sol_x_.data(), line_R_, line_p_, n_pts, tol_lin, tol_ang, &r));
+        return r;
+    }
+
     // one draw in [-1,1) of the planner's seeded stream: what `Matrix<...>::Random()` coefficients are in the reference's examples
     double random_unit() { return uniform(); }
     // motionPlanner.cpp:102-114 (Eigen::Random replaced by a SplitMix64 stream owned by the planner)
@@ -604,6 +626,8 @@ class MotionPlanner {
     int N_ = 0, max_batch_ = 0;
     std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_, retime_prof_;
     int retime_grid_ = 0;      // n_grid of the profile retime() left, 0: none
+    double line_R_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, line_p_[3] = {0, 0, 0};      // the goal pose of the last plan_tool_line
+    bool have_line_ = false;
     double sol_T_ = 0, warm_T_ = 0, guess_T_ = 0;
     bool guess_is_profile_ = false;                 // the last guess came from the jerk-limited generator
     double guess_x0_[14] = {0}, guess_xf_[14] = {0}, guess_a0_[7] = {0}, guess_aT_[7] = {0};      // states and boundary accelerations of the last jerk-limited guess
@@ -631,6 +655,7 @@ class MotionPlanner {
         chk(mpcmp_solve_batch(ctx_, 1, current_state.data(), target_state.data(), guess_x_.data(), guess_u_.data(), &guess_T_,
                               sol_x_.data(), sol_u_.data(), &sol_T_, &last_info));
         warm_x_ = sol_x_; warm_u_ = sol_u_; warm_T_ = sol_T_; have_warm_ = true;
+        have_line_ = false;
         for (int r = 0; r < 14; r++) { warm_x_[r] = current_state(r); warm_x_[(size_t)14 * (N_ - 1) + r] = target_state(r); }
     }
     void chk(int rc) { if (rc) throw std::runtime_error(std::string("mpcmp: ") + mpcmp_last_error(ctx_)); }

@@ -78,6 +78,13 @@ RETIME_DTYPE = np.dtype([("T_new", "f8"), ("rate_min", "f8"), ("s_slowest", "f8"
 RT_INFEASIBLE, RT_NAN = 1, 128
 RT_ALL_GROUPS = (1 << LIM_QD) | (1 << LIM_QDD) | (1 << LIM_TAU) | (1 << LIM_TOOL_LIN) | (1 << LIM_TOOL_ANG)
 
+# records of the tool-line moves (mpcmp_tool_line_spec, mpcmp_tool_line, mpcmp_tool_dev; include/mpcmp_toolpath.h): 56, 40 and 48 bytes
+TOOL_LINE_SPEC_DTYPE = np.dtype([("tool_lin_max", "f8"), ("tool_ang_max", "f8"), ("T_min", "f8"), ("damp", "f8"), ("manip_min", "f8"), ("eps", "f8"),
+                                 ("n_sub", "i4"), ("pad", "i4")])
+TOOL_LINE_DTYPE = np.dtype([("err_max", "f8"), ("manip_min", "f8"), ("s_manip", "f8"), ("q_excess", "f8"), ("k_fail", "i4"), ("status", "i4")])
+TOOL_DEV_DTYPE = np.dtype([("lin_max", "f8"), ("s_lin", "f8"), ("perp_max", "f8"), ("ang_max", "f8"), ("s_ang", "f8"), ("n_over", "i4"), ("status", "i4")])
+TL_STOPPED, TL_Q_OUT_OF_BOUNDS, TD_OVER, TL_NAN = 1, 2, 1, 128
+
 # one row of mpcmp_set_bounds[_device] (mpcmp_bounds, include/mpcmp.h): the six bound tables of Config, in its order
 BOUNDS_DTYPE = np.dtype([("lbx", "f8", 14), ("ubx", "f8", 14), ("lbu", "f8", 7), ("ubu", "f8", 7), ("lbg", "f8", 8), ("ubg", "f8", 8)])
 
@@ -146,6 +153,11 @@ ABI_RETIME = {
     "mpcmp_retime_batch": "pipppippp", "mpcmp_retime_batch_device": "pipppipppp", "mpcmp_retime_one": "piippppdipp",
     "mpcmp_sample_retimed_batch": "pipppipip", "mpcmp_sample_retimed_batch_device": "pipppipipp",
 }
+# ... and every function include/mpcmp_toolpath.h declares (tool-line moves), in its order
+ABI_TOOLPATH = {
+    "mpcmp_tool_line_batch": "pii" + "p" * 9, "mpcmp_tool_line_batch_device": "pii" + "p" * 10, "mpcmp_tool_line_one": "pipppppdpppp",
+    "mpcmp_tool_deviation_batch": "piipppiddp", "mpcmp_tool_deviation_batch_device": "piipppiddpp", "mpcmp_tool_deviation_one": "pipppiddp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -202,7 +214,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_TOOLPATH.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -379,6 +391,50 @@ def retime_one(models, num_seg, row, x, u, T, n_grid=200, spec=None):
     check(lib().mpcmp_retime_one(arr, narm, int(num_seg), host(row), None if spec is None else spec.ctypes.data, host(x), host(u), float(T), int(n_grid),
                                  host(prof), host(rec)))
     return prof, rec[0]
+
+
+def tool_line_spec(tool_lin_max=1.7, tool_ang_max=2.5, T_min=0.2, damp=1e-8, manip_min=1e-3, eps=1e-9, n_sub=4):
+    """one TOOL_LINE_SPEC_DTYPE record; the defaults are those of a NULL spec (include/mpcmp_toolpath.h)"""
+    t = np.zeros((), dtype=TOOL_LINE_SPEC_DTYPE)
+    t["tool_lin_max"] = tool_lin_max; t["tool_ang_max"] = tool_ang_max; t["T_min"] = T_min; t["damp"] = damp; t["manip_min"] = manip_min
+    t["eps"] = eps; t["n_sub"] = n_sub
+    return t
+
+
+def _tool_line_spec_arg(spec):
+    if spec is None:
+        return None
+    spec = np.ascontiguousarray(spec).reshape(())
+    if spec.dtype != TOOL_LINE_SPEC_DTYPE:
+        raise ValueError("spec must be one TOOL_LINE_SPEC_DTYPE record")
+    return spec
+
+
+def tool_line_one(model, num_seg, row, q_start, R1, p1, T=0.0, spec=None):
+    """mpcmp_tool_line_one: ONE straight tool line of one arm on the host (no context, no GPU) from the posture q_start [7] to the pose R1 [3][3],
+    p1 [3], as a plan under the position rows of the BOUNDS_DTYPE record `row`; T <= 0: the duration rule.  Returns (x [N][14], u [N][7], T, the
+    TOOL_LINE_DTYPE record)."""
+    N = 3 * int(num_seg) + 1
+    row = np.ascontiguousarray(row).reshape(())
+    if row.dtype != BOUNDS_DTYPE:
+        raise ValueError("row must be one BOUNDS_DTYPE record")
+    spec = _tool_line_spec_arg(spec)
+    q, R1, p1 = f64(q_start).reshape(7), f64(R1).reshape(9), f64(p1).reshape(3)
+    x, u, To, rec = np.zeros((N, 14)), np.zeros((N, 7)), np.zeros(1), np.zeros(1, dtype=TOOL_LINE_DTYPE)
+    check(lib().mpcmp_tool_line_one(C.byref(model), int(num_seg), host(row), None if spec is None else spec.ctypes.data, host(q), host(R1), host(p1),
+                                    float(T), host(x), host(u), host(To), host(rec)))
+    return x, u, float(To[0]), rec[0]
+
+
+def tool_deviation_one(model, num_seg, x, R1, p1, n_pts=200, tol_lin=np.inf, tol_ang=np.inf):
+    """mpcmp_tool_deviation_one: the TOOL_DEV_DTYPE record of ONE plan x [N][14] of one arm against the line from the tool pose of its node 0 to
+    R1, p1 (host, no GPU)"""
+    N = 3 * int(num_seg) + 1
+    x, R1, p1 = f64(x).reshape(N, 14), f64(R1).reshape(9), f64(p1).reshape(3)
+    rec = np.zeros(1, dtype=TOOL_DEV_DTYPE)
+    check(lib().mpcmp_tool_deviation_one(C.byref(model), int(num_seg), host(x), host(R1), host(p1), int(n_pts), float(tol_lin), float(tol_ang),
+                                         host(rec)))
+    return rec[0]
 
 
 def model_from_urdf(path):

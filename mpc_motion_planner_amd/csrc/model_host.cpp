@@ -1,5 +1,6 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
-// configuration, a bound row and a payload must satisfy, and the single-problem kinematics of the reference's robot wrapper.  Plain C++: no HIP
+// configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
+// statements of the tool-line moves (toolpath.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -19,6 +20,7 @@
 #include "model_host.hpp"
 #include "kinematics_host.hpp"
 #include "payload.hpp"
+#include "toolpath.hpp"
 
 using namespace mpcmp;
 
@@ -485,5 +487,44 @@ extern "C" int mpcmp_model_add_payload(const mpcmp_model *m, const mpcmp_payload
     if (!m || !p || !out) return MPCMP_EINVAL;
     if (int rc = check_payload(p, g_err)) return rc;
     add_payload(m, p, out);
+    return MPCMP_OK;
+}
+
+// ---- tool-line moves on the host (include/mpcmp_toolpath.h): one problem through the source the kernels run (toolpath.hpp) ----
+extern "C" int mpcmp_tool_line_one(const mpcmp_model *model, int num_seg, const mpcmp_bounds *row, const mpcmp_tool_line_spec *spec, const double *q_start,
+                                   const double *R1, const double *p1, double T_in, double *x, double *u, double *T, mpcmp_tool_line *out) {
+    using namespace mpcmp_tl;
+    if (!model || num_seg < 1 || 3 * num_seg + 1 > TL_MAX_NODES || !row || !q_start || !R1 || !p1 || !x || !u || !T) {
+        g_err = "mpcmp_tool_line_one: num_seg in [1, 8] and all pointers (but spec and out) required"; return MPCMP_EINVAL;
+    }
+    const mpcmp_tool_line_spec sp = spec ? *spec : tl_default_spec();
+    if (!tl_spec_ok(sp)) { g_err = "mpcmp_tool_line_one: spec values finite and > 0 (the tool maxima may be +inf), n_sub in [1, 64] required"; return MPCMP_EINVAL; }
+    if (const char *why = tl_check_problem(*model, q_start, R1, p1, T_in)) { g_err = std::string("mpcmp_tool_line_one: ") + why; return MPCMP_EINVAL; }
+    mpcmp_tool_line rec;
+    TlWork work;
+    tl_track(*model, num_seg, sp, q_start, R1, p1, T_in, x, 14, 0, 7, u, 7, 0, 0, &rec, work);
+    *T = work.T;
+    tl_q_excess(x, 14, num_seg, row->lbx, row->ubx, &rec);
+    if (out) *out = rec;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_tool_deviation_one(const mpcmp_model *model, int num_seg, const double *x, const double *R1, const double *p1, int n_pts,
+                                        double tol_lin, double tol_ang, mpcmp_tool_dev *out) {
+    using namespace mpcmp_tl;
+    if (!model || num_seg < 1 || 3 * num_seg + 1 > TL_MAX_NODES || !x || !R1 || !p1 || n_pts < 1 || n_pts > TD_MAX_PTS || !(tol_lin >= 0.0) ||
+        !(tol_ang >= 0.0) || !out) {
+        g_err = "mpcmp_tool_deviation_one: num_seg in [1, 8], n_pts in [1, 65536], tolerances >= 0 and all pointers required"; return MPCMP_EINVAL;
+    }
+    TlLine Ln;
+    tl_line_of_plan(*model, x, R1, p1, Ln);
+    TlDevAcc A;
+    tl_dev_init(A);
+    for (int i = 0; i <= n_pts; i++) {
+        double dl, dp, da;
+        tl_dev_sample(*model, Ln, num_seg, x, 14, i, n_pts, &dl, &dp, &da);
+        tl_dev_fold(A, i, dl, dp, da, tol_lin, tol_ang);
+    }
+    *out = tl_dev_record(A, n_pts);
     return MPCMP_OK;
 }

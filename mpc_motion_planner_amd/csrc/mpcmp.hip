@@ -24,6 +24,7 @@
 #include "clearance.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
+#include "toolpath.hpp"
 #include "route.hpp"
 
 using namespace mpcmp;
@@ -1177,6 +1178,98 @@ extern "C" int mpcmp_sample_retimed_batch(mpcmp_ctx *ctx, int B, const double *s
     sg.out(&dout, out, nb * (n_pts + 1) * (1 + 28 * (size_t)ctx->narm));
     if (int rc = sg.upload()) return rc;
     if (int rc = mpcmp_sample_retimed_batch_device(ctx, B, dx, du, dT, n_grid, dprof, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// tool-line moves (toolpath.hpp; the kernels are in toolpath.hip, the single-problem host statements in model_host.cpp)
+static int tool_line_check(mpcmp_ctx *ctx, int B, int arm, const double *q, const double *R1, const double *p1, const double *Tin,
+                           const mpcmp_tool_line_spec *spec, const double *sx, const double *su, const double *sT) {
+    if (!ctx) { g_err = "mpcmp_tool_line_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch) { ctx->err = "mpcmp_tool_line_batch: B must be in [1, max_batch]"; return MPCMP_EINVAL; }
+    if (arm < 0 || arm >= ctx->narm) { ctx->err = "mpcmp_tool_line_batch: arm must be in [0, narm)"; return MPCMP_EINVAL; }
+    if (!q || !R1 || !p1 || !sx || !su || !sT) { ctx->err = "mpcmp_tool_line_batch: q_start, R1, p1, sol_x, sol_u and sol_T are required"; return MPCMP_EINVAL; }
+    if (ctx->narm > 1 && !Tin) { ctx->err = "mpcmp_tool_line_batch: a multi-arm plan needs T_in (the arms share T)"; return MPCMP_EINVAL; }
+    if (spec && !mpcmp_tl::tl_spec_ok(*spec)) {
+        ctx->err = "mpcmp_tool_line_batch: spec values finite and > 0 (the tool maxima may be +inf), n_sub in [1, 64] required"; return MPCMP_EINVAL;
+    }
+    return rows_ok(ctx, B, BOUND_ROWS);
+}
+
+extern "C" int mpcmp_tool_line_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_q, const double *d_R1, const double *d_p1, const double *d_Tin,
+                                            const mpcmp_tool_line_spec *spec, double *d_sx, double *d_su, double *d_sT, mpcmp_tool_line *d_out,
+                                            void *hip_stream) {
+    if (int rc = tool_line_check(ctx, B, arm, d_q, d_R1, d_p1, d_Tin, spec, d_sx, d_su, d_sT)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    HIPCHK(ctx, mpcmp_tl::tool_line_launch(ctx->d_model + arm, ctx->nseg, B, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, ctx->nx, ctx->nu, 7 * arm,
+                                           7 * ctx->narm + 7 * arm, 7 * arm, d_q, d_R1, d_p1, d_Tin, spec ? *spec : mpcmp_tl::tl_default_spec(), d_sx,
+                                           d_su, d_sT, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_tool_line_batch(mpcmp_ctx *ctx, int B, int arm, const double *q, const double *R1, const double *p1, const double *Tin,
+                                     const mpcmp_tool_line_spec *spec, double *sx, double *su, double *sT, mpcmp_tool_line *out) {
+    if (int rc = tool_line_check(ctx, B, arm, q, R1, p1, Tin, spec, sx, su, sT)) return rc;
+    const mpcmp_model *models = ctx->narm == 1 ? &ctx->model : nullptr;
+    std::vector<mpcmp_model> hm;
+    if (!models) {                              // (the host copy of the context holds arm 0 only)
+        hm.resize(ctx->narm);
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        HIPCHK(ctx, hipMemcpy(hm.data(), ctx->d_model, sizeof(mpcmp_model) * ctx->narm, hipMemcpyDeviceToHost));
+        models = hm.data();
+    }
+    for (int b = 0; b < B; b++)
+        if (const char *why = mpcmp_tl::tl_check_problem(models[ctx->narm == 1 ? 0 : arm], q + 7 * (size_t)b, R1 + 9 * (size_t)b, p1 + 3 * (size_t)b, Tin ? Tin[b] : 0.0)) {
+            ctx->err = "mpcmp_tool_line_batch: problem " + std::to_string(b) + ": " + why;
+            return MPCMP_EINVAL;
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = B, NB = (size_t)ctx->N * nb;
+    Stage sg(ctx);
+    double *dq, *dR, *dp, *dTi, *dx, *du, *dT;
+    mpcmp_tool_line *dout;
+    sg.in(&dq, q, 7 * nb); sg.in(&dR, R1, 9 * nb); sg.in(&dp, p1, 3 * nb); sg.in(&dTi, Tin, nb);
+    if (ctx->narm > 1) { sg.inout(&dx, sx, ctx->nx * NB); sg.inout(&du, su, ctx->nu * NB); }      // the other arm's columns come back as they were
+    else { sg.out(&dx, sx, ctx->nx * NB); sg.out(&du, su, ctx->nu * NB); }
+    sg.out(&dT, sT, nb); sg.out(&dout, out, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_tool_line_batch_device(ctx, B, arm, dq, dR, dp, dTi, spec, dx, du, dT, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+static int tool_deviation_check(mpcmp_ctx *ctx, int B, int arm, const double *sx, const double *R1, const double *p1, int n_pts, double tol_lin,
+                                double tol_ang, const mpcmp_tool_dev *out) {
+    if (!ctx) { g_err = "mpcmp_tool_deviation_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch || arm < 0 || arm >= ctx->narm || n_pts < 1 || n_pts > mpcmp_tl::TD_MAX_PTS || !sx || !R1 || !p1 || !out ||
+        !(tol_lin >= 0.0) || !(tol_ang >= 0.0)) {
+        ctx->err = "mpcmp_tool_deviation_batch: B in [1, max_batch], arm in [0, narm), n_pts in [1, 65536], tolerances >= 0 and all pointers required";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_tool_deviation_batch_device(mpcmp_ctx *ctx, int B, int arm, const double *d_sx, const double *d_R1, const double *d_p1, int n_pts,
+                                                 double tol_lin, double tol_ang, mpcmp_tool_dev *d_out, void *hip_stream) {
+    if (int rc = tool_deviation_check(ctx, B, arm, d_sx, d_R1, d_p1, n_pts, tol_lin, tol_ang, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, mpcmp_tl::tool_deviation_launch(ctx->d_model + arm, ctx->nseg, B, ctx->nx, 7 * arm, d_sx, d_R1, d_p1, n_pts, tol_lin, tol_ang, d_out,
+                                                (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_tool_deviation_batch(mpcmp_ctx *ctx, int B, int arm, const double *sx, const double *R1, const double *p1, int n_pts, double tol_lin,
+                                          double tol_ang, mpcmp_tool_dev *out) {
+    if (int rc = tool_deviation_check(ctx, B, arm, sx, R1, p1, n_pts, tol_lin, tol_ang, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = B;
+    Stage sg(ctx);
+    double *dx, *dR, *dp;
+    mpcmp_tool_dev *dout;
+    sg.in(&dx, sx, ctx->nx * (size_t)ctx->N * nb); sg.in(&dR, R1, 9 * nb); sg.in(&dp, p1, 3 * nb); sg.out(&dout, out, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_tool_deviation_batch_device(ctx, B, arm, dx, dR, dp, n_pts, tol_lin, tol_ang, dout, ctx->stream)) return rc;
     return sg.finish();
 }
 

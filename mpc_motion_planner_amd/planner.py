@@ -306,6 +306,51 @@ class Solver:
         check(lib().mpcmp_sample_retimed_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_grid), prof or None,
                                                       int(n_pts), out or None, stream or None), self._ctx)
 
+    # -- tool-line moves (include/mpcmp_toolpath.h)
+    def tool_line(self, q_start, R, p, T=None, spec=None, arm=0, out=None):
+        """mpcmp_tool_line_batch: straight tool lines of arm `arm` from the postures q_start [B][7] to the poses R [B][3][3], p [B][3], written as
+        plans.  T [B] or a scalar: the durations (entries <= 0 and T None: the rule from the tool-speed maxima; a two-arm context needs T); spec: a
+        capi.TOOL_LINE_SPEC_DTYPE record (capi.tool_line_spec) or None.  out: an existing (sx, su, sT) triple to write this arm's columns into (the
+        second arm of a two-arm plan); None: new arrays, zero in the other arm's columns.  Returns (sx, su, sT, capi.TOOL_LINE_DTYPE [B])."""
+        q = f64(q_start).reshape(-1, 7); B = q.shape[0]
+        R, p = f64(R).reshape(B, 9), f64(p).reshape(B, 3)
+        T = None if T is None else np.ascontiguousarray(np.broadcast_to(f64(T), (B,)))
+        spec = capi._tool_line_spec_arg(spec)
+        if out is None:
+            sx, su, sT = np.zeros((B, self.N, self.nx)), np.zeros((B, self.N, self.nu)), np.zeros(B)
+        else:
+            sx, su, sT = out
+            for a, shape in ((sx, (B, self.N, self.nx)), (su, (B, self.N, self.nu)), (sT, (B,))):
+                if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shape):
+                    raise ValueError("out must be C-contiguous float64 arrays of shapes (%d, %d, %d), (%d, %d, %d), (%d,)" % (B, self.N, self.nx, B, self.N, self.nu, B))
+        rec = np.zeros(B, dtype=capi.TOOL_LINE_DTYPE)
+        check(lib().mpcmp_tool_line_batch(self._ctx, B, int(arm), host(q), host(R), host(p), host(T), None if spec is None else spec.ctypes.data,
+                                          host(sx), host(su), host(sT), host(rec)), self._ctx)
+        return sx, su, sT, rec
+
+    def tool_line_device(self, B, arm, q_start, R, p, T_in, sol_x, sol_u, sol_T, out=0, spec=None, stream=0):
+        """spec: a capi.TOOL_LINE_SPEC_DTYPE record on the HOST or None; everything else raw device pointers (0 = NULL for T_in and out)"""
+        check(lib().mpcmp_tool_line_batch_device(self._ctx, int(B), int(arm), q_start or None, R or None, p or None, T_in or None,
+                                                 None if spec is None else np.ascontiguousarray(spec).ctypes.data, sol_x or None, sol_u or None,
+                                                 sol_T or None, out or None, stream or None), self._ctx)
+
+    def tool_deviation(self, sx, R, p, n_pts=200, tol_lin=np.inf, tol_ang=np.inf, arm=0):
+        """mpcmp_tool_deviation_batch: capi.TOOL_DEV_DTYPE [B]: how far the tool of arm `arm` on the interpolant of the plans sx leaves the lines from
+        the tool poses of their first nodes to R [B][3][3], p [B][3], at n_pts + 1 uniform samples.  A property of the path: it holds for the
+        retimed plan too."""
+        sx = f64(sx); B = sx.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d]" % (self.N, self.nx))
+        R, p = f64(R).reshape(B, 9), f64(p).reshape(B, 3)
+        out = np.zeros(B, dtype=capi.TOOL_DEV_DTYPE)
+        check(lib().mpcmp_tool_deviation_batch(self._ctx, B, int(arm), host(sx), host(R), host(p), int(n_pts), float(tol_lin), float(tol_ang),
+                                               host(out)), self._ctx)
+        return out
+
+    def tool_deviation_device(self, B, arm, sol_x, R, p, n_pts, tol_lin, tol_ang, out, stream=0):
+        check(lib().mpcmp_tool_deviation_batch_device(self._ctx, int(B), int(arm), sol_x or None, R or None, p or None, int(n_pts), float(tol_lin),
+                                                      float(tol_ang), out or None, stream or None), self._ctx)
+
     def select_checked(self, sT, info, group, clr=None, lim=None, lim_mask=0x7F, n_groups=None):
         """mpcmp_select_checked_batch: select_clear with an optional clearance test (clr None: none) and an optional limits test (a member whose
         lim status has a bit of lim_mask, or LIM_NAN, is inadmissible).  n_groups defaults to max(group) + 1"""
@@ -661,6 +706,7 @@ class BatchMotionPlanner:
         self._payload = None
         self._via = None
         self._route = None
+        self._line = None                       # the goal poses of the last plan_tool_line, while its plans are the last solution
 
     # motionPlanner.cpp:56-90
     def set_constraint_margins(self, margin_position, margin_velocity, margin_acceleration, margin_torque, margin_jerk):
@@ -778,6 +824,26 @@ class BatchMotionPlanner:
             raise ValueError("call retime() after solve_trajectory() first (direct moves)")
         return self._solver.sample_retimed(self._sol[0], self._sol[1], self._sol[2], self._retimed[0], n_pts)
 
+    # extension beyond the reference's members: a straight tool line as the plan (include/mpcmp_toolpath.h)
+    def plan_tool_line(self, R, p, T=None, spec=None):
+        """straight tool lines from the current states' postures to the poses R [B][3][3], p [B][3] (Solver.tool_line), stored as the last solution:
+        check_limits, check_clearance, retime, get_retimed_trajectory and get_MPC_trajectory then apply to them.  Returns capi.TOOL_LINE_DTYPE [B]."""
+        R = f64(R).reshape(-1, 3, 3); B = max(R.shape[0], self.current_state.shape[0])
+        q = np.ascontiguousarray(np.broadcast_to(self.current_state[:, :7], (B, 7)))
+        sx, su, sT, rec = self._solver.tool_line(q, np.broadcast_to(R, (B, 3, 3)), np.broadcast_to(f64(p).reshape(-1, 3), (B, 3)), T, spec)
+        self._route = None
+        self._sol = (sx, su, sT)
+        self._retimed = None
+        self._warm = (sx.copy(), su.copy(), sT.copy())      # (a tool line is a legal start guess of the next solve)
+        self._line = (np.array(np.broadcast_to(R, (B, 3, 3))), np.array(np.broadcast_to(f64(p).reshape(-1, 3), (B, 3))))
+        return rec
+
+    def check_tool_line(self, n_pts=200, tol_lin=np.inf, tol_ang=np.inf):
+        """deviation records (capi.TOOL_DEV_DTYPE [B]) of the last plan_tool_line's plans from their lines"""
+        if self._route is not None or self._line is None or self._sol is None:
+            raise ValueError("call plan_tool_line() first")
+        return self._solver.tool_deviation(self._sol[0], self._line[0], self._line[1], n_pts, tol_lin, tol_ang)
+
     # extension beyond the reference's members: a move through via points (include/mpcmp.h, "via-point routes")
     def set_via_points(self, via, via_velocity=None, speed=0.5):
         """via [B][M][7] (or [M][7] for every problem): the next solve_trajectory plans x0 -> via_0 -> .. -> xf without stopping, and
@@ -808,6 +874,7 @@ class BatchMotionPlanner:
         sx, su, sT, info = self._solver.solve(x0, xf, warm)
         self._sol = (sx, su, sT)
         self._retimed = None                    # (a profile belongs to the plan it was computed for)
+        self._line = None
         # re-guess with exact end states (motionPlanner.cpp:199-207)
         gx = sx.copy(); gx[:, 0] = x0; gx[:, -1] = xf
         self._warm = (gx, su.copy(), sT.copy())
@@ -826,7 +893,7 @@ class BatchMotionPlanner:
             self._solver.set_time_windows(rep(np.broadcast_to(self._twin[0], (B,)), M), rep(np.broadcast_to(self._twin[1], (B,)), M))
         r = self._solver.solve_route(x0, via, xf, vqd, speed, self.margin_jerk_ * self.limits["jmax"] if jerk_start else None)
         self._route = r
-        self._sol = self._warm = None           # (the re-guess rule is that of a single move)
+        self._sol = self._warm = self._line = None      # (the re-guess rule is that of a single move)
         self.info = r["route_info"]
         return self.info
 
