@@ -495,6 +495,7 @@ class MotionPlanner {
         for (int i = 0; i < M; i++) for (int j = 0; j < 7; j++) via[(size_t)7 * i + j] = vias[i](j);
         route_x_.assign((size_t)14 * N_ * L, 0.0); route_u_.assign((size_t)7 * N_ * L, 0.0); route_leg_T.assign(L, 0.0);
         double T = 0.0;
+        route_grid_ = 0;           // (a profile belongs to the route it was computed for)
         use_payload(L);
         chk(mpcmp_solve_route_batch(ctx_, 1, M, current_state.data(), M ? via.data() : nullptr, nullptr, &speed, target_state.data(), input.max_jerk.data(),
                                     route_x_.data(), route_u_.data(), route_leg_T.data(), nullptr, &T, &last_info, &route_seam, nullptr));
@@ -509,6 +510,37 @@ class MotionPlanner {
         std::vector<double> out((size_t)(NP + 1) * 29);
         use_payload(L);
         chk(mpcmp_sample_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), NP, out.data()));
+        unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
+    }
+    // the last route retimed as ONE path with one rate profile across its via points (include/mpcmp_route_retime.h), at n_grid + 1 grid points per
+    // leg.  spec NULL: no tool speed limits, never faster than the plan, all groups.  The profile is kept for get_retimed_route_trajectory and the
+    // legs' new durations in route_leg_T_new; status != 0 (MPCMP_RT_INFEASIBLE, MPCMP_RT_NAN): no retimed route
+    std::vector<double> route_leg_T_new;
+    mpcmp_route_retime retime_route(int n_grid = 200, const mpcmp_retime_spec *spec = nullptr) {
+        if (route_leg_T.empty()) throw std::runtime_error("retime_route: no route solved yet (solve_route)");
+        const int L = (int)route_leg_T.size();
+        mpcmp_route_retime r;
+        route_prof_.assign((size_t)2 * L * (n_grid > 0 ? n_grid + 1 : 1), 0.0);
+        route_leg_T_new.assign(L, 0.0);
+        route_grid_ = 0;
+        use_payload(L);
+        chk(mpcmp_retime_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), n_grid, spec, route_prof_.data(),
+                                     route_leg_T_new.data(), &r));
+        route_grid_ = n_grid;
+        return r;
+    }
+    // get_route_trajectory on the retimed clock: NP + 1 samples at uniform times in [0, T_new] (mpcmp_sample_retimed_route_batch); call
+    // retime_route() first.  NaN throughout if the route could not be retimed
+    template <const int NP>
+    void get_retimed_route_trajectory(mpcmp_shim::Mat<1, NP + 1> &time, mpcmp_shim::Mat<7, NP + 1> &position_trajectory,
+                                      mpcmp_shim::Mat<7, NP + 1> &velocity_trajectory, mpcmp_shim::Mat<7, NP + 1> &acceleration_trajectory,
+                                      mpcmp_shim::Mat<7, NP + 1> &torque_trajectory) {
+        if (route_grid_ < 1 || route_leg_T.empty()) throw std::runtime_error("get_retimed_route_trajectory: call retime_route() first");
+        const int L = (int)route_leg_T.size();
+        std::vector<double> out((size_t)(NP + 1) * 29);
+        use_payload(L);
+        chk(mpcmp_sample_retimed_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), route_grid_, route_prof_.data(), NP,
+                                             out.data()));
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
     }
     // motionPlanner.hpp:73-96 — the jerk-limited trajectory of the last solve_trajectory(true) sampled uniformly, torques by
@@ -624,8 +656,9 @@ class MotionPlanner {
     friend struct mpcmp_shim::Otg;
     mpcmp_ctx *ctx_ = nullptr;
     int N_ = 0, max_batch_ = 0;
-    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_, retime_prof_;
+    std::vector<double> sol_x_, sol_u_, warm_x_, warm_u_, guess_x_, guess_u_, route_x_, route_u_, retime_prof_, route_prof_;
     int retime_grid_ = 0;      // n_grid of the profile retime() left, 0: none
+    int route_grid_ = 0;       // n_grid of the profile retime_route() left, 0: none
     double line_R_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, line_p_[3] = {0, 0, 0};      // the goal pose of the last plan_tool_line
     bool have_line_ = false;
     double sol_T_ = 0, warm_T_ = 0, guess_T_ = 0;

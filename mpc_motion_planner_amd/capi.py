@@ -76,6 +76,9 @@ LIM_NAN = 128       # status bit of mpcmp_limits: a non-finite sample value (bit
 RETIME_SPEC_DTYPE = np.dtype([("tool_lin_max", "f8"), ("tool_ang_max", "f8"), ("rate_max", "f8"), ("groups", "i4"), ("pad", "i4")])
 RETIME_DTYPE = np.dtype([("T_new", "f8"), ("rate_min", "f8"), ("s_slowest", "f8"), ("k_fail", "i4"), ("n_slowed", "i4"), ("status", "i4"), ("pad", "i4")])
 RT_INFEASIBLE, RT_NAN = 1, 128
+# the record of a retimed route (mpcmp_route_retime; include/mpcmp_route_retime.h): 48 bytes
+ROUTE_RETIME_DTYPE = np.dtype([("T_new", "f8"), ("rate_min", "f8"), ("s_slowest", "f8"), ("leg_slowest", "i4"), ("leg_fail", "i4"), ("k_fail", "i4"),
+                               ("n_slowed", "i4"), ("status", "i4"), ("pad", "i4")])
 RT_ALL_GROUPS = (1 << LIM_QD) | (1 << LIM_QDD) | (1 << LIM_TAU) | (1 << LIM_TOOL_LIN) | (1 << LIM_TOOL_ANG)
 
 # records of the tool-line moves (mpcmp_tool_line_spec, mpcmp_tool_line, mpcmp_tool_dev; include/mpcmp_toolpath.h): 56, 40 and 48 bytes
@@ -153,6 +156,11 @@ ABI_RETIME = {
     "mpcmp_retime_batch": "pipppippp", "mpcmp_retime_batch_device": "pipppipppp", "mpcmp_retime_one": "piippppdipp",
     "mpcmp_sample_retimed_batch": "pipppipip", "mpcmp_sample_retimed_batch_device": "pipppipipp",
 }
+# ... and every function include/mpcmp_route_retime.h declares (retiming of whole routes), in its order
+ABI_ROUTE_RETIME = {
+    "mpcmp_retime_route_batch": "piipppipppp", "mpcmp_retime_route_batch_device": "piipppippppp", "mpcmp_retime_route_one": "piiipppppippp",
+    "mpcmp_sample_retimed_route_batch": "piipppipip", "mpcmp_sample_retimed_route_batch_device": "piipppipipp",
+}
 # ... and every function include/mpcmp_toolpath.h declares (tool-line moves), in its order
 ABI_TOOLPATH = {
     "mpcmp_tool_line_batch": "pii" + "p" * 9, "mpcmp_tool_line_batch_device": "pii" + "p" * 10, "mpcmp_tool_line_one": "pipppppdpppp",
@@ -214,7 +222,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_TOOLPATH.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_TOOLPATH.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -391,6 +399,30 @@ def retime_one(models, num_seg, row, x, u, T, n_grid=200, spec=None):
     check(lib().mpcmp_retime_one(arr, narm, int(num_seg), host(row), None if spec is None else spec.ctypes.data, host(x), host(u), float(T), int(n_grid),
                                  host(prof), host(rec)))
     return prof, rec[0]
+
+
+def retime_route_one(models, num_seg, rows, x, u, T, n_grid=200, spec=None):
+    """mpcmp_retime_route_one: ONE route of n_legs legs x [n_legs][N][14 narm], u [n_legs][N][7 narm], T [n_legs] on the host (no context, no GPU), leg
+    m under the BOUNDS_DTYPE record rows[m] (one record: every leg under it) and the RETIME_SPEC_DTYPE record `spec` (None: no tool limits, rate_max
+    1, all groups).  models: a Model or a sequence of them, for every leg.  Returns (prof [n_legs][n_grid + 1][2] = (t_k, x_k) with leg times,
+    leg_T_new [n_legs], the ROUTE_RETIME_DTYPE record)."""
+    if isinstance(models, Model):
+        models = [models]
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    T = f64(T).reshape(-1); nl = T.shape[0]
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype != BOUNDS_DTYPE:
+        raise ValueError("rows must be BOUNDS_DTYPE records")
+    rows = np.ascontiguousarray(np.broadcast_to(rows.reshape(-1), (nl,))) if rows.size == 1 else rows.reshape(-1)
+    if rows.shape[0] != nl:
+        raise ValueError("one BOUNDS_DTYPE record per leg (or one for all): %d legs, %d rows" % (nl, rows.shape[0]))
+    spec = _retime_spec_arg(spec)
+    x, u = f64(x).reshape(nl, N, 14 * narm), f64(u).reshape(nl, N, 7 * narm)
+    prof = np.zeros((nl, max(int(n_grid), 0) + 1, 2)); leg_T = np.zeros(nl); rec = np.zeros(1, dtype=ROUTE_RETIME_DTYPE)
+    check(lib().mpcmp_retime_route_one(arr, narm, int(num_seg), nl, host(rows), None if spec is None else spec.ctypes.data, host(x), host(u), host(T),
+                                       int(n_grid), host(prof), host(leg_T), host(rec)))
+    return prof, leg_T, rec[0]
 
 
 def tool_line_spec(tool_lin_max=1.7, tool_ang_max=2.5, T_min=0.2, damp=1e-8, manip_min=1e-3, eps=1e-9, n_sub=4):

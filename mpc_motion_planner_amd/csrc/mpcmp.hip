@@ -24,6 +24,7 @@
 #include "clearance.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
+#include "route_retime.hpp"
 #include "toolpath.hpp"
 #include "route.hpp"
 
@@ -1178,6 +1179,101 @@ extern "C" int mpcmp_sample_retimed_batch(mpcmp_ctx *ctx, int B, const double *s
     sg.out(&dout, out, nb * (n_pts + 1) * (1 + 28 * (size_t)ctx->narm));
     if (int rc = sg.upload()) return rc;
     if (int rc = mpcmp_sample_retimed_batch_device(ctx, B, dx, du, dT, n_grid, dprof, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// route retiming (route_retime.hpp; the kernels are in route_retime.hip)
+static int route_shape_check(mpcmp_ctx *ctx, const char *who, int B, int M, int n_grid, int *L) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    const long long l = (long long)B * ((long long)M + 1);
+    if (B < 1 || M < 0 || l > ctx->max_batch || n_grid < 1 || n_grid > RT_MAX_GRID) {
+        ctx->err = std::string(who) + ": B >= 1, M >= 0, B (M + 1) leg slots within max_batch and 1 <= n_grid <= 4096 required"; return MPCMP_EINVAL;
+    }
+    *L = (int)l;
+    return MPCMP_OK;
+}
+
+static int retime_route_check(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                              const mpcmp_retime_spec *spec, const double *prof, const mpcmp_route_retime *out, int *L) {
+    if (int rc = route_shape_check(ctx, "mpcmp_retime_route_batch", B, M, n_grid, L)) return rc;
+    if (!sx || !su || !sT || !prof || !out) { ctx->err = "mpcmp_retime_route_batch: all pointers (but spec and leg_T_new) required"; return MPCMP_EINVAL; }
+    if (spec && !rt_spec_ok(*spec)) {
+        ctx->err = "mpcmp_retime_route_batch: tool maxima >= 0 (+inf: none), a finite rate_max > 0 and groups within MPCMP_RT_ALL_GROUPS required"; return MPCMP_EINVAL;
+    }
+    if (int rc = rows_ok(ctx, *L, BOUND_ROWS)) return rc;
+    return rows_ok(ctx, *L, PAYLOAD_ROWS);
+}
+
+static int retime_route_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                const mpcmp_retime_spec *spec, double *d_prof, double *d_legT, mpcmp_route_retime *d_out, hipStream_t st) {
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, retime_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
+                                    spec ? *spec : rt_default_spec(), d_prof, d_legT, d_out, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_retime_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                               const mpcmp_retime_spec *spec, double *d_prof, double *d_legT, mpcmp_route_retime *d_out,
+                                               void *hip_stream) {
+    int L;
+    if (int rc = retime_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return retime_route_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_legT, d_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_retime_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                                        const mpcmp_retime_spec *spec, double *prof, double *leg_T_new, mpcmp_route_retime *out) {
+    int L;
+    if (int rc = retime_route_check(ctx, B, M, sx, su, sT, n_grid, spec, prof, out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nl = L, NL = (size_t)ctx->N * nl;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof, *dleg = nullptr;
+    mpcmp_route_retime *dout;
+    sg.in(&dx, sx, ctx->nx * NL); sg.in(&du, su, ctx->nu * NL); sg.in(&dT, sT, nl); sg.out(&dprof, prof, nl * (n_grid + 1) * 2);
+    if (leg_T_new) sg.out(&dleg, leg_T_new, nl);
+    sg.out(&dout, out, (size_t)B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = retime_route_enqueue(ctx, B, M, dx, du, dT, n_grid, spec, dprof, dleg, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+static int sample_retimed_route_check(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                                      const double *prof, int n_pts, const double *out, int *L) {
+    if (int rc = route_shape_check(ctx, "mpcmp_sample_retimed_route_batch", B, M, n_grid, L)) return rc;
+    if (n_pts < 1 || !sx || !su || !sT || !prof || !out) {
+        ctx->err = "mpcmp_sample_retimed_route_batch: n_pts >= 1 and all pointers required"; return MPCMP_EINVAL;
+    }
+    return rows_ok(ctx, *L, PAYLOAD_ROWS);
+}
+
+extern "C" int mpcmp_sample_retimed_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT,
+                                                       int n_grid, const double *d_prof, int n_pts, double *d_out, void *hip_stream) {
+    int L;
+    if (int rc = sample_retimed_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, sample_retimed_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, d_sx, d_su, d_sT, d_prof, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sample_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                                                const double *prof, int n_pts, double *out) {
+    int L;
+    if (int rc = sample_retimed_route_check(ctx, B, M, sx, su, sT, n_grid, prof, n_pts, out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nl = L, NL = (size_t)ctx->N * nl;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof, *dout;
+    sg.in(&dx, sx, ctx->nx * NL); sg.in(&du, su, ctx->nu * NL); sg.in(&dT, sT, nl); sg.in(&dprof, prof, nl * (n_grid + 1) * 2);
+    sg.out(&dout, out, (size_t)B * (n_pts + 1) * (1 + 28 * (size_t)ctx->narm));
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_sample_retimed_route_batch_device(ctx, B, M, dx, du, dT, n_grid, dprof, n_pts, dout, ctx->stream)) return rc;
     return sg.finish();
 }
 

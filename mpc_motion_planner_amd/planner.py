@@ -467,6 +467,41 @@ class Solver:
         check(lib().mpcmp_sample_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_pts), out or None,
                                                     stream or None), self._ctx)
 
+    # -- route retiming (include/mpcmp_route_retime.h)
+    def retime_route(self, sx, su, sT, n_grid=200, spec=None):
+        """mpcmp_retime_route_batch: ONE rate profile per route across its via points, for the [B][M+1][..] arrays solve_route returns, under the
+        bound and payload rows of the leg slots and the capi.RETIME_SPEC_DTYPE record `spec` (None: no tool limits, never faster than the plan, all
+        groups).  Returns (prof [B][M+1][n_grid + 1][2] = (t_k, x_k) with leg times, leg_T_new [B][M+1], capi.ROUTE_RETIME_DTYPE [B])"""
+        sx, su, sT, B, M = self._route_traj(sx, su, sT)
+        spec = capi._retime_spec_arg(spec)
+        prof, leg_T = np.zeros((B, M + 1, max(int(n_grid), 0) + 1, 2)), np.zeros((B, M + 1))
+        out = np.zeros(B, dtype=capi.ROUTE_RETIME_DTYPE)
+        check(lib().mpcmp_retime_route_batch(self._ctx, B, M, host(sx), host(su), host(sT), int(n_grid), None if spec is None else spec.ctypes.data,
+                                             host(prof), host(leg_T), host(out)), self._ctx)
+        return prof, leg_T, out
+
+    def retime_route_device(self, B, M, sol_x, sol_u, sol_T, n_grid, prof, out, leg_T_new=0, spec=None, stream=0):
+        """spec: a capi.RETIME_SPEC_DTYPE record on the HOST (capi.retime_spec) or None; everything else raw device pointers (0 = NULL for leg_T_new)"""
+        check(lib().mpcmp_retime_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_grid),
+                                                    None if spec is None else np.ascontiguousarray(spec).ctypes.data, prof or None,
+                                                    leg_T_new or None, out or None, stream or None), self._ctx)
+
+    def sample_retimed_route(self, sx, su, sT, prof, n_pts=200):
+        """mpcmp_sample_retimed_route_batch: [B][n_pts + 1][1 + 28 narm] = the route time i T_new / n_pts, then per arm q, qd, qdd, tau of the routes
+        retimed by `prof` (what retime_route returned), on one clock across the junctions; NaN rows for a failed route.  One arm or two."""
+        sx, su, sT, B, M = self._route_traj(sx, su, sT)
+        prof = f64(prof)
+        if prof.ndim != 4 or prof.shape[:2] != (B, M + 1) or prof.shape[2] < 2 or prof.shape[3] != 2:
+            raise ValueError("prof must be [B][M+1][n_grid + 1][2] = [%d][%d][..][2]" % (B, M + 1))
+        out = np.zeros((B, max(int(n_pts), 0) + 1, 1 + 2 * self.nx))
+        check(lib().mpcmp_sample_retimed_route_batch(self._ctx, B, M, host(sx), host(su), host(sT), prof.shape[2] - 1, host(prof), int(n_pts),
+                                                     host(out)), self._ctx)
+        return out
+
+    def sample_retimed_route_device(self, B, M, sol_x, sol_u, sol_T, n_grid, prof, n_pts, out, stream=0):
+        check(lib().mpcmp_sample_retimed_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_grid),
+                                                            prof or None, int(n_pts), out or None, stream or None), self._ctx)
+
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
         x0, xf = f64(x0), f64(xf)
@@ -823,6 +858,23 @@ class BatchMotionPlanner:
         if self._route is not None or getattr(self, "_retimed", None) is None:
             raise ValueError("call retime() after solve_trajectory() first (direct moves)")
         return self._solver.sample_retimed(self._sol[0], self._sol[1], self._sol[2], self._retimed[0], n_pts)
+
+    def retime_route(self, n_grid=200, spec=None):
+        """the last route solve retimed as whole routes, one profile across the via points (Solver.retime_route): (prof [B][M + 1][n_grid + 1][2]
+        with leg times, leg_T_new [B][M + 1], capi.ROUTE_RETIME_DTYPE [B]).  The profiles are kept for get_retimed_route_trajectory."""
+        if self._route is None:
+            raise ValueError("call set_via_points() and solve_trajectory() first (routes); retime() retimes direct moves")
+        r = self._route
+        self._route_retimed = (r, self._solver.retime_route(r["sol_x"], r["sol_u"], r["sol_T"], n_grid, spec))
+        return self._route_retimed[1]
+
+    def get_retimed_route_trajectory(self, n_pts=200):
+        """get_MPC_trajectory on the retimed clock of the route: [B][n_pts + 1][29] from the profiles of the last retime_route call"""
+        kept = getattr(self, "_route_retimed", None)
+        if self._route is None or kept is None or kept[0] is not self._route:       # (a profile belongs to the route it was computed for)
+            raise ValueError("call retime_route() after a route solve first")
+        r = self._route
+        return self._solver.sample_retimed_route(r["sol_x"], r["sol_u"], r["sol_T"], kept[1][0], n_pts)
 
     # extension beyond the reference's members: a straight tool line as the plan (include/mpcmp_toolpath.h)
     def plan_tool_line(self, R, p, T=None, spec=None):

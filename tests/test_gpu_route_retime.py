@@ -1,0 +1,383 @@
+"""Route retiming on the GPU (mpcmp_retime_route_batch*, mpcmp_sample_retimed_route_batch*) against the NumPy restatement of
+tests/route_retime_reference.py, with the case builder, the bounds and the fair-test conditions of tests/test_route_retime_host.py.
+
+Cases: (num_seg, arms) in (1, 1), (4, 1), (6, 2); M in {0, 1, 3}; n_grid in {1, 50, 70}: n_grid 70 puts a chunk boundary inside every leg, n_grid 1
+makes every point a junction or an end.  16 routes, so at most 64 legs of 71 points.
+
+The limits (test 3) are checked at every grid point of a route with the w of the interval that STARTS there, which is what the rule enforces: a
+junction is one grid point, and its acceleration and torque rows are those of point 0 of the later leg.  tests/test_retime_host.py::
+check_limits_hold looks at the last point of a plan with the w of the interval before it, which holds for its inputs because their ends are at rest;
+at the moving last point of a leg the rule has no row with w (include/mpcmp_retime.h, "Ends"), so test_route_retime_host.py::check_route_limits_hold leaves the acceleration
+and the torque of that point to the later leg, and checks its velocity and tool speeds in both legs.
+
+Largest deviations seen (run with -s): see DESIGN.md, "Route retiming".
+"""
+import numpy as np
+import pytest
+
+import retime_reference as R
+import route_retime_reference as RR
+from test_gpu_limits import MARGINS, robot, solver
+from test_retime_host import TIGHT, rows
+from test_route_retime_host import (B, CASES, assert_reference_is_a_fair_test, case, check_route_against, check_route_limits_hold, route_moves,
+                                    route_reference, route_rows, route_tool_maxima)
+
+pytestmark = pytest.mark.gpu
+EINVAL = -1
+
+
+@pytest.fixture(scope="module")
+def M():
+    import mpc_motion_planner_amd as M
+    return M
+
+
+def route_solver(M, narm, nseg, nvia, table=None, nb=B):
+    s = solver(M, narm, nseg, max_batch=nb * (nvia + 1))
+    if table is not None:
+        s.set_bounds(np.ascontiguousarray(table).reshape(-1))
+    return s
+
+
+def flat(sx, su, sT):
+    """the [B][M+1][..] arrays as the L legs the per-leg entry points take"""
+    L = sT.size
+    return sx.reshape((L,) + sx.shape[2:]), su.reshape((L,) + su.shape[2:]), sT.reshape(L)
+
+
+# ---- 1. parity, 2. junctions (check_route_against holds the stored-twice x, leg_T_new and the sequential sum) --------------------------------
+@pytest.mark.parametrize("nseg,narm,nvia,n_grid", CASES)
+def test_parity_with_the_numpy_reference(M, nseg, narm, nvia, n_grid):
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, ref, amp = case(narm, nseg, nvia, n_grid)
+    counts = assert_reference_is_a_fair_test(ref, amp, counts=n_grid >= 50 and nvia >= 1)
+    s = route_solver(M, narm, nseg, nvia, route_rows(M, nseg, narm, nvia, n_grid))
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, M.retime_spec(lin_max, ang_max))
+    worst = [0.0, 0.0]
+    try:
+        check_route_against(ref, prof, leg_T, rec, worst=worst)
+    finally:
+        print("nseg %d, arms %d, M %d, n_grid %d: slowed / untouched / infeasible %s, amplification %.1f, max |x / ref - 1| %.1e, |T_new / ref - 1| %.1e"
+              % (nseg, narm, nvia, n_grid, counts, amp, worst[0], worst[1]))
+
+
+@pytest.mark.parametrize("nseg,narm,nvia", [(4, 1, 1), (6, 2, 3)])
+def test_junctions_in_the_samplers(M, nseg, narm, nvia):
+    """qd on the two sides of a junction, from the per-leg sampler at a leg's last and the next leg's first sample, agrees within 1e-9 of the
+    velocity bound; the route sampler gives the rows of the reference on one clock, and a junction sample is the later leg's first row"""
+    n_grid, n_pts = 50, 24
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, ref, _ = case(narm, nseg, nvia, n_grid)
+    table = route_rows(M, nseg, narm, nvia, n_grid)
+    s = route_solver(M, narm, nseg, nvia, table)
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, M.retime_spec(lin_max, ang_max))
+    ok = np.flatnonzero(rec["status"] == 0)
+    assert len(ok) >= 5
+    legs = s.sample_retimed(*flat(sx, su, sT), prof.reshape((-1,) + prof.shape[2:]), n_pts).reshape(B, nvia + 1, n_pts + 1, -1)
+    for b in ok:
+        for m in range(nvia):
+            vb = np.tile(np.asarray(table[b, m]["ubx"][7:]), narm)
+            for a in range(narm):
+                d = np.abs(legs[b, m, -1, 8 + 28 * a:15 + 28 * a] - legs[b, m + 1, 0, 8 + 28 * a:15 + 28 * a])
+                assert (d <= 1e-9 * vb[7 * a:7 * a + 7]).all(), (b, m, a, d.max())
+                assert np.abs(legs[b, m, -1, 8 + 28 * a:15 + 28 * a]).max() > 1e-3          # (the junction is moving)
+    got = s.sample_retimed_route(sx, su, sT, prof, n_pts)
+    assert got.shape == (B, n_pts + 1, 1 + 28 * narm)
+    models = robot(M, narm)
+    for b in ok[:4]:
+        want = RR.sample_retimed_route_np(models, nseg, sx[b], su[b], sT[b], prof[b], n_pts)
+        assert np.abs(got[b] - want).max() <= 1e-9, (b, np.abs(got[b] - want).max())
+        assert got[b][0, 0] == 0.0 and got[b][-1, 0] == rec[b]["T_new"]
+    for b in np.flatnonzero(rec["status"] != 0):
+        assert np.isnan(got[b]).all()
+    # a sample exactly on a junction: two legs of equal retimed length by hand, n_pts = 2, so sample 1 lies at E_0 and belongs to leg 1 at s = 0
+    hand = np.zeros((1, 2, 2, 2)); hand[0, :, :, 1] = 0.25; hand[0, :, 1, 0] = 3.0
+    one = route_solver(M, narm, nseg, 1, nb=1).sample_retimed_route(sx[:1, :2], su[:1, :2], np.full((1, 2), 1.5), hand, 2)
+    nq = 7 * narm
+    for a in range(narm):
+        assert np.abs(one[0, 1, 1 + 28 * a:8 + 28 * a] - sx[0, 1, 0, 7 * a:7 * a + 7]).max() <= 1e-12
+        assert np.abs(one[0, 1, 8 + 28 * a:15 + 28 * a] - 0.5 * sx[0, 1, 0, nq + 7 * a:nq + 7 * a + 7]).max() <= 1e-12
+    assert one[0, 1, 0] == 3.0 and one[0, 2, 0] == 6.0
+
+
+# ---- 3. the limits hold ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nseg,narm,nvia", [(4, 1, 1), (4, 1, 3), (6, 2, 1), (6, 2, 3)])
+def test_the_limits_hold(M, nseg, narm, nvia):
+    n_grid = 50
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, ref, _ = case(narm, nseg, nvia, n_grid)
+    table = route_rows(M, nseg, narm, nvia, n_grid)
+    s = route_solver(M, narm, nseg, nvia, table)
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, M.retime_spec(lin_max, ang_max))
+    ok = np.flatnonzero(rec["status"] == 0)
+    assert len(ok) >= 8
+    for b in ok:
+        check_route_limits_hold(ref[b]["P"], table[b], sT[b], prof[b, :, :, 1], lin_max, ang_max, what=b)
+
+
+# ---- 4. the gain over retiming leg by leg ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nseg,narm,nvia", [(1, 1, 1), (4, 1, 1), (4, 1, 3), (6, 2, 1), (6, 2, 3)])
+def test_the_gain_over_retiming_leg_by_leg(M, nseg, narm, nvia):
+    """at least 3 routes have a leg that is INFEASIBLE retimed on its own (its moving end is pinned to x == 1) and are feasible as routes; where
+    every leg is feasible on its own, T_new <= (the sum of the legs' T_new) (1 + 1e-9): the pinned per-leg profiles joined are one feasible
+    profile of the route problem and the forward pass is pointwise maximal; the margin covers the rounding of two sums of the same kind"""
+    n_grid = 50
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, _, _ = case(narm, nseg, nvia, n_grid)
+    spec = M.retime_spec(lin_max, ang_max)
+    s = route_solver(M, narm, nseg, nvia, route_rows(M, nseg, narm, nvia, n_grid))
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, spec)
+    _, leg_rec = s.retime(*flat(sx, su, sT), n_grid, spec)
+    leg_rec = leg_rec.reshape(B, nvia + 1)
+    some_leg_fails = (leg_rec["status"] != 0).any(axis=1)
+    gained = int((some_leg_fails & (rec["status"] == 0)).sum())
+    both = np.flatnonzero(~some_leg_fails)
+    for b in both:
+        total = leg_rec[b, 0]["T_new"]
+        for m in range(1, nvia + 1):
+            total = total + leg_rec[b, m]["T_new"]
+        assert rec[b]["status"] == 0 and rec[b]["T_new"] <= total * (1 + 1e-9), (b, rec[b]["T_new"], total)
+    feas = rec["status"] == 0
+    print("nseg %d, arms %d, M %d: feasible leg by leg %d of %d, as routes %d; %d routes gained; median T_new %.4f (routes, where both are feasible) "
+          "beside %.4f (legs)" % (nseg, narm, nvia, len(both), B, int(feas.sum()), gained, np.median(rec["T_new"][both]) if len(both) else np.nan,
+                                  np.median(leg_rec["T_new"][both].sum(axis=1)) if len(both) else np.nan))
+    assert gained >= 3, gained
+
+
+@pytest.mark.parametrize("nseg,narm,nvia", [(4, 1, 1), (6, 2, 3)])
+def test_a_route_may_pass_a_via_faster_than_planned(M, nseg, narm, nvia):
+    """rate_max 1.5 under the loose row: at least 3 routes have a junction x above 1, which no leg-by-leg retiming can give"""
+    n_grid = 50
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, ref, _ = case(narm, nseg, nvia, n_grid)
+    table = M.Solver.repeat(np.repeat(rows(M, B, nseg, narm)[0:1], B), nvia).reshape(B, nvia + 1)
+    want = route_reference(table, sT, n_grid, lin_max, ang_max, [r["P"] for r in ref], rate_max=1.5)
+    s = route_solver(M, narm, nseg, nvia, table)
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, M.retime_spec(lin_max, ang_max, 1.5))
+    check_route_against(want, prof, leg_T, rec, 1.5, "rate_max 1.5")
+    fast = int(((rec["status"] == 0) & (prof[:, :-1, n_grid, 1] > 1.0).any(axis=1)).sum())
+    assert fast >= 3 and (prof[rec["status"] == 0][..., 1] <= 1.5 ** 2).all(), fast
+    for b in np.flatnonzero(rec["status"] == 0):
+        check_route_limits_hold(ref[b]["P"], table[b], sT[b], prof[b, :, :, 1], lin_max, ang_max, what=b)
+
+
+# ---- 5. M == 0 ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nseg,narm", [(1, 1), (4, 1), (6, 2)])
+@pytest.mark.parametrize("n_grid", [1, 50, 70])
+def test_no_via_is_the_retiming_of_a_plan(M, nseg, narm, n_grid):
+    """status and k_fail equal, x and T_new within 1e-11 relative: the source text is the same, only floating-point contraction may differ between
+    the two kernels, and its 2^-53 per operation is multiplied by the asserted amplification (<= 100)"""
+    sx, su, sT = route_moves(narm, nseg, 0)
+    lin_max, ang_max, _, _ = case(narm, nseg, 0, n_grid)
+    spec = M.retime_spec(lin_max, ang_max)
+    s = route_solver(M, narm, nseg, 0, route_rows(M, nseg, narm, 0, n_grid))
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, spec)
+    p1, r1 = s.retime(*flat(sx, su, sT), n_grid, spec)
+    assert (rec["status"] == r1["status"]).all() and (rec["k_fail"] == r1["k_fail"]).all()
+    assert (rec["leg_fail"] == np.where((r1["status"] != 0) & (r1["k_fail"] >= 0), 0, -1)).all()
+    ok = r1["status"] == 0
+    assert np.allclose(prof[ok, 0], p1[ok], rtol=1e-11, atol=0.0) and np.allclose(rec["T_new"][ok], r1["T_new"][ok], rtol=1e-11, atol=0.0)
+    assert (rec["n_slowed"] == r1["n_slowed"]).all() and (rec["s_slowest"] == r1["s_slowest"]).all() and (rec["leg_slowest"][ok] == 0).all()
+    assert np.isnan(prof[~ok]).all() and (leg_T[:, 0][ok] == rec["T_new"][ok]).all()
+    print("nseg %d, arms %d, n_grid %d: M == 0 against mpcmp_retime_batch bitwise equal: %s"
+          % (nseg, narm, n_grid, prof[:, 0].tobytes() == p1.tobytes() and rec["T_new"].tobytes() == r1["T_new"].tobytes()))
+
+
+# ---- 6. identity ----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nseg,narm,nvia", [(4, 1, 3), (6, 2, 1)])
+def test_no_group_or_no_bound_is_the_route_as_planned(M, nseg, narm, nvia):
+    n_grid, n_pts = 50, 37
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    free = np.zeros((B, nvia + 1), dtype=M.BOUNDS_DTYPE)
+    for name in ("lbx", "lbu", "lbg"):
+        free[name] = -np.inf
+    for name in ("ubx", "ubu", "ubg"):
+        free[name] = np.inf
+    for table, spec in ((route_rows(M, nseg, narm, nvia), M.retime_spec(0.1, 0.1, 1.0, 0)), (free, None)):
+        s = route_solver(M, narm, nseg, nvia, table)
+        prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, spec)
+        assert (rec["status"] == 0).all() and (rec["n_slowed"] == 0).all() and (rec["rate_min"] == 1.0).all()
+        assert (rec["leg_fail"] == -1).all() and (rec["k_fail"] == -1).all() and (rec["leg_slowest"] == 0).all() and (rec["s_slowest"] == 0.0).all()
+        assert (prof[..., 1] == 1.0).all() and (np.abs(leg_T - sT) <= 1e-12).all()
+    got = s.sample_retimed_route(sx, su, sT, prof, n_pts)
+    if narm == 1:
+        assert np.abs(got - s.sample_route(sx, su, sT, n_pts)).max() <= 1e-10
+
+
+# ---- 7. a solved route ----------------------------------------------------------------------------------------------------------------------
+def test_a_solved_route(M):
+    """B = 8 routes with M = 2 vias solved at num_seg 4 (chord rule at speed 0.5, 3 SQP iterations); the rows are applied after the solve.  Under the
+    tight row of tests/test_retime_host.py: parity with the reference, and the sampler's last row reaches the route's end.  The benchmark states
+    these routes run between are MOVING (up to 0.9 of the velocity limit), so both ends of a route are pinned to x == 1, and under the tight row
+    every one of the 8 routes is infeasible at or next to its end (leg 2, k_fail 50 or 47): the end check would pass over nothing.  So the same
+    checks run a second time under the margins of the solve with the acceleration margin 0.6 and the torque margin 1 (a solved plan holds its own
+    limits to the solver's tolerances only, which a pinned end does not forgive), where the tool maxima slow the routes: at least 3 must be
+    feasible and one slowed.  The route's end is the last node of its last leg: the solve reaches the target within its terminal box (eps_target
+    = 1e-2) at best, not within 1e-9, and a sampler can only reach what the plan reaches.  A pinned end makes the reference flag every route as near
+    (hi == rate_max^2 == 1 exactly), so what is bounded here is the number of routes whose status differs under that exemption"""
+    from mpc_motion_planner_amd import scenarios
+    from test_gpu_routes import _jmax, _vias
+    nseg, nb, nvia, n_grid = 4, 8, 2, 50
+    s = M.Solver(M.default_config(nseg, 3, margins=MARGINS), nb * (nvia + 1))
+    x0, xf = scenarios.make_batch(nb, MARGINS)
+    via = _vias(M, x0, xf, nvia, 1)
+    r = s.solve_route(x0, via, xf, speed=0.5, jmax=_jmax(M))
+    sx, su, sT = r["sol_x"], r["sol_u"], r["sol_T"]
+    assert np.isfinite(sx).all() and np.isfinite(su).all() and (sT > 0).all()
+    models = robot(M, 1)
+    P = [RR.route_path_values(models, nseg, sx[b], su[b], sT[b], n_grid) for b in range(nb)]
+    lin_max, ang_max = route_tool_maxima(P)
+    for name, margins in (("tight", TIGHT), ("solve", (MARGINS[0], MARGINS[1], 0.6, 1.0, MARGINS[4]))):
+        table = np.repeat(M.bounds_from_margins(*margins), nb * (nvia + 1)).reshape(nb, nvia + 1)
+        s.set_bounds(table.reshape(-1))
+        ref = route_reference(table, sT, n_grid, lin_max, ang_max, P)
+        prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, M.retime_spec(lin_max, ang_max))
+        worst, exempt = [0.0, 0.0], None
+        try:
+            exempt = check_route_against(ref, prof, leg_T, rec, what=name, worst=worst)
+        finally:
+            ok = np.flatnonzero(rec["status"] == 0)
+            print("solved routes, %s row: %d of %d feasible, %d near an empty set on the reference, rate_min %s, (leg_fail, k_fail) %s, max |x / ref - 1| %.1e, "
+                      "|T_new / ref - 1| %.1e" % (name, len(ok), nb, sum(r_["near"] for r_ in ref), np.round(rec["rate_min"], 3), list(zip(rec["leg_fail"].tolist(), rec["k_fail"].tolist())), worst[0], worst[1]))
+        assert exempt <= 1, (exempt, sum(r_["near"] for r_ in ref))       # (routes passed over as near an empty set, with another status)
+        got = s.sample_retimed_route(sx, su, sT, prof, 30)
+        for b in ok:
+            assert np.abs(got[b, -1, 1:8] - sx[b, -1, -1, :7]).max() <= 1e-9, (name, b, np.abs(got[b, -1, 1:8] - sx[b, -1, -1, :7]).max())
+            assert got[b, -1, 0] == rec[b]["T_new"], (name, b)
+            check_route_limits_hold(P[b], table[b], sT[b], prof[b, :, :, 1], lin_max, ang_max, what=(name, b))
+        assert np.isnan(got[rec["status"] != 0]).all()
+    assert len(ok) >= 3 and (rec["rate_min"][ok] < 0.99).any(), (len(ok), rec["rate_min"])
+
+
+# ---- 8. failures and arguments --------------------------------------------------------------------------------------------------------------
+def test_a_bad_leg_fails_its_route_only(M):
+    nseg, narm, nvia, n_grid = 4, 1, 3, 70
+    sx, su, sT = [np.array(a) for a in route_moves(narm, nseg, nvia)]
+    lin_max, ang_max, _, _ = case(narm, nseg, nvia, n_grid)
+    spec = M.retime_spec(lin_max, ang_max)
+    s = route_solver(M, narm, nseg, nvia, route_rows(M, nseg, narm, nvia, n_grid))
+    clean = s.retime_route(sx, su, sT, n_grid, spec)
+    assert clean[2]["status"][[2, 4, 6]].tolist() == [0, 0, 0]
+    sx[2, 2, 5, 3] = np.nan; su[4, 0, 1, 1] = np.inf; sT[6, 3] = -1.0
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, spec)
+    for b in range(B):
+        if b in (2, 4, 6):
+            assert rec[b]["status"] == RR.NAN and (rec[b]["leg_fail"], rec[b]["k_fail"], rec[b]["leg_slowest"]) == (-1, -1, -1)
+            assert np.isnan(prof[b]).all() and np.isposinf(leg_T[b]).all() and np.isposinf(rec[b]["T_new"]) and rec[b]["rate_min"] == 0.0
+        else:
+            assert prof[b].tobytes() == clean[0][b].tobytes() and leg_T[b].tobytes() == clean[1][b].tobytes() and rec[b].tobytes() == clean[2][b].tobytes(), b
+    assert np.isnan(s.sample_retimed_route(sx, su, sT, prof, 8)[[2, 4, 6]]).all()
+
+
+def test_bad_arguments_write_nothing(M):
+    nseg, narm, nb, nvia, n_grid = 4, 1, 3, 1, 50
+    sx, su, sT = [np.ascontiguousarray(a[:nb]) for a in route_moves(narm, nseg, nvia)]
+    s = solver(M, narm, nseg, max_batch=8)
+    L, ctx = M.lib(), s._ctx
+    prof = np.full((nb, nvia + 1, n_grid + 1, 2), 7.0); leg_T = np.full((nb, nvia + 1), 7.0)
+    rec = np.zeros(nb, dtype=M.ROUTE_RETIME_DTYPE); rec["k_fail"] = -7
+    out = np.full((nb, 11, 29), 7.0)
+    good_spec = M.retime_spec(1.0, 2.0)
+    ptr = lambda a: None if a is None else a.ctypes.data
+
+    def call(B=nb, M_=nvia, x=sx, u=su, T=sT, n_grid=n_grid, spec=good_spec, p=prof, lt=leg_T, r=rec, device=False):
+        a = [ctx, B, M_, ptr(x), ptr(u), ptr(T), n_grid, ptr(spec), ptr(p), ptr(lt), ptr(r)]
+        return L.mpcmp_retime_route_batch_device(*a, None) if device else L.mpcmp_retime_route_batch(*a)
+
+    bad = [dict(B=0), dict(B=5), dict(M_=-1), dict(M_=2, B=3), dict(n_grid=0), dict(n_grid=4097), dict(x=None), dict(u=None), dict(T=None),
+           dict(p=None), dict(r=None), dict(spec=M.retime_spec(rate_max=0.0)), dict(spec=M.retime_spec(rate_max=np.inf)),
+           dict(spec=M.retime_spec(rate_max=np.nan)), dict(spec=M.retime_spec(groups=1)), dict(spec=M.retime_spec(groups=0x16E)),
+           dict(spec=M.retime_spec(-1e-3)), dict(spec=M.retime_spec(1.0, np.nan))]
+    for kw in bad:
+        assert call(**kw) == EINVAL, kw
+        assert call(device=True, **kw) == EINVAL, kw          # (nothing is launched: the host addresses are never read)
+    assert L.mpcmp_retime_route_batch(None, nb, nvia, ptr(sx), ptr(su), ptr(sT), n_grid, None, ptr(prof), ptr(leg_T), ptr(rec)) == EINVAL
+
+    def sample(B=nb, M_=nvia, x=sx, T=sT, n_grid=n_grid, p=prof, n_pts=10, o_=out, device=False):
+        a = [ctx, B, M_, ptr(x), ptr(su), ptr(T), n_grid, ptr(p), n_pts, ptr(o_)]
+        return L.mpcmp_sample_retimed_route_batch_device(*a, None) if device else L.mpcmp_sample_retimed_route_batch(*a)
+
+    for kw in (dict(B=0), dict(B=5), dict(M_=-1), dict(n_grid=0), dict(n_grid=4097), dict(n_pts=0), dict(x=None), dict(T=None), dict(p=None), dict(o_=None)):
+        assert sample(**kw) == EINVAL, kw
+        assert sample(device=True, **kw) == EINVAL, kw
+    # fewer rows in force than leg slots
+    s.set_bounds(rows(M, 5))
+    assert call() == EINVAL
+    s.clear_bounds()
+    s.set_payloads(np.ones(5))
+    assert call() == EINVAL and sample() == EINVAL
+    s.clear_payloads()
+    assert (prof == 7.0).all() and (leg_T == 7.0).all() and (rec["k_fail"] == -7).all() and (out == 7.0).all()
+    assert call() == 0 and (rec["k_fail"] != -7).all() and sample() == 0
+    ok = rec["status"] == 0
+    assert ok.any() and (leg_T[ok] == prof[ok][:, :, n_grid, 0]).all() and (out[ok][:, 0, 0] == 0.0).all() and np.isnan(out[~ok]).all()
+    again = prof.copy()
+    assert call(lt=None) == 0 and prof.tobytes() == again.tobytes()        # leg_T_new may be NULL
+
+
+@pytest.mark.parametrize("nseg,narm,nvia", [(4, 1, 3), (6, 2, 1)])
+def test_device_variant_and_independence_of_the_batch(M, nseg, narm, nvia):
+    import torch
+    n_grid = 70
+    sx, su, sT = route_moves(narm, nseg, nvia)
+    lin_max, ang_max, _, _ = case(narm, nseg, nvia, n_grid)
+    spec = M.retime_spec(lin_max, ang_max)
+    table = route_rows(M, nseg, narm, nvia, n_grid)
+    s = route_solver(M, narm, nseg, nvia, table)
+    prof, leg_T, rec = s.retime_route(sx, su, sT, n_grid, spec)
+    smp = s.sample_retimed_route(sx, su, sT, prof, 10)
+    dx, du, dT = [torch.from_numpy(np.array(a)).cuda() for a in (sx, su, sT)]
+    dprof = torch.zeros(prof.shape, dtype=torch.float64, device="cuda")
+    dleg = torch.zeros(leg_T.shape, dtype=torch.float64, device="cuda")
+    drec = torch.zeros(B * M.ROUTE_RETIME_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    dout = torch.zeros(smp.shape, dtype=torch.float64, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    s.retime_route_device(B, nvia, dx.data_ptr(), du.data_ptr(), dT.data_ptr(), n_grid, dprof.data_ptr(), drec.data_ptr(), dleg.data_ptr(), spec, stream=stream)
+    s.sample_retimed_route_device(B, nvia, dx.data_ptr(), du.data_ptr(), dT.data_ptr(), n_grid, dprof.data_ptr(), 10, dout.data_ptr(), stream=stream)
+    torch.cuda.synchronize()
+    assert dprof.cpu().numpy().tobytes() == prof.tobytes() and dleg.cpu().numpy().tobytes() == leg_T.tobytes()
+    assert drec.cpu().numpy().tobytes() == rec.tobytes() and dout.cpu().numpy().tobytes() == smp.tobytes()
+    # a route alone, and the batch in another order
+    for b in (0, 1, 7):
+        s.set_bounds(np.ascontiguousarray(table[b]))
+        p1, l1, r1 = s.retime_route(sx[b:b + 1], su[b:b + 1], sT[b:b + 1], n_grid, spec)
+        assert p1.tobytes() == prof[b:b + 1].tobytes() and l1.tobytes() == leg_T[b:b + 1].tobytes() and r1.tobytes() == rec[b:b + 1].tobytes(), b
+    perm = np.random.default_rng(5).permutation(B)
+    s.set_bounds(np.ascontiguousarray(table[perm]).reshape(-1))
+    pp, lp, rp = s.retime_route(sx[perm], su[perm], sT[perm], n_grid, spec)
+    assert pp.tobytes() == prof[perm].tobytes() and lp.tobytes() == leg_T[perm].tobytes() and rp.tobytes() == rec[perm].tobytes()
+
+
+# ---- 9. the facade --------------------------------------------------------------------------------------------------------------------------
+def test_planner_facade(M):
+    from mpc_motion_planner_amd import scenarios
+    from test_gpu_routes import _vias
+    p = M.BatchMotionPlanner(max_batch=8, num_seg=2, sqp_iters=3)
+    p.set_constraint_margins(*MARGINS)
+    x0, xf = scenarios.make_batch(2, MARGINS)
+    p.set_current_state(x0[:, :7], x0[:, 7:]); p.set_target_state(xf[:, :7], xf[:, 7:])
+    p.solve_trajectory()
+    for call in (p.retime_route, p.get_retimed_route_trajectory):
+        with pytest.raises(ValueError):
+            call()
+    p.set_via_points(_vias(M, x0, xf, 2, 1))
+    p.solve_trajectory()
+    with pytest.raises(ValueError):
+        p.get_retimed_route_trajectory()
+    spec = M.retime_spec(1.7, 2.5)
+    prof, leg_T, rec = p.retime_route(n_grid=60, spec=spec)
+    sx, su, sT = p.solution()
+    assert prof.shape == (2, 3, 61, 2) and leg_T.shape == (2, 3) and rec.shape == (2,) and rec.dtype == M.ROUTE_RETIME_DTYPE
+    want = p._solver.retime_route(sx, su, sT, 60, spec)
+    assert prof.tobytes() == want[0].tobytes() and rec.tobytes() == want[2].tobytes()
+    traj = p.get_retimed_route_trajectory(30)
+    assert traj.shape == (2, 31, 29) and traj.tobytes() == p._solver.sample_retimed_route(sx, su, sT, prof, 30).tobytes()
+    legs = p.retime(n_grid=60, spec=spec)                  # still leg by leg
+    assert legs[0].shape == (2, 3, 61, 2) and legs[1].shape == (2, 3) and legs[1].dtype == M.RETIME_DTYPE
+    with pytest.raises(ValueError):
+        p.get_retimed_trajectory()
+    p.set_via_points(None)
+    p.solve_trajectory()
+    for call in (p.retime_route, p.get_retimed_route_trajectory):
+        with pytest.raises(ValueError):
+            call()
