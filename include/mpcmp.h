@@ -553,6 +553,7 @@ int mpcmp_sample_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sol_x, 
 int mpcmp_sample_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sol_x, const double *d_sol_u, const double *d_sol_T, int n_pts,
                                     double *d_out, void *hip_stream);
 #include "mpcmp_route_retime.h"
+#include "mpcmp_retimed_check.h"
 
 /* ---- receding-horizon driver (BASELINE.json config #5) ---- */
 /* B instances; every step = re-solve warm-started from the previous solution with the reference's re-guess rule

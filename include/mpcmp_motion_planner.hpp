@@ -362,6 +362,16 @@ class MotionPlanner {
         chk(mpcmp_sample_retimed_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, retime_grid_, retime_prof_.data(), NP, out.data()));
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
     }
+    // limit record of the RETIMED plan between its grid points, at n_pts + 1 uniform times in [0, T_new] (include/mpcmp_retimed_check.h): the
+    // record of check_limits for the motion the profile of the last retime() stands for, times on the retimed clock; call retime() first.  T_new
+    // (may be NULL): the retimed duration.  status MPCMP_LIM_NAN and T_new +inf if the plan could not be retimed.  spec NULL: tol 0, no tool limits
+    mpcmp_limits check_retimed_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr, double *T_new = nullptr) {
+        if (retime_grid_ < 1) throw std::runtime_error("check_retimed_limits: call retime() first");
+        mpcmp_limits r;
+        use_payload(1);
+        chk(mpcmp_limits_retimed_batch(ctx_, 1, sol_x_.data(), sol_u_.data(), &sol_T_, retime_grid_, retime_prof_.data(), n_pts, spec, &r, T_new));
+        return r;
+    }
 
     // A straight tool line from the current state's posture to the pose (R row-major [9], p [3]) as the plan (include/mpcmp_toolpath.h): it becomes the
     // last solution, so check_limits, check_clearance, retime, get_retimed_trajectory and get_MPC_trajectory apply to it.  T <= 0: the duration
@@ -542,6 +552,17 @@ class MotionPlanner {
         chk(mpcmp_sample_retimed_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), route_grid_, route_prof_.data(), NP,
                                              out.data()));
         unpack<NP>(out, time, position_trajectory, velocity_trajectory, acceleration_trajectory, torque_trajectory);
+    }
+    // limit record of the RETIMED route between its grid points, at n_pts + 1 uniform times of the route clock (include/mpcmp_retimed_check.h),
+    // every sample under the rows of its leg; call retime_route() first.  T_new (may be NULL): the retimed duration of the route
+    mpcmp_limits check_retimed_route_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr, double *T_new = nullptr) {
+        if (route_grid_ < 1 || route_leg_T.empty()) throw std::runtime_error("check_retimed_route_limits: call retime_route() first");
+        const int L = (int)route_leg_T.size();
+        mpcmp_limits r;
+        use_payload(L);
+        chk(mpcmp_limits_retimed_route_batch(ctx_, 1, L - 1, route_x_.data(), route_u_.data(), route_leg_T.data(), route_grid_, route_prof_.data(),
+                                             n_pts, spec, &r, T_new));
+        return r;
     }
     // motionPlanner.hpp:73-96 — the jerk-limited trajectory of the last solve_trajectory(true) sampled uniformly, torques by
     // RNEA (motionPlanner.hpp:92); after a solve from another guess: that guess, resampled like the MPC solution

@@ -17,7 +17,7 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
                    LIMITS_SPEC_DTYPE, LIMITS_DTYPE, LIM_GROUPS, LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG, LIM_NAN, limits_spec, limits_config,
                    RETIME_SPEC_DTYPE, RETIME_DTYPE, RT_INFEASIBLE, RT_NAN, RT_ALL_GROUPS, retime_spec, retime_one,
-                   ROUTE_RETIME_DTYPE, retime_route_one,
+                   ROUTE_RETIME_DTYPE, retime_route_one, limits_retimed_one,
                    TOOL_LINE_SPEC_DTYPE, TOOL_LINE_DTYPE, TOOL_DEV_DTYPE, TL_STOPPED, TL_Q_OUT_OF_BOUNDS, TD_OVER, TL_NAN, tool_line_spec, tool_line_one,
                    tool_deviation_one)
 from .planner import BatchMotionPlanner, Solver
@@ -36,4 +36,4 @@ __all__ = ["TOOL_LINE_SPEC_DTYPE", "TOOL_LINE_DTYPE", "TOOL_DEV_DTYPE", "TL_STOP
            "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate",
            "LIMITS_SPEC_DTYPE", "LIMITS_DTYPE", "LIM_GROUPS", "LIM_Q", "LIM_QD", "LIM_QDD", "LIM_TAU", "LIM_HEIGHT", "LIM_TOOL_LIN", "LIM_TOOL_ANG", "LIM_NAN", "limits_spec", "limits_config",
            "RETIME_SPEC_DTYPE", "RETIME_DTYPE", "RT_INFEASIBLE", "RT_NAN", "RT_ALL_GROUPS", "retime_spec", "retime_one",
-           "ROUTE_RETIME_DTYPE", "retime_route_one"]
+           "ROUTE_RETIME_DTYPE", "retime_route_one", "limits_retimed_one"]

@@ -161,6 +161,12 @@ ABI_ROUTE_RETIME = {
     "mpcmp_retime_route_batch": "piipppipppp", "mpcmp_retime_route_batch_device": "piipppippppp", "mpcmp_retime_route_one": "piiipppppippp",
     "mpcmp_sample_retimed_route_batch": "piipppipip", "mpcmp_sample_retimed_route_batch_device": "piipppipipp",
 }
+# ... and every function include/mpcmp_retimed_check.h declares (limits of retimed plans and routes, profile scaling), in its order
+ABI_RETIMED_CHECK = {
+    "mpcmp_limits_retimed_batch": "pipppipippp", "mpcmp_limits_retimed_batch_device": "pipppipipppp",
+    "mpcmp_limits_retimed_route_batch": "piipppipippp", "mpcmp_limits_retimed_route_batch_device": "piipppipipppp",
+    "mpcmp_limits_retimed_one": "piiipppppipipp", "mpcmp_profile_scale_batch": "piipp", "mpcmp_profile_scale_batch_device": "piippp",
+}
 # ... and every function include/mpcmp_toolpath.h declares (tool-line moves), in its order
 ABI_TOOLPATH = {
     "mpcmp_tool_line_batch": "pii" + "p" * 9, "mpcmp_tool_line_batch_device": "pii" + "p" * 10, "mpcmp_tool_line_one": "pipppppdpppp",
@@ -222,7 +228,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_TOOLPATH.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -423,6 +429,37 @@ def retime_route_one(models, num_seg, rows, x, u, T, n_grid=200, spec=None):
     check(lib().mpcmp_retime_route_one(arr, narm, int(num_seg), nl, host(rows), None if spec is None else spec.ctypes.data, host(x), host(u), host(T),
                                        int(n_grid), host(prof), host(leg_T), host(rec)))
     return prof, leg_T, rec[0]
+
+
+def limits_retimed_one(models, num_seg, rows, x, u, T, prof, n_pts=200, spec=None):
+    """mpcmp_limits_retimed_one: the limit record of ONE retimed plan or route on the host (no context, no GPU): n_legs legs x [n_legs][N][14 narm],
+    u [n_legs][N][7 narm], T [n_legs] (a plan: one leg, the leading axis may be left out), leg m under the BOUNDS_DTYPE record rows[m] (one record:
+    every leg under it), prof [n_legs][n_grid + 1][2] as retime_one / retime_route_one left it, the LIMITS_SPEC_DTYPE record `spec` (None: tol 0, no
+    tool limits).  models: a Model or a sequence of them, for every leg.  Returns (the LIMITS_DTYPE record, T_new)."""
+    if isinstance(models, Model):
+        models = [models]
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    T = f64(T).reshape(-1); nl = T.shape[0]
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype != BOUNDS_DTYPE:
+        raise ValueError("rows must be BOUNDS_DTYPE records")
+    rows = np.ascontiguousarray(np.broadcast_to(rows.reshape(-1), (nl,))) if rows.size == 1 else rows.reshape(-1)
+    if rows.shape[0] != nl:
+        raise ValueError("one BOUNDS_DTYPE record per leg (or one for all): %d legs, %d rows" % (nl, rows.shape[0]))
+    if spec is not None:
+        spec = np.ascontiguousarray(spec).reshape(())
+        if spec.dtype != LIMITS_SPEC_DTYPE:
+            raise ValueError("spec must be one LIMITS_SPEC_DTYPE record")
+    x, u = f64(x).reshape(nl, N, 14 * narm), f64(u).reshape(nl, N, 7 * narm)
+    prof = f64(prof)
+    if prof.ndim < 2 or prof.shape[-1] != 2 or prof.size % (2 * nl) or prof.size < 4 * nl:
+        raise ValueError("prof must be [n_legs][n_grid + 1][2] with n_legs = %d" % nl)
+    prof = prof.reshape(nl, -1, 2)
+    rec = np.zeros(1, dtype=LIMITS_DTYPE); T_new = np.zeros(1)
+    check(lib().mpcmp_limits_retimed_one(arr, narm, int(num_seg), nl, host(rows), None if spec is None else spec.ctypes.data, host(x), host(u), host(T),
+                                         prof.shape[1] - 1, host(prof), int(n_pts), host(rec), host(T_new)))
+    return rec[0], float(T_new[0])
 
 
 def tool_line_spec(tool_lin_max=1.7, tool_ang_max=2.5, T_min=0.2, damp=1e-8, manip_min=1e-3, eps=1e-9, n_sub=4):

@@ -25,6 +25,7 @@
 #include "limits.hpp"
 #include "retime.hpp"
 #include "route_retime.hpp"
+#include "retimed_check.hpp"
 #include "toolpath.hpp"
 #include "route.hpp"
 
@@ -1274,6 +1275,130 @@ extern "C" int mpcmp_sample_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, co
     sg.out(&dout, out, (size_t)B * (n_pts + 1) * (1 + 28 * (size_t)ctx->narm));
     if (int rc = sg.upload()) return rc;
     if (int rc = mpcmp_sample_retimed_route_batch_device(ctx, B, M, dx, du, dT, n_grid, dprof, n_pts, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// limits of retimed plans and routes, profile scaling (retimed_check.hpp; the kernels are in retimed_check.hip)
+static int limits_retimed_check(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof, int n_pts,
+                                const mpcmp_limits_spec *spec, const mpcmp_limits *out) {
+    if (!ctx) { g_err = "mpcmp_limits_retimed_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || B > ctx->max_batch || n_grid < 1 || n_grid > RT_MAX_GRID || n_pts < 1 || n_pts > LIM_MAX_PTS || !sx || !su || !sT || !prof || !out) {
+        ctx->err = "mpcmp_limits_retimed_batch: B in [1, max_batch], 1 <= n_grid <= 4096, 1 <= n_pts <= 4096 and all pointers (but spec and T_new) required";
+        return MPCMP_EINVAL;
+    }
+    if (spec && !lim_spec_ok(*spec)) { ctx->err = "mpcmp_limits_retimed_batch: finite tolerances and tool maxima >= 0 (+inf: none) required"; return MPCMP_EINVAL; }
+    if (int rc = rows_ok(ctx, B, BOUND_ROWS)) return rc;
+    return rows_ok(ctx, B, PAYLOAD_ROWS);
+}
+
+static int limits_retimed_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid, const double *d_prof,
+                                  int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, limits_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
+                                      d_prof, spec ? *spec : lim_default_spec(), d_out, d_Tnew, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_limits_retimed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                                 const double *d_prof, int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out,
+                                                 double *d_Tnew, void *hip_stream) {
+    if (int rc = limits_retimed_check(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return limits_retimed_enqueue(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_limits_retimed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof,
+                                          int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *out, double *T_new) {
+    if (int rc = limits_retimed_check(ctx, B, sx, su, sT, n_grid, prof, n_pts, spec, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = B, NB = (size_t)ctx->N * nb;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof, *dTn;
+    mpcmp_limits *dout;
+    sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, nb); sg.in(&dprof, prof, nb * (n_grid + 1) * 2);
+    sg.out(&dout, out, nb); sg.out(&dTn, T_new, nb);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = limits_retimed_enqueue(ctx, B, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+static int limits_retimed_route_check(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                                      const double *prof, int n_pts, const mpcmp_limits_spec *spec, const mpcmp_limits *out, int *L) {
+    if (int rc = route_shape_check(ctx, "mpcmp_limits_retimed_route_batch", B, M, n_grid, L)) return rc;
+    if (n_pts < 1 || n_pts > LIM_MAX_PTS || !sx || !su || !sT || !prof || !out) {
+        ctx->err = "mpcmp_limits_retimed_route_batch: 1 <= n_pts <= 4096 and all pointers (but spec and T_new) required"; return MPCMP_EINVAL;
+    }
+    if (spec && !lim_spec_ok(*spec)) {
+        ctx->err = "mpcmp_limits_retimed_route_batch: finite tolerances and tool maxima >= 0 (+inf: none) required"; return MPCMP_EINVAL;
+    }
+    if (int rc = rows_ok(ctx, *L, BOUND_ROWS)) return rc;
+    return rows_ok(ctx, *L, PAYLOAD_ROWS);
+}
+
+static int limits_retimed_route_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                        const double *d_prof, int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out, double *d_Tnew,
+                                        hipStream_t st) {
+    mpcmp_bounds table;
+    mpcmp_bounds_from_config(&ctx->cfg, &table);
+    int ms;
+    const mpcmp_model *md = run_models(ctx, &ms);
+    HIPCHK(ctx, limits_retimed_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx,
+                                            d_su, d_sT, d_prof, spec ? *spec : lim_default_spec(), d_out, d_Tnew, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_limits_retimed_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT,
+                                                       int n_grid, const double *d_prof, int n_pts, const mpcmp_limits_spec *spec,
+                                                       mpcmp_limits *d_out, double *d_Tnew, void *hip_stream) {
+    int L;
+    if (int rc = limits_retimed_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return limits_retimed_route_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_limits_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
+                                                const double *prof, int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *out, double *T_new) {
+    int L;
+    if (int rc = limits_retimed_route_check(ctx, B, M, sx, su, sT, n_grid, prof, n_pts, spec, out, &L)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nl = L, NL = (size_t)ctx->N * nl;
+    Stage sg(ctx);
+    double *dx, *du, *dT, *dprof, *dTn;
+    mpcmp_limits *dout;
+    sg.in(&dx, sx, ctx->nx * NL); sg.in(&du, su, ctx->nu * NL); sg.in(&dT, sT, nl); sg.in(&dprof, prof, nl * (n_grid + 1) * 2);
+    sg.out(&dout, out, (size_t)B); sg.out(&dTn, T_new, (size_t)B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = limits_retimed_route_enqueue(ctx, B, M, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+static int profile_scale_check(mpcmp_ctx *ctx, int L, int n_grid, const double *factor, const double *prof) {
+    if (!ctx) { g_err = "mpcmp_profile_scale_batch: no context"; return MPCMP_EINVAL; }
+    if (L < 1 || L > ctx->max_batch || n_grid < 1 || n_grid > RT_MAX_GRID || !factor || !prof) {
+        ctx->err = "mpcmp_profile_scale_batch: L in [1, max_batch], 1 <= n_grid <= 4096 and both pointers required"; return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_profile_scale_batch_device(mpcmp_ctx *ctx, int L, int n_grid, const double *d_factor, double *d_prof, void *hip_stream) {
+    if (int rc = profile_scale_check(ctx, L, n_grid, d_factor, d_prof)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, profile_scale_launch(L, n_grid, d_factor, d_prof, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_profile_scale_batch(mpcmp_ctx *ctx, int L, int n_grid, const double *factor, double *prof) {
+    if (int rc = profile_scale_check(ctx, L, n_grid, factor, prof)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *df, *dprof;
+    sg.in(&df, factor, (size_t)L); sg.inout(&dprof, prof, (size_t)L * (n_grid + 1) * 2);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, profile_scale_launch(L, n_grid, df, dprof, ctx->stream));
     return sg.finish();
 }
 

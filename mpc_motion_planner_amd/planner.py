@@ -306,6 +306,48 @@ class Solver:
         check(lib().mpcmp_sample_retimed_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_grid), prof or None,
                                                       int(n_pts), out or None, stream or None), self._ctx)
 
+    # -- limits of retimed plans, profile scaling (include/mpcmp_retimed_check.h)
+    def _limits_spec(self, tol, tool_lin_max, tool_ang_max):
+        return None if tol is None and np.isposinf(tool_lin_max) and np.isposinf(tool_ang_max) else capi.limits_spec(tol, tool_lin_max, tool_ang_max)
+
+    def limits_retimed(self, sx, su, sT, prof, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """mpcmp_limits_retimed_batch: (capi.LIMITS_DTYPE [B], T_new [B]) for the plans sx, su, sT retimed by `prof` (what retime returned), at the
+        n_pts + 1 uniform physical times of sample_retimed, under the bound rows (or the configuration's tables) and payload rows in force.  A failed
+        profile: status LIM_NAN and T_new +inf.  select_checked reads the records as they are, with T_new as its sT"""
+        sx, su, sT = self._traj(sx, su, sT); B = sT.shape[0]
+        prof = f64(prof)
+        if prof.ndim != 3 or prof.shape[0] != B or prof.shape[2] != 2:
+            raise ValueError("prof must be [B][n_grid + 1][2] = [%d][..][2]" % B)
+        spec = self._limits_spec(tol, tool_lin_max, tool_ang_max)
+        out = np.zeros(B, dtype=capi.LIMITS_DTYPE); T_new = np.zeros(B)
+        check(lib().mpcmp_limits_retimed_batch(self._ctx, B, host(sx), host(su), host(sT), prof.shape[1] - 1, host(prof), int(n_pts),
+                                               None if spec is None else spec.ctypes.data, host(out), host(T_new)), self._ctx)
+        return out, T_new
+
+    def limits_retimed_device(self, B, sol_x, sol_u, sol_T, n_grid, prof, n_pts, out, T_new=0, spec=None, stream=0):
+        """spec: a capi.LIMITS_SPEC_DTYPE record on the HOST (capi.limits_spec) or None; everything else raw device pointers (0 = NULL for T_new)"""
+        check(lib().mpcmp_limits_retimed_batch_device(self._ctx, int(B), sol_x or None, sol_u or None, sol_T or None, int(n_grid), prof or None,
+                                                      int(n_pts), None if spec is None else np.ascontiguousarray(spec).ctypes.data, out or None,
+                                                      T_new or None, stream or None), self._ctx)
+
+    def profile_scale(self, prof, factor):
+        """mpcmp_profile_scale_batch: a copy of the profiles prof [..][n_grid + 1][2] (of plans [B], or of routes [B][M + 1]) slowed uniformly,
+        slot l by factor [l] (one per leading slot, in the profile's order): t_k *= f, x_k /= f^2.  f = the stretch of a limits_retimed record cures
+        its QD, QDD, TOOL_LIN and TOOL_ANG groups between ends at rest.  For routes give every leg of a route the same factor (Solver.repeat)"""
+        prof = np.array(f64(prof))
+        if prof.ndim < 3 or prof.shape[-1] != 2 or prof.shape[-2] < 2:
+            raise ValueError("prof must be [..][n_grid + 1][2]")
+        L = int(np.prod(prof.shape[:-2]))
+        factor = f64(factor).reshape(-1)
+        if factor.shape[0] != L:
+            raise ValueError("one factor per profile: %d profiles, %d factors" % (L, factor.shape[0]))
+        check(lib().mpcmp_profile_scale_batch(self._ctx, L, prof.shape[-2] - 1, host(factor), host(prof)), self._ctx)
+        return prof
+
+    def profile_scale_device(self, L, n_grid, factor, prof, stream=0):
+        """in place, raw device pointers"""
+        check(lib().mpcmp_profile_scale_batch_device(self._ctx, int(L), int(n_grid), factor or None, prof or None, stream or None), self._ctx)
+
     # -- tool-line moves (include/mpcmp_toolpath.h)
     def tool_line(self, q_start, R, p, T=None, spec=None, arm=0, out=None):
         """mpcmp_tool_line_batch: straight tool lines of arm `arm` from the postures q_start [B][7] to the poses R [B][3][3], p [B][3], written as
@@ -501,6 +543,26 @@ class Solver:
     def sample_retimed_route_device(self, B, M, sol_x, sol_u, sol_T, n_grid, prof, n_pts, out, stream=0):
         check(lib().mpcmp_sample_retimed_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_grid),
                                                             prof or None, int(n_pts), out or None, stream or None), self._ctx)
+
+    def limits_retimed_route(self, sx, su, sT, prof, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """mpcmp_limits_retimed_route_batch: (capi.LIMITS_DTYPE [B], T_new [B]) for the routes sx, su, sT [B][M+1][..] retimed by `prof` (what
+        retime_route returned), at the n_pts + 1 uniform times of sample_retimed_route on the route clock, every sample under the bound and payload
+        rows of its leg slot.  A failed route: status LIM_NAN and T_new +inf"""
+        sx, su, sT, B, M = self._route_traj(sx, su, sT)
+        prof = f64(prof)
+        if prof.ndim != 4 or prof.shape[:2] != (B, M + 1) or prof.shape[3] != 2:
+            raise ValueError("prof must be [B][M+1][n_grid + 1][2] = [%d][%d][..][2]" % (B, M + 1))
+        spec = self._limits_spec(tol, tool_lin_max, tool_ang_max)
+        out = np.zeros(B, dtype=capi.LIMITS_DTYPE); T_new = np.zeros(B)
+        check(lib().mpcmp_limits_retimed_route_batch(self._ctx, B, M, host(sx), host(su), host(sT), prof.shape[2] - 1, host(prof), int(n_pts),
+                                                     None if spec is None else spec.ctypes.data, host(out), host(T_new)), self._ctx)
+        return out, T_new
+
+    def limits_retimed_route_device(self, B, M, sol_x, sol_u, sol_T, n_grid, prof, n_pts, out, T_new=0, spec=None, stream=0):
+        """spec: a capi.LIMITS_SPEC_DTYPE record on the HOST (capi.limits_spec) or None; everything else raw device pointers (0 = NULL for T_new)"""
+        check(lib().mpcmp_limits_retimed_route_batch_device(self._ctx, int(B), int(M), sol_x or None, sol_u or None, sol_T or None, int(n_grid),
+                                                            prof or None, int(n_pts), None if spec is None else np.ascontiguousarray(spec).ctypes.data,
+                                                            out or None, T_new or None, stream or None), self._ctx)
 
     def _states(self, x0, xf):
         """(x0, xf) as contiguous [B][14] arrays; a shape mismatch raises instead of letting the C side read out of bounds"""
@@ -859,6 +921,13 @@ class BatchMotionPlanner:
             raise ValueError("call retime() after solve_trajectory() first (direct moves)")
         return self._solver.sample_retimed(self._sol[0], self._sol[1], self._sol[2], self._retimed[0], n_pts)
 
+    def check_retimed_limits(self, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """limit records of the retimed plans between the grid points (Solver.limits_retimed), from the profiles of the last retime call (direct
+        moves): (capi.LIMITS_DTYPE [B], T_new [B])"""
+        if self._route is not None or getattr(self, "_retimed", None) is None:
+            raise ValueError("call retime() after solve_trajectory() first (direct moves)")
+        return self._solver.limits_retimed(self._sol[0], self._sol[1], self._sol[2], self._retimed[0], n_pts, tol, tool_lin_max, tool_ang_max)
+
     def retime_route(self, n_grid=200, spec=None):
         """the last route solve retimed as whole routes, one profile across the via points (Solver.retime_route): (prof [B][M + 1][n_grid + 1][2]
         with leg times, leg_T_new [B][M + 1], capi.ROUTE_RETIME_DTYPE [B]).  The profiles are kept for get_retimed_route_trajectory."""
@@ -875,6 +944,15 @@ class BatchMotionPlanner:
             raise ValueError("call retime_route() after a route solve first")
         r = self._route
         return self._solver.sample_retimed_route(r["sol_x"], r["sol_u"], r["sol_T"], kept[1][0], n_pts)
+
+    def check_retimed_route_limits(self, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
+        """limit records of the retimed routes between the grid points (Solver.limits_retimed_route), from the profiles of the last retime_route call:
+        (capi.LIMITS_DTYPE [B], T_new [B]), times on the route clock"""
+        kept = getattr(self, "_route_retimed", None)
+        if self._route is None or kept is None or kept[0] is not self._route:       # (a profile belongs to the route it was computed for)
+            raise ValueError("call retime_route() after a route solve first")
+        r = self._route
+        return self._solver.limits_retimed_route(r["sol_x"], r["sol_u"], r["sol_T"], kept[1][0], n_pts, tol, tool_lin_max, tool_ang_max)
 
     # extension beyond the reference's members: a straight tool line as the plan (include/mpcmp_toolpath.h)
     def plan_tool_line(self, R, p, T=None, spec=None):
