@@ -24,7 +24,6 @@
 #include "clearance.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
-#include "route_retime.hpp"
 #include "retimed_check.hpp"
 #include "toolpath.hpp"
 #include "route.hpp"
@@ -1104,7 +1103,8 @@ extern "C" int mpcmp_select_checked_batch(mpcmp_ctx *ctx, int B, const double *s
 }
 
 // ------------------------------------------------------------------------------------------------
-// retiming (retime.hpp; the kernels are in retime.hip)
+// retiming of plans (retime.hpp; the kernels are in retime.hip).  A plan is a route of one leg: after its own checks a plan call goes through the
+// enqueue helper of the route call with M = 0
 static int retime_check(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const mpcmp_retime_spec *spec,
                         const double *prof, const mpcmp_retime *out) {
     if (!ctx) { g_err = "mpcmp_retime_batch: no context"; return MPCMP_EINVAL; }
@@ -1118,14 +1118,16 @@ static int retime_check(mpcmp_ctx *ctx, int B, const double *sx, const double *s
     return rows_ok(ctx, B, PAYLOAD_ROWS);
 }
 
-static int retime_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid, const mpcmp_retime_spec *spec,
-                          double *d_prof, mpcmp_retime *d_out, hipStream_t st) {
+// the records go to d_route_out or, for plans (M = 0), to d_plan_out
+static int retime_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                          const mpcmp_retime_spec *spec, double *d_prof, double *d_legT, mpcmp_retime *d_plan_out, mpcmp_route_retime *d_route_out,
+                          hipStream_t st) {
     mpcmp_bounds table;
     mpcmp_bounds_from_config(&ctx->cfg, &table);
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, retime_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
-                              spec ? *spec : rt_default_spec(), d_prof, d_out, st));
+    HIPCHK(ctx, retime_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
+                              spec ? *spec : rt_default_spec(), d_prof, d_legT, d_plan_out, d_route_out, st));
     return MPCMP_OK;
 }
 
@@ -1133,7 +1135,7 @@ extern "C" int mpcmp_retime_batch_device(mpcmp_ctx *ctx, int B, const double *d_
                                          const mpcmp_retime_spec *spec, double *d_prof, mpcmp_retime *d_out, void *hip_stream) {
     if (int rc = retime_check(ctx, B, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return retime_enqueue(ctx, B, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out, (hipStream_t)hip_stream);
+    return retime_enqueue(ctx, B, 0, d_sx, d_su, d_sT, n_grid, spec, d_prof, nullptr, d_out, nullptr, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_retime_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid,
@@ -1146,7 +1148,7 @@ extern "C" int mpcmp_retime_batch(mpcmp_ctx *ctx, int B, const double *sx, const
     mpcmp_retime *dout;
     sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, nb); sg.out(&dprof, prof, nb * (n_grid + 1) * 2); sg.out(&dout, out, nb);
     if (int rc = sg.upload()) return rc;
-    if (int rc = retime_enqueue(ctx, B, dx, du, dT, n_grid, spec, dprof, dout, ctx->stream)) return rc;
+    if (int rc = retime_enqueue(ctx, B, 0, dx, du, dT, n_grid, spec, dprof, nullptr, dout, nullptr, ctx->stream)) return rc;
     return sg.finish();
 }
 
@@ -1159,14 +1161,19 @@ static int sample_retimed_check(mpcmp_ctx *ctx, int B, const double *sx, const d
     return rows_ok(ctx, B, PAYLOAD_ROWS);
 }
 
-extern "C" int mpcmp_sample_retimed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
-                                                 const double *d_prof, int n_pts, double *d_out, void *hip_stream) {
-    if (int rc = sample_retimed_check(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out)) return rc;
+static int sample_retimed_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                  const double *d_prof, int n_pts, double *d_out, hipStream_t st) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, sample_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, n_pts, d_sx, d_su, d_sT, d_prof, d_out, (hipStream_t)hip_stream));
+    HIPCHK(ctx, sample_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, d_sx, d_su, d_sT, d_prof, d_out, st));
     return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sample_retimed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                                 const double *d_prof, int n_pts, double *d_out, void *hip_stream) {
+    if (int rc = sample_retimed_check(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out)) return rc;
+    return sample_retimed_enqueue(ctx, B, 0, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_sample_retimed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof,
@@ -1184,7 +1191,7 @@ extern "C" int mpcmp_sample_retimed_batch(mpcmp_ctx *ctx, int B, const double *s
 }
 
 // ------------------------------------------------------------------------------------------------
-// route retiming (route_retime.hpp; the kernels are in route_retime.hip)
+// route retiming (retime.hpp; the kernels are in retime.hip)
 static int route_shape_check(mpcmp_ctx *ctx, const char *who, int B, int M, int n_grid, int *L) {
     if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
     const long long l = (long long)B * ((long long)M + 1);
@@ -1206,24 +1213,13 @@ static int retime_route_check(mpcmp_ctx *ctx, int B, int M, const double *sx, co
     return rows_ok(ctx, *L, PAYLOAD_ROWS);
 }
 
-static int retime_route_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
-                                const mpcmp_retime_spec *spec, double *d_prof, double *d_legT, mpcmp_route_retime *d_out, hipStream_t st) {
-    mpcmp_bounds table;
-    mpcmp_bounds_from_config(&ctx->cfg, &table);
-    int ms;
-    const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, retime_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
-                                    spec ? *spec : rt_default_spec(), d_prof, d_legT, d_out, st));
-    return MPCMP_OK;
-}
-
 extern "C" int mpcmp_retime_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
                                                const mpcmp_retime_spec *spec, double *d_prof, double *d_legT, mpcmp_route_retime *d_out,
                                                void *hip_stream) {
     int L;
     if (int rc = retime_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_out, &L)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return retime_route_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_legT, d_out, (hipStream_t)hip_stream);
+    return retime_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, spec, d_prof, d_legT, nullptr, d_out, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_retime_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
@@ -1239,7 +1235,7 @@ extern "C" int mpcmp_retime_route_batch(mpcmp_ctx *ctx, int B, int M, const doub
     if (leg_T_new) sg.out(&dleg, leg_T_new, nl);
     sg.out(&dout, out, (size_t)B);
     if (int rc = sg.upload()) return rc;
-    if (int rc = retime_route_enqueue(ctx, B, M, dx, du, dT, n_grid, spec, dprof, dleg, dout, ctx->stream)) return rc;
+    if (int rc = retime_enqueue(ctx, B, M, dx, du, dT, n_grid, spec, dprof, dleg, nullptr, dout, ctx->stream)) return rc;
     return sg.finish();
 }
 
@@ -1256,11 +1252,7 @@ extern "C" int mpcmp_sample_retimed_route_batch_device(mpcmp_ctx *ctx, int B, in
                                                        int n_grid, const double *d_prof, int n_pts, double *d_out, void *hip_stream) {
     int L;
     if (int rc = sample_retimed_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out, &L)) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int ms;
-    const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, sample_retimed_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, d_sx, d_su, d_sT, d_prof, d_out, (hipStream_t)hip_stream));
-    return MPCMP_OK;
+    return sample_retimed_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, d_out, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_sample_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
@@ -1292,14 +1284,14 @@ static int limits_retimed_check(mpcmp_ctx *ctx, int B, const double *sx, const d
     return rows_ok(ctx, B, PAYLOAD_ROWS);
 }
 
-static int limits_retimed_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_su, const double *d_sT, int n_grid, const double *d_prof,
-                                  int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
+static int limits_retimed_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
+                                  const double *d_prof, int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
     mpcmp_bounds table;
     mpcmp_bounds_from_config(&ctx->cfg, &table);
     int ms;
     const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, limits_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, n_grid, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su, d_sT,
-                                      d_prof, spec ? *spec : lim_default_spec(), d_out, d_Tnew, st));
+    HIPCHK(ctx, limits_retimed_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx, d_su,
+                                      d_sT, d_prof, spec ? *spec : lim_default_spec(), d_out, d_Tnew, st));
     return MPCMP_OK;
 }
 
@@ -1308,7 +1300,7 @@ extern "C" int mpcmp_limits_retimed_batch_device(mpcmp_ctx *ctx, int B, const do
                                                  double *d_Tnew, void *hip_stream) {
     if (int rc = limits_retimed_check(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return limits_retimed_enqueue(ctx, B, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
+    return limits_retimed_enqueue(ctx, B, 0, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_limits_retimed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *su, const double *sT, int n_grid, const double *prof,
@@ -1322,7 +1314,7 @@ extern "C" int mpcmp_limits_retimed_batch(mpcmp_ctx *ctx, int B, const double *s
     sg.in(&dx, sx, ctx->nx * NB); sg.in(&du, su, ctx->nu * NB); sg.in(&dT, sT, nb); sg.in(&dprof, prof, nb * (n_grid + 1) * 2);
     sg.out(&dout, out, nb); sg.out(&dTn, T_new, nb);
     if (int rc = sg.upload()) return rc;
-    if (int rc = limits_retimed_enqueue(ctx, B, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
+    if (int rc = limits_retimed_enqueue(ctx, B, 0, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
     return sg.finish();
 }
 
@@ -1339,25 +1331,13 @@ static int limits_retimed_route_check(mpcmp_ctx *ctx, int B, int M, const double
     return rows_ok(ctx, *L, PAYLOAD_ROWS);
 }
 
-static int limits_retimed_route_enqueue(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT, int n_grid,
-                                        const double *d_prof, int n_pts, const mpcmp_limits_spec *spec, mpcmp_limits *d_out, double *d_Tnew,
-                                        hipStream_t st) {
-    mpcmp_bounds table;
-    mpcmp_bounds_from_config(&ctx->cfg, &table);
-    int ms;
-    const mpcmp_model *md = run_models(ctx, &ms);
-    HIPCHK(ctx, limits_retimed_route_launch(md, ms, ctx->narm, ctx->nseg, B, M, n_grid, n_pts, ctx->bnd_rows > 0 ? ctx->d_bnd : nullptr, table, d_sx,
-                                            d_su, d_sT, d_prof, spec ? *spec : lim_default_spec(), d_out, d_Tnew, st));
-    return MPCMP_OK;
-}
-
 extern "C" int mpcmp_limits_retimed_route_batch_device(mpcmp_ctx *ctx, int B, int M, const double *d_sx, const double *d_su, const double *d_sT,
                                                        int n_grid, const double *d_prof, int n_pts, const mpcmp_limits_spec *spec,
                                                        mpcmp_limits *d_out, double *d_Tnew, void *hip_stream) {
     int L;
     if (int rc = limits_retimed_route_check(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, &L)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return limits_retimed_route_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
+    return limits_retimed_enqueue(ctx, B, M, d_sx, d_su, d_sT, n_grid, d_prof, n_pts, spec, d_out, d_Tnew, (hipStream_t)hip_stream);
 }
 
 extern "C" int mpcmp_limits_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, const double *sx, const double *su, const double *sT, int n_grid,
@@ -1372,7 +1352,7 @@ extern "C" int mpcmp_limits_retimed_route_batch(mpcmp_ctx *ctx, int B, int M, co
     sg.in(&dx, sx, ctx->nx * NL); sg.in(&du, su, ctx->nu * NL); sg.in(&dT, sT, nl); sg.in(&dprof, prof, nl * (n_grid + 1) * 2);
     sg.out(&dout, out, (size_t)B); sg.out(&dTn, T_new, (size_t)B);
     if (int rc = sg.upload()) return rc;
-    if (int rc = limits_retimed_route_enqueue(ctx, B, M, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
+    if (int rc = limits_retimed_enqueue(ctx, B, M, dx, du, dT, n_grid, dprof, n_pts, spec, dout, dTn, ctx->stream)) return rc;
     return sg.finish();
 }
 

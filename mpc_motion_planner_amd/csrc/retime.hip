@@ -1,6 +1,7 @@
-// retime.hip — retiming of finished plans (include/mpcmp_retime.h): per trajectory the time-optimal rate along its own path under the velocity,
-// acceleration, torque and tool-speed limits at the points of a grid, the sampler of the retimed plan, and the host statement that needs no
-// context.  A translation unit of its own, so that the register-bound QP kernels of solver.hip compile exactly as before.
+// retime.hip — retiming of finished plans and of whole via-point routes (include/mpcmp_retime.h, include/mpcmp_route_retime.h): per route ONE
+// time-optimal rate profile along its own path, across its junctions, under the velocity, acceleration, torque and tool-speed limits at the points
+// of a grid; the sampler of the retimed route on one clock; and the host statements that need no context.  A plan is a route of one leg: the plan
+// calls run the same kernels with M = 0.  A translation unit of its own, so that the register-bound QP kernels of solver.hip compile exactly as before.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <vector>
@@ -29,58 +30,72 @@ __device__ __forceinline__ double rt_wave_max(double v) {
     return v;
 }
 
-// One workgroup of ONE WAVE per trajectory.  Staged in LDS once: the nodes of the trajectory and the bounds row of the problem, as in k_limits.
-// The grid is taken in chunks of 64 points.  For a chunk every lane forms the record of its point (rt_record: three rnea_dir calls and one
-// fk_task_velocity per arm, the work k_limits does per sample) and writes it to LDS, 36 doubles per point and arm, so LDS does not grow with n_grid.
-// Then the wave walks the chunk point by point: lane r holds row r of the point (28 per arm, then the two next-state rows).  Backward, a lane whose
-// row has A > 0 eliminates w against every row with A < 0 (read by v_readlane, skipped wave-uniformly otherwise) and the wave reduces the cuts
-// to [lo_k, hi_k]; forward, the lanes reduce the largest w.  The backward pass goes over the chunks from the last to the first and leaves
-// (lo_k, hi_k) in prof; the forward pass recomputes the records chunk by chunk, reads the sets back and overwrites them with (t_k, x_k).  Lane l
-// writes and reads point 64 c + l of prof (and lane 0 point 64 c + 64, its own of the next chunk), so no lane reads what another lane wrote.
-__global__ __launch_bounds__(RT_NT) void k_retime(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int n,
+// One workgroup of ONE WAVE per ROUTE of M + 1 legs (a plan: M = 0).  The wave takes the legs one after the other, backward from the last leg to the
+// first and then forward from the first to the last.  Per leg it stages that leg's nodes and bound row in LDS, as k_limits does (the same buffers for
+// every leg, so LDS grows neither with n_grid nor with M).  The grid of a leg is taken in chunks of 64 points.  For a chunk every lane forms the
+// record of its point (rt_record: three rnea_dir calls and one fk_task_velocity per arm, the work k_limits does per sample) and writes it to LDS, 36
+// doubles per point and arm.  Then the wave walks the chunk point by point: lane r holds row r of the point (28 per arm, then the two next-state
+// rows).  Backward, a lane whose row has A > 0 eliminates w against every row with A < 0 (read by v_readlane, skipped wave-uniformly otherwise) and
+// the wave reduces the cuts to [lo_k, hi_k]; forward, the lanes reduce the largest w.  The backward pass leaves (lo_k, hi_k) in the caller's prof;
+// the forward pass recomputes the records chunk by chunk, reads the sets back and overwrites them with (t_k, x_k).  What crosses a junction travels
+// in registers: backward (lo1, hi1) = K_0 of the later leg, which the last point of the earlier leg is intersected with; forward x, which the later
+// leg starts from.  Lane l reads and writes point 64 c + l of a leg (and lane 0 point 64 c + 64, its own of the next chunk), so no lane reads what
+// another lane wrote.  No global workspace, no atomics.  Lane 0 writes the record: to rout, or without its leg fields to pout.
+__global__ __launch_bounds__(RT_NT) void k_retime(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int n, int M,
                                                   const mpcmp_bounds *__restrict__ rows, mpcmp_bounds table, const double *__restrict__ sx,
                                                   const double *__restrict__ su, const double *__restrict__ sT, mpcmp_retime_spec sp,
-                                                  double *__restrict__ prof, mpcmp_retime *__restrict__ out) {
-    __shared__ double nodes[RT_MAX_NODES * 21 * RT_MAX_ARMS];      // x [N][14 narm], then u [N][7 narm]
+                                                  double *__restrict__ prof, double *__restrict__ legT, mpcmp_retime *__restrict__ pout,
+                                                  mpcmp_route_retime *__restrict__ rout) {
+    __shared__ double nodes[RT_MAX_NODES * 21 * RT_MAX_ARMS];      // x [N][14 narm], then u [N][7 narm] of the leg at hand
     __shared__ double bd[58];
     __shared__ double rec[RT_MAX_ARMS * RT_NF * RT_STRIDE];
-    const int b = blockIdx.x, lane = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm;
+    const int b = blockIdx.x, lane = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm, nl = M + 1;
+    const size_t l0 = (size_t)b * nl;
     double *Xs = nodes, *Us = nodes + 2 * nq * N;
-    const double *X = sx + (size_t)b * N * 2 * nq, *U = su + (size_t)b * N * nq;
-    const double T = sT[b];
-    int bad = !(rt_finite(T) && T > 0.0);
-    for (int e = lane; e < 2 * nq * N; e += RT_NT) { Xs[e] = X[e]; bad |= !rt_finite(Xs[e]); }
-    for (int e = lane; e < nq * N; e += RT_NT) { Us[e] = U[e]; bad |= !rt_finite(Us[e]); }
-    {
-        const double *row = reinterpret_cast<const double *>(rows + b), *tab = reinterpret_cast<const double *>(&table);
-        for (int e = lane; e < 58; e += RT_NT) bd[e] = rows ? row[e] : tab[e];
-    }
-    __syncthreads();
-    double *pf = prof + (size_t)b * (n + 1) * 2;
     const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-    int status = __any(bad) ? MPCMP_RT_NAN : 0, k_fail = -1;
+    int status, leg_fail = -1, k_fail = -1;
+    {   // a non-finite value anywhere in the route fails all of it before any pass
+        const double *X = sx + l0 * N * 2 * nq, *U = su + l0 * N * nq;
+        int bad = 0;
+        for (int e = lane; e < nl * 2 * nq * N; e += RT_NT) bad |= !rt_finite(X[e]);
+        for (int e = lane; e < nl * nq * N; e += RT_NT) bad |= !rt_finite(U[e]);
+        for (int m = lane; m < nl; m += RT_NT) { const double Tm = sT[l0 + m]; bad |= !(rt_finite(Tm) && Tm > 0.0); }
+        status = __any(bad) ? MPCMP_RT_NAN : 0;
+    }
 
-    const double h = 0.5 / T, delta = 1.0 / n, rmax2 = sp.rate_max * sp.rate_max;
-    const int nch = n / RT_CHUNK + 1, nrows = RT_ROWS_ARM * narm;
+    const double delta = 1.0 / n, rmax2 = sp.rate_max * sp.rate_max;
+    const int nch = n / RT_CHUNK + 1, half = nl * nch, nrows = RT_ROWS_ARM * narm;
     const int my_arm = lane / RT_ROWS_ARM, my_rr = lane % RT_ROWS_ARM;
-    double lo1 = 0.0, hi1 = 0.0, x = 0.0, t = 0.0, xmin = INFINITY;
-    int pin0 = 0, kmin = 0, nslow = 0;
-    for (int it = 0; it < 2 * nch && !status; it++) {
-        const bool fwd = it >= nch;
-        const int c = fwd ? it - nch : nch - 1 - it, k = c * RT_CHUNK + lane, npt = min(RT_CHUNK, n + 1 - c * RT_CHUNK);
+    double T = 1.0, h = 0.5, lo1 = 0.0, hi1 = 0.0, x = 0.0, t = 0.0, Ttot = 0.0, xmin = INFINITY;
+    int pin0 = 0, kmin = 0, legmin = 0, nslow = 0;
+    for (int it = 0; it < 2 * half && !status; it++) {
+        const bool fwd = it >= half;
+        const int j = fwd ? it - half : half - 1 - it, leg = j / nch, c = j % nch;
+        const size_t ls = l0 + leg;
+        if (c == (fwd ? 0 : nch - 1)) {             // a pass enters this leg: stage it (the iteration before ended with a barrier)
+            const double *X = sx + ls * N * 2 * nq, *U = su + ls * N * nq;
+            for (int e = lane; e < 2 * nq * N; e += RT_NT) Xs[e] = X[e];
+            for (int e = lane; e < nq * N; e += RT_NT) Us[e] = U[e];
+            const double *row = reinterpret_cast<const double *>(rows + ls), *tab = reinterpret_cast<const double *>(&table);
+            for (int e = lane; e < 58; e += RT_NT) bd[e] = rows ? row[e] : tab[e];
+            T = sT[ls]; h = 0.5 / T;
+            __syncthreads();
+        }
+        double *pf = prof + ls * (n + 1) * 2;
+        const int k = c * RT_CHUNK + lane, npt = min(RT_CHUNK, n + 1 - c * RT_CHUNK);
         if (k <= n) {
             double Lg[4];
             const int s = lagrange_segment(nseg, (double)k / n, Lg);
             for (int a = 0; a < narm; a++) {
-                const mpcmp_model *M = mdl + (size_t)b * mstride + a;
+                const mpcmp_model *Mo = mdl + ls * mstride + a;
                 double q[7], v[7], ac[7], sc[14], tc[7], t1[7], t2[7];
                 const double zero[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
                 interp_joints(Xs + 7 * a, Xs + nq + 7 * a, 2 * nq, Us + 7 * a, nq, s, Lg, q, v, ac, sc);
-                rnea_dir<false>(M, sc, zero, zero, 0, 0, tc, nullptr);
-                rnea_dir<false>(M, sc, v, ac, 0, 0, t1, nullptr);
-                rnea_dir<false>(M, sc, zero, v, 0, 0, t2, nullptr);
+                rnea_dir<false>(Mo, sc, zero, zero, 0, 0, tc, nullptr);
+                rnea_dir<false>(Mo, sc, v, ac, 0, 0, t1, nullptr);
+                rnea_dir<false>(Mo, sc, zero, v, 0, 0, t2, nullptr);
                 V3 pt, vl, va;
-                fk_task_velocity(M, sc, v, &pt, &vl, &va);
+                fk_task_velocity(Mo, sc, v, &pt, &vl, &va);
                 rt_record(bd, sp, v, ac, tc, t1, t2, sqrt(vl.x * vl.x + vl.y * vl.y + vl.z * vl.z), sqrt(va.x * va.x + va.y * va.y + va.z * va.z),
                           rec + a * RT_NF * RT_STRIDE + lane, RT_STRIDE);
             }
@@ -99,9 +114,9 @@ __global__ __launch_bounds__(RT_NT) void k_retime(const mpcmp_model *__restrict_
             double A = 0.0, B = 0.0, C = -1.0;
             if (lane < nrows) rt_row(rec + my_arm * RT_NF * RT_STRIDE + l, RT_STRIDE, bd, h, sp.groups, my_rr, A, B, C);
             if (fwd) {
-                if (kk == 0) { x = pin0 ? 1.0 : rt_lane(sethi, 0); t = 0.0; }
-                if (x < xmin) { xmin = x; kmin = kk; }
-                if (x < rmax2) nslow++;
+                if (kk == 0) { if (leg == 0) x = pin0 ? 1.0 : rt_lane(sethi, 0); t = 0.0; }       // a later leg starts from the x the leg before ended with
+                if (x < xmin) { xmin = x; kmin = kk; legmin = leg; }
+                if ((kk > 0 || leg == 0) && x < rmax2) nslow++;                                    // a junction counts once
                 if (lane == l) { mine0 = t; mine1 = x; }
                 if (kk < n) {
                     lo1 = l + 1 < RT_CHUNK ? rt_lane(setlo, l + 1) : nlo;
@@ -111,13 +126,17 @@ __global__ __launch_bounds__(RT_NT) void k_retime(const mpcmp_model *__restrict_
                     const double x1 = fmin(fmax(x + delta * w, lo1), hi1);
                     t += rt_dt(T, delta, x, x1);
                     x = x1;
+                } else {
+                    if (lane == 0 && legT) legT[ls] = t;
+                    Ttot = leg == 0 ? t : Ttot + t;
                 }
                 continue;
             }
             double cap = rec[RT_CAP * RT_STRIDE + l];
             if (narm == 2) cap = fmin(cap, rec[(RT_NF + RT_CAP) * RT_STRIDE + l]);
             int moving = 0;
-            if (kk == 0 || kk == n) moving = __any(lane < nq && rec[((lane / 7) * RT_NF + RT_V + lane % 7) * RT_STRIDE + l] != 0.0);
+            if ((kk == 0 && leg == 0) || (kk == n && leg == M))
+                moving = __any(lane < nq && rec[((lane / 7) * RT_NF + RT_V + lane % 7) * RT_STRIDE + l] != 0.0);
             RtSet S = {0.0, INFINITY, 0};
             if (kk < n) {
                 if (lane == nrows) { A = delta; B = 1.0; C = -hi1; }
@@ -125,63 +144,86 @@ __global__ __launch_bounds__(RT_NT) void k_retime(const mpcmp_model *__restrict_
             }
             if (A == 0.0) rt_cut_x(S, B, C);
             if (kk < n) {
-                for (int j = 0; j < nrows + 2; j++) {
-                    const double Aj = rt_lane(A, j);
+                for (int jj = 0; jj < nrows + 2; jj++) {
+                    const double Aj = rt_lane(A, jj);
                     if (!(Aj < 0.0)) continue;
-                    const double Bj = rt_lane(B, j), Cj = rt_lane(C, j);
+                    const double Bj = rt_lane(B, jj), Cj = rt_lane(C, jj);
                     if (A > 0.0) rt_cut_pair(S, A, B, C, Aj, Bj, Cj);
                 }
             }
             double lo = rt_wave_max(S.lo), hi = fmin(rt_wave_min(S.hi), cap);
+            if (kk == n && leg < M) { lo = fmax(lo, lo1); hi = fmin(hi, hi1); }        // a junction: within K_0 of the later leg
             bool fail = __any(S.empty) || !(lo <= hi) || hi == 0.0;
-            if (moving) {                           // a pinned end
+            if (moving) {                           // a pinned end of the route
                 fail = fail || !(lo <= 1.0 && 1.0 <= hi);
                 if (kk == n) lo = hi = 1.0;
                 else pin0 = 1;
             }
-            if (fail) { status = MPCMP_RT_INFEASIBLE; k_fail = kk; break; }
+            if (fail) { status = MPCMP_RT_INFEASIBLE; leg_fail = leg; k_fail = kk; break; }
             lo1 = lo; hi1 = hi;
             if (lane == l) { mine0 = lo; mine1 = hi; }
         }
         if (!status && lane < npt) { pf[2 * k] = mine0; pf[2 * k + 1] = mine1; }
         __syncthreads();
     }
-    if (!status && !rt_finite(t)) status = MPCMP_RT_INFEASIBLE;
-    if (status) for (int k = lane; k <= n; k += RT_NT) { pf[2 * k] = qnan; pf[2 * k + 1] = qnan; }
+    if (!status && !rt_finite(Ttot)) status = MPCMP_RT_INFEASIBLE;
+    if (status) {
+        for (int m = 0; m < nl; m++) {
+            double *pf = prof + (l0 + m) * (n + 1) * 2;
+            for (int k = lane; k <= n; k += RT_NT) { pf[2 * k] = qnan; pf[2 * k + 1] = qnan; }
+            if (lane == 0 && legT) legT[l0 + m] = INFINITY;
+        }
+    }
     if (lane == 0) {
-        mpcmp_retime r = rt_failed(status, k_fail);
-        if (!status) { r.T_new = t; r.rate_min = sqrt(xmin); r.s_slowest = (double)kmin / n; r.n_slowed = nslow; }
-        out[b] = r;
+        mpcmp_route_retime r = rrt_failed(status, leg_fail, k_fail);
+        if (!status) { r.T_new = Ttot; r.rate_min = sqrt(xmin); r.s_slowest = (double)kmin / n; r.leg_slowest = legmin; r.n_slowed = nslow; }
+        if (rout) rout[b] = r;
+        else pout[b] = rt_plan_record(r);
     }
 }
 
-// One thread per (problem, sample): the interval of the physical time by bisection on the t_k of the profile, then the retimed-sample rule.
-__global__ __launch_bounds__(128) void k_sample_retimed(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int B, int n, int n_pts,
-                                                        const double *__restrict__ sx, const double *__restrict__ su, const double *__restrict__ sT,
-                                                        const double *__restrict__ prof, double *__restrict__ out) {
+// One thread per (route, sample): the retimed leg durations are the last t of every leg's profile; the leg of the route time by a sequential
+// prefix sum over them, then the interval of the leg time by bisection on the t_k of that leg's profile and the retimed-sample rule.
+__global__ __launch_bounds__(128) void k_sample_retimed(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int B, int M, int n,
+                                                        int n_pts, const double *__restrict__ sx, const double *__restrict__ su,
+                                                        const double *__restrict__ sT, const double *__restrict__ prof, double *__restrict__ out) {
     const long idx = (long)blockIdx.x * 128 + threadIdx.x;
     if (idx >= (long)B * (n_pts + 1)) return;
-    const int b = (int)(idx / (n_pts + 1)), i = (int)(idx % (n_pts + 1)), N = 3 * nseg + 1, nq = 7 * narm, W = 1 + 28 * narm;
-    const double *pf = prof + (size_t)b * (n + 1) * 2;
+    const int b = (int)(idx / (n_pts + 1)), i = (int)(idx % (n_pts + 1)), N = 3 * nseg + 1, nq = 7 * narm, W = 1 + 28 * narm, nl = M + 1;
+    const size_t l0 = (size_t)b * nl, ps = (size_t)(n + 1) * 2;
     double *o = out + (size_t)idx * W;
-    const double Tn = pf[2 * n], T = sT[b];
-    if (!rt_finite(Tn)) {
+    double Tn = 0.0;
+    bool finite = true;
+    for (int m = 0; m < nl; m++) { const double D = prof[(l0 + m) * ps + 2 * n]; Tn = m ? Tn + D : D; finite = finite && rt_finite(D); }
+    if (!finite) {
         for (int e = 0; e < W; e++) o[e] = __longlong_as_double(0x7FF8000000000000ll);
         return;
     }
     const double t = ((double)i / n_pts) * Tn;
+    double Ep = 0.0;
+    int leg = 0;
+    for (;;) {
+        const double E = Ep + prof[(l0 + leg) * ps + 2 * n];
+        if (t < E || leg == nl - 1) break;
+        Ep = E; leg++;
+    }
+    if (i == n_pts) leg = M;
+    const size_t ls = l0 + leg;
+    const double *pf = prof + ls * ps;
+    const double T = sT[ls], tl = fmin(fmax(t - Ep, 0.0), pf[2 * n]);
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (pf[2 * mid] <= t) lo = mid; else hi = mid - 1;
+        if (pf[2 * mid] <= tl) lo = mid; else hi = mid - 1;
     }
-    const int k = lo;
+    int k = lo;
+    if (i == n_pts) k = n - 1;
     const double tk = pf[2 * k], xk = pf[2 * k + 1], x1 = pf[2 * k + 3], lk = sqrt(xk), w = (x1 - xk) * n, h = 0.5 / T;
-    double lam = lk + w * (t - tk) * h, s = (double)k / n + (t - tk) * (lk + lam) * h;
+    double lam = lk + w * (tl - tk) * h, s = (double)k / n + (tl - tk) * (lk + lam) * h;
     if (i == n_pts) { lam = sqrt(x1); s = 1.0; }
     s = fmin(fmax(s, 0.0), 1.0);
     const double xs = lam * lam;
-    const double *X = sx + (size_t)b * N * 2 * nq, *U = su + (size_t)b * N * nq;
+    const double *X = sx + ls * N * 2 * nq, *U = su + ls * N * nq;
     double Lg[4];
     const int seg = lagrange_segment(nseg, s, Lg);
     o[0] = t;
@@ -190,26 +232,31 @@ __global__ __launch_bounds__(128) void k_sample_retimed(const mpcmp_model *__res
         interp_joints(X + 7 * a, X + nq + 7 * a, 2 * nq, U + 7 * a, nq, seg, Lg, q, v, ac, sc);
 #pragma unroll
         for (int r = 0; r < 7; r++) { qd[r] = lam * v[r]; qdd[r] = xs * ac[r] + w * h * v[r]; }
-        rnea_dir<false>(mdl + (size_t)b * mstride + a, sc, qd, qdd, 0, 0, tau, nullptr);
+        rnea_dir<false>(mdl + ls * mstride + a, sc, qd, qdd, 0, 0, tau, nullptr);
 #pragma unroll
         for (int r = 0; r < 7; r++) { o[1 + 28 * a + r] = q[r]; o[8 + 28 * a + r] = qd[r]; o[15 + 28 * a + r] = qdd[r]; o[22 + 28 * a + r] = tau[r]; }
     }
 }
 
-hipError_t retime_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, const mpcmp_bounds *rows, const mpcmp_bounds &table,
-                         const double *d_sx, const double *d_su, const double *d_sT, const mpcmp_retime_spec &spec, double *d_prof, mpcmp_retime *d_out,
-                         hipStream_t st) {
-    if (narm < 1 || narm > RT_MAX_ARMS || nseg < 1 || 3 * nseg + 1 > RT_MAX_NODES || n_grid < 1 || n_grid > RT_MAX_GRID || B < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_retime, dim3(B), dim3(RT_NT), 0, st, mdl, mstride, narm, nseg, n_grid, rows, table, d_sx, d_su, d_sT, spec, d_prof, d_out);
+static bool rt_shape_ok(int narm, int nseg, int B, int M, int n_grid) {
+    return narm >= 1 && narm <= RT_MAX_ARMS && nseg >= 1 && 3 * nseg + 1 <= RT_MAX_NODES && n_grid >= 1 && n_grid <= RT_MAX_GRID && B >= 1 && M >= 0;
+}
+
+hipError_t retime_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, const mpcmp_bounds *rows,
+                         const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT, const mpcmp_retime_spec &spec,
+                         double *d_prof, double *d_leg_T, mpcmp_retime *d_plan_out, mpcmp_route_retime *d_route_out, hipStream_t st) {
+    if (!rt_shape_ok(narm, nseg, B, M, n_grid) || !d_plan_out == !d_route_out || (d_plan_out && M)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_retime, dim3(B), dim3(RT_NT), 0, st, mdl, mstride, narm, nseg, n_grid, M, rows, table, d_sx, d_su, d_sT, spec, d_prof,
+                       d_leg_T, d_plan_out, d_route_out);
     return hipGetLastError();
 }
 
-hipError_t sample_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, int n_pts, const double *d_sx,
+hipError_t sample_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts, const double *d_sx,
                                  const double *d_su, const double *d_sT, const double *d_prof, double *d_out, hipStream_t st) {
-    if (narm < 1 || narm > RT_MAX_ARMS || nseg < 1 || 3 * nseg + 1 > RT_MAX_NODES || n_grid < 1 || n_grid > RT_MAX_GRID || n_pts < 1 || B < 1) return hipErrorInvalidValue;
+    if (!rt_shape_ok(narm, nseg, B, M, n_grid) || n_pts < 1) return hipErrorInvalidValue;
     const long total = (long)B * (n_pts + 1);
-    hipLaunchKernelGGL(k_sample_retimed, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, mdl, mstride, narm, nseg, B, n_grid, n_pts, d_sx, d_su,
-                       d_sT, d_prof, d_out);
+    hipLaunchKernelGGL(k_sample_retimed, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, mdl, mstride, narm, nseg, B, M, n_grid, n_pts, d_sx,
+                       d_su, d_sT, d_prof, d_out);
     return hipGetLastError();
 }
 
@@ -218,104 +265,119 @@ hipError_t sample_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, 
 using namespace mpcmp;
 
 // ---- host statement (no GPU): the records from plain host C++, then the row, pair and clock arithmetic of retime.hpp ----
-namespace {
-// lagrange_segment and interp_joints (sample_device.hpp) for one arm on the host
-int lagrange_host(int nseg, double t, double *Lg) {
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)std::floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    return s;
-}
-}  // namespace
-
-extern "C" int mpcmp_retime_one(const mpcmp_model *models, int narm, int num_seg, const mpcmp_bounds *row, const mpcmp_retime_spec *spec,
-                                const double *x, const double *u, double T, int n_grid, double *prof, mpcmp_retime *out) {
-    if (!models || narm < 1 || narm > RT_MAX_ARMS || num_seg < 1 || 3 * num_seg + 1 > RT_MAX_NODES || !row || !x || !u || n_grid < 1 ||
-        n_grid > RT_MAX_GRID || !prof || !out) return MPCMP_EINVAL;
+// The rule over n_legs legs: rows [n_legs], x, u and prof leg after leg, T [n_legs]; leg_T_new may be NULL.
+static int retime_legs_host(const mpcmp_model *models, int narm, int num_seg, int n_legs, const mpcmp_bounds *rows, const mpcmp_retime_spec *spec,
+                            const double *x, const double *u, const double *T, int n_grid, double *prof, double *leg_T_new, mpcmp_route_retime *out) {
+    if (!models || narm < 1 || narm > RT_MAX_ARMS || num_seg < 1 || 3 * num_seg + 1 > RT_MAX_NODES || n_legs < 1 || !rows || !x || !u || !T ||
+        n_grid < 1 || n_grid > RT_MAX_GRID || !prof || !out) return MPCMP_EINVAL;
     const mpcmp_retime_spec sp = spec ? *spec : rt_default_spec();
     if (!rt_spec_ok(sp)) return MPCMP_EINVAL;
-    const int n = n_grid, N = 3 * num_seg + 1, nq = 7 * narm, nrows = RT_ROWS_ARM * narm;
-    const double *bd = reinterpret_cast<const double *>(row);
-    auto fill_nan = [&]() { for (int e = 0; e < 2 * (n + 1); e++) prof[e] = NAN; };
-    bool bad = !(std::isfinite(T) && T > 0.0);
-    for (int e = 0; e < 2 * nq * N; e++) bad = bad || !std::isfinite(x[e]);
-    for (int e = 0; e < nq * N; e++) bad = bad || !std::isfinite(u[e]);
-    if (bad) { fill_nan(); *out = rt_failed(MPCMP_RT_NAN, -1); return MPCMP_OK; }
+    const int n = n_grid, N = 3 * num_seg + 1, nq = 7 * narm, nrows = RT_ROWS_ARM * narm, nl = n_legs, Mlast = n_legs - 1;
+    const size_t P = (size_t)n + 1;                      // points per leg
+    auto fail_with = [&](int status, int leg, int k) {
+        for (size_t e = 0; e < 2 * P * nl; e++) prof[e] = NAN;
+        if (leg_T_new) for (int m = 0; m < nl; m++) leg_T_new[m] = INFINITY;
+        *out = rrt_failed(status, leg, k);
+        return MPCMP_OK;
+    };
+    bool bad = false;
+    for (int m = 0; m < nl; m++) bad = bad || !(std::isfinite(T[m]) && T[m] > 0.0);
+    for (size_t e = 0; e < (size_t)nl * 2 * nq * N; e++) bad = bad || !std::isfinite(x[e]);
+    for (size_t e = 0; e < (size_t)nl * nq * N; e++) bad = bad || !std::isfinite(u[e]);
+    if (bad) return fail_with(MPCMP_RT_NAN, -1, -1);
 
-    std::vector<double> rec((size_t)(n + 1) * narm * RT_NF), Klo(n + 1), Khi(n + 1);
-    for (int k = 0; k <= n; k++) {
-        double Lg[4];
-        const int s = lagrange_host(num_seg, (double)k / n, Lg);
-        for (int a = 0; a < narm; a++) {
-            double q[7], v[7], ac[7], tc[7], t1[7], t2[7], J[42], p[3], R[9], tw[6];
-            const double zero[7] = {0, 0, 0, 0, 0, 0, 0};
-            for (int r = 0; r < 7; r++) {
-                q[r] = v[r] = ac[r] = 0.0;
-                for (int j = 0; j < 4; j++) {
-                    q[r] += Lg[j] * x[2 * nq * (3 * s + j) + 7 * a + r];
-                    v[r] += Lg[j] * x[2 * nq * (3 * s + j) + nq + 7 * a + r];
-                    ac[r] += Lg[j] * u[nq * (3 * s + j) + 7 * a + r];
-                }
+    std::vector<double> rec(P * nl * narm * RT_NF), Klo(P * nl), Khi(P * nl);
+    for (int m = 0; m < nl; m++) {
+        const double *xm = x + (size_t)m * N * 2 * nq, *um = u + (size_t)m * N * nq, *bd = reinterpret_cast<const double *>(rows + m);
+        for (int k = 0; k <= n; k++) {
+            double Lg[4];
+            const int s = mpcmp_host::lagrange_host(num_seg, (double)k / n, Lg);
+            for (int a = 0; a < narm; a++) {
+                double q[7], v[7], ac[7], tc[7], t1[7], t2[7], J[42], p[3], R[9], tw[6];
+                const double zero[7] = {0, 0, 0, 0, 0, 0, 0};
+                mpcmp_host::interp_host(xm, um, nq, a, s, Lg, q, v, ac);
+                mpcmp_host::rnea_host(models[a], q, zero, zero, tc);
+                mpcmp_host::rnea_host(models[a], q, v, ac, t1);
+                mpcmp_host::rnea_host(models[a], q, zero, v, t2);
+                mpcmp_host::tool_jacobian(models[a], q, J, p, R);
+                for (int r = 0; r < 6; r++) { tw[r] = 0.0; for (int j = 0; j < 7; j++) tw[r] += J[7 * r + j] * v[j]; }
+                rt_record(bd, sp, v, ac, tc, t1, t2, std::sqrt(tw[0] * tw[0] + tw[1] * tw[1] + tw[2] * tw[2]),
+                          std::sqrt(tw[3] * tw[3] + tw[4] * tw[4] + tw[5] * tw[5]), &rec[((m * P + k) * narm + a) * RT_NF], 1);
             }
-            mpcmp_host::rnea_host(models[a], q, zero, zero, tc);
-            mpcmp_host::rnea_host(models[a], q, v, ac, t1);
-            mpcmp_host::rnea_host(models[a], q, zero, v, t2);
-            mpcmp_host::tool_jacobian(models[a], q, J, p, R);
-            for (int r = 0; r < 6; r++) { tw[r] = 0.0; for (int j = 0; j < 7; j++) tw[r] += J[7 * r + j] * v[j]; }
-            rt_record(bd, sp, v, ac, tc, t1, t2, std::sqrt(tw[0] * tw[0] + tw[1] * tw[1] + tw[2] * tw[2]),
-                      std::sqrt(tw[3] * tw[3] + tw[4] * tw[4] + tw[5] * tw[5]), &rec[((size_t)k * narm + a) * RT_NF], 1);
         }
     }
-    const double h = 0.5 / T, delta = 1.0 / n, rmax2 = sp.rate_max * sp.rate_max;
+    const double delta = 1.0 / n, rmax2 = sp.rate_max * sp.rate_max;
     double A[RT_ROWS_ARM * RT_MAX_ARMS + 2], Bc[RT_ROWS_ARM * RT_MAX_ARMS + 2], Cc[RT_ROWS_ARM * RT_MAX_ARMS + 2];
-    auto point_rows = [&](int k) { for (int r = 0; r < nrows; r++) rt_row(&rec[((size_t)k * narm + r / RT_ROWS_ARM) * RT_NF], 1, bd, h, sp.groups, r % RT_ROWS_ARM, A[r], Bc[r], Cc[r]); };
-    auto moving = [&](int k) { for (int a = 0; a < narm; a++) for (int j = 0; j < 7; j++) if (rec[((size_t)k * narm + a) * RT_NF + RT_V + j] != 0.0) return true; return false; };
-    auto cap_of = [&](int k) { double c = INFINITY; for (int a = 0; a < narm; a++) c = fmin(c, rec[((size_t)k * narm + a) * RT_NF + RT_CAP]); return c; };
-    const bool pin0 = moving(0), pinn = moving(n);
+    auto point_rows = [&](int m, int k) {
+        const double *bd = reinterpret_cast<const double *>(rows + m);
+        const double h = 0.5 / T[m];
+        for (int r = 0; r < nrows; r++) rt_row(&rec[((m * P + k) * narm + r / RT_ROWS_ARM) * RT_NF], 1, bd, h, sp.groups, r % RT_ROWS_ARM, A[r], Bc[r], Cc[r]);
+    };
+    auto moving = [&](int m, int k) { for (int a = 0; a < narm; a++) for (int j = 0; j < 7; j++) if (rec[((m * P + k) * narm + a) * RT_NF + RT_V + j] != 0.0) return true; return false; };
+    auto cap_of = [&](int m, int k) { double c = INFINITY; for (int a = 0; a < narm; a++) c = fmin(c, rec[((m * P + k) * narm + a) * RT_NF + RT_CAP]); return c; };
+    const bool pin0 = moving(0, 0), pinn = moving(Mlast, n);
     // backward
-    for (int k = n; k >= 0; k--) {
-        point_rows(k);
-        int m = nrows;
-        if (k < n) { A[m] = delta; Bc[m] = 1.0; Cc[m] = -Khi[k + 1]; m++; A[m] = -delta; Bc[m] = -1.0; Cc[m] = Klo[k + 1]; m++; }
-        RtSet S = {0.0, INFINITY, 0};
-        for (int i = 0; i < m; i++) {
-            if (A[i] == 0.0) rt_cut_x(S, Bc[i], Cc[i]);
-            if (k < n && A[i] > 0.0) for (int j = 0; j < m; j++) if (A[j] < 0.0) rt_cut_pair(S, A[i], Bc[i], Cc[i], A[j], Bc[j], Cc[j]);
+    for (int m = Mlast; m >= 0; m--) {
+        for (int k = n; k >= 0; k--) {
+            point_rows(m, k);
+            int nr = nrows;
+            if (k < n) { A[nr] = delta; Bc[nr] = 1.0; Cc[nr] = -Khi[m * P + k + 1]; nr++; A[nr] = -delta; Bc[nr] = -1.0; Cc[nr] = Klo[m * P + k + 1]; nr++; }
+            RtSet S = {0.0, INFINITY, 0};
+            for (int i = 0; i < nr; i++) {
+                if (A[i] == 0.0) rt_cut_x(S, Bc[i], Cc[i]);
+                if (k < n && A[i] > 0.0) for (int j = 0; j < nr; j++) if (A[j] < 0.0) rt_cut_pair(S, A[i], Bc[i], Cc[i], A[j], Bc[j], Cc[j]);
+            }
+            double lo = S.lo, hi = fmin(S.hi, cap_of(m, k));
+            if (k == n && m < Mlast) { lo = fmax(lo, Klo[(m + 1) * P]); hi = fmin(hi, Khi[(m + 1) * P]); }
+            bool fail = S.empty || !(lo <= hi) || hi == 0.0;
+            if ((k == n && m == Mlast && pinn) || (k == 0 && m == 0 && pin0)) {
+                fail = fail || !(lo <= 1.0 && 1.0 <= hi);
+                if (k == n) lo = hi = 1.0;
+            }
+            if (fail) return fail_with(MPCMP_RT_INFEASIBLE, m, k);
+            Klo[m * P + k] = lo; Khi[m * P + k] = hi;
         }
-        double lo = S.lo, hi = fmin(S.hi, cap_of(k));
-        bool fail = S.empty || !(lo <= hi) || hi == 0.0;
-        if ((k == n && pinn) || (k == 0 && pin0)) {
-            fail = fail || !(lo <= 1.0 && 1.0 <= hi);
-            if (k == n) lo = hi = 1.0;
-        }
-        if (fail) { fill_nan(); *out = rt_failed(MPCMP_RT_INFEASIBLE, k); return MPCMP_OK; }
-        Klo[k] = lo; Khi[k] = hi;
     }
     // forward
-    double xk = pin0 ? 1.0 : Khi[0], t = 0.0, xmin = INFINITY;
-    int kmin = 0, nslow = 0;
-    for (int k = 0; k <= n; k++) {
-        if (xk < xmin) { xmin = xk; kmin = k; }
-        if (xk < rmax2) nslow++;
-        prof[2 * k] = t; prof[2 * k + 1] = xk;
-        if (k == n) break;
-        point_rows(k);
-        double w = rt_w_max(delta, 1.0, -Khi[k + 1], xk);
-        for (int r = 0; r < nrows; r++) if (A[r] > 0.0) w = fmin(w, rt_w_max(A[r], Bc[r], Cc[r], xk));
-        const double x1 = fmin(fmax(xk + delta * w, Klo[k + 1]), Khi[k + 1]);
-        t += rt_dt(T, delta, xk, x1);
-        xk = x1;
+    double xk = pin0 ? 1.0 : Khi[0], Ttot = 0.0, xmin = INFINITY;
+    int kmin = 0, legmin = 0, nslow = 0;
+    for (int m = 0; m < nl; m++) {
+        double t = 0.0;
+        double *pf = prof + 2 * P * m;
+        for (int k = 0; k <= n; k++) {
+            if (xk < xmin) { xmin = xk; kmin = k; legmin = m; }
+            if ((k > 0 || m == 0) && xk < rmax2) nslow++;
+            pf[2 * k] = t; pf[2 * k + 1] = xk;
+            if (k == n) break;
+            point_rows(m, k);
+            double w = rt_w_max(delta, 1.0, -Khi[m * P + k + 1], xk);
+            for (int r = 0; r < nrows; r++) if (A[r] > 0.0) w = fmin(w, rt_w_max(A[r], Bc[r], Cc[r], xk));
+            const double x1 = fmin(fmax(xk + delta * w, Klo[m * P + k + 1]), Khi[m * P + k + 1]);
+            t += rt_dt(T[m], delta, xk, x1);
+            xk = x1;
+        }
+        if (leg_T_new) leg_T_new[m] = t;
+        Ttot = m == 0 ? t : Ttot + t;
     }
-    if (!std::isfinite(t)) { fill_nan(); *out = rt_failed(MPCMP_RT_INFEASIBLE, -1); return MPCMP_OK; }
-    mpcmp_retime r = rt_failed(0, -1);
-    r.T_new = t; r.rate_min = std::sqrt(xmin); r.s_slowest = (double)kmin / n; r.n_slowed = nslow;
+    if (!std::isfinite(Ttot)) return fail_with(MPCMP_RT_INFEASIBLE, -1, -1);
+    mpcmp_route_retime r = rrt_failed(0, -1, -1);
+    r.T_new = Ttot; r.rate_min = std::sqrt(xmin); r.s_slowest = (double)kmin / n; r.leg_slowest = legmin; r.n_slowed = nslow;
     *out = r;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_retime_route_one(const mpcmp_model *models, int narm, int num_seg, int n_legs, const mpcmp_bounds *rows,
+                                      const mpcmp_retime_spec *spec, const double *x, const double *u, const double *T, int n_grid, double *prof,
+                                      double *leg_T_new, mpcmp_route_retime *out) {
+    return retime_legs_host(models, narm, num_seg, n_legs, rows, spec, x, u, T, n_grid, prof, leg_T_new, out);
+}
+
+// a plan is a route of one leg with one bounds row; its record is that route's without the leg fields
+extern "C" int mpcmp_retime_one(const mpcmp_model *models, int narm, int num_seg, const mpcmp_bounds *row, const mpcmp_retime_spec *spec,
+                                const double *x, const double *u, double T, int n_grid, double *prof, mpcmp_retime *out) {
+    if (!out) return MPCMP_EINVAL;
+    mpcmp_route_retime r;
+    if (int rc = retime_legs_host(models, narm, num_seg, 1, row, spec, x, u, &T, n_grid, prof, nullptr, &r)) return rc;
+    *out = rt_plan_record(r);
     return MPCMP_OK;
 }

@@ -1,7 +1,8 @@
-// retime.hpp — what retiming (include/mpcmp_retime.h) shares between the host entry points (mpcmp.hip), its kernels (retime.hip) and the host
-// statement mpcmp_retime_one: the record of a grid point, the rows it stands for, the elimination of w over a pair of rows, the forward step and the
-// clock, each one text for host and device.  The kernels themselves live in retime.hip, a translation unit of its own: nothing here is a kernel, so
-// including this header does not change what any other translation unit compiles to.
+// retime.hpp — what retiming of plans and of whole via-point routes (include/mpcmp_retime.h, include/mpcmp_route_retime.h) shares between the host
+// entry points (mpcmp.hip), its kernels and the host statements mpcmp_retime_one / mpcmp_retime_route_one (retime.hip): the record of a grid point,
+// the rows it stands for, the elimination of w over a pair of rows, the forward step and the clock, each one text for host and device.  A plan is a
+// route of one leg: there is one kernel set, and the plan calls run it with M = 0.  The kernels themselves live in retime.hip, a translation unit of
+// its own: nothing here is a kernel, so including this header does not change what any other translation unit compiles to.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -89,18 +90,27 @@ inline bool rt_spec_ok(const mpcmp_retime_spec &s) {
     return s.tool_lin_max >= 0.0 && s.tool_ang_max >= 0.0 && std::isfinite(s.rate_max) && s.rate_max > 0.0 && (s.groups & ~MPCMP_RT_ALL_GROUPS) == 0;
 }
 
-// the record of a plan that is not retimed (status INFEASIBLE or NAN)
-__host__ __device__ inline mpcmp_retime rt_failed(int status, int k_fail) {
-    mpcmp_retime r;
-    r.T_new = INFINITY; r.rate_min = 0.0; r.s_slowest = -1.0; r.k_fail = k_fail; r.n_slowed = 0; r.status = status; r.pad = 0;
+// the record of a route that is not retimed (status INFEASIBLE or NAN)
+__host__ __device__ inline mpcmp_route_retime rrt_failed(int status, int leg_fail, int k_fail) {
+    mpcmp_route_retime r;
+    r.T_new = INFINITY; r.rate_min = 0.0; r.s_slowest = -1.0; r.leg_slowest = -1; r.leg_fail = leg_fail; r.k_fail = k_fail; r.n_slowed = 0;
+    r.status = status; r.pad = 0;
     return r;
 }
+// the record of a plan from that of its one-leg route: the same values without the leg fields
+__host__ __device__ inline mpcmp_retime rt_plan_record(const mpcmp_route_retime &r) {
+    mpcmp_retime p;
+    p.T_new = r.T_new; p.rate_min = r.rate_min; p.s_slowest = r.s_slowest; p.k_fail = r.k_fail; p.n_slowed = r.n_slowed; p.status = r.status; p.pad = 0;
+    return p;
+}
 
-// mdl / mstride as k_sample takes them (problem b, arm a: mdl + b * mstride + a); rows [B] or NULL: then `table`, the configuration's, for everyone
-hipError_t retime_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, const mpcmp_bounds *rows, const mpcmp_bounds &table,
-                         const double *d_sx, const double *d_su, const double *d_sT, const mpcmp_retime_spec &spec, double *d_prof, mpcmp_retime *d_out,
-                         hipStream_t st);
-hipError_t sample_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, int n_pts, const double *d_sx,
+// B routes of M + 1 legs each (plans: M = 0).  mdl / mstride as k_sample takes them (leg slot l, arm a: mdl + l * mstride + a); rows [B (M + 1)] or
+// NULL: then `table`, the configuration's, for every leg slot; d_leg_T may be NULL.  The records go to d_route_out or, for plans (M = 0 only), to
+// d_plan_out: exactly one of the two is given.
+hipError_t retime_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, const mpcmp_bounds *rows,
+                         const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT, const mpcmp_retime_spec &spec,
+                         double *d_prof, double *d_leg_T, mpcmp_retime *d_plan_out, mpcmp_route_retime *d_route_out, hipStream_t st);
+hipError_t sample_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts, const double *d_sx,
                                  const double *d_su, const double *d_sT, const double *d_prof, double *d_out, hipStream_t st);
 
 }  // namespace mpcmp

@@ -1,7 +1,7 @@
 // retimed_check.hip — the limit checker of retimed plans and routes (include/mpcmp_retimed_check.h): per plan or route the record of mpcmp_limits.h
 // for the motion its rate profile stands for, at the uniform physical times of the retimed samplers; the uniform scaling of a profile; and the host
-// statement that needs no context.  A translation unit of its own, so that k_limits, k_retime, k_retime_route, the samplers and the register-bound
-// QP kernels compile exactly as before.
+// statement that needs no context.  A plan is a route of one leg: the plan call runs k_limits_retimed with M = 0.  A translation unit of its own, so
+// that k_limits, k_retime, the samplers and the register-bound QP kernels compile exactly as before.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "retimed_check.hpp"
@@ -92,58 +92,24 @@ __device__ __forceinline__ void rc_write_failed(const mpcmp_limits_spec &sp, int
     if (Tnew) Tnew[b] = INFINITY;
 }
 
-// One workgroup per plan, the shape of k_limits.  Staged in LDS once: the nodes of the plan (x and u, at most 25 x 42 doubles) and the bounds row of
-// the problem.  Then one thread per sample, strided over the n_pts + 1 samples: a bisection on the t_k of the profile in global memory (at most 12
-// steps over at most 64 KB per plan, which stay in L2), the retimed-sample rule, and rc_fold_sample.  Nothing of a sample is stored: a thread keeps
-// its LimAcc in registers over all its samples, and one workgroup reduction ends the kernel.
-__global__ __launch_bounds__(LIM_NT) void k_limits_retimed(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int n, int n_pts,
-                                                           const mpcmp_bounds *__restrict__ rows, mpcmp_bounds table,
+// One workgroup per route of M + 1 legs (a plan: M = 0), the shape of k_limits.  Every thread forms the retimed leg durations D_m = the last t of
+// each leg's profile and their sum T_new sequentially, as k_sample_retimed does.  Then the legs in turn: the nodes (x and u, at most 25 x 42 doubles)
+// and the bounds row of the leg slot are staged in LDS, and every thread takes those of its samples (strided, so increasing in time) that the
+// sampler's rule places in this leg: with E_m the sequential prefix sums, the first leg with t < E_m, leg M for what is left and for sample n_pts.
+// Per sample a bisection on the t_k of the leg's profile in global memory (at most 12 steps over at most 64 KB per leg, which stay in L2), the
+// retimed-sample rule, and rc_fold_sample.  Nothing of a sample is stored: a thread keeps its LimAcc in registers over all its samples, and one
+// workgroup reduction ends the kernel.  Static LDS only, and none of it grows with n_pts, n_grid or M.  The key stays sample << 4 | channel: ties go
+// to the lowest sample of the route clock.  ONE_LEG: the same text compiled with M == 0 known, which the launcher takes for M = 0: without it a plan
+// call measured 1.8 % slower than the plan kernel this one replaces ("One kernel set for plans and routes").
+template <bool ONE_LEG>
+__global__ __launch_bounds__(LIM_NT) void k_limits_retimed(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int n, int legs_m,
+                                                           int n_pts, const mpcmp_bounds *__restrict__ rows, mpcmp_bounds table,
                                                            const double *__restrict__ sx, const double *__restrict__ su,
-                                                           const double *__restrict__ sT, const double *__restrict__ prof, mpcmp_limits_spec sp,
-                                                           mpcmp_limits *__restrict__ out, double *__restrict__ Tnew) {
-    __shared__ double nodes[LIM_MAX_NODES * 21 * LIM_MAX_ARMS];      // x [N][14 narm], then u [N][7 narm]
-    __shared__ double bd[58];
-    const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm;
-    const double *pf = prof + (size_t)b * (n + 1) * 2;
-    const double Tn = pf[2 * n];
-    if (!lim_finite(Tn)) {                       // (the same for every thread of the workgroup)
-        if (tid == 0) rc_write_failed(sp, n_pts, out, Tnew, b);
-        return;
-    }
-    double *Xs = nodes, *Us = nodes + 2 * nq * N;
-    const double *X = sx + (size_t)b * N * 2 * nq, *U = su + (size_t)b * N * nq;
-    for (int e = tid; e < 2 * nq * N; e += LIM_NT) Xs[e] = X[e];
-    for (int e = tid; e < nq * N; e += LIM_NT) Us[e] = U[e];
-    {
-        const double *row = reinterpret_cast<const double *>(rows + b), *tab = reinterpret_cast<const double *>(&table);
-        for (int e = tid; e < 58; e += LIM_NT) bd[e] = rows ? row[e] : tab[e];
-    }
-    __syncthreads();
-
-    const double T = sT[b], h = 0.5 / T;
-    LimAcc A;
-    lim_init(A);
-    if (!lim_finite(T)) A.nan = 1;
-    for (int ip = tid; ip <= n_pts; ip += LIM_NT) {
-        const double t = ((double)ip / n_pts) * Tn;
-        const RcPlace pl = rc_place(pf, n, t, h, ip == n_pts);
-        rc_fold_sample(A, mdl + (size_t)b * mstride, narm, nseg, Xs, Us, bd, sp, ip, pl);
-    }
-    rc_reduce_write(A, tid, sp, n_pts, Tn, out, Tnew, b);
-}
-
-// One workgroup per route.  Every thread forms the retimed leg durations D_m = the last t of each leg's profile and their sum T_new sequentially, as
-// k_sample_retimed_route does.  Then the legs in turn: the nodes and the bounds row of the leg slot are staged in the LDS the plan kernel uses, and
-// every thread takes those of its samples (strided, so increasing in time) that the sampler's rule places in this leg: with E_m the sequential prefix
-// sums, the first leg with t < E_m, leg M for what is left and for sample n_pts.  Static LDS only, and none of it grows with n_pts, n_grid or M.
-// The key stays sample << 4 | channel: ties go to the lowest sample of the route clock.
-__global__ __launch_bounds__(LIM_NT) void k_limits_retimed_route(const mpcmp_model *__restrict__ mdl, int mstride, int narm, int nseg, int n, int M,
-                                                                 int n_pts, const mpcmp_bounds *__restrict__ rows, mpcmp_bounds table,
-                                                                 const double *__restrict__ sx, const double *__restrict__ su,
-                                                                 const double *__restrict__ sT, const double *__restrict__ prof,
-                                                                 mpcmp_limits_spec sp, mpcmp_limits *__restrict__ out, double *__restrict__ Tnew) {
+                                                           const double *__restrict__ sT, const double *__restrict__ prof,
+                                                           mpcmp_limits_spec sp, mpcmp_limits *__restrict__ out, double *__restrict__ Tnew) {
     __shared__ double nodes[LIM_MAX_NODES * 21 * LIM_MAX_ARMS];      // x [N][14 narm], then u [N][7 narm] of the leg in hand
     __shared__ double bd[58];
+    const int M = ONE_LEG ? 0 : legs_m;
     const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm, nl = M + 1;
     const size_t l0 = (size_t)b * nl, ps = (size_t)(n + 1) * 2;
     double Tn = 0.0;
@@ -204,21 +170,13 @@ static bool rc_shape_ok(int narm, int nseg, int B, int M, int n_grid, int n_pts)
            n_pts <= LIM_MAX_PTS && B >= 1 && M >= 0;
 }
 
-hipError_t limits_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, int n_pts, const mpcmp_bounds *rows,
-                                 const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT, const double *d_prof,
-                                 const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
-    if (!rc_shape_ok(narm, nseg, B, 0, n_grid, n_pts)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_limits_retimed, dim3(B), dim3(LIM_NT), 0, st, mdl, mstride, narm, nseg, n_grid, n_pts, rows, table, d_sx, d_su, d_sT, d_prof,
-                       spec, d_out, d_Tnew);
-    return hipGetLastError();
-}
-
-hipError_t limits_retimed_route_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts,
-                                       const mpcmp_bounds *rows, const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT,
-                                       const double *d_prof, const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
+hipError_t limits_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts,
+                                 const mpcmp_bounds *rows, const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT,
+                                 const double *d_prof, const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st) {
     if (!rc_shape_ok(narm, nseg, B, M, n_grid, n_pts)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_limits_retimed_route, dim3(B), dim3(LIM_NT), 0, st, mdl, mstride, narm, nseg, n_grid, M, n_pts, rows, table, d_sx, d_su, d_sT,
-                       d_prof, spec, d_out, d_Tnew);
+    const auto kernel = M == 0 ? k_limits_retimed<true> : k_limits_retimed<false>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(LIM_NT), 0, st, mdl, mstride, narm, nseg, n_grid, M, n_pts, rows, table, d_sx, d_su, d_sT, d_prof, spec,
+                       d_out, d_Tnew);
     return hipGetLastError();
 }
 
@@ -234,23 +192,6 @@ hipError_t profile_scale_launch(int L, int n_grid, const double *d_factor, doubl
 using namespace mpcmp;
 
 // ---- host statement (no GPU): the samples from plain host C++, then the place, fold and record arithmetic of retimed_check.hpp / limits.hpp ----
-namespace {
-// lagrange_segment (sample_device.hpp) on the host
-int rc_lagrange_host(int nseg, double t, double *Lg) {
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)std::floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    return s;
-}
-}  // namespace
-
 extern "C" int mpcmp_limits_retimed_one(const mpcmp_model *models, int narm, int num_seg, int n_legs, const mpcmp_bounds *rows,
                                         const mpcmp_limits_spec *spec, const double *x, const double *u, const double *T, int n_grid,
                                         const double *prof, int n_pts, mpcmp_limits *out, double *T_new) {
@@ -291,20 +232,12 @@ extern "C" int mpcmp_limits_retimed_one(const mpcmp_model *models, int narm, int
         const RcPlace pl = rc_place(pf, n, tl, 0.5 / T[leg], ip == n_pts);
         const double xs = pl.lam * pl.lam;
         double Lg[4];
-        const int s = rc_lagrange_host(num_seg, pl.s, Lg);
+        const int s = mpcmp_host::lagrange_host(num_seg, pl.s, Lg);
         bool over = false;
         for (int a = 0; a < narm; a++) {
-            double q[7], qd[7], qdd[7], tau[7], J[42], p[3], R[9], tw[6];
-            for (int r = 0; r < 7; r++) {
-                double v = 0.0, ac = 0.0;
-                q[r] = 0.0;
-                for (int j = 0; j < 4; j++) {
-                    q[r] += Lg[j] * xm[2 * nq * (3 * s + j) + 7 * a + r];
-                    v += Lg[j] * xm[2 * nq * (3 * s + j) + nq + 7 * a + r];
-                    ac += Lg[j] * um[nq * (3 * s + j) + 7 * a + r];
-                }
-                qd[r] = pl.lam * v; qdd[r] = xs * ac + pl.wh * v;
-            }
+            double q[7], v[7], ac[7], qd[7], qdd[7], tau[7], J[42], p[3], R[9], tw[6];
+            mpcmp_host::interp_host(xm, um, nq, a, s, Lg, q, v, ac);
+            for (int r = 0; r < 7; r++) { qd[r] = pl.lam * v[r]; qdd[r] = xs * ac[r] + pl.wh * v[r]; }
             mpcmp_host::rnea_host(models[a], q, qd, qdd, tau);
             mpcmp_host::tool_jacobian(models[a], q, J, p, R);
             for (int r = 0; r < 6; r++) { tw[r] = 0.0; for (int j = 0; j < 7; j++) tw[r] += J[7 * r + j] * qd[j]; }

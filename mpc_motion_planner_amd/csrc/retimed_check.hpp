@@ -50,14 +50,11 @@ __host__ __device__ inline mpcmp_limits rc_record(const LimAcc &A, const mpcmp_l
     return r;
 }
 
-// mdl / mstride as k_sample takes them (slot l, arm a: mdl + l * mstride + a); rows [B] (routes: [L]) or NULL: then `table`, the configuration's, for
-// everyone; d_Tnew may be NULL
-hipError_t limits_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int n_grid, int n_pts, const mpcmp_bounds *rows,
-                                 const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT, const double *d_prof,
-                                 const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st);
-hipError_t limits_retimed_route_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts,
-                                       const mpcmp_bounds *rows, const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT,
-                                       const double *d_prof, const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st);
+// B routes of M + 1 legs each (plans: M = 0).  mdl / mstride as k_sample takes them (leg slot l, arm a: mdl + l * mstride + a); rows [B (M + 1)] or
+// NULL: then `table`, the configuration's, for everyone; d_Tnew may be NULL
+hipError_t limits_retimed_launch(const mpcmp_model *mdl, int mstride, int narm, int nseg, int B, int M, int n_grid, int n_pts,
+                                 const mpcmp_bounds *rows, const mpcmp_bounds &table, const double *d_sx, const double *d_su, const double *d_sT,
+                                 const double *d_prof, const mpcmp_limits_spec &spec, mpcmp_limits *d_out, double *d_Tnew, hipStream_t st);
 hipError_t profile_scale_launch(int L, int n_grid, const double *d_factor, double *d_prof, hipStream_t st);
 
 }  // namespace mpcmp

@@ -290,22 +290,25 @@ def test_the_limits_hold(M, nseg, narm, nvia):
 
 @pytest.mark.parametrize("nseg,narm", [(4, 1), (6, 2)])
 def test_one_leg_is_the_rule_of_a_single_plan(M, nseg, narm):
-    """M == 0: status and k_fail equal those of mpcmp_retime_one, x and T_new within 1e-11 relative (one source text in two translation units: only
-    floating-point contraction may differ, 2^-53 per operation times the asserted amplification of 100)"""
+    """n_legs == 1: the whole profile and every field the two records share equal those of mpcmp_retime_one bit for bit: a plan is a route of one
+    leg, and mpcmp_retime_one runs the host statement of mpcmp_retime_route_one"""
     n_grid = 50
     sx, su, sT = route_moves(narm, nseg, 0)
     models, table = robot(M, narm), route_rows(M, nseg, narm, 0)
-    bitwise = True
+    retimed = 0
     for b in range(B):
         prof, leg_T, rec = M.retime_route_one(models, nseg, table[b], sx[b], su[b], sT[b], n_grid, None)
         p1, r1 = M.retime_one(models, nseg, table[b, 0], sx[b, 0], su[b, 0], sT[b, 0], n_grid, None)
-        assert (rec["status"], rec["k_fail"], rec["leg_fail"]) == (r1["status"], r1["k_fail"], 0 if r1["status"] and r1["k_fail"] >= 0 else -1), b
+        assert np.ascontiguousarray(prof[0]).tobytes() == p1.tobytes(), b
+        for f in ("T_new", "rate_min", "s_slowest", "k_fail", "n_slowed", "status"):
+            assert np.asarray(rec[f]).tobytes() == np.asarray(r1[f]).tobytes(), (b, f)
+        assert rec["leg_fail"] == (0 if r1["status"] and r1["k_fail"] >= 0 else -1), b
         if r1["status"]:
+            assert np.isnan(p1).all(), b
             continue
-        assert np.allclose(prof[0], p1, rtol=1e-11, atol=0.0) and abs(rec["T_new"] - r1["T_new"]) <= 1e-11 * r1["T_new"] and rec["n_slowed"] == r1["n_slowed"], b
-        assert rec["leg_slowest"] == 0 and rec["s_slowest"] == r1["s_slowest"] and leg_T[0] == rec["T_new"], b
-        bitwise = bitwise and prof[0].tobytes() == p1.tobytes()
-    print("nseg %d, arms %d: one-leg routes against mpcmp_retime_one bitwise equal: %s" % (nseg, narm, bitwise))
+        assert rec["leg_slowest"] == 0 and leg_T[0] == rec["T_new"], b
+        retimed += 1
+    assert retimed >= 1
 
 
 def test_bad_inputs_and_arguments(M):
