@@ -44,10 +44,11 @@ def joint7_height(model, q):
     return p[:, 2]
 
 
-def sample_states(B, margins, seed=SEED, stream_offset=0, min_height=0.05, model=None, salt=0):
-    """[B,14] random feasible states. margins = (position, velocity, ...)."""
+def sample_states(B, margins, seed=SEED, stream_offset=0, min_height=0.05, model=None, salt=0, limits=None):
+    """[B,14] random feasible states. margins = (position, velocity, ...).  model / limits: the arm and its limit tables (a dict with qmin, qmax,
+    vmax); by default the compiled-in ones of the library."""
     model = model or capi.default_model()
-    L = capi.default_limits()
+    L = limits or capi.default_limits()
     mp, mv = margins[0], margins[1]
     s = (1 - mp) * (L["qmax"] - L["qmin"]) / 2
     base = (int(seed) * 0x100000001B3 + int(salt)) & _M64
@@ -78,8 +79,9 @@ def ik_seeds(B, S, cfg, seed=SEED):
     return (0.5 * (u.reshape(B, S, 7) * (hi - lo) + (hi + lo))).copy()
 
 
-def make_batch(B, margins=(0.9, 0.9, 0.5, 0.9, 0.1), seed=SEED, stream_offset=0):
-    """(x0 [B,14], xf [B,14]) — margins default to examples/offline_trajectory.cpp:9."""
-    x0 = sample_states(B, margins, seed, stream_offset, salt=0)
-    xf = sample_states(B, margins, seed, stream_offset, salt=1)
+def make_batch(B, margins=(0.9, 0.9, 0.5, 0.9, 0.1), seed=SEED, stream_offset=0, model=None, limits=None):
+    """(x0 [B,14], xf [B,14]) — margins default to examples/offline_trajectory.cpp:9.  model / limits: as sample_states (given both, the
+    library is not needed)."""
+    x0 = sample_states(B, margins, seed, stream_offset, salt=0, model=model, limits=limits)
+    xf = sample_states(B, margins, seed, stream_offset, salt=1, model=model, limits=limits)
     return x0, xf

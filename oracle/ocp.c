@@ -11,7 +11,8 @@
  * /root/reference (.gitmodules:1-4), so that layer follows the published algorithms
  * (Chebyshev-Gauss-Lobatto collocation on splines; OSQP-form ADMM, Stellato et al. 2020;
  * l1-merit line-search SQP, Nocedal&Wright ch.18) with every free choice explicit in orc_config.
- * PARITY UNPINNED at digit level for this layer (see oracle.h).
+ * PARITY UNPINNED at digit level for this layer as far as the choice of algorithm goes; what the code below computes is pinned to the
+ * dense statement of the specification in tests/ocp_reference.py (see oracle.h).
  *
  * NLP:
  *   z = [x_0..x_{N-1} | u_0..u_{N-1} | T],  N = 3*NUM_SEG+1, ascending time

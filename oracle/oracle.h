@@ -11,7 +11,12 @@
  *   - RNEA derivatives / mass matrix: pinned indirectly (finite differences of the pinned RNEA).
  *   - jerk-limited warm start (jerk.c, restating the Ruckig call): PINNED by the reference's stored Ruckig trajectory
  *     (tests/golden/gold_traj.json: duration to 6 digits, all seven joints to the stored precision).
- *   - collocation / SQP / box-ADMM layer: "PARITY UNPINNED" at digit level. The arithmetic of
+ *   - collocation / SQP / box-ADMM layer, two questions:
+ *       what this code computes — PINNED to an independent dense statement of include/mpcmp.h and SURVEY.md Appendix B
+ *       (tests/ocp_reference.py, numpy, long double: constraint Jacobian and Hessian arrow against differences, the QP's
+ *       epsilon-KKT certificate, the ADMM trajectory iteration for iteration, line search, multiplier update and result
+ *       record; tests/test_ocp_reference_host.py);
+ *       whether that statement is the reference's algorithm — "PARITY UNPINNED" at digit level. The arithmetic of
  *     that layer lives in polympc (https://gitlab.epfl.ch/listov/polympc.git, branch
  *     collocation_fix_jw, commit not recoverable), which is an empty submodule in the
  *     reference snapshot. It is restated from the reference's call sites

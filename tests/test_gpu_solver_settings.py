@@ -210,11 +210,12 @@ def _problems(narm, nseg, locked):
     if key not in _PROB:
         from mpc_motion_planner_amd import scenarios
         offs = OFFSETS[(narm, nseg)]
+        tables = dict(model=o.default_model(), limits=o.default_limits())     # (the oracle's, the same numbers as the library's: tests/test_ocp_reference_host.py builds these problems without the GPU library)
         x0, xf = [], []
         for off in offs:
-            a0, af = scenarios.make_batch(1, MARGINS, stream_offset=off)
+            a0, af = scenarios.make_batch(1, MARGINS, stream_offset=off, **tables)
             if narm == 2:
-                b0, bf = scenarios.make_batch(1, MARGINS, stream_offset=off + 7919)
+                b0, bf = scenarios.make_batch(1, MARGINS, stream_offset=off + 7919, **tables)
                 a0, af = o.merge_arm_states([a0[0], b0[0]])[None], o.merge_arm_states([af[0], bf[0]])[None]
             x0.append(a0[0]); xf.append(af[0])
         x0, xf = np.array(x0), np.array(xf)
