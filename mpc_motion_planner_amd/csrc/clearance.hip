@@ -5,12 +5,13 @@
 #include <cmath>
 #include <cstring>
 #include "clearance.hpp"
+#include "plan_interp.hpp"
 
 namespace mpcmp {
 
 // One workgroup per trajectory.  Staged in LDS once: the joint placements of the arms, the node positions of the trajectory, the sphere tables and
 // the problem's obstacles (in the form of clr_obs_prepare).  Then the n_pts + 1 samples in chunks of `chunk`, four phases per chunk:
-//   A1  one thread per (sample, joint): Lagrange interpolation of the joint position (the rule of k_sample) and its sine / cosine;
+//   A1  one thread per (sample, joint): the node interpolant of the joint position (plan_interp.hpp) and its sine / cosine;
 //   A2  one thread per (sample, arm): the forward-kinematics chain, once per sample: world rotation and origin of the 7 joint frames;
 //   B   one thread per (sample, sphere): world centre, then every obstacle (a uniform loop: all lanes read one obstacle, broadcast from LDS);
 //   C   one thread per (sample, sphere s): every partner sphere t > s that clr_pair admits.
@@ -67,20 +68,9 @@ __global__ __launch_bounds__(CLR_NT) void k_clearance(const mpcmp_model *__restr
         // A1
         for (int it = tid; it < ns * nq; it += CLR_NT) {
             const int sl = it / nq, j = it % nq;
-            const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-            const double t = (double)(ip0 + sl) / n_pts;
-            int s = (int)floor(t * nseg);
-            if (s >= nseg) s = nseg - 1;
-            if (s < 0) s = 0;
-            const double xx = 2.0 * (t * nseg - s) - 1.0;
-            double q = 0.0;
-#pragma unroll
-            for (int jj = 0; jj < 4; jj++) {
-                double v = 1.0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) if (k != jj) v *= (xx - xi[k]) / (xi[jj] - xi[k]);
-                q += v * nodes[(3 * s + jj) * nq + j];
-            }
+            double Lg[4];
+            const int s = mpcmp_plan::lagrange_segment(nseg, (double)(ip0 + sl) / n_pts, Lg);
+            const double q = mpcmp_plan::interp_channel(nodes + j, nq, s, Lg);
             if (!isfinite(q)) nan_flag = 1;
             double sn, cs;
             sincos(q, &sn, &cs);

@@ -52,32 +52,11 @@ __global__ __launch_bounds__(64) void k_mpc_point(const mpcmp_model *mdl, int ms
     const int N = 3 * nseg + 1;
     const double T = sT[b];
     const double t = (time[b] < T) ? time[b] / T : T;
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
     double Lg[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        double w = 1.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (k != j) w *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = w;
-    }
+    const int s = lagrange_segment(nseg, t, Lg);
     const double *X = sx + (size_t)b * 14 * N, *U = su + (size_t)b * 7 * N;
     double q[7], v[7], a[7], tau[7], sc[14];
-#pragma unroll
-    for (int r = 0; r < 7; r++) {
-        q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            q[r] += Lg[j] * X[14 * (3 * s + j) + r];
-            v[r] += Lg[j] * X[14 * (3 * s + j) + 7 + r];
-            a[r] += Lg[j] * U[7 * (3 * s + j) + r];
-        }
-        sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
-    }
+    interp_joints(X, X + 7, 14, U, 7, s, Lg, q, v, a, sc);
     rnea_dir<false>(mdl, sc, v, a, 0, 0, tau, nullptr);
     double *o = out + (size_t)b * 28;
 #pragma unroll
@@ -111,25 +90,11 @@ __global__ __launch_bounds__(256) void k_advance(int nseg, int nx, int B, double
         for (int r = 0; r < nx; r++) xo[r] = X[(size_t)(N - 1) * nx + r];
         arrive = true;
     } else {
-        const double t = dt / T;
-        const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-        int s = (int)floor(t * nseg);
-        if (s >= nseg) s = nseg - 1;
-        if (s < 0) s = 0;
-        const double xx = 2.0 * (t * nseg - s) - 1.0;
         double w[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double v = 1.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-            w[j] = v;
-        }
+        const double *Xs = X + (size_t)(3 * lagrange_segment(nseg, dt / T, w)) * nx;       // the first node of the segment
         double far = 0.0;
         for (int r = 0; r < nx; r++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc += w[j] * X[(size_t)(3 * s + j) * nx + r];
+            const double acc = mpcmp_plan::interp_channel(Xs + r, nx, 0, w);
             xo[r] = acc;
             far = fmax(far, fabs(acc - xf[(size_t)b * nx + r]));
         }
@@ -182,33 +147,11 @@ __global__ __launch_bounds__(256) void k_traj_stats(const mpcmp_model *mdl, int 
     const double T = sT[b];
     if (tid < 4) fl[tid] = 1;
     __syncthreads();
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
     for (int ip = tid; ip <= n_pts; ip += blockDim.x) {
-        const double t = (double)ip / n_pts;
-        int s = (int)floor(t * nseg);
-        if (s >= nseg) s = nseg - 1;
-        if (s < 0) s = 0;
-        const double xx = 2.0 * (t * nseg - s) - 1.0;
         double Lg[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            double v = 1.0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-            Lg[j] = v;
-        }
+        const int s = lagrange_segment(nseg, (double)ip / n_pts, Lg);
         double q[7], v[7], a[7], tau[7], sc[14];
-#pragma unroll
-        for (int r = 0; r < 7; r++) {
-            q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                q[r] += Lg[j] * X[14 * (3 * s + j) + r];
-                v[r] += Lg[j] * X[14 * (3 * s + j) + 7 + r];
-                a[r] += Lg[j] * U[7 * (3 * s + j) + r];
-            }
-            sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
-        }
+        interp_joints(X, X + 7, 14, U, 7, s, Lg, q, v, a, sc);
         rnea_dir<false>(mdl, sc, v, a, 0, 0, tau, nullptr);
         V3 pt, vl, va;
         fk_task_velocity(mdl, sc, v, &pt, &vl, &va);

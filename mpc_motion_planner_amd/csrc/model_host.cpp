@@ -20,6 +20,7 @@
 #include "model_host.hpp"
 #include "kinematics_host.hpp"
 #include "payload.hpp"
+#include "plan_interp.hpp"
 #include "toolpath.hpp"
 
 using namespace mpcmp;
@@ -34,9 +35,7 @@ extern "C" int mpcmp_num_nodes(int num_seg) { return 3 * num_seg + 1; }
 
 extern "C" int mpcmp_time_nodes(int num_seg, double *tau) {
     if (num_seg < 1 || !tau) return MPCMP_EINVAL;
-    static const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    for (int s = 0; s < num_seg; s++)
-        for (int j = 0; j < 4; j++) tau[3 * s + j] = (s + 0.5 * (xi[j] + 1.0)) / num_seg;
+    for (int k = 0; k <= 3 * num_seg; k++) tau[k] = mpcmp_plan::node_time(num_seg, k);
     return MPCMP_OK;
 }
 

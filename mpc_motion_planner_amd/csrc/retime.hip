@@ -291,11 +291,11 @@ static int retime_legs_host(const mpcmp_model *models, int narm, int num_seg, in
         const double *xm = x + (size_t)m * N * 2 * nq, *um = u + (size_t)m * N * nq, *bd = reinterpret_cast<const double *>(rows + m);
         for (int k = 0; k <= n; k++) {
             double Lg[4];
-            const int s = mpcmp_host::lagrange_host(num_seg, (double)k / n, Lg);
+            const int s = mpcmp_plan::lagrange_segment(num_seg, (double)k / n, Lg);
             for (int a = 0; a < narm; a++) {
                 double q[7], v[7], ac[7], tc[7], t1[7], t2[7], J[42], p[3], R[9], tw[6];
                 const double zero[7] = {0, 0, 0, 0, 0, 0, 0};
-                mpcmp_host::interp_host(xm, um, nq, a, s, Lg, q, v, ac);
+                mpcmp_plan::interp_qva(xm + 7 * a, xm + nq + 7 * a, 2 * nq, um + 7 * a, nq, s, Lg, q, v, ac);
                 mpcmp_host::rnea_host(models[a], q, zero, zero, tc);
                 mpcmp_host::rnea_host(models[a], q, v, ac, t1);
                 mpcmp_host::rnea_host(models[a], q, zero, v, t2);

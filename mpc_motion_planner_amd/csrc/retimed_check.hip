@@ -232,11 +232,11 @@ extern "C" int mpcmp_limits_retimed_one(const mpcmp_model *models, int narm, int
         const RcPlace pl = rc_place(pf, n, tl, 0.5 / T[leg], ip == n_pts);
         const double xs = pl.lam * pl.lam;
         double Lg[4];
-        const int s = mpcmp_host::lagrange_host(num_seg, pl.s, Lg);
+        const int s = mpcmp_plan::lagrange_segment(num_seg, pl.s, Lg);
         bool over = false;
         for (int a = 0; a < narm; a++) {
             double q[7], v[7], ac[7], qd[7], qdd[7], tau[7], J[42], p[3], R[9], tw[6];
-            mpcmp_host::interp_host(xm, um, nq, a, s, Lg, q, v, ac);
+            mpcmp_plan::interp_qva(xm + 7 * a, xm + nq + 7 * a, 2 * nq, um + 7 * a, nq, s, Lg, q, v, ac);
             for (int r = 0; r < 7; r++) { qd[r] = pl.lam * v[r]; qdd[r] = xs * ac[r] + pl.wh * v[r]; }
             mpcmp_host::rnea_host(models[a], q, qd, qdd, tau);
             mpcmp_host::tool_jacobian(models[a], q, J, p, R);

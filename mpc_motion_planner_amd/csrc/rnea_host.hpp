@@ -1,4 +1,4 @@
-// rnea_host.hpp — the Newton-Euler recursion and the node interpolation in plain host C++, for the host statements of the checkers
+// rnea_host.hpp — the Newton-Euler recursion in plain host C++, for the host statements of the checkers
 // (mpcmp_limits_config, mpcmp_retime_one, mpcmp_retime_route_one, mpcmp_limits_retimed_one), which run without a context and without a GPU.
 #pragma once
 #include <cmath>
@@ -41,33 +41,6 @@ inline void rnea_host(const mpcmp_model &M, const double *q, const double *v, co
         }
         f = fi; n = ni;
         tau[i] = n.z;
-    }
-}
-
-// lagrange_segment (sample_device.hpp) on the host: the segment of t in [0, 1] and the four weights of its nodes
-inline int lagrange_host(int nseg, double t, double *Lg) {
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)std::floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    return s;
-}
-
-// interp_joints (sample_device.hpp) for arm a on the host: q, v and a of the arm from the nodes x [N][2 nq], u [N][nq] of segment s
-inline void interp_host(const double *x, const double *u, int nq, int a, int s, const double *Lg, double *q, double *v, double *ac) {
-    for (int r = 0; r < 7; r++) {
-        q[r] = v[r] = ac[r] = 0.0;
-        for (int j = 0; j < 4; j++) {
-            q[r] += Lg[j] * x[2 * nq * (3 * s + j) + 7 * a + r];
-            v[r] += Lg[j] * x[2 * nq * (3 * s + j) + nq + 7 * a + r];
-            ac[r] += Lg[j] * u[nq * (3 * s + j) + 7 * a + r];
-        }
     }
 }
 

@@ -1,44 +1,25 @@
 // sample_device.hpp — one row of get_MPC_trajectory (motionPlanner.hpp:99-116) as a device function: the state and control of a trajectory at a
-// normalised time, Lagrange interpolation on the segment, and the RNEA torque.  k_sample (solver_kernels.hpp) and k_sample_route (route.hip) both
-// call it, so that a route sample is the row a plain sample of its leg gives; k_limits (limits.hip) interpolates with the two pieces it is made
-// of.  Nothing here is a kernel.
+// normalised time, the node interpolant of plan_interp.hpp, and the RNEA torque.  k_sample (leaf_kernels.hpp) and k_sample_route (route.hip) both
+// call it, so that a route sample is the row a plain sample of its leg gives; the other device readers of a plan interpolate with the two pieces it
+// is made of.  Nothing here is a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "plan_interp.hpp"
 #include "rbd_device.hpp"
 
 namespace mpcmp {
 
-// The segment of the normalised time t in [0, 1] and the four Lagrange weights of its nodes 3 s .. 3 s + 3: the interpolation rule of every sampler
-// (k_sample, k_sample_route, k_limits)
-__device__ __forceinline__ int lagrange_segment(int nseg, double t, double *Lg) {
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    return s;
-}
+using mpcmp_plan::lagrange_segment;
 
-// q, qd, qdd [7] of one arm on segment s with the weights Lg, and sc [14] = sine, cosine of q.  Q / V / A point at the arm's seven positions /
-// velocities / accelerations in node 0; xs / us doubles lie between two nodes of the state / control arrays (any arm layout)
+// interp_qva (plan_interp.hpp) on the device, plus sc [14] = sine, cosine of q.  Joint by joint, each sine / cosine beside the sums it follows: the
+// order the kernels' register budgets were measured with (with the sines after all the sums k_traj_stats and k_sample_retimed spill 8 B more)
 __device__ __forceinline__ void interp_joints(const double *Q, const double *V, int xs, const double *A, int us, int s, const double *Lg,
                                               double *q, double *v, double *a, double *sc) {
 #pragma unroll
     for (int r = 0; r < 7; r++) {
-        q[r] = v[r] = a[r] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            q[r] += Lg[j] * Q[xs * (3 * s + j) + r];
-            v[r] += Lg[j] * V[xs * (3 * s + j) + r];
-            a[r] += Lg[j] * A[us * (3 * s + j) + r];
-        }
+        q[r] = mpcmp_plan::interp_channel(Q + r, xs, s, Lg);
+        v[r] = mpcmp_plan::interp_channel(V + r, xs, s, Lg);
+        a[r] = mpcmp_plan::interp_channel(A + r, us, s, Lg);
         sincos(q[r], &sc[2 * r], &sc[2 * r + 1]);
     }
 }

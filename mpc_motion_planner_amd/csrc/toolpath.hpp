@@ -7,6 +7,7 @@
 #include <cmath>
 #include "../../include/mpcmp.h"
 #include "kinematics_host.hpp"
+#include "plan_interp.hpp"
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TL_UNROLL _Pragma("unroll")
@@ -456,22 +457,6 @@ MPCMP_HD void tl_q_excess(const double *Q, int xs, int nseg, const double *lbq, 
 }
 
 // ---- the deviation of a plan from its line ----
-// the segment of t in [0, 1] and the four Lagrange weights of its nodes 3 s .. 3 s + 3: the arithmetic of lagrange_segment (sample_device.hpp)
-MPCMP_HD int tl_lagrange(int nseg, double t, double *Lg) {
-    const double xi[4] = {-1.0, -0.5, 0.5, 1.0};
-    int s = (int)std::floor(t * nseg);
-    if (s >= nseg) s = nseg - 1;
-    if (s < 0) s = 0;
-    const double xx = 2.0 * (t * nseg - s) - 1.0;
-    TL_UNROLL
-    for (int j = 0; j < 4; j++) {
-        double v = 1.0;
-        TL_UNROLL
-        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - xi[k]) / (xi[j] - xi[k]);
-        Lg[j] = v;
-    }
-    return s;
-}
 // the line of a plan: from the tool pose of node 0 (Q: the arm's positions there) to (R1, p1)
 MPCMP_HD void tl_line_of_plan(const mpcmp_model &M, const double *Q, const double *R1, const double *p1, TlLine &Ln) {
     double q[7], R0[9], p0[3];
@@ -485,13 +470,8 @@ MPCMP_HD void tl_dev_sample(const mpcmp_model &M, const TlLine &Ln, int nseg, co
                             double *dang) {
     const double s = (double)i / n_pts;
     double Lg[4], q[7];
-    const int seg = tl_lagrange(nseg, s, Lg);
-    TL_UNROLL
-    for (int r = 0; r < 7; r++) {
-        q[r] = 0.0;
-        TL_UNROLL
-        for (int j = 0; j < 4; j++) q[r] += Lg[j] * Q[(size_t)xs * (3 * seg + j) + r];
-    }
+    const int seg = mpcmp_plan::lagrange_segment(nseg, s, Lg);
+    mpcmp_plan::interp_q(Q, xs, seg, Lg, q);
     double R[9], p[3], Rd[9], pd[3];
     tl_fk(M, q, R, p);
     tl_pose(Ln, tl_sigma(s), Rd, pd);
