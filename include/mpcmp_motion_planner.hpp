@@ -331,6 +331,15 @@ class MotionPlanner {
         chk(mpcmp_clearance_batch(ctx_, 1, sol_x_.data(), &sol_T_, n_pts, margin, self_gap, &r));
         return r;
     }
+    // certified clearance record of the last solution (include/mpcmp_clearance_cert.h): status 0 means that no clearance falls below `margin` at ANY
+    // time of the plan, not only at samples; MPCMP_CLR_UNDECIDED: not decided within max_depth halvings of the num_seg n_start first intervals.
+    // *cert (may be null): the lower bound d_lower of the true minimum (which lies in [d_lower, d_min]) and the work done
+    mpcmp_clearance check_clearance_certified(double margin = 0.0, int self_gap = 0, int n_start = 4, int max_depth = 10,
+                                              mpcmp_clearance_cert *cert = nullptr) {
+        mpcmp_clearance r;
+        chk(mpcmp_clearance_certified_batch(ctx_, 1, sol_x_.data(), &sol_T_, margin, self_gap, n_start, max_depth, &r, cert));
+        return r;
+    }
     // limit record of the last solution BETWEEN its nodes, at n_pts + 1 uniform samples (include/mpcmp_limits.h): excess per group under the bounds
     // the plan was solved with, and the stretch of T that makes the kinematic groups hold.  spec NULL: tol 0, no tool speed limits
     mpcmp_limits check_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr) {

@@ -62,6 +62,10 @@ OBSTACLE_DTYPE = np.dtype([("type", "i4"), ("pad", "i4"), ("a", "f8", 3), ("b", 
 CLEARANCE_DTYPE = np.dtype([("d_min", "f8"), ("t_min", "f8"), ("t_first", "f8"), ("sphere", "i4"), ("other", "i4"), ("n_hit", "i4"), ("status", "i4")])
 OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE = 0, 1, 2, 3
 CLR_HIT, CLR_NAN = 1, 2
+# the certified check (mpcmp_clearance_cert, include/mpcmp_clearance_cert.h): 32 bytes; CLR_UNDECIDED is a status bit of CLEARANCE_DTYPE records
+CLR_UNDECIDED = 4
+CLEARANCE_CERT_DTYPE = np.dtype([("d_lower", "f8"), ("t_lower", "f8"), ("n_eval", "i4"), ("n_clear", "i4"), ("n_undecided", "i4"), ("depth", "i4")])
+CLR_CERT_CAPACITY = 4096
 MAX_SPHERES, MAX_OBSTACLES = 64, 256
 
 # records of the between-node limit checks (mpcmp_limits_spec, mpcmp_limits; include/mpcmp.h): 72 and 168 bytes
@@ -172,6 +176,11 @@ ABI_TOOLPATH = {
     "mpcmp_tool_line_batch": "pii" + "p" * 9, "mpcmp_tool_line_batch_device": "pii" + "p" * 10, "mpcmp_tool_line_one": "pipppppdpppp",
     "mpcmp_tool_deviation_batch": "piipppiddp", "mpcmp_tool_deviation_batch_device": "piipppiddpp", "mpcmp_tool_deviation_one": "pipppiddp",
 }
+# ... and every function include/mpcmp_clearance_cert.h declares (certified clearance), in its order
+ABI_CLEARANCE_CERT = {
+    "mpcmp_clearance_certified_batch": "pippdiiipp", "mpcmp_clearance_certified_batch_device": "pippdiiippp",
+    "mpcmp_clearance_certified_one": "piippippddiiipp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -228,7 +237,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -339,6 +348,26 @@ def clearance_config(models, spheres_per_arm, obstacles, q, self_gap=0):
     check(lib().mpcmp_clearance_config(arr, narm, host(cnt), host(tab), obs.shape[0], host(obs), int(self_gap), host(q), C.byref(d), C.byref(sp),
                                        C.byref(ot)))
     return d.value, sp.value, ot.value
+
+
+def clearance_certified_one(models, num_seg, spheres_per_arm, obstacles, x, T, margin=0.0, self_gap=0, n_start=4, max_depth=10):
+    """mpcmp_clearance_certified_one: the certified check of ONE plan x [N][14 narm] of duration T on the host (no context, no GPU).  models,
+    spheres_per_arm and obstacles as for clearance_config.  Returns (the CLEARANCE_DTYPE record, the CLEARANCE_CERT_DTYPE record)."""
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    obs = np.zeros(0, dtype=OBSTACLE_DTYPE) if obstacles is None else _records(obstacles, OBSTACLE_DTYPE, "obstacle").reshape(-1)
+    x = f64(x).reshape(N, 14 * narm)
+    rec, cert = np.zeros(1, dtype=CLEARANCE_DTYPE), np.zeros(1, dtype=CLEARANCE_CERT_DTYPE)
+    check(lib().mpcmp_clearance_certified_one(arr, narm, int(num_seg), host(cnt), host(tab), obs.shape[0], host(obs), host(x), float(T), float(margin),
+                                              int(self_gap), int(n_start), int(max_depth), host(rec), host(cert)))
+    return rec[0], cert[0]
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

@@ -1,5 +1,6 @@
 // clearance.hpp — what the clearance checker shares between the host entry points (mpcmp.hip), its kernels (clearance.hip) and the host
-// restatement mpcmp_clearance_config: the obstacle distance formulas, the pair rules, the ordering of ties, the LDS budget and the launchers.
+// restatement mpcmp_clearance_config: the obstacle distance formulas, the pair rules and the ordering of ties (clearance_rule.hpp, plain C++, read by
+// the host-only unit as well), the LDS budget and the launchers.
 // The kernels themselves live in clearance.hip, a translation unit of their own: nothing here is a kernel, so including this header does not
 // change what any other translation unit compiles to.
 #pragma once
@@ -7,11 +8,10 @@
 #include <cmath>
 #include <cstddef>
 #include "../../include/mpcmp.h"
+#include "clearance_rule.hpp"
 
 namespace mpcmp {
 
-constexpr int CLR_MAX_SPH = 64;      // robot spheres per arm
-constexpr int CLR_MAX_OBS = 256;     // obstacles per set
 constexpr int CLR_MAX_PTS = 4096;    // n_pts
 constexpr int CLR_NT = 256;          // threads per workgroup of k_clearance
 
@@ -20,58 +20,6 @@ struct ClrSphere {
     double c[3], r;
     int joint, arm;
 };
-
-// An obstacle in the form the distance function reads, k[8] = a(3), b'(3), r, w: for a capsule b' = b - a and w = 1 / |b - a|^2 (0 when a == b),
-// formed once per obstacle instead of once per pair; every other type b' = b, w = 0.
-__host__ __device__ inline void clr_obs_prepare(const mpcmp_obstacle &o, double *k) {
-    for (int d = 0; d < 3; d++) { k[d] = o.a[d]; k[3 + d] = o.b[d]; }
-    k[6] = o.r; k[7] = 0.0;
-    if (o.type == MPCMP_OBS_CAPSULE) {
-        double l2 = 0.0;
-        for (int d = 0; d < 3; d++) { k[3 + d] = o.b[d] - o.a[d]; l2 += k[3 + d] * k[3 + d]; }
-        k[7] = l2 > 0.0 ? 1.0 / l2 : 0.0;
-    }
-}
-
-// signed distance of the world point (x, y, z) to an obstacle (include/mpcmp.h, "Signed distance")
-__host__ __device__ inline double clr_sd(int type, const double *k, double x, double y, double z) {
-    const double dx = x - k[0], dy = y - k[1], dz = z - k[2];
-    if (type == MPCMP_OBS_SPHERE) return sqrt(dx * dx + dy * dy + dz * dz) - k[6];
-    if (type == MPCMP_OBS_CAPSULE) {
-        double t = (dx * k[3] + dy * k[4] + dz * k[5]) * k[7];
-        t = fmin(fmax(t, 0.0), 1.0);
-        const double ex = dx - t * k[3], ey = dy - t * k[4], ez = dz - t * k[5];
-        return sqrt(ex * ex + ey * ey + ez * ez) - k[6];
-    }
-    if (type == MPCMP_OBS_BOX) {
-        const double qx = fabs(dx) - k[3], qy = fabs(dy) - k[4], qz = fabs(dz) - k[5];
-        const double ox = fmax(qx, 0.0), oy = fmax(qy, 0.0), oz = fmax(qz, 0.0);
-        return sqrt(ox * ox + oy * oy + oz * oz) + fmin(fmax(qx, fmax(qy, qz)), 0.0) - k[6];
-    }
-    return k[0] * x + k[1] * y + k[2] * z - k[3];      // MPCMP_OBS_HALFSPACE
-}
-
-// robot pair (s, t), s < t in table order: always across arms; within one arm only with self_gap > 0 and joint indices at least self_gap apart
-__host__ __device__ inline bool clr_pair(int arm_s, int joint_s, int arm_t, int joint_t, int self_gap) {
-    if (arm_s != arm_t) return true;
-    const int d = joint_s > joint_t ? joint_s - joint_t : joint_t - joint_s;
-    return self_gap > 0 && d >= self_gap;
-}
-
-// Ties of d_min: lowest sample, then lowest sphere, then obstacles before robot pairs, then lowest index = the order of this key.
-// sample < 2^13, sphere < 2^7, index < 2^8.
-__host__ __device__ inline unsigned clr_pack(int ip, int sphere, int robot, int idx) {
-    return ((unsigned)ip << 17) | ((unsigned)sphere << 9) | ((unsigned)robot << 8) | (unsigned)idx;
-}
-constexpr unsigned CLR_NO_PAIR = 0xFFFFFFFFu;
-__host__ __device__ inline bool clr_better(double d, unsigned k, double bd, unsigned bk) { return d < bd || (d == bd && k < bk); }
-
-// a double as an unsigned key of the same order (the key of time_sync.hpp, restated here because that header defines kernels)
-__host__ __device__ inline unsigned long long clr_tkey(double x) {
-    unsigned long long u;
-    __builtin_memcpy(&u, &x, 8);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 // samples per chunk: as many as keep chunk x spheres <= 1024 world centres in LDS, at most 32
 inline int clr_chunk(int nsph) {
@@ -98,6 +46,10 @@ struct ClrTables {
 hipError_t clearance_prepare();     // the kernel's dynamic-LDS ceiling; called by a context's first check
 hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
                             mpcmp_clearance *d_out, hipStream_t st);
+// the certified check (include/mpcmp_clearance_cert.h; the kernel is in clearance_cert.hip, the rule in clearance_cert.hpp); d_cert may be NULL
+hipError_t clearance_cert_prepare();
+hipError_t clearance_cert_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, double margin, int self_gap, int n_start,
+                                 int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, hipStream_t st);
 // keys [n_groups] scratch; chosen [n_groups].  d_clr and d_lim may each be NULL (that test is skipped); lim_mask: the bits of mpcmp_limits.status that
 // make a member inadmissible (MPCMP_LIM_NAN always does)
 hipError_t select_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const mpcmp_limits *d_lim, int lim_mask,

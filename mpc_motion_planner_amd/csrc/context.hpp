@@ -51,6 +51,7 @@ struct mpcmp_ctx {
     mpcmp_obstacle *d_clr_obs = nullptr;
     size_t clr_obs_cap = 0;
     int clr_sets = 0, clr_nobs = 0;
+    bool clr_cert_ready = false;     // ... and the certified check's (mpcmp_clearance_certified_batch*), by its first call
     bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
     unsigned long long *d_sel_key = nullptr;
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their

@@ -1,6 +1,6 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
 // configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
-// statements of the tool-line moves (toolpath.hpp).  Plain C++: no HIP
+// statements of the tool-line moves (toolpath.hpp) and of the certified clearance check (clearance_cert.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -22,6 +22,7 @@
 #include "payload.hpp"
 #include "plan_interp.hpp"
 #include "toolpath.hpp"
+#include "clearance_cert.hpp"
 
 using namespace mpcmp;
 
@@ -525,5 +526,122 @@ extern "C" int mpcmp_tool_deviation_one(const mpcmp_model *model, int num_seg, c
         tl_dev_fold(A, i, dl, dp, da, tol_lin, tol_ang);
     }
     *out = tl_dev_record(A, n_pts);
+    return MPCMP_OK;
+}
+
+// ---- certified clearance on the host (include/mpcmp_clearance_cert.h): one plan through the source the kernel runs (clearance_cert.hpp) ----
+extern "C" int mpcmp_clearance_certified_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                                             const mpcmp_obstacle *obs, const double *x, double T, double margin, int self_gap, int n_start, int max_depth,
+                                             mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (!models || narm < 1 || narm > 2 || num_seg < 1 || !n_spheres || !x || !out || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_obs > 0 && !obs) ||
+        self_gap < 0 || !std::isfinite(margin) || n_start < 1 || n_start > CERT_CAP || (long)num_seg * n_start > CERT_CAP || max_depth < 0 ||
+        max_depth > CERT_MAX_DEPTH) {
+        g_err = "mpcmp_clearance_certified_one: one or two arms, num_seg >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a finite "
+                "margin, self_gap >= 0, n_obs in [0, 256] and all pointers (but cert) required";
+        return MPCMP_EINVAL;
+    }
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
+    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
+    const int nq = 7 * narm, N = 3 * num_seg + 1, n0 = num_seg * n_start;
+    // the tables in the form the kernel stages them
+    std::vector<double> mk(84 * narm), nodes((size_t)nq * N), reach(7 * (nsph > 0 ? nsph : 1)), ok(8 * (n_obs > 0 ? n_obs : 1));
+    std::vector<int> arm(nsph), jnt(nsph);
+    for (int a = 0; a < narm; a++)
+        for (int i = 0; i < 7; i++) {
+            for (int c = 0; c < 9; c++) mk[84 * a + 12 * i + c] = models[a].R0[i][c];
+            for (int c = 0; c < 3; c++) mk[84 * a + 12 * i + 9 + c] = models[a].p[i][c];
+        }
+    bool nan = false;
+    for (int k = 0; k < N; k++)
+        for (int j = 0; j < nq; j++) { nodes[(size_t)k * nq + j] = x[(size_t)k * 2 * nq + j]; if (!std::isfinite(x[(size_t)k * 2 * nq + j])) nan = true; }
+    for (int a = 0, s = 0; a < narm; a++)
+        for (int k = 0; k < n_spheres[a]; k++, s++) {
+            arm[s] = a; jnt[s] = spheres[s].joint;
+            cert_reach(mk.data() + 84 * a + 9, 12, jnt[s], spheres[s].c, reach.data() + 7 * s);
+        }
+    for (int o = 0; o < n_obs; o++) clr_obs_prepare(obs[o], ok.data() + 8 * o);
+    mpcmp_clearance r;
+    mpcmp_clearance_cert c;
+    if (nan) {
+        r.d_min = std::nan(""); r.t_min = -1.0; r.t_first = -1.0; r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
+        c.d_lower = std::nan(""); c.t_lower = -1.0; c.n_eval = 0; c.n_clear = 0; c.n_undecided = 0; c.depth = 0;
+        *out = r;
+        if (cert) *cert = c;
+        return MPCMP_OK;
+    }
+    double best_d = INFINITY, best_L = INFINITY;
+    unsigned long long best_k = CERT_NO_PAIR, best_Lk = CERT_NO_PAIR;
+    unsigned first = CERT_NO_TIME;
+    int n_hit = 0, n_clear = 0, n_und = 0, n_eval = 0, depth = 0;
+    std::vector<int> cur(n0), nxt;
+    for (int i = 0; i < n0; i++) cur[i] = i;
+    std::vector<double> cen(3 * (nsph > 0 ? nsph : 1)), Ds(nsph > 0 ? nsph : 1);
+    for (int l = 0; !cur.empty(); l++) {
+        depth = l;
+        nxt.clear();
+        int n_split = 0;
+        for (int i : cur) {
+            const CertInterval v = cert_interval(n0, n_start, l, i);
+            const unsigned tk = cert_tkey(l, i);
+            double dev[14], sc[28], fr[2 * 84];
+            for (int j = 0; j < nq; j++) {
+                double qm;
+                dev[j] = cert_deviation(nodes.data() + j, nq, num_seg, v, &qm);
+                sc[2 * j] = std::sin(qm); sc[2 * j + 1] = std::cos(qm);
+            }
+            for (int a = 0; a < narm; a++) cert_frames(mk.data() + 84 * a, sc + 14 * a, fr + 84 * a);
+            for (int s = 0; s < nsph; s++) {
+                Ds[s] = cert_motion(reach.data() + 7 * s, dev + 7 * arm[s]);
+                cert_centre(fr + 84 * arm[s] + 12 * jnt[s], spheres[s].c, cen.data() + 3 * s);
+            }
+            double d_mid = INFINITY, L = INFINITY;
+            for (int s = 0; s < nsph; s++) {
+                const double *C = cen.data() + 3 * s;
+                for (int o = 0; o < n_obs; o++) {
+                    const double d = clr_sd(obs[o].type, ok.data() + 8 * o, C[0], C[1], C[2]) - spheres[s].r;
+                    const unsigned long long key = cert_key(tk, s, 0, o);
+                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s]);
+                }
+                for (int t = s + 1; t < nsph; t++) {
+                    if (!clr_pair(arm[s], jnt[s], arm[t], jnt[t], self_gap)) continue;
+                    const double ex = C[0] - cen[3 * t], ey = C[1] - cen[3 * t + 1], ez = C[2] - cen[3 * t + 2];
+                    const double d = std::sqrt(ex * ex + ey * ey + ez * ez) - spheres[s].r - spheres[t].r;
+                    const unsigned long long key = cert_key(tk, s, 1, t);
+                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s] - Ds[t]);
+                }
+            }
+            n_eval++;
+            int what = cert_decide(d_mid, L, margin, l, max_depth);
+            if (what == CERT_SPLIT_IT) {
+                if (n_split < CERT_SPLIT) { n_split++; nxt.push_back(2 * i); nxt.push_back(2 * i + 1); continue; }
+                what = CERT_UNDECIDED;          // (the capacity rule)
+            }
+            if (what == CERT_HIT) { n_hit++; if (tk < first) first = tk; }
+            else if (what == CERT_CLEAR) n_clear++;
+            else n_und++;
+            const unsigned long long lk = cert_key(tk, 0, 0, 0);
+            if (cert_better(L, lk, best_L, best_Lk)) { best_L = L; best_Lk = lk; }
+        }
+        cur.swap(nxt);
+    }
+    r.d_min = best_d;
+    if (best_k == CERT_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
+    else {
+        const int idx = (int)(best_k & 0xFFu);
+        r.t_min = cert_time(n0, (unsigned)(best_k >> 16)) * T;
+        r.sphere = (int)((best_k >> 9) & 0x7Fu);
+        r.other = (best_k & 0x100u) ? -1 - idx : idx;
+    }
+    r.t_first = first != CERT_NO_TIME ? cert_time(n0, first) * T : -1.0;
+    r.n_hit = n_hit;
+    r.status = (n_hit > 0 ? MPCMP_CLR_HIT : 0) | (n_und > 0 ? MPCMP_CLR_UNDECIDED : 0);
+    c.d_lower = best_L; c.t_lower = cert_time(n0, (unsigned)(best_Lk >> 16)) * T;
+    c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
+    *out = r;
+    if (cert) *cert = c;
     return MPCMP_OK;
 }

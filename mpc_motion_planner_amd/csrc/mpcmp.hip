@@ -992,6 +992,57 @@ extern "C" int mpcmp_clearance_batch(mpcmp_ctx *ctx, int B, const double *sx, co
     return sg.finish();
 }
 
+// the certified check (include/mpcmp_clearance_cert.h; the kernel is in clearance_cert.hip)
+static int clearance_cert_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int self_gap, int n_start, int max_depth,
+                                const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_certified_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0 || n_start < 1 || n_start > MPCMP_CLR_CERT_CAPACITY ||
+        ctx->nseg * n_start > MPCMP_CLR_CERT_CAPACITY || max_depth < 0 || max_depth > 16) {
+        ctx->err = "mpcmp_clearance_certified_batch: B >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a finite margin, "
+                   "self_gap >= 0 and all pointers (but cert) required";
+        return MPCMP_EINVAL;
+    }
+    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+static int clearance_cert_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, double margin, int self_gap, int n_start, int max_depth,
+                                  mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, hipStream_t st) {
+    ClrTables t;
+    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
+    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
+    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    if (!ctx->clr_cert_ready) { HIPCHK(ctx, clearance_cert_prepare()); ctx->clr_cert_ready = true; }
+    HIPCHK(ctx, clearance_cert_launch(t, B, d_sx, d_sT, margin, self_gap, n_start, max_depth, d_out, d_cert, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, double margin, int self_gap,
+                                                      int n_start, int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert,
+                                                      void *hip_stream) {
+    if (int rc = clearance_cert_check(ctx, B, d_sx, d_sT, margin, self_gap, n_start, max_depth, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return clearance_cert_enqueue(ctx, B, d_sx, d_sT, margin, self_gap, n_start, max_depth, d_out, d_cert, (hipStream_t)hip_stream);
+}
+
+extern "C" int mpcmp_clearance_certified_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int self_gap, int n_start,
+                                               int max_depth, mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (int rc = clearance_cert_check(ctx, B, sx, sT, margin, self_gap, n_start, max_depth, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT;
+    mpcmp_clearance *dout;
+    mpcmp_clearance_cert *dcert = nullptr;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.out(&dout, out, B);
+    if (cert) sg.out(&dcert, cert, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = clearance_cert_enqueue(ctx, B, dx, dT, margin, self_gap, n_start, max_depth, dout, dcert, ctx->stream)) return rc;
+    return sg.finish();
+}
+
 // `who`: the entry point's name; clr is required by mpcmp_select_clear_batch only
 static int select_check(mpcmp_ctx *ctx, const char *who, bool need_clr, int B, const double *sT, const mpcmp_info *info, const mpcmp_clearance *clr,
                         const int *group, int n_groups, const int *chosen) {

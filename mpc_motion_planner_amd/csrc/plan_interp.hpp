@@ -53,6 +53,38 @@ MPCMP_HD int lagrange_segment(int nseg, double t, double *Lg) {
     return s;
 }
 
+// The four weights of the normalised time t on a segment s THE CALLER NAMES: the cubic of segment s, also at a t that is the segment's end (where
+// lagrange_segment would answer with the next segment) or outside it
+MPCMP_HD void lagrange_on_segment(int nseg, int s, double t, double *Lg) {
+    const double xx = 2.0 * (t * nseg - s) - 1.0;
+    PLAN_UNROLL
+    for (int j = 0; j < 4; j++) {
+        double v = 1.0;
+        PLAN_UNROLL
+        for (int k = 0; k < 4; k++) if (k != j) v *= (xx - node_xi(k)) / (node_xi(j) - node_xi(k));
+        Lg[j] = v;
+    }
+}
+
+// ... and the weights dLg of the DERIVATIVE of that cubic in normalised time (d xi / d t = 2 nseg): sum_j dLg[j] C[node 3 s + j] is the slope of the
+// position interpolant itself, which is not the velocity channel of a plan
+MPCMP_HD void lagrange_derivative_on_segment(int nseg, int s, double t, double *dLg) {
+    const double xx = 2.0 * (t * nseg - s) - 1.0;
+    PLAN_UNROLL
+    for (int j = 0; j < 4; j++) {
+        double d = 0.0;
+        PLAN_UNROLL
+        for (int m = 0; m < 4; m++) {
+            if (m == j) continue;
+            double v = 1.0 / (node_xi(j) - node_xi(m));
+            PLAN_UNROLL
+            for (int k = 0; k < 4; k++) if (k != j && k != m) v *= (xx - node_xi(k)) / (node_xi(j) - node_xi(k));
+            d += v;
+        }
+        dLg[j] = 2.0 * nseg * d;
+    }
+}
+
 // One scalar channel on segment s with the weights Lg: C points at the channel in node 0, `stride` doubles lie between two nodes
 MPCMP_HD double interp_channel(const double *C, int stride, int s, const double *Lg) {
     double c = 0.0;

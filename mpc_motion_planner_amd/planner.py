@@ -238,6 +238,21 @@ class Solver:
         check(lib().mpcmp_clearance_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_pts), float(margin), int(self_gap),
                                                  out or None, stream or None), self._ctx)
 
+    def clearance_certified(self, sx, sT, margin=0.0, self_gap=0, n_start=4, max_depth=10):
+        """mpcmp_clearance_certified_batch: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE [B]) for the trajectories sx [B][N][nx], sT [B]:
+        status 0 means no clearance below `margin` at ANY time of the plan (include/mpcmp_clearance_cert.h)"""
+        sx, sT = f64(sx), f64(sT).reshape(-1); B = sT.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
+        out, cert = np.zeros(B, dtype=capi.CLEARANCE_DTYPE), np.zeros(B, dtype=capi.CLEARANCE_CERT_DTYPE)
+        check(lib().mpcmp_clearance_certified_batch(self._ctx, B, host(sx), host(sT), float(margin), int(self_gap), int(n_start), int(max_depth),
+                                                    host(out), host(cert)), self._ctx)
+        return out, cert
+
+    def clearance_certified_device(self, B, sol_x, sol_T, margin, self_gap, n_start, max_depth, out, cert=0, stream=0):
+        check(lib().mpcmp_clearance_certified_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, float(margin), int(self_gap), int(n_start),
+                                                           int(max_depth), out or None, cert or None, stream or None), self._ctx)
+
     def select_clear(self, sT, info, clr, group, n_groups=None):
         """mpcmp_select_clear_batch: per group the admissible member (clean solve status, clearance status 0) with the smallest final time,
         ties to the lowest index, -1 if none.  n_groups defaults to max(group) + 1"""
@@ -891,6 +906,18 @@ class BatchMotionPlanner:
             clr = self._solver.clearance(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin, self_gap)
             return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
         return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
+
+    def check_clearance_certified(self, margin=0.0, self_gap=0, n_start=4, max_depth=10):
+        """certified clearance of the last solve_trajectory's solutions: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE); status 0 holds at every
+        time of the plan, not at samples.  Of routes: the legs' records joined per route [B] (an undecided or hit leg marks its route) and the
+        certificates per leg [B][M + 1] (times are leg times)"""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            clr, cert = self._solver.clearance_certified(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), margin, self_gap, n_start,
+                                                         max_depth)
+            return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3], cert.reshape(r["sol_T"].shape)
+        return self._solver.clearance_certified(self._sol[0], self._sol[2], margin, self_gap, n_start, max_depth)
 
     def check_limits(self, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
         """limit records (capi.LIMITS_DTYPE) of the last solve_trajectory's solutions between their nodes, [B]; of routes: one record per leg,
