@@ -340,6 +340,30 @@ class MotionPlanner {
         chk(mpcmp_clearance_certified_batch(ctx_, 1, sol_x_.data(), &sol_T_, margin, self_gap, n_start, max_depth, &r, cert));
         return r;
     }
+    // The obstacles of set_obstacles that move (include/mpcmp_moving.h): track_of [n_obs] (-1: stands still), offsets [n_tracks][n_key][3] on the
+    // world clock t0 + k dt.  n_tracks == 0: the world stands still again, as it does after the next set_obstacles
+    void set_moving_obstacles(int n_obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets) {
+        chk(mpcmp_set_obstacle_tracks(ctx_, 1, n_obs, track_of, n_tracks, n_key, t0, dt, offsets));
+    }
+    // clearance record of the last solution started at the world time t_start in the moving world, times on the running clock; retimed: on the
+    // profile of the last retime() (call it first), otherwise on the plan's own clock
+    mpcmp_clearance check_clearance_timed(double t_start = 0.0, int n_pts = 200, double margin = 0.0, int self_gap = 0, bool retimed = false) {
+        if (retimed && retime_grid_ < 1) throw std::runtime_error("check_clearance_timed: call retime() first");
+        mpcmp_clearance r;
+        chk(mpcmp_clearance_timed_batch(ctx_, 1, sol_x_.data(), &sol_T_, retimed ? retime_grid_ : 0, retimed ? retime_prof_.data() : nullptr, &t_start,
+                                        n_pts, margin, self_gap, &r));
+        return r;
+    }
+    // the lowest of the K candidate start delays (ascending, >= 0) whose run has no sample under `margin`; check_wait: the wait at the start posture is
+    // checked at the candidate delays too.  d_min_all [K] may be null
+    mpcmp_start_delay first_clear_start(const double *delays, int K, bool check_wait = true, int n_pts = 200, double margin = 0.0, int self_gap = 0,
+                                        bool retimed = false, double *d_min_all = nullptr) {
+        if (retimed && retime_grid_ < 1) throw std::runtime_error("first_clear_start: call retime() first");
+        mpcmp_start_delay r;
+        chk(mpcmp_start_delay_batch(ctx_, 1, sol_x_.data(), &sol_T_, retimed ? retime_grid_ : 0, retimed ? retime_prof_.data() : nullptr, K, delays,
+                                    check_wait ? 1 : 0, n_pts, margin, self_gap, d_min_all, &r));
+        return r;
+    }
     // limit record of the last solution BETWEEN its nodes, at n_pts + 1 uniform samples (include/mpcmp_limits.h): excess per group under the bounds
     // the plan was solved with, and the stretch of T that makes the kinematic groups hold.  spec NULL: tol 0, no tool speed limits
     mpcmp_limits check_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr) {

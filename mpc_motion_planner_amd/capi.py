@@ -66,6 +66,9 @@ CLR_HIT, CLR_NAN = 1, 2
 CLR_UNDECIDED = 4
 CLEARANCE_CERT_DTYPE = np.dtype([("d_lower", "f8"), ("t_lower", "f8"), ("n_eval", "i4"), ("n_clear", "i4"), ("n_undecided", "i4"), ("depth", "i4")])
 CLR_CERT_CAPACITY = 4096
+# the start-delay search (mpcmp_start_delay, include/mpcmp_moving.h): 32 bytes; the limits of a track table and of the delays
+START_DELAY_DTYPE = np.dtype([("delay", "f8"), ("d_min", "f8"), ("index", "i4"), ("n_clear", "i4"), ("status", "i4"), ("pad", "i4")])
+MAX_TRACKS, MAX_TRACK_KEYS, MAX_DELAYS = 64, 1024, 256
 MAX_SPHERES, MAX_OBSTACLES = 64, 256
 
 # records of the between-node limit checks (mpcmp_limits_spec, mpcmp_limits; include/mpcmp.h): 72 and 168 bytes
@@ -181,6 +184,15 @@ ABI_CLEARANCE_CERT = {
     "mpcmp_clearance_certified_batch": "pippdiiipp", "mpcmp_clearance_certified_batch_device": "pippdiiippp",
     "mpcmp_clearance_certified_one": "piippippddiiipp",
 }
+# ... and every function include/mpcmp_moving.h declares (clearance in a moving world), in its order
+ABI_MOVING = {
+    "mpcmp_set_obstacle_tracks": "piipiiddp", "mpcmp_set_obstacle_tracks_device": "piipiiddpp",
+    "mpcmp_clearance_timed_batch": "pippippidip", "mpcmp_clearance_timed_batch_device": "pippippidipp",
+    "mpcmp_start_delay_batch": "pippipipiidipp", "mpcmp_start_delay_batch_device": "pippipipiidippp",
+    "mpcmp_sphere_tracks_batch": "pippippddip", "mpcmp_sphere_tracks_batch_device": "pippippddipp",
+    "mpcmp_track_offset": "iddpdp", "mpcmp_clearance_timed_one": "piippipp" + "iiddp" + "pdipd" + "idip",
+    "mpcmp_start_delay_one": "piippipp" + "iiddp" + "pdip" + "ipi" + "idi" + "pp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -237,7 +249,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -368,6 +380,68 @@ def clearance_certified_one(models, num_seg, spheres_per_arm, obstacles, x, T, m
     check(lib().mpcmp_clearance_certified_one(arr, narm, int(num_seg), host(cnt), host(tab), obs.shape[0], host(obs), host(x), float(T), float(margin),
                                               int(self_gap), int(n_start), int(max_depth), host(rec), host(cert)))
     return rec[0], cert[0]
+
+
+def track_offset(P, t0, dt, tau):
+    """mpcmp_track_offset: the offset [3] of the track P [n_key][3] on the clock t0 + k dt at world time tau (include/mpcmp_moving.h)"""
+    P = f64(P).reshape(-1, 3); out = np.zeros(3)
+    check(lib().mpcmp_track_offset(P.shape[0], float(t0), float(dt), host(P), float(tau), host(out)))
+    return out
+
+
+def _moving_one_args(models, num_seg, spheres_per_arm, obstacles, tracks, x):
+    """the leading arguments mpcmp_clearance_timed_one and mpcmp_start_delay_one share; tracks: None or (track_of [n_obs], offsets
+    [n_tracks][n_key][3], t0, dt).  Returns (the argument list through x, the arrays it points into)"""
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    obs = np.zeros(0, dtype=OBSTACLE_DTYPE) if obstacles is None else _records(obstacles, OBSTACLE_DTYPE, "obstacle").reshape(-1)
+    if tracks is None:
+        tof, off, n_tracks, n_key, t0, dt = np.zeros(0, dtype=np.int32), np.zeros(0), 0, 1, 0.0, 1.0
+    else:
+        tof = np.ascontiguousarray(tracks[0], dtype=np.int32).reshape(-1); off = f64(tracks[1])
+        if off.ndim != 3 or off.shape[2] != 3 or tof.shape[0] != obs.shape[0]:
+            raise ValueError("tracks: track_of [n_obs] and offsets [n_tracks][n_key][3]")
+        n_tracks, n_key, t0, dt = off.shape[0], off.shape[1], float(tracks[2]), float(tracks[3])
+    x = f64(x).reshape(N, 14 * narm)
+    keep = (arr, cnt, tab, obs, tof, off, x)
+    return [arr, narm, int(num_seg), host(cnt), host(tab), obs.shape[0], host(obs), host(tof), n_tracks, n_key, t0, dt, host(off), host(x)], keep
+
+
+def _profile_arg(prof):
+    if prof is None:
+        return 0, None, None
+    prof = f64(prof)
+    if prof.ndim != 2 or prof.shape[1] != 2 or prof.shape[0] < 2:
+        raise ValueError("prof must be [n_grid + 1][2]")
+    return prof.shape[0] - 1, host(prof), prof
+
+
+def clearance_timed_one(models, num_seg, spheres_per_arm, obstacles, tracks, x, T, prof=None, t_start=0.0, n_pts=200, margin=0.0, self_gap=0):
+    """mpcmp_clearance_timed_one: the timed check of ONE plan x [N][14 narm] of duration T on the host (no context, no GPU) in the world `obstacles`
+    moved by tracks = (track_of, offsets [n_tracks][n_key][3], t0, dt) or None; prof [n_grid + 1][2] or None.  Returns the CLEARANCE_DTYPE record"""
+    args, keep = _moving_one_args(models, num_seg, spheres_per_arm, obstacles, tracks, x)
+    n_grid, pp, keep2 = _profile_arg(prof)
+    rec = np.zeros(1, dtype=CLEARANCE_DTYPE)
+    check(lib().mpcmp_clearance_timed_one(*args, float(T), n_grid, pp, float(t_start), int(n_pts), float(margin), int(self_gap), host(rec)))
+    return rec[0]
+
+
+def start_delay_one(models, num_seg, spheres_per_arm, obstacles, tracks, x, T, delays, prof=None, check_wait=False, n_pts=200, margin=0.0, self_gap=0):
+    """mpcmp_start_delay_one: the start-delay search of ONE plan on the host.  Returns (the START_DELAY_DTYPE record, d_min_all [K])"""
+    args, keep = _moving_one_args(models, num_seg, spheres_per_arm, obstacles, tracks, x)
+    n_grid, pp, keep2 = _profile_arg(prof)
+    delays = f64(delays).reshape(-1)
+    rec, d_all = np.zeros(1, dtype=START_DELAY_DTYPE), np.zeros(max(delays.shape[0], 1))
+    check(lib().mpcmp_start_delay_one(*args, float(T), n_grid, pp, delays.shape[0], host(delays), int(bool(check_wait)), int(n_pts), float(margin),
+                                      int(self_gap), host(d_all), host(rec)))
+    return rec[0], d_all[:delays.shape[0]]
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

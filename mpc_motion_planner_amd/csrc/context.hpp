@@ -54,6 +54,15 @@ struct mpcmp_ctx {
     bool clr_cert_ready = false;     // ... and the certified check's (mpcmp_clearance_certified_batch*), by its first call
     bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
     unsigned long long *d_sel_key = nullptr;
+    // the track table of the obstacle sets (mpcmp_set_obstacle_tracks*, include/mpcmp_moving.h): d_mv_track_of [clr_sets][clr_nobs] and d_mv_off
+    // [clr_sets][mv_tracks][mv_keys][3], allocated and grown by the setters; mv_tracks == 0: the world stands still.  Read by the checks of
+    // mpcmp_moving.h only
+    int *d_mv_track_of = nullptr;
+    double *d_mv_off = nullptr;
+    size_t mv_tof_cap = 0, mv_off_cap = 0;
+    int mv_tracks = 0, mv_keys = 1;
+    double mv_t0 = 0.0, mv_dt = 1.0;
+    bool mv_ready = false;           // the dynamic-LDS ceilings of its kernels, by the first call of the family
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
     // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;

@@ -1,6 +1,7 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
 // configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
-// statements of the tool-line moves (toolpath.hpp) and of the certified clearance check (clearance_cert.hpp).  Plain C++: no HIP
+// statements of the tool-line moves (toolpath.hpp), of the certified clearance check (clearance_cert.hpp) and of the checks in a moving world
+// (moving_rule.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -23,6 +24,7 @@
 #include "plan_interp.hpp"
 #include "toolpath.hpp"
 #include "clearance_cert.hpp"
+#include "moving_rule.hpp"
 
 using namespace mpcmp;
 
@@ -643,5 +645,185 @@ extern "C" int mpcmp_clearance_certified_one(const mpcmp_model *models, int narm
     c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
     *out = r;
     if (cert) *cert = c;
+    return MPCMP_OK;
+}
+
+// ---- clearance in a moving world on the host (include/mpcmp_moving.h): one plan through the source the kernels run (moving_rule.hpp) ----
+extern "C" int mpcmp_track_offset(int n_key, double t0, double dt, const double *P, double tau, double *p) {
+    if (!P || !p || n_key < 1 || n_key > MV_MAX_KEYS || !std::isfinite(t0) || !std::isfinite(dt) || !(dt > 0.0) || !std::isfinite(tau)) {
+        g_err = "mpcmp_track_offset: n_key in [1, 1024], a finite clock with dt > 0, a finite tau and both pointers required";
+        return MPCMP_EINVAL;
+    }
+    mv_offset(P, mv_place(n_key, t0, dt, tau), p);
+    return MPCMP_OK;
+}
+
+namespace {
+// one plan's tables in the form the kernels stage them
+struct MvHost {
+    int narm = 0, nseg = 0, nsph = 0, n_obs = 0, n_tracks = 0, n_key = 1, n_grid = 0;
+    double t0 = 0.0, dt = 1.0, T = 0.0, T_run = 0.0;
+    const mpcmp_sphere *sph = nullptr;
+    const mpcmp_obstacle *obs = nullptr;
+    const double *off = nullptr, *prof = nullptr;
+    std::vector<double> mk, nodes, ok;
+    std::vector<int> arm, jnt, tof;
+    bool nan = false;
+    // world centres cen [nsph][3] at the plan's normalised time s
+    void centres(double s, double *cen) const {
+        const int nq = 7 * narm;
+        double Lg[4], sc[28], fr[2 * 84];
+        const int seg = mpcmp_plan::lagrange_segment(nseg, s, Lg);
+        for (int j = 0; j < nq; j++) {
+            const double q = mpcmp_plan::interp_channel(nodes.data() + j, nq, seg, Lg);
+            sc[2 * j] = std::sin(q); sc[2 * j + 1] = std::cos(q);
+        }
+        for (int a = 0; a < narm; a++) cert_frames(mk.data() + 84 * a, sc + 14 * a, fr + 84 * a);
+        for (int i = 0; i < nsph; i++) cert_centre(fr + 84 * arm[i] + 12 * jnt[i], sph[i].c, cen + 3 * i);
+    }
+    // the clearance of sphere i at the centre c against obstacle o, shifted to the place w of the tracks' clock when it is tracked
+    double obstacle(int i, const double *c, int o, const MvPlace &w) const {
+        double p[3] = {0.0, 0.0, 0.0};
+        if (tof[o] >= 0) mv_offset(off + (size_t)tof[o] * n_key * 3, w, p);
+        return clr_sd(obs[o].type, ok.data() + 8 * o, c[0] - p[0], c[1] - p[1], c[2] - p[2]) - sph[i].r;
+    }
+    double pair(int i, int t, const double *cen) const {
+        const double ex = cen[3 * i] - cen[3 * t], ey = cen[3 * i + 1] - cen[3 * t + 1], ez = cen[3 * i + 2] - cen[3 * t + 2];
+        return std::sqrt(ex * ex + ey * ey + ez * ez) - sph[i].r - sph[t].r;
+    }
+};
+}  // namespace
+
+// the checks and tables the two statements below share; `who` for the message
+static int mv_host_setup(const char *who, const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                         const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets,
+                         const double *x, double T, int n_grid, const double *prof, int n_pts, double margin, int self_gap, const void *out, MvHost *H) {
+    if (!models || narm < 1 || narm > 2 || num_seg < 1 || !n_spheres || !x || !out || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_obs > 0 && !obs) ||
+        self_gap < 0 || !std::isfinite(margin) || n_pts < 1 || n_pts > 4096 || (prof && (n_grid < 1 || n_grid > MV_MAX_GRID)) || n_tracks < 0 ||
+        n_tracks > MV_MAX_TRACKS) {
+        g_err = std::string(who) + ": one or two arms, num_seg >= 1, 1 <= n_pts <= 4096, a finite margin, self_gap >= 0, n_obs in [0, 256], n_tracks in "
+                "[0, 64], with a profile 1 <= n_grid <= 4096 and all pointers (but prof) required";
+        return MPCMP_EINVAL;
+    }
+    if (n_tracks > 0) {
+        bool ok = n_key >= 1 && n_key <= MV_MAX_KEYS && std::isfinite(t0) && std::isfinite(dt) && dt > 0.0 && offsets && (n_obs == 0 || track_of);
+        for (int o = 0; ok && o < n_obs; o++) ok = track_of[o] >= -1 && track_of[o] < n_tracks;
+        for (size_t e = 0; ok && e < (size_t)n_tracks * n_key * 3; e++) ok = std::isfinite(offsets[e]);
+        if (!ok) {
+            g_err = std::string(who) + ": n_key in [1, 1024], a finite clock with dt > 0, track_of in [-1, n_tracks) and finite offsets required";
+            return MPCMP_EINVAL;
+        }
+    }
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
+    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
+    const int nq = 7 * narm, N = 3 * num_seg + 1;
+    H->narm = narm; H->nseg = num_seg; H->nsph = nsph; H->n_obs = n_obs; H->n_tracks = n_tracks; H->n_key = n_tracks > 0 ? n_key : 1;
+    H->t0 = t0; H->dt = dt; H->T = T; H->n_grid = n_grid; H->prof = prof; H->sph = spheres; H->obs = obs; H->off = offsets;
+    H->mk.resize(84 * narm); H->nodes.resize((size_t)nq * N); H->ok.resize(8 * (n_obs > 0 ? n_obs : 1));
+    H->arm.resize(nsph); H->jnt.resize(nsph); H->tof.resize(n_obs);
+    for (int a = 0; a < narm; a++)
+        for (int i = 0; i < 7; i++) {
+            for (int c = 0; c < 9; c++) H->mk[84 * a + 12 * i + c] = models[a].R0[i][c];
+            for (int c = 0; c < 3; c++) H->mk[84 * a + 12 * i + 9 + c] = models[a].p[i][c];
+        }
+    bool nan = !std::isfinite(T);
+    for (int k = 0; k < N; k++)
+        for (int j = 0; j < nq; j++) { H->nodes[(size_t)k * nq + j] = x[(size_t)k * 2 * nq + j]; if (!std::isfinite(x[(size_t)k * 2 * nq + j])) nan = true; }
+    if (prof) for (int e = 0; e < 2 * (n_grid + 1); e++) if (!std::isfinite(prof[e])) nan = true;
+    for (int a = 0, s = 0; a < narm; a++)
+        for (int k = 0; k < n_spheres[a]; k++, s++) { H->arm[s] = a; H->jnt[s] = spheres[s].joint; }
+    for (int o = 0; o < n_obs; o++) { clr_obs_prepare(obs[o], H->ok.data() + 8 * o); H->tof[o] = n_tracks > 0 ? mv_track(track_of[o], n_tracks) : -1; }
+    H->nan = nan;
+    H->T_run = nan ? 0.0 : mv_run_time(prof, n_grid, T);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_timed_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                                         const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
+                                         const double *offsets, const double *x, double T, int n_grid, const double *prof, double t_start, int n_pts,
+                                         double margin, int self_gap, mpcmp_clearance *out) {
+    MvHost H;
+    if (int rc = mv_host_setup("mpcmp_clearance_timed_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0, dt,
+                               offsets, x, T, n_grid, prof, n_pts, margin, self_gap, out, &H)) return rc;
+    if (H.nan || !std::isfinite(t_start)) { *out = mv_clearance_nan(); return MPCMP_OK; }
+    std::vector<double> cen(3 * (H.nsph > 0 ? H.nsph : 1));
+    double best_d = INFINITY;
+    unsigned best_k = CLR_NO_PAIR;
+    int n_hit = 0, first = -1;
+    for (int i = 0; i <= n_pts; i++) {
+        double t, s;
+        mv_sample(prof, n_grid, T, H.T_run, i, n_pts, &t, &s);
+        H.centres(s, cen.data());
+        const MvPlace w = mv_place(H.n_key, t0, dt, t_start + t);
+        bool hit = false;
+        for (int sp = 0; sp < H.nsph; sp++) {
+            for (int o = 0; o < n_obs; o++) {
+                const double d = H.obstacle(sp, cen.data() + 3 * sp, o, w);
+                const unsigned key = clr_pack(i, sp, 0, o);
+                if (clr_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                hit = hit || d < margin;
+            }
+            for (int tp = sp + 1; tp < H.nsph; tp++) {
+                if (!clr_pair(H.arm[sp], H.jnt[sp], H.arm[tp], H.jnt[tp], self_gap)) continue;
+                const double d = H.pair(sp, tp, cen.data());
+                const unsigned key = clr_pack(i, sp, 1, tp);
+                if (clr_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                hit = hit || d < margin;
+            }
+        }
+        if (hit) { if (first < 0) first = i; n_hit++; }
+    }
+    mpcmp_clearance r;
+    r.d_min = best_d;
+    if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
+    else {
+        const int ip = (int)(best_k >> 17), idx = (int)(best_k & 0xFFu);
+        r.t_min = ((double)ip / n_pts) * H.T_run;
+        r.sphere = (int)((best_k >> 9) & 0x7Fu);
+        r.other = (best_k & 0x100u) ? -1 - idx : idx;
+    }
+    r.t_first = first >= 0 ? ((double)first / n_pts) * H.T_run : -1.0;
+    r.n_hit = n_hit;
+    r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
+    *out = r;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_start_delay_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                                     const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets,
+                                     const double *x, double T, int n_grid, const double *prof, int K, const double *delays, int check_wait, int n_pts,
+                                     double margin, int self_gap, double *d_min_all, mpcmp_start_delay *out) {
+    bool ok = K >= 1 && K <= MV_MAX_DELAYS && delays;
+    for (int k = 0; ok && k < K; k++) ok = std::isfinite(delays[k]) && delays[k] >= 0.0 && (k == 0 || delays[k] >= delays[k - 1]);
+    if (!ok) { g_err = "mpcmp_start_delay_one: 1 <= K <= 256 delays, finite, >= 0 and ascending, required"; return MPCMP_EINVAL; }
+    MvHost H;
+    if (int rc = mv_host_setup("mpcmp_start_delay_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0, dt,
+                               offsets, x, T, n_grid, prof, n_pts, margin, self_gap, out, &H)) return rc;
+    if (H.nan) { *out = mv_delay_nan(K, d_min_all); return MPCMP_OK; }
+    std::vector<double> cen(3 * (H.nsph > 0 ? H.nsph : 1)), dk(K, INFINITY), w0(K, INFINITY);
+    double best = INFINITY;          // over the obstacles that stand still and the robot pairs: it does not depend on the delay
+    for (int i = 0; i <= n_pts; i++) {
+        double t, s;
+        mv_sample(prof, n_grid, T, H.T_run, i, n_pts, &t, &s);
+        H.centres(s, cen.data());
+        const MvPlace none = mv_place(1, 0.0, 1.0, 0.0);
+        for (int sp = 0; sp < H.nsph; sp++) {
+            for (int o = 0; o < n_obs; o++) if (H.tof[o] < 0) best = std::fmin(best, H.obstacle(sp, cen.data() + 3 * sp, o, none));
+            for (int tp = sp + 1; tp < H.nsph; tp++)
+                if (clr_pair(H.arm[sp], H.jnt[sp], H.arm[tp], H.jnt[tp], self_gap)) best = std::fmin(best, H.pair(sp, tp, cen.data()));
+        }
+        for (int k = 0; k < K; k++) {
+            const MvPlace w = mv_place(H.n_key, t0, dt, delays[k] + t);
+            double dm = INFINITY;
+            for (int sp = 0; sp < H.nsph; sp++)
+                for (int o = 0; o < n_obs; o++) if (H.tof[o] >= 0) dm = std::fmin(dm, H.obstacle(sp, cen.data() + 3 * sp, o, w));
+            dk[k] = std::fmin(dk[k], dm);
+            if (i == 0) w0[k] = dm;
+        }
+    }
+    for (int k = 0; k < K; k++) dk[k] = std::fmin(dk[k], best);
+    *out = mv_delay_record(K, delays, dk.data(), w0.data(), check_wait, margin, d_min_all);
     return MPCMP_OK;
 }

@@ -22,6 +22,7 @@
 #include "payload.hpp"
 #include "time_sync.hpp"
 #include "clearance.hpp"
+#include "moving.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
 #include "retimed_check.hpp"
@@ -934,6 +935,7 @@ extern "C" int mpcmp_set_obstacles(mpcmp_ctx *ctx, int n_sets, int n_obs, const 
     HIPCHK(ctx, hipDeviceSynchronize());          // (checks may be in flight on any stream of the caller: they read these sets)
     if (n_sets > 0 && n_obs > 0) HIPCHK(ctx, hipMemcpy(ctx->d_clr_obs, obs, sizeof(mpcmp_obstacle) * n_sets * n_obs, hipMemcpyHostToDevice));
     ctx->clr_sets = n_obs > 0 ? n_sets : 0; ctx->clr_nobs = n_sets > 0 ? n_obs : 0;
+    ctx->mv_tracks = 0;                           // (new obstacle sets stand still until mpcmp_set_obstacle_tracks says otherwise)
     return MPCMP_OK;
 }
 
@@ -946,6 +948,7 @@ extern "C" int mpcmp_set_obstacles_device(mpcmp_ctx *ctx, int n_sets, int n_obs,
                 return MPCMP_OK;
             })) return rc;
     ctx->clr_sets = n_obs > 0 ? n_sets : 0; ctx->clr_nobs = n_sets > 0 ? n_obs : 0;
+    ctx->mv_tracks = 0;
     return MPCMP_OK;
 }
 
@@ -1040,6 +1043,212 @@ extern "C" int mpcmp_clearance_certified_batch(mpcmp_ctx *ctx, int B, const doub
     if (cert) sg.out(&dcert, cert, B);
     if (int rc = sg.upload()) return rc;
     if (int rc = clearance_cert_enqueue(ctx, B, dx, dT, margin, self_gap, n_start, max_depth, dout, dcert, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ---- clearance in a moving world (include/mpcmp_moving.h; the kernels are in moving.hip, the rule in moving_rule.hpp) ----
+static int tracks_check(mpcmp_ctx *ctx, int n_sets, int n_obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
+                        const double *offsets) {
+    if (!ctx) { g_err = "mpcmp_set_obstacle_tracks: no context"; return MPCMP_EINVAL; }
+    if (n_tracks == 0) return MPCMP_OK;
+    if (n_tracks < 0 || n_tracks > MV_MAX_TRACKS || n_key < 1 || n_key > MV_MAX_KEYS || !track_of || !offsets || !std::isfinite(t0) ||
+        !std::isfinite(dt) || !(dt > 0.0)) {
+        ctx->err = "mpcmp_set_obstacle_tracks: n_tracks in [0, 64], n_key in [1, 1024], a finite clock with dt > 0 and both arrays required";
+        return MPCMP_EINVAL;
+    }
+    if (n_sets < 1 || n_sets != ctx->clr_sets || n_obs != ctx->clr_nobs) {
+        ctx->err = "mpcmp_set_obstacle_tracks: " + std::to_string(n_sets) + " sets of " + std::to_string(n_obs) + " obstacles, but " +
+                   std::to_string(ctx->clr_sets) + " sets of " + std::to_string(ctx->clr_nobs) + " are in force: see mpcmp_set_obstacles";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+// room for the table; growth waits for the checks that read the old buffers
+static int tracks_reserve(mpcmp_ctx *ctx, size_t n_tof, size_t n_off) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (n_tof > ctx->mv_tof_cap) {
+        void *q = nullptr;
+        HIPCHK(ctx, hipMalloc(&q, n_tof * sizeof(int)));
+        if (ctx->d_mv_track_of) {
+            HIPCHK(ctx, hipDeviceSynchronize());
+            ctx->allocs.erase(std::find(ctx->allocs.begin(), ctx->allocs.end(), (void *)ctx->d_mv_track_of));
+            (void)hipFree(ctx->d_mv_track_of);
+        }
+        ctx->allocs.push_back(q); ctx->d_mv_track_of = (int *)q; ctx->mv_tof_cap = n_tof;
+    }
+    if (n_off > ctx->mv_off_cap) {
+        void *q = nullptr;
+        HIPCHK(ctx, hipMalloc(&q, n_off * sizeof(double)));
+        if (ctx->d_mv_off) {
+            HIPCHK(ctx, hipDeviceSynchronize());
+            ctx->allocs.erase(std::find(ctx->allocs.begin(), ctx->allocs.end(), (void *)ctx->d_mv_off));
+            (void)hipFree(ctx->d_mv_off);
+        }
+        ctx->allocs.push_back(q); ctx->d_mv_off = (double *)q; ctx->mv_off_cap = n_off;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_obstacle_tracks(mpcmp_ctx *ctx, int n_sets, int n_obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
+                                         const double *offsets) {
+    if (int rc = tracks_check(ctx, n_sets, n_obs, track_of, n_tracks, n_key, t0, dt, offsets)) return rc;
+    if (n_tracks == 0) { ctx->mv_tracks = 0; return MPCMP_OK; }
+    const size_t n_tof = (size_t)n_sets * n_obs, n_off = (size_t)n_sets * n_tracks * n_key * 3;
+    for (size_t i = 0; i < n_tof; i++)
+        if (track_of[i] < -1 || track_of[i] >= n_tracks) {
+            ctx->err = "mpcmp_set_obstacle_tracks: track_of[" + std::to_string(i) + "] must be in [-1, n_tracks)"; return MPCMP_EINVAL;
+        }
+    for (size_t i = 0; i < n_off; i++)
+        if (!std::isfinite(offsets[i])) { ctx->err = "mpcmp_set_obstacle_tracks: offset " + std::to_string(i) + " is not finite"; return MPCMP_EINVAL; }
+    if (int rc = tracks_reserve(ctx, n_tof, n_off)) return rc;
+    HIPCHK(ctx, hipDeviceSynchronize());          // (checks may be in flight on any stream of the caller: they read this table)
+    HIPCHK(ctx, hipMemcpy(ctx->d_mv_track_of, track_of, sizeof(int) * n_tof, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->d_mv_off, offsets, sizeof(double) * n_off, hipMemcpyHostToDevice));
+    ctx->mv_tracks = n_tracks; ctx->mv_keys = n_key; ctx->mv_t0 = t0; ctx->mv_dt = dt;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_obstacle_tracks_device(mpcmp_ctx *ctx, int n_sets, int n_obs, const int *d_track_of, int n_tracks, int n_key, double t0,
+                                                double dt, const double *d_offsets, void *hip_stream) {
+    if (int rc = tracks_check(ctx, n_sets, n_obs, d_track_of, n_tracks, n_key, t0, dt, d_offsets)) return rc;
+    if (n_tracks == 0) { ctx->mv_tracks = 0; return MPCMP_OK; }
+    const size_t n_tof = (size_t)n_sets * n_obs, n_off = (size_t)n_sets * n_tracks * n_key * 3;
+    if (int rc = tracks_reserve(ctx, n_tof, n_off)) return rc;
+    if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_mv_track_of, d_track_of, sizeof(int) * n_tof, hipMemcpyDeviceToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->d_mv_off, d_offsets, sizeof(double) * n_off, hipMemcpyDeviceToDevice, st));
+            return MPCMP_OK;
+        })) return rc;
+    ctx->mv_tracks = n_tracks; ctx->mv_keys = n_key; ctx->mv_t0 = t0; ctx->mv_dt = dt;
+    return MPCMP_OK;
+}
+
+static ClrTables moving_tables(const mpcmp_ctx *ctx, MvTracks *trk) {
+    ClrTables t;
+    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
+    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
+    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    trk->d_track_of = ctx->d_mv_track_of; trk->d_offsets = ctx->d_mv_off; trk->n_tracks = ctx->mv_tracks;
+    trk->n_key = ctx->mv_tracks > 0 ? ctx->mv_keys : 1; trk->t0 = ctx->mv_t0; trk->dt = ctx->mv_dt;
+    return t;
+}
+static int moving_ready(mpcmp_ctx *ctx) {
+    if (!ctx->mv_ready) { HIPCHK(ctx, moving_prepare()); ctx->mv_ready = true; }
+    return MPCMP_OK;
+}
+static bool profile_args_ok(const double *prof, int n_grid) { return !prof || (n_grid >= 1 && n_grid <= MV_MAX_GRID); }
+
+static int clearance_timed_check(mpcmp_ctx *ctx, const char *who, int B, const double *sx, const double *sT, int n_grid, const double *prof, int n_pts,
+                                 double margin, int self_gap, const void *out) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_pts < 1 || n_pts > CLR_MAX_PTS || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0 || !profile_args_ok(prof, n_grid)) {
+        ctx->err = std::string(who) + ": B >= 1, 1 <= n_pts <= 4096, a finite margin, self_gap >= 0, with a profile 1 <= n_grid <= 4096 and all "
+                   "pointers (but prof, t_start, d_min_all) required";
+        return MPCMP_EINVAL;
+    }
+    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_timed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_grid, const double *d_prof,
+                                                  const double *d_t_start, int n_pts, double margin, int self_gap, mpcmp_clearance *d_out,
+                                                  void *hip_stream) {
+    if (int rc = clearance_timed_check(ctx, "mpcmp_clearance_timed_batch", B, d_sx, d_sT, n_grid, d_prof, n_pts, margin, self_gap, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = moving_ready(ctx)) return rc;
+    MvTracks trk;
+    const ClrTables t = moving_tables(ctx, &trk);
+    const MvPlans p = {d_sx, d_sT, d_prof, d_t_start, n_grid};
+    HIPCHK(ctx, clearance_timed_launch(t, trk, p, B, n_pts, margin, self_gap, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_timed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_grid, const double *prof,
+                                           const double *t_start, int n_pts, double margin, int self_gap, mpcmp_clearance *out) {
+    if (int rc = clearance_timed_check(ctx, "mpcmp_clearance_timed_batch", B, sx, sT, n_grid, prof, n_pts, margin, self_gap, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT, *dp, *dts;
+    mpcmp_clearance *dout;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.in(&dp, prof, prof ? (size_t)B * (n_grid + 1) * 2 : 0);
+    sg.in(&dts, t_start, B); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_clearance_timed_batch_device(ctx, B, dx, dT, n_grid, dp, dts, n_pts, margin, self_gap, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+extern "C" int mpcmp_start_delay_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_grid, const double *d_prof, int K,
+                                              const double *d_delays, int check_wait, int n_pts, double margin, int self_gap, double *d_min_all,
+                                              mpcmp_start_delay *d_out, void *hip_stream) {
+    if (int rc = clearance_timed_check(ctx, "mpcmp_start_delay_batch", B, d_sx, d_sT, n_grid, d_prof, n_pts, margin, self_gap, d_out)) return rc;
+    if (K < 1 || K > MV_MAX_DELAYS || !d_delays) { ctx->err = "mpcmp_start_delay_batch: 1 <= K <= 256 delays required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = moving_ready(ctx)) return rc;
+    MvTracks trk;
+    const ClrTables t = moving_tables(ctx, &trk);
+    const MvPlans p = {d_sx, d_sT, d_prof, nullptr, n_grid};
+    HIPCHK(ctx, start_delay_launch(t, trk, p, B, K, d_delays, check_wait, n_pts, margin, self_gap, d_min_all, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_start_delay_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_grid, const double *prof, int K,
+                                       const double *delays, int check_wait, int n_pts, double margin, int self_gap, double *d_min_all,
+                                       mpcmp_start_delay *out) {
+    if (int rc = clearance_timed_check(ctx, "mpcmp_start_delay_batch", B, sx, sT, n_grid, prof, n_pts, margin, self_gap, out)) return rc;
+    bool ok = K >= 1 && K <= MV_MAX_DELAYS && delays;
+    for (int k = 0; ok && k < K; k++) ok = std::isfinite(delays[k]) && delays[k] >= 0.0 && (k == 0 || delays[k] >= delays[k - 1]);
+    if (!ok) { ctx->err = "mpcmp_start_delay_batch: 1 <= K <= 256 delays, finite, >= 0 and ascending, required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT, *dp, *dd, *dall;
+    mpcmp_start_delay *dout;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.in(&dp, prof, prof ? (size_t)B * (n_grid + 1) * 2 : 0);
+    sg.in(&dd, delays, K); sg.out(&dall, d_min_all, (size_t)B * K); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_start_delay_batch_device(ctx, B, dx, dT, n_grid, dp, K, dd, check_wait, n_pts, margin, self_gap, dall, dout, ctx->stream))
+        return rc;
+    return sg.finish();
+}
+
+static int sphere_tracks_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_grid, const double *prof, double t0, double dt,
+                               int n_key, const double *out) {
+    if (!ctx) { g_err = "mpcmp_sphere_tracks_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !sx || !sT || !out || n_key < 1 || n_key > MV_MAX_KEYS || !std::isfinite(t0) || !std::isfinite(dt) || !(dt > 0.0) ||
+        !profile_args_ok(prof, n_grid)) {
+        ctx->err = "mpcmp_sphere_tracks_batch: B >= 1, n_key in [1, 1024], a finite clock with dt > 0, with a profile 1 <= n_grid <= 4096 and all "
+                   "pointers (but prof, t_start) required";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sphere_tracks_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_grid, const double *d_prof,
+                                                const double *d_t_start, double t0, double dt, int n_key, double *d_out, void *hip_stream) {
+    if (int rc = sphere_tracks_check(ctx, B, d_sx, d_sT, n_grid, d_prof, t0, dt, n_key, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = moving_ready(ctx)) return rc;
+    MvTracks trk;
+    const ClrTables t = moving_tables(ctx, &trk);
+    const MvPlans p = {d_sx, d_sT, d_prof, d_t_start, n_grid};
+    HIPCHK(ctx, sphere_tracks_launch(t, p, B, t0, dt, n_key, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_sphere_tracks_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_grid, const double *prof,
+                                         const double *t_start, double t0, double dt, int n_key, double *out) {
+    if (int rc = sphere_tracks_check(ctx, B, sx, sT, n_grid, prof, t0, dt, n_key, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int nsph = ctx->clr_nsph[0] + (ctx->narm > 1 ? ctx->clr_nsph[1] : 0);
+    if (nsph < 1) return MPCMP_OK;
+    Stage sg(ctx);
+    double *dx, *dT, *dp, *dts, *dout;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.in(&dp, prof, prof ? (size_t)B * (n_grid + 1) * 2 : 0);
+    sg.in(&dts, t_start, B); sg.out(&dout, out, (size_t)B * nsph * n_key * 3);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_sphere_tracks_batch_device(ctx, B, dx, dT, n_grid, dp, dts, t0, dt, n_key, dout, ctx->stream)) return rc;
     return sg.finish();
 }
 

@@ -1,34 +1,14 @@
 // retimed_check.hpp — what the limit checker of retimed plans and routes (include/mpcmp_retimed_check.h) shares between the host entry points
-// (mpcmp.hip), its kernels and the host statement mpcmp_limits_retimed_one (retimed_check.hip): the place of a sample on a profile and the record a
-// finished accumulator stands for, each one text for host and device.  The excess, ratio and tie rules are those of limits.hpp and the sizes of a
-// profile those of retime.hpp; both are included and not changed.  Nothing here is a kernel, so including this header does not change what any other
+// (mpcmp.hip), its kernels and the host statement mpcmp_limits_retimed_one (retimed_check.hip): the place of a sample on a profile (profile_place.hpp,
+// plain C++, read by the host-only unit as well) and the record a finished accumulator stands for, each one text for host and device.  The excess,
+// ratio and tie rules are those of limits.hpp and the sizes of a profile those of retime.hpp; both are included and not changed.  Nothing here is a kernel, so including this header does not change what any other
 // translation unit compiles to.
 #pragma once
 #include "limits.hpp"
 #include "retime.hpp"
+#include "profile_place.hpp"
 
 namespace mpcmp {
-
-// Where the time t of a leg lies on that leg's profile pf [n + 1][2] = (t_k, x_k), by the retimed-sample rule of mpcmp_retime.h: the interval
-// k = the largest k <= n - 1 with t_k <= t (a bisection, at most 12 steps), then lambda, s and w_k.  `last`: the sample is the end of the plan or
-// route (s = 1 with lambda = sqrt(x_n) and the w of the last interval).  h = 1 / 2T.
-struct RcPlace { double lam, s, wh; };          // wh = w_k / 2T
-__host__ __device__ inline RcPlace rc_place(const double *pf, int n, double t, double h, bool last) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pf[2 * mid] <= t) lo = mid; else hi = mid - 1;
-    }
-    const int k = last ? n - 1 : lo;
-    const double tk = pf[2 * k], xk = pf[2 * k + 1], x1 = pf[2 * k + 3], lk = sqrt(xk), w = (x1 - xk) * n;
-    RcPlace p;
-    p.lam = lk + w * (t - tk) * h;
-    p.s = (double)k / n + (t - tk) * (lk + p.lam) * h;
-    if (last) { p.lam = sqrt(x1); p.s = 1.0; }
-    p.s = fmin(fmax(p.s, 0.0), 1.0);
-    p.wh = w * h;
-    return p;
-}
 
 // the record of a finished accumulator: times are (double)sample / n_pts * Tn, the retimed clock
 __host__ __device__ inline mpcmp_limits rc_record(const LimAcc &A, const mpcmp_limits_spec &sp, int n_pts, double Tn) {

@@ -208,6 +208,7 @@ class Solver:
         """sphere table of one arm: capi.SPHERE_DTYPE [n], n <= 64 (capi.link_spheres, capi.spheres); None or an empty table clears it"""
         t = np.zeros(0, dtype=capi.SPHERE_DTYPE) if spheres is None else capi._records(spheres, capi.SPHERE_DTYPE, "sphere").reshape(-1)
         check(lib().mpcmp_set_robot_spheres(self._ctx, int(arm), t.shape[0], host(t)), self._ctx)
+        self._nsph = {**getattr(self, "_nsph", {}), int(arm): t.shape[0]}          # (sphere_tracks sizes its output by it)
 
     def set_obstacles(self, obstacles):
         """obstacles: capi.OBSTACLE_DTYPE [n_obs] (one world for every problem) or [n_sets][n_obs] (set i for problem i)"""
@@ -252,6 +253,88 @@ class Solver:
     def clearance_certified_device(self, B, sol_x, sol_T, margin, self_gap, n_start, max_depth, out, cert=0, stream=0):
         check(lib().mpcmp_clearance_certified_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, float(margin), int(self_gap), int(n_start),
                                                            int(max_depth), out or None, cert or None, stream or None), self._ctx)
+
+    # -- clearance in a moving world: tracked obstacles, timed checks, start delays, a plan as another robot's world (include/mpcmp_moving.h)
+    def set_obstacle_tracks(self, track_of, offsets, t0, dt):
+        """the track table of the obstacle sets in force: track_of [n_obs] or [n_sets][n_obs] (-1: the obstacle stands still), offsets
+        [n_tracks][n_key][3] or [n_sets][n_tracks][n_key][3] on the clock t0 + k dt.  None / no tracks: the world stands still again"""
+        if track_of is None or offsets is None or np.asarray(offsets).size == 0:
+            check(lib().mpcmp_set_obstacle_tracks(self._ctx, 0, 0, None, 0, 1, 0.0, 1.0, None), self._ctx)
+            return
+        tof, off = np.ascontiguousarray(track_of, dtype=np.int32), f64(offsets)
+        if tof.ndim == 1:
+            tof = tof[None, :]
+        if off.ndim == 3:
+            off = off[None]
+        if tof.ndim != 2 or off.ndim != 4 or off.shape[3] != 3 or off.shape[0] != tof.shape[0]:
+            raise ValueError("track_of must be [n_sets][n_obs] and offsets [n_sets][n_tracks][n_key][3], got %s and %s" % (tof.shape, off.shape))
+        check(lib().mpcmp_set_obstacle_tracks(self._ctx, tof.shape[0], tof.shape[1], host(tof), off.shape[1], off.shape[2], float(t0), float(dt),
+                                              host(off)), self._ctx)
+
+    def clear_obstacle_tracks(self):
+        self.set_obstacle_tracks(None, None, 0.0, 1.0)
+
+    def set_obstacle_tracks_device(self, n_sets, n_obs, track_of, n_tracks, n_key, t0, dt, offsets, stream=0):
+        """the table at the device pointers track_of (int32) and offsets (float64), ordered on `stream` (values not checked)"""
+        check(lib().mpcmp_set_obstacle_tracks_device(self._ctx, int(n_sets), int(n_obs), track_of or None, int(n_tracks), int(n_key), float(t0),
+                                                     float(dt), offsets or None, stream or None), self._ctx)
+
+    def _plans(self, sx, sT, prof, t_start=None):
+        sx, sT = f64(sx), f64(sT).reshape(-1); B = sT.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
+        n_grid = 0
+        if prof is not None:
+            prof = f64(prof)
+            if prof.ndim != 3 or prof.shape[0] != B or prof.shape[2] != 2 or prof.shape[1] < 2:
+                raise ValueError("prof must be [B][n_grid + 1][2], got %s" % (prof.shape,))
+            n_grid = prof.shape[1] - 1
+        if t_start is not None:
+            t_start = f64(np.broadcast_to(np.asarray(t_start, dtype=np.float64), (B,)))
+        return B, sx, sT, n_grid, prof, t_start
+
+    def clearance_timed(self, sx, sT, prof=None, t_start=None, n_pts=200, margin=0.0, self_gap=0):
+        """mpcmp_clearance_timed_batch: capi.CLEARANCE_DTYPE [B] of the plans sx, sT, run on the profiles prof [B][n_grid + 1][2] (Solver.retime) or on
+        their own clock (None), started at the world times t_start (a scalar, [B] or None: 0), in the world moved by set_obstacle_tracks"""
+        B, sx, sT, n_grid, prof, t_start = self._plans(sx, sT, prof, t_start)
+        out = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
+        check(lib().mpcmp_clearance_timed_batch(self._ctx, B, host(sx), host(sT), n_grid, host(prof), host(t_start), int(n_pts), float(margin),
+                                                int(self_gap), host(out)), self._ctx)
+        return out
+
+    def clearance_timed_device(self, B, sol_x, sol_T, n_grid, prof, t_start, n_pts, margin, self_gap, out, stream=0):
+        check(lib().mpcmp_clearance_timed_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_grid), prof or None, t_start or None,
+                                                       int(n_pts), float(margin), int(self_gap), out or None, stream or None), self._ctx)
+
+    def start_delay(self, sx, sT, delays, prof=None, check_wait=False, n_pts=200, margin=0.0, self_gap=0, all_minima=True):
+        """mpcmp_start_delay_batch: (capi.START_DELAY_DTYPE [B], d_min_all [B][K] or None) — per plan the lowest of the candidate start delays
+        [K] (ascending, >= 0) whose run has no sample under `margin`; check_wait joins each run with the wait at the start posture"""
+        B, sx, sT, n_grid, prof, _ = self._plans(sx, sT, prof)
+        delays = f64(delays).reshape(-1); K = delays.shape[0]
+        out = np.zeros(B, dtype=capi.START_DELAY_DTYPE)
+        d_all = np.zeros((B, max(K, 1))) if all_minima else None
+        check(lib().mpcmp_start_delay_batch(self._ctx, B, host(sx), host(sT), n_grid, host(prof), K, host(delays), int(bool(check_wait)), int(n_pts),
+                                            float(margin), int(self_gap), host(d_all), host(out)), self._ctx)
+        return out, (d_all[:, :K] if all_minima else None)
+
+    def start_delay_device(self, B, sol_x, sol_T, n_grid, prof, K, delays, check_wait, n_pts, margin, self_gap, d_min_all, out, stream=0):
+        check(lib().mpcmp_start_delay_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_grid), prof or None, int(K), delays or None,
+                                                   int(bool(check_wait)), int(n_pts), float(margin), int(self_gap), d_min_all or None, out or None,
+                                                   stream or None), self._ctx)
+
+    def sphere_tracks(self, sx, sT, t0, dt, n_key, prof=None, t_start=None):
+        """mpcmp_sphere_tracks_batch: [B][nsph][n_key][3], the world centres of the robot spheres at the world times t0 + k dt, held at the first /
+        last posture outside the plan: the layout of one set's track table"""
+        B, sx, sT, n_grid, prof, t_start = self._plans(sx, sT, prof, t_start)
+        nsph = sum(getattr(self, "_nsph", {}).values())
+        out = np.zeros((B, nsph, int(n_key), 3))
+        check(lib().mpcmp_sphere_tracks_batch(self._ctx, B, host(sx), host(sT), n_grid, host(prof), host(t_start), float(t0), float(dt), int(n_key),
+                                              host(out) or host(np.zeros(1))), self._ctx)
+        return out
+
+    def sphere_tracks_device(self, B, sol_x, sol_T, n_grid, prof, t_start, t0, dt, n_key, out, stream=0):
+        check(lib().mpcmp_sphere_tracks_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_grid), prof or None, t_start or None,
+                                                     float(t0), float(dt), int(n_key), out or None, stream or None), self._ctx)
 
     def select_clear(self, sT, info, clr, group, n_groups=None):
         """mpcmp_select_clear_batch: per group the admissible member (clean solve status, clearance status 0) with the smallest final time,
@@ -895,7 +978,8 @@ class BatchMotionPlanner:
         if obstacles is None:
             self._solver.clear_obstacles()
             return
-        self._solver.set_robot_spheres(capi.link_spheres(self.model, sphere_radius, sphere_spacing) if spheres is None else spheres)
+        self._spheres = capi.link_spheres(self.model, sphere_radius, sphere_spacing) if spheres is None else spheres
+        self._solver.set_robot_spheres(self._spheres)
         self._solver.set_obstacles(obstacles)
 
     def check_clearance(self, n_pts=200, margin=0.0, self_gap=0):
@@ -906,6 +990,56 @@ class BatchMotionPlanner:
             clr = self._solver.clearance(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin, self_gap)
             return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
         return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
+
+    # -- clearance in a moving world (include/mpcmp_moving.h): direct moves; a route's leg slots are checked with Solver.clearance_timed, each with
+    # t_start = the route's start plus the running times of the legs before it
+    def set_moving_obstacles(self, track_of, offsets, t0, dt):
+        """which of the obstacles of set_obstacles move, and how: track_of [n_obs] or [B][n_obs] (-1: stands still), offsets [n_tracks][n_key][3]
+        or [B][n_tracks][n_key][3] on the world clock t0 + k dt.  None: the world stands still again (as after the next set_obstacles)"""
+        self._solver.set_obstacle_tracks(track_of, offsets, t0, dt)
+
+    def _timed_plans(self, retimed, who):
+        if self._route is not None or self._sol is None:
+            raise ValueError("%s: direct moves only, after solve_trajectory (check a route's leg slots with Solver.clearance_timed)" % who)
+        if retimed and getattr(self, "_retimed", None) is None:
+            raise ValueError("%s: call retime() first" % who)
+        return self._sol[0], self._sol[2], (self._retimed[0] if retimed else None)
+
+    def check_clearance_timed(self, t_start=None, n_pts=200, margin=0.0, self_gap=0, retimed=False):
+        """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions started at the world times t_start (a scalar, [B] or
+        None: 0) in the moving world; retimed: run on the profiles of the last retime().  Times are on the running clock"""
+        sx, sT, prof = self._timed_plans(retimed, "check_clearance_timed")
+        return self._solver.clearance_timed(sx, sT, prof, t_start, n_pts, margin, self_gap)
+
+    def first_clear_start(self, delays, check_wait=True, n_pts=200, margin=0.0, self_gap=0, retimed=False):
+        """(capi.START_DELAY_DTYPE [B], d_min_all [B][K]): per plan the lowest of the candidate start delays [K] whose run is clear of the moving
+        world; check_wait: the wait at the start posture is checked at the candidate delays too"""
+        sx, sT, prof = self._timed_plans(retimed, "first_clear_start")
+        return self._solver.start_delay(sx, sT, delays, prof, check_wait, n_pts, margin, self_gap)
+
+    def plan_as_moving_world(self, other, obstacles=None, t_start=None, n_key=256, horizon=None, retimed=False):
+        """This planner's last plans become the moving world of the planner `other` (prioritised planning: `other` is checked against them): problem
+        b of `other` sees the obstacles `obstacles` (capi.OBSTACLE_DTYPE [n_obs], standing still; None: none) and this robot's spheres, moving as
+        plan b does when started at the world time t_start (a scalar, [B] or None: 0), held at its first / last posture outside the plan.  The
+        tracks have n_key keys from world time 0 to `horizon` (default: the latest end of a plan).  Returns the tracks [B][nsph][n_key][3]"""
+        sx, sT, prof = self._timed_plans(retimed, "plan_as_moving_world")
+        B = sT.shape[0]
+        if getattr(self, "_spheres", None) is None:
+            self._spheres = capi.link_spheres(self.model, 0.06, 0.08)
+            self._solver.set_robot_spheres(self._spheres)
+        ts = np.zeros(B) if t_start is None else np.broadcast_to(np.asarray(t_start, dtype=np.float64), (B,))
+        T_run = prof[:, -1, 0] if retimed else sT
+        if horizon is None:
+            horizon = float(np.max(ts + T_run))
+        dt = horizon / max(int(n_key) - 1, 1) if horizon > 0 else 1.0
+        tracks = self._solver.sphere_tracks(sx, sT, 0.0, dt, n_key, prof, ts)
+        still = np.zeros(0, dtype=capi.OBSTACLE_DTYPE) if obstacles is None else capi._records(obstacles, capi.OBSTACLE_DTYPE, "obstacle").reshape(-1)
+        mine = np.array([capi.obstacle(capi.OBS_SPHERE, (0, 0, 0), (0, 0, 0), float(r)) for r in self._spheres["r"]], dtype=capi.OBSTACLE_DTYPE)
+        world = np.ascontiguousarray(np.broadcast_to(np.concatenate([still, mine]), (B, still.shape[0] + mine.shape[0])))
+        track_of = np.concatenate([np.full(still.shape[0], -1), np.arange(mine.shape[0])]).astype(np.int32)
+        other.set_obstacles(world) if getattr(other, "_spheres", None) is None else other.set_obstacles(world, spheres=other._spheres)
+        other.set_moving_obstacles(np.broadcast_to(track_of, (B, track_of.shape[0])), tracks, 0.0, dt)
+        return tracks
 
     def check_clearance_certified(self, margin=0.0, self_gap=0, n_start=4, max_depth=10):
         """certified clearance of the last solve_trajectory's solutions: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE); status 0 holds at every
