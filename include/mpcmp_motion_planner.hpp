@@ -364,6 +364,18 @@ class MotionPlanner {
                                     check_wait ? 1 : 0, n_pts, margin, self_gap, d_min_all, &r));
         return r;
     }
+    // certified clearance record of the last solution in the moving world (include/mpcmp_moving_cert.h): the motion starts at the world time t_start
+    // after a wait of wait_before at the start posture and is followed by a hold of hold_after at the target; status 0 means that no clearance falls
+    // below `margin` at ANY world time in [t_start - wait_before, t_start + T + hold_after].  Times are on the record clock, which starts with the
+    // wait.  On the plan's own clock only: the certificate does not survive retiming.  *cert may be null
+    mpcmp_clearance check_clearance_certified_timed(double t_start = 0.0, double wait_before = 0.0, double hold_after = 0.0, double margin = 0.0,
+                                                    int self_gap = 0, int n_start = 4, int n_rest = 4, int max_depth = 10,
+                                                    mpcmp_clearance_cert *cert = nullptr) {
+        mpcmp_clearance r;
+        chk(mpcmp_clearance_certified_timed_batch(ctx_, 1, sol_x_.data(), &sol_T_, &t_start, &wait_before, &hold_after, margin, self_gap, n_start,
+                                                  n_rest, max_depth, &r, cert));
+        return r;
+    }
     // limit record of the last solution BETWEEN its nodes, at n_pts + 1 uniform samples (include/mpcmp_limits.h): excess per group under the bounds
     // the plan was solved with, and the stretch of T that makes the kinematic groups hold.  spec NULL: tol 0, no tool speed limits
     mpcmp_limits check_limits(int n_pts = 200, const mpcmp_limits_spec *spec = nullptr) {

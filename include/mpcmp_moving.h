@@ -34,7 +34,7 @@
  *   t_start = delays[k].  With check_wait != 0 run k is joined with the robot WAITING at its start posture q(0) until it leaves: the wait is sampled
  *   at the world times delays[0 .. k], a prefix minimum over the candidate grid itself, so it sees the wait only as finely as the delays are
  *   spaced.  A run is clear when none of its samples (and wait samples) has a clearance under `margin`.
- * What happens AFTER the plan's end, with the robot resting at its target, is checked by neither call.
+ * What happens AFTER the plan's end, with the robot resting at its target, is checked by neither call.  mpcmp_clearance_certified_timed_batch (mpcmp_moving_cert.h) checks both rests and the time between samples.
  * Records do not depend on the launch or on the batch around a problem: minima of doubles by their ordered integer keys, lowest indices, counts. */
 #define MPCMP_MAX_TRACKS 64
 #define MPCMP_MAX_TRACK_KEYS 1024

@@ -13,7 +13,7 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    default_model, forward_velocities, inverse_kinematic, inverse_velocities, lib, library_path,
                    model_add_payload, model_from_urdf, models_from_urdf, num_nodes, payload, time_nodes, tool_jacobian,
                    SPHERE_DTYPE, OBSTACLE_DTYPE, CLEARANCE_DTYPE, OBS_SPHERE, OBS_CAPSULE, OBS_BOX, OBS_HALFSPACE, CLR_HIT, CLR_NAN,
-                   CLR_UNDECIDED, CLEARANCE_CERT_DTYPE, clearance_certified_one,
+                   CLR_UNDECIDED, CLEARANCE_CERT_DTYPE, clearance_certified_one, clearance_certified_timed_one,
                    START_DELAY_DTYPE, MAX_TRACKS, MAX_TRACK_KEYS, MAX_DELAYS, track_offset, clearance_timed_one, start_delay_one,
                    spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
                    ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
@@ -33,7 +33,7 @@ __all__ = ["TOOL_LINE_SPEC_DTYPE", "TOOL_LINE_DTYPE", "TOOL_DEV_DTYPE", "TL_STOP
            "time_nodes", "BatchMotionPlanner", "Solver", "forward_velocities", "inverse_kinematic",
            "inverse_velocities", "tool_jacobian", "arm_models", "DUAL_BASES", "Payload", "payload", "model_add_payload",
            "SPHERE_DTYPE", "OBSTACLE_DTYPE", "CLEARANCE_DTYPE", "OBS_SPHERE", "OBS_CAPSULE", "OBS_BOX", "OBS_HALFSPACE", "CLR_HIT", "CLR_NAN",
-           "CLR_UNDECIDED", "CLEARANCE_CERT_DTYPE", "clearance_certified_one",
+           "CLR_UNDECIDED", "CLEARANCE_CERT_DTYPE", "clearance_certified_one", "clearance_certified_timed_one",
            "START_DELAY_DTYPE", "MAX_TRACKS", "MAX_TRACK_KEYS", "MAX_DELAYS", "track_offset", "clearance_timed_one", "start_delay_one",
            "spheres", "obstacle", "link_spheres", "clearance_config",
            "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",

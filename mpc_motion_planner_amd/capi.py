@@ -193,6 +193,11 @@ ABI_MOVING = {
     "mpcmp_track_offset": "iddpdp", "mpcmp_clearance_timed_one": "piippipp" + "iiddp" + "pdipd" + "idip",
     "mpcmp_start_delay_one": "piippipp" + "iiddp" + "pdip" + "ipi" + "idi" + "pp",
 }
+# ... and every function include/mpcmp_moving_cert.h declares (certified clearance in a moving world), in its order
+ABI_MOVING_CERT = {
+    "mpcmp_clearance_certified_timed_batch": "pipppppdiiiipp", "mpcmp_clearance_certified_timed_batch_device": "pipppppdiiiippp",
+    "mpcmp_clearance_certified_timed_one": "piippipp" + "iiddp" + "pdddd" + "diiii" + "pp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -249,7 +254,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -442,6 +447,19 @@ def start_delay_one(models, num_seg, spheres_per_arm, obstacles, tracks, x, T, d
     check(lib().mpcmp_start_delay_one(*args, float(T), n_grid, pp, delays.shape[0], host(delays), int(bool(check_wait)), int(n_pts), float(margin),
                                       int(self_gap), host(d_all), host(rec)))
     return rec[0], d_all[:delays.shape[0]]
+
+
+def clearance_certified_timed_one(models, num_seg, spheres_per_arm, obstacles, tracks, x, T, t_start=0.0, wait_before=0.0, hold_after=0.0, margin=0.0,
+                                  self_gap=0, n_start=4, n_rest=4, max_depth=10):
+    """mpcmp_clearance_certified_timed_one: the certified check of ONE plan x [N][14 narm] of duration T in the moving world (tracks as for
+    clearance_timed_one), the motion starting at the world time t_start after a wait of wait_before at the first posture and followed by a hold of
+    hold_after at the last, on the host (no context, no GPU).  Returns (the CLEARANCE_DTYPE record, the CLEARANCE_CERT_DTYPE record); times are on
+    the record clock, which starts with the wait (include/mpcmp_moving_cert.h)"""
+    args, keep = _moving_one_args(models, num_seg, spheres_per_arm, obstacles, tracks, x)
+    rec, cert = np.zeros(1, dtype=CLEARANCE_DTYPE), np.zeros(1, dtype=CLEARANCE_CERT_DTYPE)
+    check(lib().mpcmp_clearance_certified_timed_one(*args, float(T), float(t_start), float(wait_before), float(hold_after), float(margin), int(self_gap),
+                                                    int(n_start), int(n_rest), int(max_depth), host(rec), host(cert)))
+    return rec[0], cert[0]
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

@@ -63,6 +63,7 @@ struct mpcmp_ctx {
     int mv_tracks = 0, mv_keys = 1;
     double mv_t0 = 0.0, mv_dt = 1.0;
     bool mv_ready = false;           // the dynamic-LDS ceilings of its kernels, by the first call of the family
+    bool mvc_ready = false;          // ... and of the certified check in a moving world (mpcmp_clearance_certified_timed_batch*), by its first call
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
     // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;

@@ -1,7 +1,7 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
 // configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
-// statements of the tool-line moves (toolpath.hpp), of the certified clearance check (clearance_cert.hpp) and of the checks in a moving world
-// (moving_rule.hpp).  Plain C++: no HIP
+// statements of the tool-line moves (toolpath.hpp), of the certified clearance check (clearance_cert.hpp), of the checks in a moving world
+// (moving_rule.hpp) and of the certified check in a moving world (moving_cert_rule.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -25,6 +25,7 @@
 #include "toolpath.hpp"
 #include "clearance_cert.hpp"
 #include "moving_rule.hpp"
+#include "moving_cert_rule.hpp"
 
 using namespace mpcmp;
 
@@ -825,5 +826,119 @@ extern "C" int mpcmp_start_delay_one(const mpcmp_model *models, int narm, int nu
     }
     for (int k = 0; k < K; k++) dk[k] = std::fmin(dk[k], best);
     *out = mv_delay_record(K, delays, dk.data(), w0.data(), check_wait, margin, d_min_all);
+    return MPCMP_OK;
+}
+
+// ---- certified clearance in a moving world on the host (include/mpcmp_moving_cert.h): one plan through the source the kernel runs
+// (moving_cert_rule.hpp on top of clearance_cert.hpp and moving_rule.hpp) ----
+extern "C" int mpcmp_clearance_certified_timed_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres,
+                                                   int n_obs, const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
+                                                   const double *offsets, const double *x, double T, double t_start, double wait_before,
+                                                   double hold_after, double margin, int self_gap, int n_start, int n_rest, int max_depth,
+                                                   mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (n_start < 1 || n_start > CERT_CAP || n_rest < 1 || n_rest > CERT_CAP || num_seg < 1 || (long)num_seg * n_start + 2l * n_rest > CERT_CAP ||
+        max_depth < 0 || max_depth > CERT_MAX_DEPTH || wait_before < 0.0 || hold_after < 0.0) {
+        g_err = "mpcmp_clearance_certified_timed_one: n_start >= 1 and n_rest >= 1 with num_seg n_start + 2 n_rest <= 4096, max_depth in [0, 16], "
+                "wait_before >= 0 and hold_after >= 0 required";
+        return MPCMP_EINVAL;
+    }
+    MvHost H;
+    if (int rc = mv_host_setup("mpcmp_clearance_certified_timed_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0,
+                               dt, offsets, x, T, 0, nullptr, 1, margin, self_gap, out, &H)) return rc;
+    mpcmp_clearance_cert c;
+    if (H.nan || !mvc_times_ok(T, t_start, wait_before, hold_after)) {
+        c.d_lower = std::nan(""); c.t_lower = -1.0; c.n_eval = 0; c.n_clear = 0; c.n_undecided = 0; c.depth = 0;
+        *out = mv_clearance_nan();
+        if (cert) *cert = c;
+        return MPCMP_OK;
+    }
+    const int nq = 7 * narm, N = 3 * num_seg + 1, nsph = H.nsph;
+    const MvcTimeline tl = mvc_timeline(num_seg, n_start, n_rest, T, t_start, wait_before, hold_after);
+    std::vector<double> reach(7 * (nsph > 0 ? nsph : 1)), cen(3 * (nsph > 0 ? nsph : 1)), Ds(nsph > 0 ? nsph : 1), pm(3 * (H.n_tracks > 0 ? H.n_tracks : 1)),
+        Ek(H.n_tracks > 0 ? H.n_tracks : 1);
+    for (int s = 0; s < nsph; s++) cert_reach(H.mk.data() + 84 * H.arm[s] + 9, 12, H.jnt[s], spheres[s].c, reach.data() + 7 * s);
+    double best_d = INFINITY, best_L = INFINITY;
+    unsigned long long best_k = CERT_NO_PAIR, best_Lk = CERT_NO_PAIR;
+    unsigned first = CERT_NO_TIME;
+    int n_hit = 0, n_clear = 0, n_und = 0, n_eval = 0, depth = 0;
+    std::vector<int> cur(tl.n0), nxt;
+    for (int i = 0; i < tl.n0; i++) cur[i] = i;
+    for (int l = 0; !cur.empty(); l++) {
+        depth = l;
+        nxt.clear();
+        int n_split = 0;
+        for (int i : cur) {
+            const MvcInterval v = mvc_interval(tl, n_start, l, i);
+            const unsigned tk = cert_tkey(l, i);
+            for (int k = 0; k < H.n_tracks; k++)
+                Ek[k] = mvc_track_bound(offsets + (size_t)k * H.n_key * 3, H.n_key, t0, dt, tl.tau0 + v.ta, tl.tau0 + v.tm, tl.tau0 + v.tb, pm.data() + 3 * k);
+            double dev[14], sc[28], fr[2 * 84];
+            for (int j = 0; j < nq; j++) {
+                double qm;
+                if (v.phase == MVC_MOTION) dev[j] = cert_deviation(H.nodes.data() + j, nq, num_seg, v.v, &qm);
+                else { dev[j] = 0.0; qm = H.nodes[(size_t)(v.phase == MVC_HOLD ? (N - 1) * nq : 0) + j]; }
+                sc[2 * j] = std::sin(qm); sc[2 * j + 1] = std::cos(qm);
+            }
+            for (int a = 0; a < narm; a++) cert_frames(H.mk.data() + 84 * a, sc + 14 * a, fr + 84 * a);
+            for (int s = 0; s < nsph; s++) {
+                Ds[s] = cert_motion(reach.data() + 7 * s, dev + 7 * H.arm[s]);
+                cert_centre(fr + 84 * H.arm[s] + 12 * H.jnt[s], spheres[s].c, cen.data() + 3 * s);
+            }
+            double d_mid = INFINITY, L = INFINITY;
+            for (int s = 0; s < nsph; s++) {
+                const double *C = cen.data() + 3 * s;
+                for (int o = 0; o < n_obs; o++) {
+                    const int k = H.tof[o];
+                    double d, bound;
+                    if (k >= 0) {
+                        const double *M = pm.data() + 3 * k;
+                        d = clr_sd(obs[o].type, H.ok.data() + 8 * o, C[0] - M[0], C[1] - M[1], C[2] - M[2]) - spheres[s].r;
+                        bound = d - Ds[s] - Ek[k];
+                    } else {
+                        d = clr_sd(obs[o].type, H.ok.data() + 8 * o, C[0], C[1], C[2]) - spheres[s].r;
+                        bound = d - Ds[s];
+                    }
+                    const unsigned long long key = cert_key(tk, s, 0, o);
+                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, bound);
+                }
+                for (int t = s + 1; t < nsph; t++) {
+                    if (!clr_pair(H.arm[s], H.jnt[s], H.arm[t], H.jnt[t], self_gap)) continue;
+                    const double d = H.pair(s, t, cen.data());
+                    const unsigned long long key = cert_key(tk, s, 1, t);
+                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s] - Ds[t]);
+                }
+            }
+            n_eval++;
+            int what = cert_decide(d_mid, L, margin, l, max_depth);
+            if (what == CERT_SPLIT_IT) {
+                if (n_split < CERT_SPLIT) { n_split++; nxt.push_back(2 * i); nxt.push_back(2 * i + 1); continue; }
+                what = CERT_UNDECIDED;          // (the capacity rule)
+            }
+            if (what == CERT_HIT) { n_hit++; if (tk < first) first = tk; }
+            else if (what == CERT_CLEAR) n_clear++;
+            else n_und++;
+            const unsigned long long lk = cert_key(tk, 0, 0, 0);
+            if (cert_better(L, lk, best_L, best_Lk)) { best_L = L; best_Lk = lk; }
+        }
+        cur.swap(nxt);
+    }
+    mpcmp_clearance r;
+    r.d_min = best_d;
+    if (best_k == CERT_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
+    else {
+        const int idx = (int)(best_k & 0xFFu);
+        r.t_min = mvc_time(tl, (unsigned)(best_k >> 16));
+        r.sphere = (int)((best_k >> 9) & 0x7Fu);
+        r.other = (best_k & 0x100u) ? -1 - idx : idx;
+    }
+    r.t_first = first != CERT_NO_TIME ? mvc_time(tl, first) : -1.0;
+    r.n_hit = n_hit;
+    r.status = (n_hit > 0 ? MPCMP_CLR_HIT : 0) | (n_und > 0 ? MPCMP_CLR_UNDECIDED : 0);
+    c.d_lower = best_L; c.t_lower = mvc_time(tl, (unsigned)(best_Lk >> 16));
+    c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
+    *out = r;
+    if (cert) *cert = c;
     return MPCMP_OK;
 }

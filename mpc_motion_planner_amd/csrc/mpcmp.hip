@@ -23,6 +23,7 @@
 #include "time_sync.hpp"
 #include "clearance.hpp"
 #include "moving.hpp"
+#include "moving_cert.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
 #include "retimed_check.hpp"
@@ -1249,6 +1250,60 @@ extern "C" int mpcmp_sphere_tracks_batch(mpcmp_ctx *ctx, int B, const double *sx
     sg.in(&dts, t_start, B); sg.out(&dout, out, (size_t)B * nsph * n_key * 3);
     if (int rc = sg.upload()) return rc;
     if (int rc = mpcmp_sphere_tracks_batch_device(ctx, B, dx, dT, n_grid, dp, dts, t0, dt, n_key, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ---- certified clearance in a moving world (include/mpcmp_moving_cert.h; the kernel is in moving_cert.hip, the rule in moving_cert_rule.hpp) ----
+static int clearance_cert_timed_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int self_gap, int n_start, int n_rest,
+                                      int max_depth, const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_certified_timed_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0 || n_start < 1 || n_start > MPCMP_CLR_CERT_CAPACITY || n_rest < 1 ||
+        n_rest > MPCMP_CLR_CERT_CAPACITY || (long)ctx->nseg * n_start + 2l * n_rest > MPCMP_CLR_CERT_CAPACITY || max_depth < 0 || max_depth > 16) {
+        ctx->err = "mpcmp_clearance_certified_timed_batch: B >= 1, n_start >= 1 and n_rest >= 1 with num_seg n_start + 2 n_rest <= 4096, max_depth in "
+                   "[0, 16], a finite margin, self_gap >= 0 and all pointers (but t_start, wait_before, hold_after, cert) required";
+        return MPCMP_EINVAL;
+    }
+    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
+        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_timed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, const double *d_t_start,
+                                                            const double *d_wait, const double *d_hold, double margin, int self_gap, int n_start,
+                                                            int n_rest, int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert,
+                                                            void *hip_stream) {
+    if (int rc = clearance_cert_timed_check(ctx, B, d_sx, d_sT, margin, self_gap, n_start, n_rest, max_depth, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->mvc_ready) { HIPCHK(ctx, moving_cert_prepare()); ctx->mvc_ready = true; }
+    MvTracks trk;
+    const ClrTables t = moving_tables(ctx, &trk);
+    const MvcPlans p = {d_sx, d_sT, d_t_start, d_wait, d_hold};
+    HIPCHK(ctx, moving_cert_launch(t, trk, p, B, margin, self_gap, n_start, n_rest, max_depth, d_out, d_cert, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_timed_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, const double *t_start,
+                                                     const double *wait_before, const double *hold_after, double margin, int self_gap, int n_start,
+                                                     int n_rest, int max_depth, mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (int rc = clearance_cert_timed_check(ctx, B, sx, sT, margin, self_gap, n_start, n_rest, max_depth, out)) return rc;
+    for (int b = 0; b < B; b++)
+        if ((wait_before && wait_before[b] < 0.0) || (hold_after && hold_after[b] < 0.0)) {
+            ctx->err = "mpcmp_clearance_certified_timed_batch: wait_before and hold_after must not be negative (problem " + std::to_string(b) + ")";
+            return MPCMP_EINVAL;
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT, *dts, *dw, *dh;
+    mpcmp_clearance *dout;
+    mpcmp_clearance_cert *dcert = nullptr;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.in(&dts, t_start, B); sg.in(&dw, wait_before, B); sg.in(&dh, hold_after, B);
+    sg.out(&dout, out, B);
+    if (cert) sg.out(&dcert, cert, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_clearance_certified_timed_batch_device(ctx, B, dx, dT, dts, dw, dh, margin, self_gap, n_start, n_rest, max_depth, dout, dcert,
+                                                              ctx->stream)) return rc;
     return sg.finish();
 }
 

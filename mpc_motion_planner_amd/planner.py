@@ -336,6 +336,27 @@ class Solver:
         check(lib().mpcmp_sphere_tracks_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_grid), prof or None, t_start or None,
                                                      float(t0), float(dt), int(n_key), out or None, stream or None), self._ctx)
 
+    # -- certified clearance in a moving world, with the rests before and after the plan (include/mpcmp_moving_cert.h)
+    def clearance_certified_timed(self, sx, sT, t_start=None, wait_before=None, hold_after=None, margin=0.0, self_gap=0, n_start=4, n_rest=4,
+                                  max_depth=10):
+        """mpcmp_clearance_certified_timed_batch: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE [B]) of the plans sx, sT on their own clock in
+        the world moved by set_obstacle_tracks: the motion starts at the world time t_start after a wait of wait_before at the first posture and is
+        followed by a hold of hold_after at the last (each a scalar, [B] or None: 0).  status 0: no clearance below `margin` at ANY world time in
+        [t_start - wait_before, t_start + T + hold_after]; times are on the record clock, which starts with the wait"""
+        B, sx, sT, _, _, t_start = self._plans(sx, sT, None, t_start)
+        w = None if wait_before is None else f64(np.broadcast_to(np.asarray(wait_before, dtype=np.float64), (B,)))
+        h = None if hold_after is None else f64(np.broadcast_to(np.asarray(hold_after, dtype=np.float64), (B,)))
+        out, cert = np.zeros(B, dtype=capi.CLEARANCE_DTYPE), np.zeros(B, dtype=capi.CLEARANCE_CERT_DTYPE)
+        check(lib().mpcmp_clearance_certified_timed_batch(self._ctx, B, host(sx), host(sT), host(t_start), host(w), host(h), float(margin),
+                                                          int(self_gap), int(n_start), int(n_rest), int(max_depth), host(out), host(cert)), self._ctx)
+        return out, cert
+
+    def clearance_certified_timed_device(self, B, sol_x, sol_T, t_start, wait_before, hold_after, margin, self_gap, n_start, n_rest, max_depth, out,
+                                         cert=0, stream=0):
+        check(lib().mpcmp_clearance_certified_timed_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, t_start or None, wait_before or None,
+                                                                 hold_after or None, float(margin), int(self_gap), int(n_start), int(n_rest),
+                                                                 int(max_depth), out or None, cert or None, stream or None), self._ctx)
+
     def select_clear(self, sT, info, clr, group, n_groups=None):
         """mpcmp_select_clear_batch: per group the admissible member (clean solve status, clearance status 0) with the smallest final time,
         ties to the lowest index, -1 if none.  n_groups defaults to max(group) + 1"""
@@ -1016,6 +1037,46 @@ class BatchMotionPlanner:
         world; check_wait: the wait at the start posture is checked at the candidate delays too"""
         sx, sT, prof = self._timed_plans(retimed, "first_clear_start")
         return self._solver.start_delay(sx, sT, delays, prof, check_wait, n_pts, margin, self_gap)
+
+    def check_clearance_certified_timed(self, t_start=None, wait_before=None, hold_after=None, margin=0.0, self_gap=0, n_start=4, n_rest=4,
+                                        max_depth=10, retimed=False):
+        """certified clearance of the last solve_trajectory's solutions in the moving world (include/mpcmp_moving_cert.h): (capi.CLEARANCE_DTYPE [B],
+        capi.CLEARANCE_CERT_DTYPE [B]).  The motion starts at the world time t_start after a wait of wait_before at the start posture and is followed
+        by a hold of hold_after at the target (each a scalar, [B] or None: 0); status 0 holds at every world time of that span, not at samples.
+        Direct moves on their own clock only: the certificate does not survive retiming"""
+        if retimed:
+            raise ValueError("check_clearance_certified_timed: there is no certificate on a retimed clock (the rule has no retime profile); check the "
+                             "plan on its own clock, or sample the retimed plan with check_clearance_timed(retimed=True)")
+        if self._route is not None or self._sol is None:
+            raise ValueError("check_clearance_certified_timed: direct moves only, after solve_trajectory (check a route's leg slots with "
+                             "Solver.clearance_certified_timed, each with t_start = the route's start plus the durations of the legs before it)")
+        return self._solver.clearance_certified_timed(self._sol[0], self._sol[2], t_start, wait_before, hold_after, margin, self_gap, n_start, n_rest,
+                                                      max_depth)
+
+    def first_certified_start(self, delays, margin=0.0, self_gap=0, n_pts=200, hold_after=None, n_start=4, n_rest=4, max_depth=10, max_rounds=4):
+        """(index [B], capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE [B]): per plan the lowest of the candidate start delays [K] that
+        first_clear_start(check_wait=True) calls clear AND whose certified record (t_start = delays[k], wait_before = delays[k] - delays[0]) has status
+        0; -1: none within max_rounds candidates.  A host loop over the two checks: a problem whose record is not 0 moves to its next sampled-clear
+        candidate.  The records are those of the last candidate tried (all zero for a problem without any sampled-clear delay)"""
+        delays = np.asarray(delays, dtype=np.float64).reshape(-1)
+        _, d_all = self.first_clear_start(delays, True, n_pts, margin, self_gap)
+        B = d_all.shape[0]
+        cand = [list(np.nonzero(~(d_all[b] < margin))[0]) for b in range(B)]
+        pos, index = np.zeros(B, dtype=int), np.full(B, -1, dtype=int)
+        pending = np.array([len(c) > 0 for c in cand])
+        clr, cert = np.zeros(B, dtype=capi.CLEARANCE_DTYPE), np.zeros(B, dtype=capi.CLEARANCE_CERT_DTYPE)
+        for _ in range(int(max_rounds)):
+            if not pending.any():
+                break
+            k = np.array([cand[b][pos[b]] if pending[b] else 0 for b in range(B)])
+            c, ce = self.check_clearance_certified_timed(delays[k], delays[k] - delays[0], hold_after, margin, self_gap, n_start, n_rest, max_depth)
+            clr[pending], cert[pending] = c[pending], ce[pending]
+            ok = pending & (c["status"] == 0)
+            index[ok] = k[ok]
+            pending &= ~ok
+            pos[pending] += 1
+            pending &= np.array([pos[b] < len(cand[b]) for b in range(B)])
+        return index, clr, cert
 
     def plan_as_moving_world(self, other, obstacles=None, t_start=None, n_key=256, horizon=None, retimed=False):
         """This planner's last plans become the moving world of the planner `other` (prioritised planning: `other` is checked against them): problem
