@@ -36,12 +36,22 @@ def M():
 
 
 @functools.lru_cache(maxsize=None)
-def robot(narm):
+def _panda(narm):
+    import mpc_motion_planner_amd as M
+    return robot(narm, list(M.arm_models(M.DUAL_BASES)) if narm == 2 else [M.default_model()])
+
+
+def robot(narm, models=None, tables=None):
     """(ctypes Models [narm], their arrays for the reference, the sphere table of every arm).  The table is the skeleton of mpcmp_link_spheres without
     the sphere at the origin of joints 1 .. 6: that one lies exactly where the last sphere of the link before it lies, so the two would tie in
-    every clearance, and which of them a record names would be decided by the last bit of the forward kinematics"""
+    every clearance, and which of them a record names would be decided by the last bit of the forward kinematics.
+    models: the Panda(s) of narm, computed once, unless given; tables: that skeleton of every model unless given"""
     import mpc_motion_planner_amd as M
-    models = list(M.arm_models(M.DUAL_BASES)) if narm == 2 else [M.default_model()]
+    if models is None:
+        return _panda(narm)
+    models = list(models)
+    if tables is not None:
+        return models, [R.model_arrays(m) for m in models], list(tables)
     tables = []
     for m in models:
         t = M.link_spheres(m, 0.06, 0.08)
@@ -50,9 +60,11 @@ def robot(narm):
 
 
 @functools.lru_cache(maxsize=None)
-def world(narm):
-    """one of each primitive, near the workspace"""
+def world(narm, rows=None):
+    """one of each primitive, near the workspace; rows: (type, a, b, r) tuples of another scene"""
     import mpc_motion_planner_amd as M
+    if rows is not None:
+        return np.array([M.obstacle(*r) for r in rows], dtype=M.OBSTACLE_DTYPE)
     rows = [(M.OBS_SPHERE, (0.55, 0.0, 0.75), (0, 0, 0), 0.10), (M.OBS_BOX, (0.6, -0.5, 0.15), (0.1, 0.1, 0.15), 0.01),
             (M.OBS_CAPSULE, (-0.5, 0.5, 0.2), (-0.5, 0.5, 1.0), 0.04), (M.OBS_HALFSPACE, (0.0, 0.0, 1.0), (-0.05, 0, 0), 0.0)]
     if narm == 2:
@@ -123,16 +135,16 @@ def check_records(clr, cert, ref, what=""):
         assert close(float(cert[f]), float(rt[f])), (what, f, cert, rt)
 
 
-def one(M, narm, nseg, obstacles, x, T, margin, self_gap, n_start, max_depth, tables=None):
-    models, _, tabs = robot(narm)
+def one(M, narm, nseg, obstacles, x, T, margin, self_gap, n_start, max_depth, tables=None, models=None):
+    models, _, tabs = robot(narm, models, tables)
     return M.clearance_certified_one(models, nseg, tabs if tables is None else tables, obstacles, x, T, margin, self_gap, n_start, max_depth)
 
 
-def dense_min(M, narm, nseg, obstacles, x, self_gap, n=20000, tables=None):
+def dense_min(M, narm, nseg, obstacles, x, self_gap, n=20000, tables=None, models=None):
     """the smallest clearance over n + 1 uniform samples by mpcmp_clearance_config (called directly: the tables are marshalled once): (minimum,
     per-sample values)"""
     from mpc_motion_planner_amd.capi import host
-    models, _, tabs = robot(narm)
+    models, _, tabs = robot(narm, models, tables)
     tabs = tabs if tables is None else tables
     arr = (M.Model * narm)(*[M.Model.from_buffer_copy(m) for m in models])
     cnt = np.array([t.shape[0] for t in tabs], dtype=np.int32)

@@ -39,11 +39,11 @@ def M():
 
 
 @functools.lru_cache(maxsize=None)
-def moves(narm, nseg, n=B):
-    """tests/test_gpu_clearance.py::moves, with the accelerations: sx [n][N][14 narm], su [n][N][7 narm], sT [n]"""
+def moves(narm, nseg, n=B, seed=SEED):
+    """tests/test_gpu_clearance.py::moves, with the accelerations: sx [n][N][14 narm], su [n][N][7 narm], sT [n]; seed: another stream of moves"""
     lim = o.default_limits()
     vmax, amax, jmax = MARGINS[1] * lim["vmax"], MARGINS[2] * lim["amax"], MARGINS[4] * lim["jmax"]
-    rng = np.random.default_rng(SEED)
+    rng = np.random.default_rng(seed)
     span = np.tile(lim["qmax"] - lim["qmin"], narm)
     q0 = np.tile(lim["qmin"], narm) + (0.05 + 0.9 * rng.random((n, 7 * narm))) * span
     q1 = np.tile(lim["qmin"], narm) + (0.05 + 0.9 * rng.random((n, 7 * narm))) * span
@@ -68,7 +68,10 @@ def rows(M, n=B, nseg=4):
     return t
 
 
-def robot(M, narm):
+def robot(M, narm, models=None):
+    """the Panda(s) of narm, or the models given"""
+    if models is not None:
+        return list(models)
     return list(M.arm_models(M.DUAL_BASES)) if narm == 2 else [M.default_model()]
 
 
@@ -135,7 +138,11 @@ def check_records(got, ref, sT, n_pts, tol, what="", worst=None):
             assert g["status"] == r["status"] and g["n_viol"] == r["n_viol"] and g["t_first"] == r["t_first"], (tag, g, r["status"], r["n_viol"], r["t_first"])
 
 
-def solver(M, narm, nseg, max_batch=B, sqp=1):
+def solver(M, narm, nseg, max_batch=B, sqp=1, models=None):
+    """a context of the Panda(s) of narm, or of the models given (a ctypes array of narm Models)"""
+    if models is not None:
+        cfg = M.default_config(nseg, sqp, margins=MARGINS)
+        return M.Solver(cfg, max_batch, models=models) if narm == 2 else M.Solver(cfg, max_batch, model=models[0])
     return M.Solver(M.default_config(nseg, sqp, margins=MARGINS), max_batch, models=M.arm_models(M.DUAL_BASES) if narm == 2 else None)
 
 

@@ -69,9 +69,11 @@ def moving_rows(M, narm, rng=None):
 
 
 @functools.lru_cache(maxsize=None)
-def case_data(case):
+def case_data(case, still=None, shift=(0.0, 0.0, 0.0)):
     """dict: x [NP][N][14 narm], T, ts, w, h [NP]; obs [NP] record arrays and tracks [NP] = (track_of, offsets [n_tracks][n_key][3], t0, dt): the
-    same objects for every plan unless the case has one set per problem"""
+    same objects for every plan unless the case has one set per problem.
+    For robots that stand elsewhere: still: the (type, a, b, r) rows of the four standing obstacles (default: H.world(narm)); shift: a translation of
+    the tracked obstacles' paths (the defaults are the cases as they always were)"""
     import mpc_motion_planner_amd as M
     lim = M.default_limits()
     narm, nseg = case.narm, case.nseg
@@ -98,11 +100,11 @@ def case_data(case):
         if case.n_key > 2 and n_mv > 2:
             path[2, :, 1] += 0.1 * np.sin(2 * np.pi * fr)          # (a wobble that only more than two keys can show)
         off = np.random.default_rng(case.seed + 2000 + b).uniform(-1.0, 1.0, (case.n_tracks, case.n_key, 3))      # (tracks nobody follows)
-        off[slots] = path - PARK
-        still = H.world(narm)
+        off[slots] = path - PARK + np.asarray(shift, dtype=np.float64)
+        standing = H.world(narm, still)
         moving = np.array([M.obstacle(*r) for r in rows[:n_mv]], dtype=M.OBSTACLE_DTYPE)
         # tracked and standing obstacles interleaved, so that the obstacle loop changes branch
-        order = [still[0], moving[0]] + ([still[1], moving[1], moving[2], still[2], still[3], moving[3]] if n_mv == 4 else list(still[1:]))
+        order = [standing[0], moving[0]] + ([standing[1], moving[1], moving[2], standing[2], standing[3], moving[3]] if n_mv == 4 else list(standing[1:]))
         tof = [-1, slots[0]] + ([-1, slots[1], slots[2], -1, -1, slots[3]] if n_mv == 4 else [-1] * 3)
         obs.append(np.array(order, dtype=M.OBSTACLE_DTYPE))
         tracks.append((np.array(tof, dtype=np.int32), np.ascontiguousarray(off), t0, dt))
@@ -131,8 +133,8 @@ def assert_fair(case, ref):
     assert n_hit >= 2 and n_clear >= 2, ("reference: too few hits or certified plans", case.name, n_hit, n_clear)
 
 
-def one(M, narm, nseg, obstacles, tracks, x, T, ts, w, h, margin, self_gap, n_start, n_rest, max_depth, tables=None):
-    models, _, tabs = robot(narm)
+def one(M, narm, nseg, obstacles, tracks, x, T, ts, w, h, margin, self_gap, n_start, n_rest, max_depth, tables=None, models=None):
+    models, _, tabs = robot(narm, models, tables)
     return M.clearance_certified_timed_one(models, nseg, tabs if tables is None else tables, obstacles, tracks, x, T, ts, w, h, margin, self_gap,
                                            n_start, n_rest, max_depth)
 
@@ -222,11 +224,11 @@ def shifted(obs, tof, p):
     return out
 
 
-def dense_minimum(M, narm, nseg, obs, tracks, x, T, ts, w, h, self_gap, tables=None, n_motion=20000, n_rest=5000):
+def dense_minimum(M, narm, nseg, obs, tracks, x, T, ts, w, h, self_gap, tables=None, n_motion=20000, n_rest=5000, models=None):
     """the smallest clearance over n_motion + 1 samples of the motion and n_rest + 1 of each rest, by mpcmp_clearance_config on the posture (the
     reference's interpolant) against the obstacles moved by mpcmp_track_offset; the motion also by mpcmp_clearance_timed_one at the 4,097 samples it
     takes at most"""
-    models, _, tabs = robot(narm)
+    models, _, tabs = robot(narm, models, tables)
     tabs = tabs if tables is None else tables
     tof, off, t0, dt = tracks if tracks is not None else (np.full(obs.shape[0], -1), np.zeros((0, 1, 3)), 0.0, 1.0)
     best = M.clearance_timed_one(models, nseg, tabs, obs, tracks, x, T, None, ts, 4096, 0.0, self_gap)["d_min"]

@@ -121,9 +121,12 @@ def test_oracle_vs_reference_on_the_panda(robots):
     oracle_vs_reference(robots["panda"], 50, 21, "panda")
 
 
-@pytest.mark.parametrize("name", ["general_%d" % s for s in GENERAL_SEEDS] + ["tilted_%d" % TILTED_SEED])
+@pytest.mark.parametrize("name", ["general_%d" % s for s in GENERAL_SEEDS] + ["tilted_%d" % TILTED_SEED]
+                         + ["dual_%d_chain%d" % (DUAL_SEED, c) for c in (0, 1)])
 def test_oracle_vs_reference_on_general_robots(robots, name):
-    """THE pin on the oracle off the Panda: 50 random (q, qd, qdd) per robot, velocities and accelerations up to the limits"""
+    """THE pin on the oracle off the Panda: 50 random (q, qd, qdd) per robot, velocities and accelerations up to the limits.  Both chains of the
+    two-chain robot are robots of their own here (chain 1 turns about random axes): the references of the finished-plan readers take rnea, fk and
+    frame_jacobian from the oracle on them (tests/test_general_robot_readers_host.py)"""
     m = robots[name]
     if name.startswith("tilted"):
         assert min(abs(m.gravity[0]), abs(m.gravity[1])) > 1.0
