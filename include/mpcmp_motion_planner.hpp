@@ -340,6 +340,37 @@ class MotionPlanner {
         chk(mpcmp_clearance_certified_batch(ctx_, 1, sol_x_.data(), &sol_T_, margin, self_gap, n_start, max_depth, &r, cert));
         return r;
     }
+    // A voxel world (include/mpcmp_field.h): the occupancy occ [n[2]][n[1]][n[0]] of the grid `desc`, or the voxels that contain the points
+    // [n_points][3]; desc == nullptr removes it.  The robot is the skeleton of set_obstacles, set again by each of these calls
+    void field_spheres(double sphere_radius, double sphere_spacing) {
+        mpcmp_sphere sph[64];
+        int n = 0;
+        if (mpcmp_link_spheres(&robot.model, sphere_radius, sphere_spacing, 64, sph, &n) != MPCMP_OK)
+            throw std::runtime_error("mpcmp: voxel world: sphere radius and spacing must be > 0 and give at most 64 spheres");
+        chk(mpcmp_set_robot_spheres(ctx_, 0, n, sph));
+    }
+    void set_voxel_world(const mpcmp_field_desc *desc, const unsigned char *occ, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        if (desc) field_spheres(sphere_radius, sphere_spacing);
+        chk(mpcmp_set_field(ctx_, desc, occ));
+    }
+    void set_point_cloud(const mpcmp_field_desc &desc, int n_points, const double *points, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        field_spheres(sphere_radius, sphere_spacing);
+        chk(mpcmp_set_field_points(ctx_, &desc, n_points, points));
+    }
+    // the grid in force and (d2 may be null) its squared distance field d2 [n[2]][n[1]][n[0]] as the GPU built it
+    void voxel_field(mpcmp_field_desc *desc, unsigned *d2 = nullptr) { chk(mpcmp_get_field(ctx_, desc, d2)); }
+    // clearance record of the last solution against the voxel world (`other` is the linear index of a voxel).  merge: joined with the record of
+    // clearance(n_pts, margin, self_gap) by mpcmp_clearance_merge_batch; *source (may be null) is then 1 where d_min is the field's
+    mpcmp_clearance check_clearance_field(int n_pts = 200, double margin = 0.0, bool merge = false, int self_gap = 0, int *source = nullptr) {
+        mpcmp_clearance r;
+        chk(mpcmp_clearance_field_batch(ctx_, 1, sol_x_.data(), &sol_T_, n_pts, margin, &r));
+        if (source) *source = 1;
+        if (merge) {
+            const mpcmp_clearance a = clearance(n_pts, margin, self_gap);
+            chk(mpcmp_clearance_merge_batch(ctx_, 1, &a, &r, &r, source));
+        }
+        return r;
+    }
     // The obstacles of set_obstacles that move (include/mpcmp_moving.h): track_of [n_obs] (-1: stands still), offsets [n_tracks][n_key][3] on the
     // world clock t0 + k dt.  n_tracks == 0: the world stands still again, as it does after the next set_obstacles
     void set_moving_obstacles(int n_obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets) {

@@ -70,6 +70,9 @@ CLR_CERT_CAPACITY = 4096
 START_DELAY_DTYPE = np.dtype([("delay", "f8"), ("d_min", "f8"), ("index", "i4"), ("n_clear", "i4"), ("status", "i4"), ("pad", "i4")])
 MAX_TRACKS, MAX_TRACK_KEYS, MAX_DELAYS = 64, 1024, 256
 MAX_SPHERES, MAX_OBSTACLES = 64, 256
+# the grid of a voxel world (mpcmp_field_desc, include/mpcmp_field.h): 48 bytes; the field entry of an empty world and the limits of a grid
+FIELD_DESC_DTYPE = np.dtype([("origin", "f8", 3), ("h", "f8"), ("n", "i4", 3), ("pad", "i4")])
+FIELD_EMPTY, FIELD_MAX_DIM, FIELD_MAX_VOXELS = 0xFFFFFFFF, 1024, 1 << 24
 
 # records of the between-node limit checks (mpcmp_limits_spec, mpcmp_limits; include/mpcmp.h): 72 and 168 bytes
 LIMITS_SPEC_DTYPE = np.dtype([("tol", "f8", 7), ("tool_lin_max", "f8"), ("tool_ang_max", "f8")])
@@ -198,6 +201,13 @@ ABI_MOVING_CERT = {
     "mpcmp_clearance_certified_timed_batch": "pipppppdiiiipp", "mpcmp_clearance_certified_timed_batch_device": "pipppppdiiiippp",
     "mpcmp_clearance_certified_timed_one": "piippipp" + "iiddp" + "pdddd" + "diiii" + "pp",
 }
+# ... and every function include/mpcmp_field.h declares (voxel worlds: clearance against a distance field built on the GPU), in its order
+ABI_FIELD = {
+    "mpcmp_field_edt": "ppp", "mpcmp_field_sd": "ppppp", "mpcmp_clearance_field_config": "pipppppppp",
+    "mpcmp_set_field": "ppp", "mpcmp_set_field_device": "pppp", "mpcmp_set_field_points": "ppip", "mpcmp_set_field_points_device": "ppipp",
+    "mpcmp_get_field": "ppp", "mpcmp_clearance_field_batch": "pippidp", "mpcmp_clearance_field_batch_device": "pippidpp",
+    "mpcmp_clearance_merge_batch": "pipppp", "mpcmp_clearance_merge_batch_device": "pippppp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -254,7 +264,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()) + list(ABI_FIELD.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -460,6 +470,68 @@ def clearance_certified_timed_one(models, num_seg, spheres_per_arm, obstacles, t
     check(lib().mpcmp_clearance_certified_timed_one(*args, float(T), float(t_start), float(wait_before), float(hold_after), float(margin), int(self_gap),
                                                     int(n_start), int(n_rest), int(max_depth), host(rec), host(cert)))
     return rec[0], cert[0]
+
+
+def field_desc(origin, h, n):
+    """one FIELD_DESC_DTYPE record: the grid of n = (n0, n1, n2) cubes of edge h whose lowest corner is `origin` (world frame); voxel (i, j, k) has
+    the linear index (k n1 + j) n0 + i, so an occupancy array is indexed occ[k][j][i]"""
+    t = np.zeros((), dtype=FIELD_DESC_DTYPE)
+    t["origin"] = f64(origin).reshape(3); t["h"] = float(h); t["n"] = np.asarray(n, dtype=np.int32).reshape(3)
+    return t
+
+
+def _field_desc_arg(desc):
+    desc = np.ascontiguousarray(desc).reshape(())
+    if desc.dtype != FIELD_DESC_DTYPE:
+        raise ValueError("desc must be one FIELD_DESC_DTYPE record (field_desc)")
+    return desc
+
+
+def _field_array(desc, a, dtype, what):
+    """a [n2][n1][n0] (or flat) as a contiguous array of `dtype` with the voxel count of desc"""
+    n = [int(v) for v in desc["n"]]
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.size != n[0] * n[1] * n[2]:
+        raise ValueError("%s must hold n2 x n1 x n0 = %d x %d x %d entries, got %s" % (what, n[2], n[1], n[0], a.shape))
+    return a.reshape(n[2], n[1], n[0])
+
+
+def field_edt(desc, occ):
+    """mpcmp_field_edt: the exact squared distance field d2 [n2][n1][n0] (uint32, voxel units, FIELD_EMPTY everywhere when nothing is occupied) of
+    the occupancy occ [n2][n1][n0] (nonzero: solid) on the host (no GPU)"""
+    desc = _field_desc_arg(desc)
+    occ = _field_array(desc, np.asarray(occ) != 0, np.uint8, "occ")
+    d2 = np.zeros(occ.shape, dtype=np.uint32)
+    check(lib().mpcmp_field_edt(desc.ctypes.data, host(occ), host(d2)))
+    return d2
+
+
+def field_sd(desc, d2, x):
+    """mpcmp_field_sd: (sd_field(x), the linear index of the voxel read) for the world point x [3] (include/mpcmp_field.h, "Distance")"""
+    desc = _field_desc_arg(desc); d2 = _field_array(desc, d2, np.uint32, "d2"); x = f64(x).reshape(3)
+    sd, v = C.c_double(0), C.c_int(0)
+    check(lib().mpcmp_field_sd(desc.ctypes.data, host(d2), host(x), C.byref(sd), C.byref(v)))
+    return sd.value, v.value
+
+
+def clearance_field_config(models, spheres_per_arm, desc, d2, q):
+    """mpcmp_clearance_field_config: minimum field clearance of ONE configuration q [7 narm] on the host; models and spheres_per_arm as for
+    clearance_config.  Returns (d_min, sphere, voxel)."""
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models)
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    desc = _field_desc_arg(desc); d2 = _field_array(desc, d2, np.uint32, "d2")
+    q = f64(q).reshape(7 * narm)
+    d, sp, vx = C.c_double(0), C.c_int(0), C.c_int(0)
+    check(lib().mpcmp_clearance_field_config(arr, narm, host(cnt), host(tab), desc.ctypes.data, host(d2), host(q), C.byref(d), C.byref(sp),
+                                             C.byref(vx)))
+    return d.value, sp.value, vx.value
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

@@ -64,6 +64,15 @@ struct mpcmp_ctx {
     double mv_t0 = 0.0, mv_dt = 1.0;
     bool mv_ready = false;           // the dynamic-LDS ceilings of its kernels, by the first call of the family
     bool mvc_ready = false;          // ... and of the certified check in a moving world (mpcmp_clearance_certified_timed_batch*), by its first call
+    // the voxel world (mpcmp_set_field*, include/mpcmp_field.h): the grid in force, its occupancy, its squared distance field and the transform's
+    // scratch, fld_cap entries each, allocated and grown by the setters and by nothing else; fld_set == false: no field.  Read by
+    // mpcmp_clearance_field_batch* and mpcmp_get_field only
+    mpcmp_field_desc fld_desc{};
+    unsigned char *d_fld_occ = nullptr;
+    unsigned *d_fld_d2 = nullptr, *d_fld_tmp = nullptr;
+    size_t fld_cap = 0;
+    bool fld_set = false;
+    bool fld_ready = false;          // the dynamic-LDS ceiling of k_clearance_field, by the first field check
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
     // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;

@@ -1,7 +1,7 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
 // configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
 // statements of the tool-line moves (toolpath.hpp), of the certified clearance check (clearance_cert.hpp), of the checks in a moving world
-// (moving_rule.hpp) and of the certified check in a moving world (moving_cert_rule.hpp).  Plain C++: no HIP
+// (moving_rule.hpp), of the certified check in a moving world (moving_cert_rule.hpp) and of the voxel worlds (field_rule.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -26,6 +26,7 @@
 #include "clearance_cert.hpp"
 #include "moving_rule.hpp"
 #include "moving_cert_rule.hpp"
+#include "field_rule.hpp"
 
 using namespace mpcmp;
 
@@ -940,5 +941,76 @@ extern "C" int mpcmp_clearance_certified_timed_one(const mpcmp_model *models, in
     c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
     *out = r;
     if (cert) *cert = c;
+    return MPCMP_OK;
+}
+
+// ---- voxel worlds on the host (include/mpcmp_field.h): the transform, the distance and one configuration through the source the kernels run
+// (field_rule.hpp) ----
+extern "C" int mpcmp_field_edt(const mpcmp_field_desc *desc, const unsigned char *occ, unsigned *d2) {
+    if (!desc || !occ || !d2 || !fld_desc_ok(*desc)) {
+        g_err = "mpcmp_field_edt: 1 <= n[d] <= 1024 with at most 2^24 voxels, a finite origin, a finite h > 0 and all pointers required";
+        return MPCMP_EINVAL;
+    }
+    const int n[3] = {desc->n[0], desc->n[1], desc->n[2]};
+    const size_t stride[3] = {1, (size_t)n[0], (size_t)n[0] * n[1]}, nv = (size_t)fld_voxels(*desc);
+    for (size_t v = 0; v < nv; v++) d2[v] = occ[v] ? 0u : FLD_INF;
+    std::vector<unsigned> line(FLD_MAX_DIM);
+    // pass x, y, z: every line along the axis through the sweep of fld_minplus, in place by way of a copy of the line
+    for (int ax = 0; ax < 3; ax++) {
+        const int a1 = (ax + 1) % 3, a2 = (ax + 2) % 3;
+        for (int p = 0; p < n[a1]; p++)
+            for (int q = 0; q < n[a2]; q++) {
+                unsigned *L = d2 + p * stride[a1] + q * stride[a2];
+                for (int k = 0; k < n[ax]; k++) line[k] = L[k * stride[ax]];
+                for (int j = 0; j < n[ax]; j++) L[j * stride[ax]] = fld_minplus(line.data(), n[ax], j);
+            }
+    }
+    for (size_t v = 0; v < nv; v++) if (d2[v] >= FLD_INF) d2[v] = MPCMP_FIELD_EMPTY;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_field_sd(const mpcmp_field_desc *desc, const unsigned *d2, const double *x, double *sd, int *voxel) {
+    if (!desc || !d2 || !x || !sd || !fld_desc_ok(*desc) || !std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2])) {
+        g_err = "mpcmp_field_sd: a valid grid, a finite point and the pointers desc, d2, x and sd required";
+        return MPCMP_EINVAL;
+    }
+    int v;
+    *sd = fld_sd(*desc, d2, x[0], x[1], x[2], &v);
+    if (voxel) *voxel = v;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_field_config(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres,
+                                            const mpcmp_field_desc *desc, const unsigned *d2, const double *q, double *d_min, int *sphere, int *voxel) {
+    if (!models || narm < 1 || narm > 2 || !n_spheres || !q || !d_min || !desc || !d2 || !fld_desc_ok(*desc)) {
+        g_err = "mpcmp_clearance_field_config: one or two arms, a valid grid and the pointers models, n_spheres, desc, d2, q and d_min required";
+        return MPCMP_EINVAL;
+    }
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
+    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
+    for (int j = 0; j < 7 * narm; j++) if (!std::isfinite(q[j])) return MPCMP_EINVAL;
+    double best = INFINITY;
+    int bs = -1, bv = 0;
+    for (int a = 0, s = 0; a < narm; a++) {
+        double mk[84], sc[14], fr[84];
+        for (int i = 0; i < 7; i++) {
+            for (int c = 0; c < 9; c++) mk[12 * i + c] = models[a].R0[i][c];
+            for (int c = 0; c < 3; c++) mk[12 * i + 9 + c] = models[a].p[i][c];
+            sc[2 * i] = std::sin(q[7 * a + i]); sc[2 * i + 1] = std::cos(q[7 * a + i]);
+        }
+        cert_frames(mk, sc, fr);
+        for (int k = 0; k < n_spheres[a]; k++, s++) {
+            double c[3];
+            int v;
+            cert_centre(fr + 12 * spheres[s].joint, spheres[s].c, c);
+            const double d = fld_sd(*desc, d2, c[0], c[1], c[2], &v) - spheres[s].r;
+            if (d < best) { best = d; bs = s; bv = v; }      // (ascending spheres: ties stay with the lowest)
+        }
+    }
+    *d_min = best;
+    if (sphere) *sphere = bs;
+    if (voxel) *voxel = bv;
     return MPCMP_OK;
 }

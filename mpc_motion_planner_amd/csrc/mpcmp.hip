@@ -24,6 +24,7 @@
 #include "clearance.hpp"
 #include "moving.hpp"
 #include "moving_cert.hpp"
+#include "field.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
 #include "retimed_check.hpp"
@@ -1304,6 +1305,179 @@ extern "C" int mpcmp_clearance_certified_timed_batch(mpcmp_ctx *ctx, int B, cons
     if (int rc = sg.upload()) return rc;
     if (int rc = mpcmp_clearance_certified_timed_batch_device(ctx, B, dx, dT, dts, dw, dh, margin, self_gap, n_start, n_rest, max_depth, dout, dcert,
                                                               ctx->stream)) return rc;
+    return sg.finish();
+}
+
+// ---- voxel worlds (include/mpcmp_field.h; the kernels are in field.hip, the rule in field_rule.hpp) ----
+// the checks the four setters share; `given`: the occupancy or the points are there (or none are needed).  desc == NULL (clear) passes
+static int field_set_check(mpcmp_ctx *ctx, const char *who, const mpcmp_field_desc *desc, bool given) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    if (!desc) return MPCMP_OK;
+    if (!fld_desc_ok(*desc) || !given) {
+        ctx->err = std::string(who) + ": 1 <= n[d] <= 1024 with at most 2^24 voxels, a finite origin, a finite h > 0 and the data required";
+        return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+// the three arrays of a grid of `desc` (the only allocation of this family): grown when the grid grows; the launches that read the old ones are waited for
+static int field_reserve(mpcmp_ctx *ctx, const mpcmp_field_desc &desc) {
+    const size_t want = (size_t)fld_voxels(desc);
+    if (want <= ctx->fld_cap) return MPCMP_OK;
+    void *q[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes[3] = {want, want * sizeof(unsigned), want * sizeof(unsigned)};
+    for (int i = 0; i < 3; i++)
+        if (hipMalloc(&q[i], bytes[i]) != hipSuccess) {
+            for (int k = 0; k < i; k++) (void)hipFree(q[k]);
+            ctx->err = "mpcmp_set_field: device allocation of " + std::to_string(want) + " voxels failed"; return MPCMP_ERUNTIME;
+        }
+    if (ctx->d_fld_occ) {
+        HIPCHK(ctx, hipDeviceSynchronize());
+        void *old[3] = {ctx->d_fld_occ, ctx->d_fld_d2, ctx->d_fld_tmp};
+        for (void *o : old) { ctx->allocs.erase(std::find(ctx->allocs.begin(), ctx->allocs.end(), o)); (void)hipFree(o); }
+    }
+    for (void *p : q) ctx->allocs.push_back(p);
+    ctx->d_fld_occ = (unsigned char *)q[0]; ctx->d_fld_d2 = (unsigned *)q[1]; ctx->d_fld_tmp = (unsigned *)q[2];
+    ctx->fld_cap = want;
+    ctx->fld_set = false;              // (the old field went with its arrays; the caller sets the new one)
+    return MPCMP_OK;
+}
+static FldArrays field_arrays(const mpcmp_ctx *ctx, const mpcmp_field_desc &desc) {
+    FldArrays f;
+    f.desc = desc; f.d_occ = ctx->d_fld_occ; f.d_d2 = ctx->d_fld_d2; f.d_tmp = ctx->d_fld_tmp;
+    return f;
+}
+
+extern "C" int mpcmp_set_field(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, const unsigned char *occ) {
+    if (int rc = field_set_check(ctx, "mpcmp_set_field", desc, occ != nullptr)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());          // (checks may be in flight on any stream of the caller: they read this field)
+    if (!desc) { ctx->fld_set = false; return MPCMP_OK; }
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    HIPCHK(ctx, hipMemcpy(f.d_occ, occ, (size_t)fld_voxels(*desc), hipMemcpyHostToDevice));
+    HIPCHK(ctx, field_build_launch(f, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_field_device(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, const unsigned char *d_occ, void *hip_stream) {
+    if (int rc = field_set_check(ctx, "mpcmp_set_field_device", desc, d_occ != nullptr)) return rc;
+    if (!desc) { ctx->fld_set = false; return MPCMP_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+            HIPCHK(ctx, hipMemcpyAsync(f.d_occ, d_occ, (size_t)fld_voxels(*desc), hipMemcpyDeviceToDevice, st));
+            HIPCHK(ctx, field_build_launch(f, st));
+            return MPCMP_OK;
+        })) return rc;
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_field_points(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int n_points, const double *points) {
+    if (int rc = field_set_check(ctx, "mpcmp_set_field_points", desc, n_points >= 0 && (n_points == 0 || points))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (!desc) { ctx->fld_set = false; return MPCMP_OK; }
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    Stage sg(ctx);
+    double *dp = nullptr;
+    if (n_points > 0) sg.in(&dp, points, (size_t)3 * n_points);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, field_mark_launch(f, n_points, dp, ctx->stream));
+    HIPCHK(ctx, field_build_launch(f, ctx->stream));
+    if (int rc = sg.finish()) return rc;
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_field_points_device(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int n_points, const double *d_points, void *hip_stream) {
+    if (int rc = field_set_check(ctx, "mpcmp_set_field_points_device", desc, n_points >= 0 && (n_points == 0 || d_points))) return rc;
+    if (!desc) { ctx->fld_set = false; return MPCMP_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+            HIPCHK(ctx, field_mark_launch(f, n_points, d_points, st));
+            HIPCHK(ctx, field_build_launch(f, st));
+            return MPCMP_OK;
+        })) return rc;
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_get_field(mpcmp_ctx *ctx, mpcmp_field_desc *desc_out, unsigned *d2_out) {
+    if (!ctx) { g_err = "mpcmp_get_field: no context"; return MPCMP_EINVAL; }
+    if (!ctx->fld_set || !desc_out) { ctx->err = "mpcmp_get_field: no field is set (mpcmp_set_field), or desc_out is NULL"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());          // (a device-side setter may have built it on any stream)
+    *desc_out = ctx->fld_desc;
+    if (d2_out) HIPCHK(ctx, hipMemcpy(d2_out, ctx->d_fld_d2, sizeof(unsigned) * (size_t)fld_voxels(ctx->fld_desc), hipMemcpyDeviceToHost));
+    return MPCMP_OK;
+}
+
+static int clearance_field_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_field_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_pts < 1 || n_pts > CLR_MAX_PTS || !sx || !sT || !out || !std::isfinite(margin)) {
+        ctx->err = "mpcmp_clearance_field_batch: B >= 1, 1 <= n_pts <= 4096, a finite margin and all pointers required"; return MPCMP_EINVAL;
+    }
+    if (!ctx->fld_set) { ctx->err = "mpcmp_clearance_field_batch: no field is set: see mpcmp_set_field"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_field_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_pts, double margin,
+                                                  mpcmp_clearance *d_out, void *hip_stream) {
+    if (int rc = clearance_field_check(ctx, B, d_sx, d_sT, n_pts, margin, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ClrTables t;
+    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
+    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
+    t.d_obs = nullptr; t.n_obs = 0; t.obs_stride = 0;
+    if (!ctx->fld_ready) { HIPCHK(ctx, field_prepare()); ctx->fld_ready = true; }
+    HIPCHK(ctx, clearance_field_launch(t, field_arrays(ctx, ctx->fld_desc), B, d_sx, d_sT, n_pts, margin, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_field_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, mpcmp_clearance *out) {
+    if (int rc = clearance_field_check(ctx, B, sx, sT, n_pts, margin, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT;
+    mpcmp_clearance *dout;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_clearance_field_batch_device(ctx, B, dx, dT, n_pts, margin, dout, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+extern "C" int mpcmp_clearance_merge_batch_device(mpcmp_ctx *ctx, int B, const mpcmp_clearance *d_a, const mpcmp_clearance *d_b, mpcmp_clearance *d_out,
+                                                  int *d_source, void *hip_stream) {
+    if (!ctx) { g_err = "mpcmp_clearance_merge_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !d_a || !d_b || !d_out) { ctx->err = "mpcmp_clearance_merge_batch: B >= 1 and a, b and out required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, clearance_merge_launch(B, d_a, d_b, d_out, d_source, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_merge_batch(mpcmp_ctx *ctx, int B, const mpcmp_clearance *a, const mpcmp_clearance *b, mpcmp_clearance *out,
+                                           int *source) {
+    if (!ctx) { g_err = "mpcmp_clearance_merge_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !a || !b || !out) { ctx->err = "mpcmp_clearance_merge_batch: B >= 1 and a, b and out required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    mpcmp_clearance *da, *db, *dout;
+    int *dsrc = nullptr;
+    sg.in(&da, a, B); sg.in(&db, b, B); sg.out(&dout, out, B);
+    if (source) sg.out(&dsrc, source, B);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, clearance_merge_launch(B, da, db, dout, dsrc, ctx->stream));
     return sg.finish();
 }
 

@@ -254,6 +254,68 @@ class Solver:
         check(lib().mpcmp_clearance_certified_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, float(margin), int(self_gap), int(n_start),
                                                            int(max_depth), out or None, cert or None, stream or None), self._ctx)
 
+    # -- voxel worlds: an occupancy grid or a point cloud as the world, read through a distance field built on the GPU (include/mpcmp_field.h)
+    def set_field(self, desc, occ=None):
+        """mpcmp_set_field: desc a capi.FIELD_DESC_DTYPE record (capi.field_desc), occ [n2][n1][n0] (nonzero: solid); desc None clears"""
+        if desc is None:
+            check(lib().mpcmp_set_field(self._ctx, None, None), self._ctx)
+            return
+        desc = capi._field_desc_arg(desc)
+        occ = capi._field_array(desc, np.asarray(occ) != 0, np.uint8, "occ")
+        check(lib().mpcmp_set_field(self._ctx, desc.ctypes.data, host(occ)), self._ctx)
+
+    def set_field_device(self, desc, occ, stream=0):
+        """the occupancy (one byte per voxel) at the device pointer occ, ordered on `stream`; desc None clears"""
+        desc = None if desc is None else capi._field_desc_arg(desc)
+        check(lib().mpcmp_set_field_device(self._ctx, None if desc is None else desc.ctypes.data, occ or None, stream or None), self._ctx)
+
+    def set_field_points(self, desc, points):
+        """mpcmp_set_field_points: the voxels that contain the points [n][3] (world frame) are solid; non-finite points and points outside the
+        grid are skipped"""
+        desc = capi._field_desc_arg(desc); pts = f64(points).reshape(-1, 3)
+        check(lib().mpcmp_set_field_points(self._ctx, desc.ctypes.data, pts.shape[0], host(pts)), self._ctx)
+
+    def set_field_points_device(self, desc, n_points, points, stream=0):
+        desc = capi._field_desc_arg(desc)
+        check(lib().mpcmp_set_field_points_device(self._ctx, desc.ctypes.data, int(n_points), points or None, stream or None), self._ctx)
+
+    def field(self, with_d2=True):
+        """mpcmp_get_field: (the FIELD_DESC_DTYPE record in force, d2 [n2][n1][n0] uint32 or None)"""
+        desc = np.zeros((), dtype=capi.FIELD_DESC_DTYPE)
+        check(lib().mpcmp_get_field(self._ctx, desc.ctypes.data, None), self._ctx)
+        if not with_d2:
+            return desc, None
+        n = [int(v) for v in desc["n"]]
+        d2 = np.zeros((n[2], n[1], n[0]), dtype=np.uint32)
+        check(lib().mpcmp_get_field(self._ctx, desc.ctypes.data, host(d2)), self._ctx)
+        return desc, d2
+
+    def clearance_field(self, sx, sT, n_pts=200, margin=0.0):
+        """mpcmp_clearance_field_batch: capi.CLEARANCE_DTYPE [B] of the trajectories sx [B][N][nx], sT [B] against the field; `other` is a voxel"""
+        sx, sT = f64(sx), f64(sT).reshape(-1); B = sT.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
+        out = np.zeros(B, dtype=capi.CLEARANCE_DTYPE)
+        check(lib().mpcmp_clearance_field_batch(self._ctx, B, host(sx), host(sT), int(n_pts), float(margin), host(out)), self._ctx)
+        return out
+
+    def clearance_field_device(self, B, sol_x, sol_T, n_pts, margin, out, stream=0):
+        check(lib().mpcmp_clearance_field_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, int(n_pts), float(margin), out or None,
+                                                       stream or None), self._ctx)
+
+    def clearance_merge(self, a, b):
+        """mpcmp_clearance_merge_batch: (one CLEARANCE_DTYPE record per problem from the records a [B] and b [B], source [B] = 0 / 1: where d_min
+        came from)"""
+        a = capi._records(a, capi.CLEARANCE_DTYPE, "clearance").reshape(-1); b = capi._records(b, capi.CLEARANCE_DTYPE, "clearance").reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError("a and b must hold one record per problem each, got %s and %s" % (a.shape, b.shape))
+        out, src = np.zeros(a.shape[0], dtype=capi.CLEARANCE_DTYPE), np.zeros(a.shape[0], dtype=np.int32)
+        check(lib().mpcmp_clearance_merge_batch(self._ctx, a.shape[0], host(a), host(b), host(out), host(src)), self._ctx)
+        return out, src
+
+    def clearance_merge_device(self, B, a, b, out, source=0, stream=0):
+        check(lib().mpcmp_clearance_merge_batch_device(self._ctx, int(B), a or None, b or None, out or None, source or None, stream or None), self._ctx)
+
     # -- clearance in a moving world: tracked obstacles, timed checks, start delays, a plan as another robot's world (include/mpcmp_moving.h)
     def set_obstacle_tracks(self, track_of, offsets, t0, dt):
         """the track table of the obstacle sets in force: track_of [n_obs] or [n_sets][n_obs] (-1: the obstacle stands still), offsets
@@ -998,10 +1060,12 @@ class BatchMotionPlanner:
         the skeleton of capi.link_spheres(model, sphere_radius, sphere_spacing)"""
         if obstacles is None:
             self._solver.clear_obstacles()
+            self._has_obstacles = False
             return
         self._spheres = capi.link_spheres(self.model, sphere_radius, sphere_spacing) if spheres is None else spheres
         self._solver.set_robot_spheres(self._spheres)
         self._solver.set_obstacles(obstacles)
+        self._has_obstacles = True
 
     def check_clearance(self, n_pts=200, margin=0.0, self_gap=0):
         """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions; of routes: the legs' records joined per route"""
@@ -1011,6 +1075,45 @@ class BatchMotionPlanner:
             clr = self._solver.clearance(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin, self_gap)
             return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
         return self._solver.clearance(self._sol[0], self._sol[2], n_pts, margin, self_gap)
+
+    # -- voxel worlds (include/mpcmp_field.h): what a depth camera saw as the world, beside or instead of the primitives of set_obstacles
+    def _field_spheres(self, sphere_radius, sphere_spacing, spheres):
+        if spheres is not None or getattr(self, "_spheres", None) is None:
+            self._spheres = capi.link_spheres(self.model, sphere_radius, sphere_spacing) if spheres is None else spheres
+            self._solver.set_robot_spheres(self._spheres)
+
+    def set_voxel_world(self, origin, h, occ, sphere_radius=0.06, sphere_spacing=0.08, spheres=None):
+        """an occupancy grid occ [n2][n1][n0] (nonzero: solid) of cubes of edge h whose lowest corner is `origin`; occ None removes the voxel world.
+        The robot is the sphere table already in force, `spheres`, or the skeleton of capi.link_spheres(model, sphere_radius, sphere_spacing)"""
+        if occ is None:
+            self._solver.set_field(None)
+            return
+        occ = np.asarray(occ)
+        if occ.ndim != 3:
+            raise ValueError("occ must be [n2][n1][n0], got %s" % (occ.shape,))
+        self._field_spheres(sphere_radius, sphere_spacing, spheres)
+        self._solver.set_field(capi.field_desc(origin, h, occ.shape[::-1]), occ)
+
+    def set_point_cloud(self, origin, h, n, points, sphere_radius=0.06, sphere_spacing=0.08, spheres=None):
+        """a point cloud points [n_points][3] (world frame) as the world: the voxels of the grid (origin, h, n = (n0, n1, n2)) that contain a
+        point are solid; points outside the grid and non-finite points are skipped"""
+        self._field_spheres(sphere_radius, sphere_spacing, spheres)
+        self._solver.set_field_points(capi.field_desc(origin, h, n), points)
+
+    def check_clearance_field(self, n_pts=200, margin=0.0, merge=True, self_gap=0):
+        """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions against the voxel world; of routes: the legs'
+        records joined per route.  merge: when obstacles are set (set_obstacles) or self_gap > 0, the records are merged with those of
+        check_clearance(n_pts, margin, self_gap), and (records, source [B]) is returned: source 1 where d_min is the field's and `other` a voxel"""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            clr = self._solver.clearance_field(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), n_pts, margin)
+            fld = self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
+        else:
+            fld = self._solver.clearance_field(self._sol[0], self._sol[2], n_pts, margin)
+        if not merge or not (getattr(self, "_has_obstacles", False) or self_gap > 0):
+            return fld
+        return self._solver.clearance_merge(self.check_clearance(n_pts, margin, self_gap), fld)
 
     # -- clearance in a moving world (include/mpcmp_moving.h): direct moves; a route's leg slots are checked with Solver.clearance_timed, each with
     # t_start = the route's start plus the running times of the legs before it
