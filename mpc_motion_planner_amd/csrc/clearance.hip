@@ -4,15 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
-#include "clearance.hpp"
-#include "plan_interp.hpp"
+#include "clearance_phases.hpp"
 
 namespace mpcmp {
 
 // One workgroup per trajectory.  Staged in LDS once: the joint placements of the arms, the node positions of the trajectory, the sphere tables and
 // the problem's obstacles (in the form of clr_obs_prepare).  Then the n_pts + 1 samples in chunks of `chunk`, four phases per chunk:
 //   A1  one thread per (sample, joint): the node interpolant of the joint position (plan_interp.hpp) and its sine / cosine;
-//   A2  one thread per (sample, arm): the forward-kinematics chain, once per sample: world rotation and origin of the 7 joint frames;
+//   A2  one thread per (sample, arm): the forward-kinematics chain, once per sample: world rotation and origin of the 7 joint frames
+//       (A1 and A2 are clr_frames of clearance_phases.hpp, which the kernels of moving.hip and field.hip run as well);
 //   B   one thread per (sample, sphere): world centre, then every obstacle (a uniform loop: all lanes read one obstacle, broadcast from LDS);
 //   C   one thread per (sample, sphere s): every partner sphere t > s that clr_pair admits.
 // Every thread keeps its best (clearance, packed index) pair in registers over all chunks; one workgroup reduction at the end orders them by
@@ -21,107 +21,38 @@ __global__ __launch_bounds__(CLR_NT) void k_clearance(const mpcmp_model *__restr
                                                       const ClrSphere *__restrict__ sph, int n0, int n1,
                                                       const mpcmp_obstacle *__restrict__ obs, int n_obs, int obs_stride,
                                                       const double *__restrict__ sx, const double *__restrict__ sT, double margin, int self_gap,
-                                                      int chunk, mpcmp_clearance *__restrict__ out) {
+                                                      int chunk_, mpcmp_clearance *__restrict__ out) {
+    const ClrShape h = {narm, nseg, n0, n1, n_obs, obs_stride, chunk_};      // (scalar arguments: as one struct the kernel takes two registers more)
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double red_d[CLR_NT / 64];
-    __shared__ unsigned red_k[CLR_NT / 64];
     __shared__ int nan_flag;
-    const int b = blockIdx.x, tid = threadIdx.x, N = 3 * nseg + 1, nq = 7 * narm, nsph = n0 + n1;
-    double *mk_ = lds;                                   // [narm][7][12] = R0 (9), p (3)
-    double *nodes = mk_ + 84 * narm;                     // [N][nq]
-    double *sk = nodes + (size_t)nq * N;                 // [nsph][4] = c, r
-    double *ok = sk + 4 * nsph;                          // [n_obs][8]
-    double *sc = ok + 8 * n_obs;                         // [chunk][nq][2]
-    double *fr = sc + (size_t)chunk * nq * 2;            // [chunk][nq][12] = Rw (9), pw (3)
-    double *cen = fr + (size_t)chunk * nq * 12;          // [chunk][nsph][3]
-    int *sj = reinterpret_cast<int *>(cen + (size_t)chunk * nsph * 3);   // [nsph] arm * 7 + joint
-    int *sa = sj + nsph;                                 // [nsph] arm
-    int *ot = sa + nsph;                                 // [n_obs] type
-    int *hit = ot + n_obs;                               // [chunk]
-
-    for (int e = tid; e < 84 * narm; e += CLR_NT) {
-        const int a = e / 84, i = (e % 84) / 12, c = e % 12;
-        mk_[e] = c < 9 ? mdl[a].R0[i][c] : mdl[a].p[i][c - 9];
-    }
-    const double *X = sx + (size_t)b * N * 2 * nq;
-    for (int e = tid; e < nq * N; e += CLR_NT) nodes[e] = X[(size_t)(e / nq) * 2 * nq + e % nq];
-    for (int s = tid; s < nsph; s += CLR_NT) {
-        const ClrSphere S = sph[s];
-        sk[4 * s] = S.c[0]; sk[4 * s + 1] = S.c[1]; sk[4 * s + 2] = S.c[2]; sk[4 * s + 3] = S.r;
-        sj[s] = 7 * S.arm + S.joint; sa[s] = S.arm;
-    }
-    const mpcmp_obstacle *O = obs + (size_t)b * obs_stride;
-    for (int o = tid; o < n_obs; o += CLR_NT) {
-        clr_obs_prepare(O[o], ok + 8 * o);
-        ot[o] = O[o].type;
-    }
-    for (int e = tid; e < chunk; e += CLR_NT) hit[e] = 0;
+    const int b = blockIdx.x, tid = threadIdx.x, nsph = h.n0 + h.n1, chunk = h.chunk;
+    LdsCursor<true> cur = {reinterpret_cast<char *>(lds), 0};
+    const ClrLds L = clr_carve(cur, h, CLR_LDS_SAMPLED, 0);
+    clr_stage(L, h, mdl, sph, obs, sx, b);               // (a NaN is flagged by the interpolated sample, below, not by the node)
     if (tid == 0) nan_flag = 0;
     __syncthreads();
 
     double best_d = INFINITY;
     unsigned best_k = CLR_NO_PAIR;
     int n_hit = 0, first = -1;                           // (thread 0 only)
-    const bool pairs = narm > 1 || self_gap > 0;
+    const bool pairs = h.narm > 1 || self_gap > 0;
     for (int ip0 = 0; ip0 <= n_pts; ip0 += chunk) {
         const int ns = (n_pts + 1 - ip0 < chunk) ? n_pts + 1 - ip0 : chunk;      // samples of this chunk
-        // A1
-        for (int it = tid; it < ns * nq; it += CLR_NT) {
-            const int sl = it / nq, j = it % nq;
-            double Lg[4];
-            const int s = mpcmp_plan::lagrange_segment(nseg, (double)(ip0 + sl) / n_pts, Lg);
-            const double q = mpcmp_plan::interp_channel(nodes + j, nq, s, Lg);
-            if (!isfinite(q)) nan_flag = 1;
-            double sn, cs;
-            sincos(q, &sn, &cs);
-            sc[2 * it] = sn; sc[2 * it + 1] = cs;
-        }
-        __syncthreads();
-        // A2: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i)
-        for (int it = tid; it < ns * narm; it += CLR_NT) {
-            const int sl = it / narm, a = it % narm;
-            const double *M = mk_ + 84 * a, *SC = sc + (size_t)(sl * nq + 7 * a) * 2;
-            double *F = fr + (size_t)(sl * nq + 7 * a) * 12;
-            double Rw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pw[3] = {0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 7; i++) {
-                const double *A = M + 12 * i;
-                const double s = SC[2 * i], c = SC[2 * i + 1];
-                double R[9], Rn[9];
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    R[3 * r] = A[3 * r] * c + A[3 * r + 1] * s;
-                    R[3 * r + 1] = -A[3 * r] * s + A[3 * r + 1] * c;
-                    R[3 * r + 2] = A[3 * r + 2];
-                }
-#pragma unroll
-                for (int r = 0; r < 3; r++) pw[r] += Rw[3 * r] * A[9] + Rw[3 * r + 1] * A[10] + Rw[3 * r + 2] * A[11];
-#pragma unroll
-                for (int r = 0; r < 3; r++)
-#pragma unroll
-                    for (int c2 = 0; c2 < 3; c2++) Rn[3 * r + c2] = Rw[3 * r] * R[c2] + Rw[3 * r + 1] * R[3 + c2] + Rw[3 * r + 2] * R[6 + c2];
-#pragma unroll
-                for (int k = 0; k < 9; k++) { Rw[k] = Rn[k]; F[12 * i + k] = Rn[k]; }
-#pragma unroll
-                for (int r = 0; r < 3; r++) F[12 * i + 9 + r] = pw[r];
-            }
-        }
-        __syncthreads();
+        // A1, A2
+        clr_frames(L, h, ns, [&](int sl) { return (double)(ip0 + sl) / n_pts; }, &nan_flag);
         // B
         for (int it = tid; it < ns * nsph; it += CLR_NT) {
             const int sl = it / nsph, s = it % nsph;
-            const double *F = fr + (size_t)(sl * nq + sj[s]) * 12, *S = sk + 4 * s;
-            const double cx = F[9] + F[0] * S[0] + F[1] * S[1] + F[2] * S[2];
-            const double cy = F[10] + F[3] * S[0] + F[4] * S[1] + F[5] * S[2];
-            const double cz = F[11] + F[6] * S[0] + F[7] * S[1] + F[8] * S[2];
-            cen[3 * it] = cx; cen[3 * it + 1] = cy; cen[3 * it + 2] = cz;
+            double c[3];
+            clr_centre(L, h, sl, s, c);
+            L.cen[3 * it] = c[0]; L.cen[3 * it + 1] = c[1]; L.cen[3 * it + 2] = c[2];
             double dm = INFINITY;
             int om = 0;
-            for (int o = 0; o < n_obs; o++) {
-                const double d = clr_sd(ot[o], ok + 8 * o, cx, cy, cz) - S[3];
+            for (int o = 0; o < h.n_obs; o++) {
+                const double d = clr_sd(L.ot[o], L.ok + 8 * o, c[0], c[1], c[2]) - L.sk[4 * s + 3];
                 if (d < dm) { dm = d; om = o; }
             }
-            if (dm < margin) hit[sl] = 1;
+            if (dm < margin) L.hit[sl] = 1;
             const unsigned k = clr_pack(ip0 + sl, s, 0, om);
             if (dm < INFINITY && clr_better(dm, k, best_d, best_k)) { best_d = dm; best_k = k; }
         }
@@ -130,61 +61,18 @@ __global__ __launch_bounds__(CLR_NT) void k_clearance(const mpcmp_model *__restr
         if (pairs) {
             for (int it = tid; it < ns * nsph; it += CLR_NT) {
                 const int sl = it / nsph, s = it % nsph;
-                const double *C = cen + (size_t)sl * nsph * 3;
-                const double cx = C[3 * s], cy = C[3 * s + 1], cz = C[3 * s + 2], rs = sk[4 * s + 3];
-                const int as = sa[s], js = sj[s];
-                double dm = INFINITY;
-                int tm = 0;
-                for (int t = s + 1; t < nsph; t++) {
-                    if (!clr_pair(as, js, sa[t], sj[t], self_gap)) continue;      // (sj holds arm * 7 + joint: differences within one arm are joint differences)
-                    const double ex = cx - C[3 * t], ey = cy - C[3 * t + 1], ez = cz - C[3 * t + 2];
-                    const double d = sqrt(ex * ex + ey * ey + ez * ez) - rs - sk[4 * t + 3];
-                    if (d < dm) { dm = d; tm = t; }
-                }
-                if (dm < margin) hit[sl] = 1;
+                int tm;
+                const double dm = clr_pairs(L, nsph, sl, s, self_gap, &tm);
+                if (dm < margin) L.hit[sl] = 1;
                 const unsigned k = clr_pack(ip0 + sl, s, 1, tm);
                 if (dm < INFINITY && clr_better(dm, k, best_d, best_k)) { best_d = dm; best_k = k; }
             }
             __syncthreads();
         }
-        if (tid == 0)
-            for (int sl = 0; sl < ns; sl++) {
-                if (hit[sl]) { if (first < 0) first = ip0 + sl; n_hit++; }
-                hit[sl] = 0;
-            }
+        if (tid == 0) clr_count_hits(L, ns, ip0, &first, &n_hit);
     }
-    // workgroup reduction of (clearance, packed index) by clr_better
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_down(best_d, off);
-        const unsigned okk = __shfl_down(best_k, off);
-        if (clr_better(od, okk, best_d, best_k)) { best_d = od; best_k = okk; }
-    }
-    if ((tid & 63) == 0) { red_d[tid >> 6] = best_d; red_k[tid >> 6] = best_k; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < CLR_NT / 64; w++)
-            if (clr_better(red_d[w], red_k[w], best_d, best_k)) { best_d = red_d[w]; best_k = red_k[w]; }
-        const double T = sT[b];
-        mpcmp_clearance r;
-        if (nan_flag) {
-            r.d_min = __longlong_as_double(0x7FF8000000000000ll); r.t_min = -1.0; r.t_first = -1.0;
-            r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
-        } else {
-            r.d_min = best_d;
-            if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
-            else {
-                const int ip = (int)(best_k >> 17), idx = (int)(best_k & 0xFFu);
-                r.t_min = ((double)ip / n_pts) * T;
-                r.sphere = (int)((best_k >> 9) & 0x7Fu);
-                r.other = (best_k & 0x100u) ? -1 - idx : idx;
-            }
-            r.t_first = first >= 0 ? ((double)first / n_pts) * T : -1.0;
-            r.n_hit = n_hit;
-            r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
-        }
-        out[b] = r;
-    }
+    clr_reduce(best_d, best_k, nullptr);
+    if (tid == 0) out[b] = nan_flag ? clr_nan_record() : clr_record(best_d, best_k, first, n_hit, n_pts, sT[b]);
 }
 
 // ---- choice of the fastest admissible member of each group (mpcmp_select_clear_batch, mpcmp_select_checked_batch) ----
@@ -216,22 +104,16 @@ __global__ __launch_bounds__(256) void k_select_finish(int n_groups, int *chosen
 }
 
 hipError_t clearance_prepare() {
-    // the largest tables need more than the 64 KB a kernel may use without asking: the ceiling over every sphere count (the chunk shrinks as the
-    // sphere tables grow), two arms, 25 nodes, 256 obstacles: 96 KB
-    size_t mx = 0;
-    for (int s = 0; s <= 2 * CLR_MAX_SPH; s++) {
-        const size_t b = clr_lds_bytes(2, 25, s, CLR_MAX_OBS, clr_chunk(s));
-        if (b > mx) mx = b;
-    }
+    // the largest tables need more than the 64 KB a kernel may use without asking: two arms, 25 nodes, 256 obstacles: 96 KB
+    const size_t mx = lds_ceiling([](int s) { return clr_lds_bytes(ClrShape{2, 8, s, 0, CLR_MAX_OBS, 0, clr_chunk(s)}, CLR_LDS_SAMPLED, 0); });
     return hipFuncSetAttribute((const void *)k_clearance, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx);
 }
 
 hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
                             mpcmp_clearance *d_out, hipStream_t st) {
-    const int nsph = t.n_sph[0] + t.n_sph[1], chunk = clr_chunk(nsph);
-    const size_t lds = clr_lds_bytes(t.narm, 3 * t.nseg + 1, nsph, t.n_obs, chunk);
-    hipLaunchKernelGGL(k_clearance, dim3(B), dim3(CLR_NT), lds, st, t.d_model, t.narm, t.nseg, n_pts, t.d_sph, t.n_sph[0], t.n_sph[1], t.d_obs, t.n_obs,
-                       t.obs_stride, d_sx, d_sT, margin, self_gap, chunk, d_out);
+    const ClrShape h = clr_shape(t, true);
+    hipLaunchKernelGGL(k_clearance, dim3(B), dim3(CLR_NT), clr_lds_bytes(h, CLR_LDS_SAMPLED, 0), st, t.d_model, h.narm, h.nseg, n_pts, t.d_sph, h.n0, h.n1, t.d_obs,
+                       h.n_obs, h.obs_stride, d_sx, d_sT, margin, self_gap, h.chunk, d_out);
     return hipGetLastError();
 }
 
@@ -278,7 +160,8 @@ extern "C" int mpcmp_link_spheres(const mpcmp_model *model, double radius, doubl
     return MPCMP_OK;
 }
 
-// world placement of every joint frame: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i)
+// World placement of every joint frame: p_w[i] = p_w[i-1] + R_w[i-1] p[i], R_w[i] = R_w[i-1] R0[i] Rz(q_i).  Not cert_frames: this statement adds the
+// three products to p_w one after the other, cert_frames (and every kernel) adds their sum, and the last bits of mpcmp_clearance_config are public
 static void fk_frames(const mpcmp_model *m, const double *q, double Rw[7][9], double pw[7][3]) {
     double Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pp[3] = {0, 0, 0};
     for (int i = 0; i < 7; i++) {
@@ -330,9 +213,10 @@ extern "C" int mpcmp_clearance_config(const mpcmp_model *models, int narm, const
             if (clr_better(d, key, best, bk)) { best = d; bk = key; }
         }
     }
+    int sp = -1, ot = 0;
+    if (bk != CLR_NO_PAIR) clr_unpack(bk, &sp, &ot);
     *d_min = best;
-    const int idx = (int)(bk & 0xFFu);
-    if (sphere) *sphere = bk == CLR_NO_PAIR ? -1 : (int)((bk >> 9) & 0x7Fu);
-    if (other) *other = bk == CLR_NO_PAIR ? 0 : ((bk & 0x100u) ? -1 - idx : idx);
+    if (sphere) *sphere = sp;
+    if (other) *other = ot;
     return MPCMP_OK;
 }

@@ -1,6 +1,6 @@
 // clearance.hpp — what the clearance checker shares between the host entry points (mpcmp.hip), its kernels (clearance.hip) and the host
 // restatement mpcmp_clearance_config: the obstacle distance formulas, the pair rules and the ordering of ties (clearance_rule.hpp, plain C++, read by
-// the host-only unit as well), the LDS budget and the launchers.
+// the host-only unit as well), the LDS layouts (clearance_lds.hpp) and the launchers.
 // The kernels themselves live in clearance.hip, a translation unit of their own: nothing here is a kernel, so including this header does not
 // change what any other translation unit compiles to.
 #pragma once
@@ -9,6 +9,7 @@
 #include <cstddef>
 #include "../../include/mpcmp.h"
 #include "clearance_rule.hpp"
+#include "clearance_lds.hpp"
 
 namespace mpcmp {
 
@@ -20,19 +21,6 @@ struct ClrSphere {
     double c[3], r;
     int joint, arm;
 };
-
-// samples per chunk: as many as keep chunk x spheres <= 1024 world centres in LDS, at most 32
-inline int clr_chunk(int nsph) {
-    const int c = nsph > 0 ? 1024 / nsph : 32;
-    return c > 32 ? 32 : (c < 1 ? 1 : c);
-}
-// dynamic LDS of k_clearance in bytes: it depends on the tables and the chunk, not on n_pts
-inline size_t clr_lds_bytes(int narm, int N, int nsph, int n_obs, int chunk) {
-    const size_t dbl = (size_t)84 * narm + (size_t)7 * narm * N + (size_t)4 * nsph + (size_t)8 * n_obs + (size_t)chunk * narm * 14 +
-                       (size_t)chunk * narm * 84 + (size_t)chunk * nsph * 3;
-    const size_t ints = (size_t)2 * nsph + (size_t)n_obs + (size_t)chunk;
-    return dbl * sizeof(double) + (ints + 1) / 2 * 2 * sizeof(int);
-}
 
 struct ClrTables {
     const mpcmp_model *d_model;      // [narm]
@@ -46,10 +34,16 @@ struct ClrTables {
 hipError_t clearance_prepare();     // the kernel's dynamic-LDS ceiling; called by a context's first check
 hipError_t clearance_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
                             mpcmp_clearance *d_out, hipStream_t st);
-// the certified check (include/mpcmp_clearance_cert.h; the kernel is in clearance_cert.hip, the rule in clearance_cert.hpp); d_cert may be NULL
-hipError_t clearance_cert_prepare();
-hipError_t clearance_cert_launch(const ClrTables &t, int B, const double *d_sx, const double *d_sT, double margin, int self_gap, int n_start,
-                                 int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, hipStream_t st);
+// The certified check, without a timeline (include/mpcmp_clearance_cert.h) and with one (include/mpcmp_moving_cert.h): the kernel is in
+// clearance_cert.hip, the rule in clearance_cert.hpp and moving_cert_rule.hpp.  B finished plans on their own clock with their start times, waits
+// and holds (each [B] or NULL: 0); trk (moving.hpp) NULL: the static certificate, which reads d_sx and d_sT only; d_cert may be NULL
+struct MvTracks;
+struct CertPlans {
+    const double *d_sx, *d_sT, *d_t_start, *d_wait, *d_hold;
+};
+hipError_t clearance_cert_prepare();    // the dynamic-LDS ceilings of both instantiations
+hipError_t clearance_cert_launch(const ClrTables &t, const MvTracks *trk, const CertPlans &p, int B, double margin, int self_gap, int n_start,
+                                 int n_rest, int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, hipStream_t st);
 // keys [n_groups] scratch; chosen [n_groups].  d_clr and d_lim may each be NULL (that test is skipped); lim_mask: the bits of mpcmp_limits.status that
 // make a member inadmissible (MPCMP_LIM_NAN always does)
 hipError_t select_launch(int B, const double *d_sT, const mpcmp_info *d_info, const mpcmp_clearance *d_clr, const mpcmp_limits *d_lim, int lim_mask,

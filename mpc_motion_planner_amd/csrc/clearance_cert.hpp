@@ -1,8 +1,9 @@
 // clearance_cert.hpp — the rule of the certified clearance check (include/mpcmp_clearance_cert.h) as host/device functions: the geometry of an
-// interval, the Bezier deviation of a joint, the reach table, the frames of one arm, the decision and the tie keys.  The kernel (clearance_cert.hip)
-// and the host statement mpcmp_clearance_certified_one (model_host.cpp) both run this source.  Plain C++: no HIP header, and nothing here is a kernel.
+// interval, the Bezier deviation of a joint, the reach table, the frames of one arm, the decision, the tie keys, the two records and the kernel's LDS
+// layout.  The kernel (clearance_cert.hip, with and without a timeline) and the host statements of model_host.cpp both run this source.  Plain C++: no HIP header, and nothing here is a kernel.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include "clearance_rule.hpp"
 #include "plan_interp.hpp"
 
@@ -40,7 +41,7 @@ MPCMP_HD unsigned long long cert_key(unsigned tkey, int sphere, int robot, int i
     return ((unsigned long long)tkey << 16) | ((unsigned long long)sphere << 9) | ((unsigned long long)robot << 8) | (unsigned long long)idx;
 }
 constexpr unsigned long long CERT_NO_PAIR = ~0ull;
-MPCMP_HD bool cert_better(double d, unsigned long long k, double bd, unsigned long long bk) { return d < bd || (d == bd && k < bk); }
+MPCMP_HD bool cert_better(double d, unsigned long long k, double bd, unsigned long long bk) { return clr_better(d, k, bd, bk); }
 
 // dev of one joint column on an interval, and q(t_m): C points at the column in node 0, `stride` doubles lie between two nodes
 MPCMP_HD double cert_deviation(const double *C, int stride, int nseg, const CertInterval &v, double *q_m) {
@@ -117,6 +118,84 @@ MPCMP_HD int cert_decide(double d_mid, double L, double margin, int l, int max_d
     if (L >= margin) return CERT_CLEAR;
     if (l == max_depth) return CERT_UNDECIDED;
     return CERT_SPLIT_IT;
+}
+
+// What the search keeps: the best (d, key) over every pair met, the best (L, key) and the counts over the leaves, the earliest hit, the last level
+struct CertBest {
+    double d = INFINITY, L = INFINITY;
+    unsigned long long k = CERT_NO_PAIR, Lk = CERT_NO_PAIR;
+    unsigned first = CERT_NO_TIME;
+    int n_hit = 0, n_clear = 0, n_und = 0, n_eval = 0, depth = 0;
+};
+// ... and the two records made of it; time_of turns a midpoint key into a record time (cert_time x T, or mvc_time of moving_cert_rule.hpp)
+template <class TimeOf> MPCMP_HD void cert_records(const CertBest &s, TimeOf time_of, mpcmp_clearance *r, mpcmp_clearance_cert *c) {
+    r->d_min = s.d;
+    if (s.k == CERT_NO_PAIR) { r->t_min = -1.0; r->sphere = -1; r->other = 0; }
+    else {
+        r->t_min = time_of((unsigned)(s.k >> 16));
+        clr_unpack(s.k, &r->sphere, &r->other);
+    }
+    r->t_first = s.first != CERT_NO_TIME ? time_of(s.first) : -1.0;
+    r->n_hit = s.n_hit;
+    r->status = (s.n_hit > 0 ? MPCMP_CLR_HIT : 0) | (s.n_und > 0 ? MPCMP_CLR_UNDECIDED : 0);
+    c->d_lower = s.L; c->t_lower = time_of((unsigned)(s.Lk >> 16));
+    c->n_eval = s.n_eval; c->n_clear = s.n_clear; c->n_undecided = s.n_und; c->depth = s.depth;
+}
+// the certificate that goes with clr_nan_record()
+MPCMP_HD mpcmp_clearance_cert cert_nan_record() {
+    mpcmp_clearance_cert c;
+    c.d_lower = NAN; c.t_lower = -1.0; c.n_eval = 0; c.n_clear = 0; c.n_undecided = 0; c.depth = 0;
+    return c;
+}
+
+// intervals per chunk: as many as keep chunk x spheres <= 512 per-sphere records in LDS, at most 16 (one lane of the first wave decides each)
+inline int cert_chunk(int nsph) {
+    const int c = nsph > 0 ? 512 / nsph : 16;
+    return c > 16 ? 16 : (c < 1 ? 1 : c);
+}
+// The dynamic LDS of k_clearance_cert: the tables, the chunk and the two level lists; with a timeline also the chunk's track table (n_tracks tracks)
+// and the obstacles' tracks, which the static certificate does not pay for.  It does not depend on n_start, n_rest or max_depth
+struct CertShape { int narm, nseg, ns0, ns1, n_obs, obs_stride, chunk, n_start, n_rest, max_depth; };
+struct CertLds {
+    double *mk, *nodes, *sk, *rch, *ok, *sc, *dv, *fr, *cen, *Dl, *pd, *pl, *tk;
+    int *cur, *nxt, *sj, *sa, *ot, *tof, *end;
+};
+// The layout: plain pointer arithmetic on the LDS base, stated once as the text below.  The kernel expands it among its own locals; cert_layout
+// expands it for the launch's byte count and for tests/host/clearance_lds_check.cpp.  It is neither a carve over the cursor of clearance_lds.hpp, as
+// the sampled kernels have it, nor a function the kernel calls: through either the kernel with a timeline compiles to other code and is 0.5 - 0.9 %
+// slower (docs/HISTORY.md D.4).  TL_: with a timeline; L.end: where the last array ends
+#define MPCMP_CERT_LAYOUT(L, lds, narm, nq, N, nsph, n_obs, chunk, TL_, n_tracks)                                                                    \
+    L.mk = lds;                                              /* [narm][7][12] = R0 (9), p (3) */                                                      \
+    L.nodes = L.mk + 84 * narm;                              /* [N][nq] */                                                                            \
+    L.sk = L.nodes + (size_t)nq * N;                         /* [nsph][4] = c, r */                                                                   \
+    L.rch = L.sk + 4 * nsph;                                 /* [nsph][7] */                                                                          \
+    L.ok = L.rch + 7 * nsph;                                 /* [n_obs][8] */                                                                         \
+    L.sc = L.ok + 8 * n_obs;                                 /* [chunk][nq][2] */                                                                     \
+    L.dv = L.sc + (size_t)chunk * nq * 2;                    /* [chunk][nq] */                                                                        \
+    L.fr = L.dv + (size_t)chunk * nq;                        /* [chunk][nq][12] = Rw (9), pw (3) */                                                   \
+    L.cen = L.fr + (size_t)chunk * nq * 12;                  /* [chunk][nsph][3] */                                                                   \
+    L.Dl = L.cen + (size_t)chunk * nsph * 3;                 /* [chunk][nsph] D_s */                                                                  \
+    L.pd = L.Dl + (size_t)chunk * nsph;                      /* [chunk][nsph] smallest d of the sphere's pairs */                                     \
+    L.pl = L.pd + (size_t)chunk * nsph;                      /* [chunk][nsph] smallest bound of the sphere's pairs */                                 \
+    L.tk = L.pl + (size_t)chunk * nsph;                      /* [chunk][n_tracks][4] = p_m (3), E_k (with a timeline) */                              \
+    L.cur = reinterpret_cast<int *>(L.tk + (TL_ ? (size_t)chunk * n_tracks * 4 : 0));      /* [CERT_CAP] */                                           \
+    L.nxt = L.cur + CERT_CAP;                                /* [CERT_CAP] */                                                                         \
+    L.sj = L.nxt + CERT_CAP;                                 /* [nsph] arm * 7 + joint */                                                             \
+    L.sa = L.sj + nsph;                                      /* [nsph] arm */                                                                         \
+    L.ot = L.sa + nsph;                                      /* [n_obs] type */                                                                       \
+    L.tof = L.ot + n_obs;                                    /* [n_obs] track, -1: none (with a timeline) */                                          \
+    L.end = L.tof + (TL_ ? n_obs : 0);
+inline CertLds cert_layout(double *lds, const CertShape &h, bool timeline, int n_tracks) {
+    const int narm = h.narm, N = 3 * h.nseg + 1, nq = 7 * narm, nsph = h.ns0 + h.ns1, n_obs = h.n_obs, chunk = h.chunk;
+    CertLds L;
+    MPCMP_CERT_LAYOUT(L, lds, narm, nq, N, nsph, n_obs, chunk, timeline, n_tracks)
+    return L;
+}
+// the bytes of that layout, a whole number of doubles: the layout itself on a base that is never read (one double, so that no pointer is null)
+inline size_t cert_lds_bytes(const CertShape &h, bool timeline, int n_tracks) {
+    static double base[1];
+    const CertLds L = cert_layout(base, h, timeline, n_tracks);
+    return ((size_t)(reinterpret_cast<const char *>(L.end) - reinterpret_cast<const char *>(base)) + 7) / 8 * 8;
 }
 
 }  // namespace mpcmp

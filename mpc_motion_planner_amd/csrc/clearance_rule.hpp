@@ -62,7 +62,34 @@ MPCMP_HD unsigned clr_pack(int ip, int sphere, int robot, int idx) {
     return ((unsigned)ip << 17) | ((unsigned)sphere << 9) | ((unsigned)robot << 8) | (unsigned)idx;
 }
 constexpr unsigned CLR_NO_PAIR = 0xFFFFFFFFu;
-MPCMP_HD bool clr_better(double d, unsigned k, double bd, unsigned bk) { return d < bd || (d == bd && k < bk); }
+template <class K> MPCMP_HD bool clr_better(double d, K k, double bd, K bk) { return d < bd || (d == bd && k < bk); }
+
+// The low 16 bits of a key, which clr_pack and cert_key (clearance_cert.hpp) share: the sphere, and the obstacle's index or -1 - the partner sphere
+MPCMP_HD void clr_unpack(unsigned long long k, int *sphere, int *other) {
+    const int idx = (int)(k & 0xFFu);
+    *sphere = (int)((k >> 9) & 0x7Fu);
+    *other = (k & 0x100u) ? -1 - idx : idx;
+}
+// the MPCMP_CLR_NAN record, the one statement of it for every member of the family on the host and on the device
+MPCMP_HD mpcmp_clearance clr_nan_record() {
+    mpcmp_clearance r;
+    r.d_min = NAN; r.t_min = -1.0; r.t_first = -1.0; r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
+    return r;
+}
+// the record of a sampled check from its best (d, key), the first sample that hit and the count of those: sample ip lies at (ip / n_pts) T_run
+MPCMP_HD mpcmp_clearance clr_record(double best_d, unsigned best_k, int first, int n_hit, int n_pts, double T_run) {
+    mpcmp_clearance r;
+    r.d_min = best_d;
+    if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
+    else {
+        r.t_min = ((double)(int)(best_k >> 17) / n_pts) * T_run;
+        clr_unpack(best_k, &r.sphere, &r.other);
+    }
+    r.t_first = first >= 0 ? ((double)first / n_pts) * T_run : -1.0;
+    r.n_hit = n_hit;
+    r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
+    return r;
+}
 
 // a double as an unsigned key of the same order (the key of time_sync.hpp, restated here because that header defines kernels)
 MPCMP_HD unsigned long long clr_tkey(double x) {

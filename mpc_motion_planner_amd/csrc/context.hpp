@@ -51,7 +51,7 @@ struct mpcmp_ctx {
     mpcmp_obstacle *d_clr_obs = nullptr;
     size_t clr_obs_cap = 0;
     int clr_sets = 0, clr_nobs = 0;
-    bool clr_cert_ready = false;     // ... and the certified check's (mpcmp_clearance_certified_batch*), by its first call
+    bool clr_cert_ready = false;     // ... and the certified kernel's, with and without a timeline, by the first certified call
     bool clr_ready = false;          // the kernel's dynamic-LDS ceiling is set by the first check, so that a context that never checks never asks for it
     unsigned long long *d_sel_key = nullptr;
     // the track table of the obstacle sets (mpcmp_set_obstacle_tracks*, include/mpcmp_moving.h): d_mv_track_of [clr_sets][clr_nobs] and d_mv_off
@@ -63,7 +63,6 @@ struct mpcmp_ctx {
     int mv_tracks = 0, mv_keys = 1;
     double mv_t0 = 0.0, mv_dt = 1.0;
     bool mv_ready = false;           // the dynamic-LDS ceilings of its kernels, by the first call of the family
-    bool mvc_ready = false;          // ... and of the certified check in a moving world (mpcmp_clearance_certified_timed_batch*), by its first call
     // the voxel world (mpcmp_set_field*, include/mpcmp_field.h): the grid in force, its occupancy, its squared distance field and the transform's
     // scratch, fld_cap entries each, allocated and grown by the setters and by nothing else; fld_set == false: no field.  Read by
     // mpcmp_clearance_field_batch* and mpcmp_get_field only

@@ -5,8 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "field.hpp"
-#include "clearance_cert.hpp"
-#include "plan_interp.hpp"
+#include "clearance_phases.hpp"
 
 namespace mpcmp {
 
@@ -88,37 +87,15 @@ __global__ __launch_bounds__(FLD_NT) void k_field_pass(const unsigned *__restric
 //   A2  one thread per (sample, arm): the forward-kinematics chain;
 //   B   one thread per (sample, sphere): world centre, one entry of the field, sqrt in double.
 // The field stays in global memory: one dword gather per (sample, sphere).  The voxel read is carried beside the (value, key) pair.
-struct FldShape { int narm, nseg, n0, n1, chunk; };
-
-__global__ __launch_bounds__(CLR_NT) void k_clearance_field(const mpcmp_model *__restrict__ mdl, FldShape h, int n_pts, const ClrSphere *__restrict__ sph,
+__global__ __launch_bounds__(CLR_NT) void k_clearance_field(const mpcmp_model *__restrict__ mdl, ClrShape h, int n_pts, const ClrSphere *__restrict__ sph,
                                                             mpcmp_field_desc g, const unsigned *__restrict__ d2, const double *__restrict__ sx,
                                                             const double *__restrict__ sT, double margin, mpcmp_clearance *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double red_d[CLR_NT / 64];
-    __shared__ unsigned red_k[CLR_NT / 64];
-    __shared__ int red_v[CLR_NT / 64];
     __shared__ int nan_flag;
-    const int b = blockIdx.x, tid = threadIdx.x, N = 3 * h.nseg + 1, nq = 7 * h.narm, nsph = h.n0 + h.n1, chunk = h.chunk;
-    double *mk = lds;                                        // [narm][7][12] = R0 (9), p (3)
-    double *nodes = mk + 84 * h.narm;                        // [N][nq]
-    double *sk = nodes + (size_t)nq * N;                     // [nsph][4] = c, r
-    double *sc = sk + 4 * nsph;                              // [chunk][nq][2]
-    double *fr = sc + (size_t)chunk * nq * 2;                // [chunk][nq][12] = Rw (9), pw (3)
-    int *sj = reinterpret_cast<int *>(fr + (size_t)chunk * nq * 12);      // [nsph] arm * 7 + joint
-    int *hit = sj + nsph;                                    // [chunk]
-
-    for (int e = tid; e < 84 * h.narm; e += CLR_NT) {
-        const int a = e / 84, i = (e % 84) / 12, c = e % 12;
-        mk[e] = c < 9 ? mdl[a].R0[i][c] : mdl[a].p[i][c - 9];
-    }
-    const double *X = sx + (size_t)b * N * 2 * nq;
-    for (int e = tid; e < nq * N; e += CLR_NT) nodes[e] = X[(size_t)(e / nq) * 2 * nq + e % nq];
-    for (int s = tid; s < nsph; s += CLR_NT) {
-        const ClrSphere S = sph[s];
-        sk[4 * s] = S.c[0]; sk[4 * s + 1] = S.c[1]; sk[4 * s + 2] = S.c[2]; sk[4 * s + 3] = S.r;
-        sj[s] = 7 * S.arm + S.joint;
-    }
-    for (int e = tid; e < chunk; e += CLR_NT) hit[e] = 0;
+    const int b = blockIdx.x, tid = threadIdx.x, nsph = h.n0 + h.n1, chunk = h.chunk;
+    LdsCursor<true> cur = {reinterpret_cast<char *>(lds), 0};
+    const ClrLds L = clr_carve(cur, h, CLR_LDS_FIELD, 0);
+    clr_stage(L, h, mdl, sph, nullptr, sx, b);               // (h.n_obs == 0: no obstacle is read; a NaN is flagged by the interpolated sample)
     if (tid == 0) nan_flag = 0;
     __syncthreads();
 
@@ -128,76 +105,29 @@ __global__ __launch_bounds__(CLR_NT) void k_clearance_field(const mpcmp_model *_
     int n_hit = 0, first = -1;                               // (thread 0 only)
     for (int ip0 = 0; ip0 <= n_pts; ip0 += chunk) {
         const int ns = (n_pts + 1 - ip0 < chunk) ? n_pts + 1 - ip0 : chunk;
-        // A1
-        for (int it = tid; it < ns * nq; it += CLR_NT) {
-            const int sl = it / nq, j = it % nq;
-            double Lg[4];
-            const int s = mpcmp_plan::lagrange_segment(h.nseg, (double)(ip0 + sl) / n_pts, Lg);
-            const double q = mpcmp_plan::interp_channel(nodes + j, nq, s, Lg);
-            if (!fld_finite(q)) nan_flag = 1;
-            double sn, cs;
-            sincos(q, &sn, &cs);
-            sc[2 * it] = sn; sc[2 * it + 1] = cs;
-        }
-        __syncthreads();
-        // A2
-        for (int it = tid; it < ns * h.narm; it += CLR_NT) {
-            const int sl = it / h.narm, a = it % h.narm;
-            cert_frames(mk + 84 * a, sc + (size_t)(sl * nq + 7 * a) * 2, fr + (size_t)(sl * nq + 7 * a) * 12);
-        }
-        __syncthreads();
+        // A1, A2
+        clr_frames(L, h, ns, [&](int sl) { return (double)(ip0 + sl) / n_pts; }, &nan_flag);
         // B.  A NaN plan's centres are not looked up (its record is the NaN record whatever is found here); fld_sd clamps every finite centre onto
         // the grid, so the gather stays inside the field
         if (!nan_flag)
             for (int it = tid; it < ns * nsph; it += CLR_NT) {
                 const int sl = it / nsph, s = it % nsph;
-                const double *S = sk + 4 * s;
                 double c[3];
-                cert_centre(fr + (size_t)(sl * nq + sj[s]) * 12, S, c);
+                clr_centre(L, h, sl, s, c);
                 int v = 0;
                 double dm = INFINITY;
-                if (fld_finite(c[0]) && fld_finite(c[1]) && fld_finite(c[2])) dm = fld_sd(g, d2, c[0], c[1], c[2], &v) - S[3];
-                if (dm < margin) hit[sl] = 1;
+                if (fld_finite(c[0]) && fld_finite(c[1]) && fld_finite(c[2])) dm = fld_sd(g, d2, c[0], c[1], c[2], &v) - L.sk[4 * s + 3];
+                if (dm < margin) L.hit[sl] = 1;
                 const unsigned k = clr_pack(ip0 + sl, s, 0, 0);
                 if (dm < INFINITY && clr_better(dm, k, best_d, best_k)) { best_d = dm; best_k = k; best_v = v; }
             }
         __syncthreads();
-        if (tid == 0)
-            for (int sl = 0; sl < ns; sl++) {
-                if (hit[sl]) { if (first < 0) first = ip0 + sl; n_hit++; }
-                hit[sl] = 0;
-            }
+        if (tid == 0) clr_count_hits(L, ns, ip0, &first, &n_hit);
     }
-    // workgroup reduction of (clearance, packed index) by clr_better, the voxel carried along
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) {
-        const double od = __shfl_down(best_d, o2);
-        const unsigned okk = __shfl_down(best_k, o2);
-        const int ov = __shfl_down(best_v, o2);
-        if (clr_better(od, okk, best_d, best_k)) { best_d = od; best_k = okk; best_v = ov; }
-    }
-    if ((tid & 63) == 0) { red_d[tid >> 6] = best_d; red_k[tid >> 6] = best_k; red_v[tid >> 6] = best_v; }
-    __syncthreads();
+    clr_reduce(best_d, best_k, &best_v);                     // (the voxel carried beside the key)
     if (tid == 0) {
-        for (int w = 1; w < CLR_NT / 64; w++)
-            if (clr_better(red_d[w], red_k[w], best_d, best_k)) { best_d = red_d[w]; best_k = red_k[w]; best_v = red_v[w]; }
-        const double T = sT[b];
-        mpcmp_clearance r;
-        if (nan_flag) {
-            r.d_min = __longlong_as_double(0x7FF8000000000000ll); r.t_min = -1.0; r.t_first = -1.0;
-            r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
-        } else {
-            r.d_min = best_d;
-            if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
-            else {
-                r.t_min = ((double)(int)(best_k >> 17) / n_pts) * T;
-                r.sphere = (int)((best_k >> 9) & 0x7Fu);
-                r.other = best_v;
-            }
-            r.t_first = first >= 0 ? ((double)first / n_pts) * T : -1.0;
-            r.n_hit = n_hit;
-            r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
-        }
+        mpcmp_clearance r = nan_flag ? clr_nan_record() : clr_record(best_d, best_k, first, n_hit, n_pts, sT[b]);
+        if (!nan_flag && best_k != CLR_NO_PAIR) r.other = best_v;
         out[b] = r;
     }
 }
@@ -213,12 +143,8 @@ __global__ __launch_bounds__(256) void k_clearance_merge(int B, const mpcmp_clea
 }
 
 hipError_t field_prepare() {
-    // as clearance_prepare: the ceiling over every sphere count (the chunk shrinks as the sphere tables grow), two arms, 25 nodes
-    size_t mx = 0;
-    for (int s = 0; s <= 2 * CLR_MAX_SPH; s++) {
-        const size_t b = fld_lds_bytes(2, 25, s, clr_chunk(s));
-        if (b > mx) mx = b;
-    }
+    // as clearance_prepare: two arms, 25 nodes
+    const size_t mx = lds_ceiling([](int s) { return clr_lds_bytes(ClrShape{2, 8, s, 0, 0, 0, clr_chunk(s)}, CLR_LDS_FIELD, 0); });
     return hipFuncSetAttribute((const void *)k_clearance_field, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mx);
 }
 
@@ -257,9 +183,8 @@ hipError_t field_build_launch(const FldArrays &f, hipStream_t st) {
 
 hipError_t clearance_field_launch(const ClrTables &t, const FldArrays &f, int B, const double *d_sx, const double *d_sT, int n_pts, double margin,
                                   mpcmp_clearance *d_out, hipStream_t st) {
-    FldShape h;
-    h.narm = t.narm; h.nseg = t.nseg; h.n0 = t.n_sph[0]; h.n1 = t.n_sph[1]; h.chunk = clr_chunk(h.n0 + h.n1);
-    const size_t lds = fld_lds_bytes(h.narm, 3 * h.nseg + 1, h.n0 + h.n1, h.chunk);
+    const ClrShape h = clr_shape(t, false);
+    const size_t lds = clr_lds_bytes(h, CLR_LDS_FIELD, 0);
     hipLaunchKernelGGL(k_clearance_field, dim3(B), dim3(CLR_NT), lds, st, t.d_model, h, n_pts, t.d_sph, f.desc, f.d_d2, d_sx, d_sT, margin, d_out);
     return hipGetLastError();
 }

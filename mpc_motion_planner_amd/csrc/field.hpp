@@ -1,5 +1,5 @@
 // field.hpp — what the voxel-world checks (include/mpcmp_field.h) share between the host entry points (mpcmp.hip) and their kernels (field.hip):
-// the field as a kernel reads it, the LDS budget and the launchers.  The rule's arithmetic is in field_rule.hpp (plain C++, read by the host
+// the field as a kernel reads it and the launchers (the LDS layout is clearance_lds.hpp).  The rule's arithmetic is in field_rule.hpp (plain C++, read by the host
 // statements of model_host.cpp as well).  The kernels live in field.hip, a translation unit of their own: nothing here is a kernel, so including
 // this header does not change what any other translation unit compiles to.
 #pragma once
@@ -21,13 +21,6 @@ struct FldArrays {
     unsigned char *d_occ;
     unsigned *d_d2, *d_tmp;
 };
-
-// dynamic LDS of k_clearance_field in bytes: the tables and the chunk of k_clearance without its obstacles and centres
-inline size_t fld_lds_bytes(int narm, int N, int nsph, int chunk) {
-    const size_t dbl = (size_t)84 * narm + (size_t)7 * narm * N + (size_t)4 * nsph + (size_t)chunk * narm * 14 + (size_t)chunk * narm * 84;
-    const size_t ints = (size_t)nsph + (size_t)chunk;
-    return dbl * sizeof(double) + (ints + 1) / 2 * 2 * sizeof(int);
-}
 
 hipError_t field_prepare();         // the check kernel's dynamic-LDS ceiling; called by a context's first field check
 // zero the occupancy and mark the voxels of n_points points (device) in it

@@ -533,123 +533,6 @@ extern "C" int mpcmp_tool_deviation_one(const mpcmp_model *model, int num_seg, c
     return MPCMP_OK;
 }
 
-// ---- certified clearance on the host (include/mpcmp_clearance_cert.h): one plan through the source the kernel runs (clearance_cert.hpp) ----
-extern "C" int mpcmp_clearance_certified_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
-                                             const mpcmp_obstacle *obs, const double *x, double T, double margin, int self_gap, int n_start, int max_depth,
-                                             mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
-    if (!models || narm < 1 || narm > 2 || num_seg < 1 || !n_spheres || !x || !out || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_obs > 0 && !obs) ||
-        self_gap < 0 || !std::isfinite(margin) || n_start < 1 || n_start > CERT_CAP || (long)num_seg * n_start > CERT_CAP || max_depth < 0 ||
-        max_depth > CERT_MAX_DEPTH) {
-        g_err = "mpcmp_clearance_certified_one: one or two arms, num_seg >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a finite "
-                "margin, self_gap >= 0, n_obs in [0, 256] and all pointers (but cert) required";
-        return MPCMP_EINVAL;
-    }
-    int nsph = 0;
-    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
-    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
-    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
-    const int nq = 7 * narm, N = 3 * num_seg + 1, n0 = num_seg * n_start;
-    // the tables in the form the kernel stages them
-    std::vector<double> mk(84 * narm), nodes((size_t)nq * N), reach(7 * (nsph > 0 ? nsph : 1)), ok(8 * (n_obs > 0 ? n_obs : 1));
-    std::vector<int> arm(nsph), jnt(nsph);
-    for (int a = 0; a < narm; a++)
-        for (int i = 0; i < 7; i++) {
-            for (int c = 0; c < 9; c++) mk[84 * a + 12 * i + c] = models[a].R0[i][c];
-            for (int c = 0; c < 3; c++) mk[84 * a + 12 * i + 9 + c] = models[a].p[i][c];
-        }
-    bool nan = false;
-    for (int k = 0; k < N; k++)
-        for (int j = 0; j < nq; j++) { nodes[(size_t)k * nq + j] = x[(size_t)k * 2 * nq + j]; if (!std::isfinite(x[(size_t)k * 2 * nq + j])) nan = true; }
-    for (int a = 0, s = 0; a < narm; a++)
-        for (int k = 0; k < n_spheres[a]; k++, s++) {
-            arm[s] = a; jnt[s] = spheres[s].joint;
-            cert_reach(mk.data() + 84 * a + 9, 12, jnt[s], spheres[s].c, reach.data() + 7 * s);
-        }
-    for (int o = 0; o < n_obs; o++) clr_obs_prepare(obs[o], ok.data() + 8 * o);
-    mpcmp_clearance r;
-    mpcmp_clearance_cert c;
-    if (nan) {
-        r.d_min = std::nan(""); r.t_min = -1.0; r.t_first = -1.0; r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
-        c.d_lower = std::nan(""); c.t_lower = -1.0; c.n_eval = 0; c.n_clear = 0; c.n_undecided = 0; c.depth = 0;
-        *out = r;
-        if (cert) *cert = c;
-        return MPCMP_OK;
-    }
-    double best_d = INFINITY, best_L = INFINITY;
-    unsigned long long best_k = CERT_NO_PAIR, best_Lk = CERT_NO_PAIR;
-    unsigned first = CERT_NO_TIME;
-    int n_hit = 0, n_clear = 0, n_und = 0, n_eval = 0, depth = 0;
-    std::vector<int> cur(n0), nxt;
-    for (int i = 0; i < n0; i++) cur[i] = i;
-    std::vector<double> cen(3 * (nsph > 0 ? nsph : 1)), Ds(nsph > 0 ? nsph : 1);
-    for (int l = 0; !cur.empty(); l++) {
-        depth = l;
-        nxt.clear();
-        int n_split = 0;
-        for (int i : cur) {
-            const CertInterval v = cert_interval(n0, n_start, l, i);
-            const unsigned tk = cert_tkey(l, i);
-            double dev[14], sc[28], fr[2 * 84];
-            for (int j = 0; j < nq; j++) {
-                double qm;
-                dev[j] = cert_deviation(nodes.data() + j, nq, num_seg, v, &qm);
-                sc[2 * j] = std::sin(qm); sc[2 * j + 1] = std::cos(qm);
-            }
-            for (int a = 0; a < narm; a++) cert_frames(mk.data() + 84 * a, sc + 14 * a, fr + 84 * a);
-            for (int s = 0; s < nsph; s++) {
-                Ds[s] = cert_motion(reach.data() + 7 * s, dev + 7 * arm[s]);
-                cert_centre(fr + 84 * arm[s] + 12 * jnt[s], spheres[s].c, cen.data() + 3 * s);
-            }
-            double d_mid = INFINITY, L = INFINITY;
-            for (int s = 0; s < nsph; s++) {
-                const double *C = cen.data() + 3 * s;
-                for (int o = 0; o < n_obs; o++) {
-                    const double d = clr_sd(obs[o].type, ok.data() + 8 * o, C[0], C[1], C[2]) - spheres[s].r;
-                    const unsigned long long key = cert_key(tk, s, 0, o);
-                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
-                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s]);
-                }
-                for (int t = s + 1; t < nsph; t++) {
-                    if (!clr_pair(arm[s], jnt[s], arm[t], jnt[t], self_gap)) continue;
-                    const double ex = C[0] - cen[3 * t], ey = C[1] - cen[3 * t + 1], ez = C[2] - cen[3 * t + 2];
-                    const double d = std::sqrt(ex * ex + ey * ey + ez * ez) - spheres[s].r - spheres[t].r;
-                    const unsigned long long key = cert_key(tk, s, 1, t);
-                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
-                    d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s] - Ds[t]);
-                }
-            }
-            n_eval++;
-            int what = cert_decide(d_mid, L, margin, l, max_depth);
-            if (what == CERT_SPLIT_IT) {
-                if (n_split < CERT_SPLIT) { n_split++; nxt.push_back(2 * i); nxt.push_back(2 * i + 1); continue; }
-                what = CERT_UNDECIDED;          // (the capacity rule)
-            }
-            if (what == CERT_HIT) { n_hit++; if (tk < first) first = tk; }
-            else if (what == CERT_CLEAR) n_clear++;
-            else n_und++;
-            const unsigned long long lk = cert_key(tk, 0, 0, 0);
-            if (cert_better(L, lk, best_L, best_Lk)) { best_L = L; best_Lk = lk; }
-        }
-        cur.swap(nxt);
-    }
-    r.d_min = best_d;
-    if (best_k == CERT_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
-    else {
-        const int idx = (int)(best_k & 0xFFu);
-        r.t_min = cert_time(n0, (unsigned)(best_k >> 16)) * T;
-        r.sphere = (int)((best_k >> 9) & 0x7Fu);
-        r.other = (best_k & 0x100u) ? -1 - idx : idx;
-    }
-    r.t_first = first != CERT_NO_TIME ? cert_time(n0, first) * T : -1.0;
-    r.n_hit = n_hit;
-    r.status = (n_hit > 0 ? MPCMP_CLR_HIT : 0) | (n_und > 0 ? MPCMP_CLR_UNDECIDED : 0);
-    c.d_lower = best_L; c.t_lower = cert_time(n0, (unsigned)(best_Lk >> 16)) * T;
-    c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
-    *out = r;
-    if (cert) *cert = c;
-    return MPCMP_OK;
-}
-
 // ---- clearance in a moving world on the host (include/mpcmp_moving.h): one plan through the source the kernels run (moving_rule.hpp) ----
 extern "C" int mpcmp_track_offset(int n_key, double t0, double dt, const double *P, double tau, double *p) {
     if (!P || !p || n_key < 1 || n_key > MV_MAX_KEYS || !std::isfinite(t0) || !std::isfinite(dt) || !(dt > 0.0) || !std::isfinite(tau)) {
@@ -696,7 +579,32 @@ struct MvHost {
 };
 }  // namespace
 
-// the checks and tables the two statements below share; `who` for the message
+// one plan's tables without a timeline: the checks of the sphere tables, then the arrays as the kernels stage them; H->nan: a position node that is
+// not finite.  Every statement of the family fills its tables here; what the timed members add is mv_host_setup
+static int host_tables(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                       const mpcmp_obstacle *obs, const double *x, MvHost *H) {
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
+    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
+    const int nq = 7 * narm, N = 3 * num_seg + 1;
+    H->narm = narm; H->nseg = num_seg; H->nsph = nsph; H->n_obs = n_obs; H->sph = spheres; H->obs = obs;
+    H->mk.resize(84 * narm); H->nodes.resize((size_t)nq * N); H->ok.resize(8 * (n_obs > 0 ? n_obs : 1));
+    H->arm.resize(nsph); H->jnt.resize(nsph); H->tof.assign(n_obs, -1);
+    for (int a = 0; a < narm; a++)
+        for (int i = 0; i < 7; i++) {
+            for (int c = 0; c < 9; c++) H->mk[84 * a + 12 * i + c] = models[a].R0[i][c];
+            for (int c = 0; c < 3; c++) H->mk[84 * a + 12 * i + 9 + c] = models[a].p[i][c];
+        }
+    for (int k = 0; k < N; k++)
+        for (int j = 0; j < nq; j++) { H->nodes[(size_t)k * nq + j] = x[(size_t)k * 2 * nq + j]; if (!std::isfinite(x[(size_t)k * 2 * nq + j])) H->nan = true; }
+    for (int a = 0, s = 0; a < narm; a++)
+        for (int k = 0; k < n_spheres[a]; k++, s++) { H->arm[s] = a; H->jnt[s] = spheres[s].joint; }
+    for (int o = 0; o < n_obs; o++) clr_obs_prepare(obs[o], H->ok.data() + 8 * o);
+    return MPCMP_OK;
+}
+
+// the checks and tables the timed statements share (the tables of host_tables, the tracks, sol_T and the profile); `who` for the message
 static int mv_host_setup(const char *who, const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
                          const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets,
                          const double *x, double T, int n_grid, const double *prof, int n_pts, double margin, int self_gap, const void *out, MvHost *H) {
@@ -716,29 +624,12 @@ static int mv_host_setup(const char *who, const mpcmp_model *models, int narm, i
             return MPCMP_EINVAL;
         }
     }
-    int nsph = 0;
-    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return MPCMP_EINVAL; nsph += n_spheres[a]; }
-    if (nsph > 0 && !spheres) return MPCMP_EINVAL;
-    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return MPCMP_EINVAL;
-    const int nq = 7 * narm, N = 3 * num_seg + 1;
-    H->narm = narm; H->nseg = num_seg; H->nsph = nsph; H->n_obs = n_obs; H->n_tracks = n_tracks; H->n_key = n_tracks > 0 ? n_key : 1;
-    H->t0 = t0; H->dt = dt; H->T = T; H->n_grid = n_grid; H->prof = prof; H->sph = spheres; H->obs = obs; H->off = offsets;
-    H->mk.resize(84 * narm); H->nodes.resize((size_t)nq * N); H->ok.resize(8 * (n_obs > 0 ? n_obs : 1));
-    H->arm.resize(nsph); H->jnt.resize(nsph); H->tof.resize(n_obs);
-    for (int a = 0; a < narm; a++)
-        for (int i = 0; i < 7; i++) {
-            for (int c = 0; c < 9; c++) H->mk[84 * a + 12 * i + c] = models[a].R0[i][c];
-            for (int c = 0; c < 3; c++) H->mk[84 * a + 12 * i + 9 + c] = models[a].p[i][c];
-        }
-    bool nan = !std::isfinite(T);
-    for (int k = 0; k < N; k++)
-        for (int j = 0; j < nq; j++) { H->nodes[(size_t)k * nq + j] = x[(size_t)k * 2 * nq + j]; if (!std::isfinite(x[(size_t)k * 2 * nq + j])) nan = true; }
-    if (prof) for (int e = 0; e < 2 * (n_grid + 1); e++) if (!std::isfinite(prof[e])) nan = true;
-    for (int a = 0, s = 0; a < narm; a++)
-        for (int k = 0; k < n_spheres[a]; k++, s++) { H->arm[s] = a; H->jnt[s] = spheres[s].joint; }
-    for (int o = 0; o < n_obs; o++) { clr_obs_prepare(obs[o], H->ok.data() + 8 * o); H->tof[o] = n_tracks > 0 ? mv_track(track_of[o], n_tracks) : -1; }
-    H->nan = nan;
-    H->T_run = nan ? 0.0 : mv_run_time(prof, n_grid, T);
+    if (int rc = host_tables(models, narm, num_seg, n_spheres, spheres, n_obs, obs, x, H)) return rc;
+    H->n_tracks = n_tracks; H->n_key = n_tracks > 0 ? n_key : 1; H->t0 = t0; H->dt = dt; H->T = T; H->n_grid = n_grid; H->prof = prof; H->off = offsets;
+    if (!std::isfinite(T)) H->nan = true;
+    if (prof) for (int e = 0; e < 2 * (n_grid + 1); e++) if (!std::isfinite(prof[e])) H->nan = true;
+    if (n_tracks > 0) for (int o = 0; o < n_obs; o++) H->tof[o] = mv_track(track_of[o], n_tracks);
+    H->T_run = H->nan ? 0.0 : mv_run_time(prof, n_grid, T);
     return MPCMP_OK;
 }
 
@@ -749,7 +640,7 @@ extern "C" int mpcmp_clearance_timed_one(const mpcmp_model *models, int narm, in
     MvHost H;
     if (int rc = mv_host_setup("mpcmp_clearance_timed_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0, dt,
                                offsets, x, T, n_grid, prof, n_pts, margin, self_gap, out, &H)) return rc;
-    if (H.nan || !std::isfinite(t_start)) { *out = mv_clearance_nan(); return MPCMP_OK; }
+    if (H.nan || !std::isfinite(t_start)) { *out = clr_nan_record(); return MPCMP_OK; }
     std::vector<double> cen(3 * (H.nsph > 0 ? H.nsph : 1));
     double best_d = INFINITY;
     unsigned best_k = CLR_NO_PAIR;
@@ -777,19 +668,7 @@ extern "C" int mpcmp_clearance_timed_one(const mpcmp_model *models, int narm, in
         }
         if (hit) { if (first < 0) first = i; n_hit++; }
     }
-    mpcmp_clearance r;
-    r.d_min = best_d;
-    if (best_k == CLR_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
-    else {
-        const int ip = (int)(best_k >> 17), idx = (int)(best_k & 0xFFu);
-        r.t_min = ((double)ip / n_pts) * H.T_run;
-        r.sphere = (int)((best_k >> 9) & 0x7Fu);
-        r.other = (best_k & 0x100u) ? -1 - idx : idx;
-    }
-    r.t_first = first >= 0 ? ((double)first / n_pts) * H.T_run : -1.0;
-    r.n_hit = n_hit;
-    r.status = n_hit > 0 ? MPCMP_CLR_HIT : 0;
-    *out = r;
+    *out = clr_record(best_d, best_k, first, n_hit, n_pts, H.T_run);
     return MPCMP_OK;
 }
 
@@ -830,49 +709,35 @@ extern "C" int mpcmp_start_delay_one(const mpcmp_model *models, int narm, int nu
     return MPCMP_OK;
 }
 
-// ---- certified clearance in a moving world on the host (include/mpcmp_moving_cert.h): one plan through the source the kernel runs
-// (moving_cert_rule.hpp on top of clearance_cert.hpp and moving_rule.hpp) ----
-extern "C" int mpcmp_clearance_certified_timed_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres,
-                                                   int n_obs, const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
-                                                   const double *offsets, const double *x, double T, double t_start, double wait_before,
-                                                   double hold_after, double margin, int self_gap, int n_start, int n_rest, int max_depth,
-                                                   mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
-    if (n_start < 1 || n_start > CERT_CAP || n_rest < 1 || n_rest > CERT_CAP || num_seg < 1 || (long)num_seg * n_start + 2l * n_rest > CERT_CAP ||
-        max_depth < 0 || max_depth > CERT_MAX_DEPTH || wait_before < 0.0 || hold_after < 0.0) {
-        g_err = "mpcmp_clearance_certified_timed_one: n_start >= 1 and n_rest >= 1 with num_seg n_start + 2 n_rest <= 4096, max_depth in [0, 16], "
-                "wait_before >= 0 and hold_after >= 0 required";
-        return MPCMP_EINVAL;
+// ---- certified clearance on the host, without a timeline (include/mpcmp_clearance_cert.h) and with one (include/mpcmp_moving_cert.h): one plan
+// through the source the kernel runs (clearance_cert.hpp, and moving_cert_rule.hpp on top of it and of moving_rule.hpp) ----
+// The search both statements run on the tables of H.  `timed`: the record times are those of the timeline; otherwise tl holds the motion alone
+// (no rests, and H no tracks) and a time is cert_time x T, the static member's own product
+static void cert_host(const MvHost &H, bool timed, const MvcTimeline &tl, int n_start, double margin, int self_gap, int max_depth, mpcmp_clearance *out,
+                      mpcmp_clearance_cert *cert) {
+    if (H.nan) {
+        *out = clr_nan_record();
+        if (cert) *cert = cert_nan_record();
+        return;
     }
-    MvHost H;
-    if (int rc = mv_host_setup("mpcmp_clearance_certified_timed_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0,
-                               dt, offsets, x, T, 0, nullptr, 1, margin, self_gap, out, &H)) return rc;
-    mpcmp_clearance_cert c;
-    if (H.nan || !mvc_times_ok(T, t_start, wait_before, hold_after)) {
-        c.d_lower = std::nan(""); c.t_lower = -1.0; c.n_eval = 0; c.n_clear = 0; c.n_undecided = 0; c.depth = 0;
-        *out = mv_clearance_nan();
-        if (cert) *cert = c;
-        return MPCMP_OK;
-    }
-    const int nq = 7 * narm, N = 3 * num_seg + 1, nsph = H.nsph;
-    const MvcTimeline tl = mvc_timeline(num_seg, n_start, n_rest, T, t_start, wait_before, hold_after);
+    const int narm = H.narm, num_seg = H.nseg, nq = 7 * narm, N = 3 * num_seg + 1, nsph = H.nsph, n_obs = H.n_obs;
+    const mpcmp_sphere *spheres = H.sph;
+    const mpcmp_obstacle *obs = H.obs;
     std::vector<double> reach(7 * (nsph > 0 ? nsph : 1)), cen(3 * (nsph > 0 ? nsph : 1)), Ds(nsph > 0 ? nsph : 1), pm(3 * (H.n_tracks > 0 ? H.n_tracks : 1)),
         Ek(H.n_tracks > 0 ? H.n_tracks : 1);
     for (int s = 0; s < nsph; s++) cert_reach(H.mk.data() + 84 * H.arm[s] + 9, 12, H.jnt[s], spheres[s].c, reach.data() + 7 * s);
-    double best_d = INFINITY, best_L = INFINITY;
-    unsigned long long best_k = CERT_NO_PAIR, best_Lk = CERT_NO_PAIR;
-    unsigned first = CERT_NO_TIME;
-    int n_hit = 0, n_clear = 0, n_und = 0, n_eval = 0, depth = 0;
+    CertBest B;
     std::vector<int> cur(tl.n0), nxt;
     for (int i = 0; i < tl.n0; i++) cur[i] = i;
     for (int l = 0; !cur.empty(); l++) {
-        depth = l;
+        B.depth = l;
         nxt.clear();
         int n_split = 0;
         for (int i : cur) {
             const MvcInterval v = mvc_interval(tl, n_start, l, i);
             const unsigned tk = cert_tkey(l, i);
             for (int k = 0; k < H.n_tracks; k++)
-                Ek[k] = mvc_track_bound(offsets + (size_t)k * H.n_key * 3, H.n_key, t0, dt, tl.tau0 + v.ta, tl.tau0 + v.tm, tl.tau0 + v.tb, pm.data() + 3 * k);
+                Ek[k] = mvc_track_bound(H.off + (size_t)k * H.n_key * 3, H.n_key, H.t0, H.dt, tl.tau0 + v.ta, tl.tau0 + v.tm, tl.tau0 + v.tb, pm.data() + 3 * k);
             double dev[14], sc[28], fr[2 * 84];
             for (int j = 0; j < nq; j++) {
                 double qm;
@@ -900,47 +765,68 @@ extern "C" int mpcmp_clearance_certified_timed_one(const mpcmp_model *models, in
                         bound = d - Ds[s];
                     }
                     const unsigned long long key = cert_key(tk, s, 0, o);
-                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    if (cert_better(d, key, B.d, B.k)) { B.d = d; B.k = key; }
                     d_mid = std::fmin(d_mid, d); L = std::fmin(L, bound);
                 }
                 for (int t = s + 1; t < nsph; t++) {
                     if (!clr_pair(H.arm[s], H.jnt[s], H.arm[t], H.jnt[t], self_gap)) continue;
                     const double d = H.pair(s, t, cen.data());
                     const unsigned long long key = cert_key(tk, s, 1, t);
-                    if (cert_better(d, key, best_d, best_k)) { best_d = d; best_k = key; }
+                    if (cert_better(d, key, B.d, B.k)) { B.d = d; B.k = key; }
                     d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - Ds[s] - Ds[t]);
                 }
             }
-            n_eval++;
+            B.n_eval++;
             int what = cert_decide(d_mid, L, margin, l, max_depth);
             if (what == CERT_SPLIT_IT) {
                 if (n_split < CERT_SPLIT) { n_split++; nxt.push_back(2 * i); nxt.push_back(2 * i + 1); continue; }
                 what = CERT_UNDECIDED;          // (the capacity rule)
             }
-            if (what == CERT_HIT) { n_hit++; if (tk < first) first = tk; }
-            else if (what == CERT_CLEAR) n_clear++;
-            else n_und++;
+            if (what == CERT_HIT) { B.n_hit++; if (tk < B.first) B.first = tk; }
+            else if (what == CERT_CLEAR) B.n_clear++;
+            else B.n_und++;
             const unsigned long long lk = cert_key(tk, 0, 0, 0);
-            if (cert_better(L, lk, best_L, best_Lk)) { best_L = L; best_Lk = lk; }
+            if (cert_better(L, lk, B.L, B.Lk)) { B.L = L; B.Lk = lk; }
         }
         cur.swap(nxt);
     }
-    mpcmp_clearance r;
-    r.d_min = best_d;
-    if (best_k == CERT_NO_PAIR) { r.t_min = -1.0; r.sphere = -1; r.other = 0; }
-    else {
-        const int idx = (int)(best_k & 0xFFu);
-        r.t_min = mvc_time(tl, (unsigned)(best_k >> 16));
-        r.sphere = (int)((best_k >> 9) & 0x7Fu);
-        r.other = (best_k & 0x100u) ? -1 - idx : idx;
-    }
-    r.t_first = first != CERT_NO_TIME ? mvc_time(tl, first) : -1.0;
-    r.n_hit = n_hit;
-    r.status = (n_hit > 0 ? MPCMP_CLR_HIT : 0) | (n_und > 0 ? MPCMP_CLR_UNDECIDED : 0);
-    c.d_lower = best_L; c.t_lower = mvc_time(tl, (unsigned)(best_Lk >> 16));
-    c.n_eval = n_eval; c.n_clear = n_clear; c.n_undecided = n_und; c.depth = depth;
-    *out = r;
+    mpcmp_clearance_cert c;
+    cert_records(B, [&](unsigned tkey) { return timed ? mvc_time(tl, tkey) : cert_time(tl.n0, tkey) * tl.T; }, out, &c);
     if (cert) *cert = c;
+}
+
+extern "C" int mpcmp_clearance_certified_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres, int n_obs,
+                                             const mpcmp_obstacle *obs, const double *x, double T, double margin, int self_gap, int n_start, int max_depth,
+                                             mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (!models || narm < 1 || narm > 2 || num_seg < 1 || !n_spheres || !x || !out || n_obs < 0 || n_obs > CLR_MAX_OBS || (n_obs > 0 && !obs) ||
+        self_gap < 0 || !std::isfinite(margin) || n_start < 1 || n_start > CERT_CAP || (long)num_seg * n_start > CERT_CAP || max_depth < 0 ||
+        max_depth > CERT_MAX_DEPTH) {
+        g_err = "mpcmp_clearance_certified_one: one or two arms, num_seg >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a finite "
+                "margin, self_gap >= 0, n_obs in [0, 256] and all pointers (but cert) required";
+        return MPCMP_EINVAL;
+    }
+    MvHost H;          // (no tracks, and sol_T is not tested)
+    if (int rc = host_tables(models, narm, num_seg, n_spheres, spheres, n_obs, obs, x, &H)) return rc;
+    cert_host(H, false, mvc_timeline(num_seg, n_start, 0, T, 0.0, 0.0, 0.0), n_start, margin, self_gap, max_depth, out, cert);
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_timed_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres,
+                                                   int n_obs, const mpcmp_obstacle *obs, const int *track_of, int n_tracks, int n_key, double t0, double dt,
+                                                   const double *offsets, const double *x, double T, double t_start, double wait_before,
+                                                   double hold_after, double margin, int self_gap, int n_start, int n_rest, int max_depth,
+                                                   mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (n_start < 1 || n_start > CERT_CAP || n_rest < 1 || n_rest > CERT_CAP || num_seg < 1 || (long)num_seg * n_start + 2l * n_rest > CERT_CAP ||
+        max_depth < 0 || max_depth > CERT_MAX_DEPTH || wait_before < 0.0 || hold_after < 0.0) {
+        g_err = "mpcmp_clearance_certified_timed_one: n_start >= 1 and n_rest >= 1 with num_seg n_start + 2 n_rest <= 4096, max_depth in [0, 16], "
+                "wait_before >= 0 and hold_after >= 0 required";
+        return MPCMP_EINVAL;
+    }
+    MvHost H;
+    if (int rc = mv_host_setup("mpcmp_clearance_certified_timed_one", models, narm, num_seg, n_spheres, spheres, n_obs, obs, track_of, n_tracks, n_key, t0,
+                               dt, offsets, x, T, 0, nullptr, 1, margin, self_gap, out, &H)) return rc;
+    if (!mvc_times_ok(T, t_start, wait_before, hold_after)) H.nan = true;
+    cert_host(H, true, mvc_timeline(num_seg, n_start, n_rest, T, t_start, wait_before, hold_after), n_start, margin, self_gap, max_depth, out, cert);
     return MPCMP_OK;
 }
 

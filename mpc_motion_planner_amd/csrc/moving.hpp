@@ -1,5 +1,5 @@
 // moving.hpp — what the checks in a moving world (include/mpcmp_moving.h) share between the host entry points (mpcmp.hip) and their kernels
-// (moving.hip): the track table as a kernel reads it, the plan with its profile and start times, the LDS budget and the launchers.  The rule's
+// (moving.hip): the track table as a kernel reads it, the plan with its profile and start times, and the launchers (the LDS layout is clearance_lds.hpp).  The rule's
 // arithmetic is in moving_rule.hpp (plain C++, read by the host statements of model_host.cpp as well).  The kernels live in moving.hip, a translation
 // unit of their own: nothing here is a kernel, so including this header does not change what any other translation unit compiles to.
 #pragma once
@@ -23,14 +23,6 @@ struct MvPlans {
     const double *d_sx, *d_sT, *d_prof, *d_t_start;
     int n_grid;
 };
-
-// dynamic LDS of the three kernels in bytes: the tables and the chunk of k_clearance, the clock of a chunk's samples and (k_start_delay) K delays
-inline size_t mv_lds_bytes(int narm, int N, int nsph, int n_obs, int chunk, int K) {
-    const size_t dbl = (size_t)84 * narm + (size_t)7 * narm * N + (size_t)4 * nsph + (size_t)8 * n_obs + (size_t)chunk * narm * 14 +
-                       (size_t)chunk * narm * 84 + (size_t)chunk * nsph * 3 + (size_t)3 * chunk + (size_t)3 * K;
-    const size_t ints = (size_t)2 * nsph + (size_t)3 * n_obs + (size_t)3 * chunk;
-    return dbl * sizeof(double) + (ints + 1) / 2 * 2 * sizeof(int);
-}
 
 hipError_t moving_prepare();        // the kernels' dynamic-LDS ceilings; called by a context's first call of this family
 hipError_t clearance_timed_launch(const ClrTables &t, const MvTracks &trk, const MvPlans &p, int B, int n_pts, double margin, int self_gap,

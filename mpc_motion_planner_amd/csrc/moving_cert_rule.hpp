@@ -1,7 +1,7 @@
 // moving_cert_rule.hpp — what the certified check in a moving world (include/mpcmp_moving_cert.h) adds to the static certificate
 // (clearance_cert.hpp) and to the tracks (moving_rule.hpp): the timeline of wait, motion and hold, the phase geometry of an interval, the
-// conversion of a midpoint key to a record time, and the displacement bound E_k of a track on an interval.  The kernel (moving_cert.hip) and the
-// host statement mpcmp_clearance_certified_timed_one (model_host.cpp) both run this source.  Plain C++: no HIP header, and nothing here is a kernel.
+// conversion of a midpoint key to a record time, and the displacement bound E_k of a track on an interval.  The kernel (k_clearance_cert with a
+// timeline, clearance_cert.hip) and the host statement mpcmp_clearance_certified_timed_one (model_host.cpp) both run this source.  Plain C++: no HIP header, and nothing here is a kernel.
 #pragma once
 #include <cmath>
 #include "clearance_cert.hpp"

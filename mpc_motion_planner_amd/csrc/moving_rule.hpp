@@ -74,11 +74,5 @@ MPCMP_HD mpcmp_start_delay mv_delay_nan(int K, double *d_all) {
     if (d_all) for (int k = 0; k < K; k++) d_all[k] = NAN;
     return r;
 }
-// the MPCMP_CLR_NAN record of mpcmp_clearance_batch
-MPCMP_HD mpcmp_clearance mv_clearance_nan() {
-    mpcmp_clearance r;
-    r.d_min = NAN; r.t_min = -1.0; r.t_first = -1.0; r.sphere = -1; r.other = 0; r.n_hit = 0; r.status = MPCMP_CLR_NAN;
-    return r;
-}
 
 }  // namespace mpcmp

@@ -23,7 +23,6 @@
 #include "time_sync.hpp"
 #include "clearance.hpp"
 #include "moving.hpp"
-#include "moving_cert.hpp"
 #include "field.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
@@ -954,11 +953,16 @@ extern "C" int mpcmp_set_obstacles_device(mpcmp_ctx *ctx, int n_sets, int n_obs,
     return MPCMP_OK;
 }
 
-static int clearance_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, int self_gap, const mpcmp_clearance *out) {
-    if (!ctx) { g_err = "mpcmp_clearance_batch: no context"; return MPCMP_EINVAL; }
-    if (B < 1 || n_pts < 1 || n_pts > CLR_MAX_PTS || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0) {
-        ctx->err = "mpcmp_clearance_batch: B >= 1, 1 <= n_pts <= 4096, a finite margin, self_gap >= 0 and all pointers required"; return MPCMP_EINVAL;
-    }
+// the tables of every clearance check as its kernel reads them: the arms, the spheres and the obstacle sets in force
+static ClrTables clearance_tables(const mpcmp_ctx *ctx) {
+    ClrTables t;
+    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
+    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
+    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    return t;
+}
+// with more than one obstacle set, problem b reads set b
+static int obstacle_sets_check(mpcmp_ctx *ctx, int B) {
     if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
         ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
         return MPCMP_EINVAL;
@@ -966,12 +970,17 @@ static int clearance_check(mpcmp_ctx *ctx, int B, const double *sx, const double
     return MPCMP_OK;
 }
 
+static int clearance_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, int n_pts, double margin, int self_gap, const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || n_pts < 1 || n_pts > CLR_MAX_PTS || !sx || !sT || !out || !std::isfinite(margin) || self_gap < 0) {
+        ctx->err = "mpcmp_clearance_batch: B >= 1, 1 <= n_pts <= 4096, a finite margin, self_gap >= 0 and all pointers required"; return MPCMP_EINVAL;
+    }
+    return obstacle_sets_check(ctx, B);
+}
+
 static int clearance_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_pts, double margin, int self_gap,
                              mpcmp_clearance *d_out, hipStream_t st) {
-    ClrTables t;
-    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
-    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
-    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    const ClrTables t = clearance_tables(ctx);
     if (!ctx->clr_ready) { HIPCHK(ctx, clearance_prepare()); ctx->clr_ready = true; }
     HIPCHK(ctx, clearance_launch(t, B, d_sx, d_sT, n_pts, margin, self_gap, d_out, st));
     return MPCMP_OK;
@@ -1007,21 +1016,16 @@ static int clearance_cert_check(mpcmp_ctx *ctx, int B, const double *sx, const d
                    "self_gap >= 0 and all pointers (but cert) required";
         return MPCMP_EINVAL;
     }
-    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
-        return MPCMP_EINVAL;
-    }
-    return MPCMP_OK;
+    return obstacle_sets_check(ctx, B);
 }
 
 static int clearance_cert_enqueue(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, double margin, int self_gap, int n_start, int max_depth,
                                   mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, hipStream_t st) {
-    ClrTables t;
-    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
-    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
-    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
+    const ClrTables t = clearance_tables(ctx);
     if (!ctx->clr_cert_ready) { HIPCHK(ctx, clearance_cert_prepare()); ctx->clr_cert_ready = true; }
-    HIPCHK(ctx, clearance_cert_launch(t, B, d_sx, d_sT, margin, self_gap, n_start, max_depth, d_out, d_cert, st));
+    const CertPlans p = {d_sx, d_sT, nullptr, nullptr, nullptr};
+    // (no timeline: the obstacles stand where mpcmp_set_obstacles put them, whatever tracks the context holds)
+    HIPCHK(ctx, clearance_cert_launch(t, nullptr, p, B, margin, self_gap, n_start, 0, max_depth, d_out, d_cert, st));
     return MPCMP_OK;
 }
 
@@ -1125,14 +1129,12 @@ extern "C" int mpcmp_set_obstacle_tracks_device(mpcmp_ctx *ctx, int n_sets, int 
     return MPCMP_OK;
 }
 
-static ClrTables moving_tables(const mpcmp_ctx *ctx, MvTracks *trk) {
-    ClrTables t;
-    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
-    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
-    t.d_obs = ctx->d_clr_obs; t.n_obs = ctx->clr_nobs; t.obs_stride = ctx->clr_sets > 1 ? ctx->clr_nobs : 0;
-    trk->d_track_of = ctx->d_mv_track_of; trk->d_offsets = ctx->d_mv_off; trk->n_tracks = ctx->mv_tracks;
-    trk->n_key = ctx->mv_tracks > 0 ? ctx->mv_keys : 1; trk->t0 = ctx->mv_t0; trk->dt = ctx->mv_dt;
-    return t;
+// the track table in force beside clearance_tables
+static MvTracks moving_tracks(const mpcmp_ctx *ctx) {
+    MvTracks trk;
+    trk.d_track_of = ctx->d_mv_track_of; trk.d_offsets = ctx->d_mv_off; trk.n_tracks = ctx->mv_tracks;
+    trk.n_key = ctx->mv_tracks > 0 ? ctx->mv_keys : 1; trk.t0 = ctx->mv_t0; trk.dt = ctx->mv_dt;
+    return trk;
 }
 static int moving_ready(mpcmp_ctx *ctx) {
     if (!ctx->mv_ready) { HIPCHK(ctx, moving_prepare()); ctx->mv_ready = true; }
@@ -1148,11 +1150,7 @@ static int clearance_timed_check(mpcmp_ctx *ctx, const char *who, int B, const d
                    "pointers (but prof, t_start, d_min_all) required";
         return MPCMP_EINVAL;
     }
-    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
-        return MPCMP_EINVAL;
-    }
-    return MPCMP_OK;
+    return obstacle_sets_check(ctx, B);
 }
 
 extern "C" int mpcmp_clearance_timed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, int n_grid, const double *d_prof,
@@ -1161,8 +1159,8 @@ extern "C" int mpcmp_clearance_timed_batch_device(mpcmp_ctx *ctx, int B, const d
     if (int rc = clearance_timed_check(ctx, "mpcmp_clearance_timed_batch", B, d_sx, d_sT, n_grid, d_prof, n_pts, margin, self_gap, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (int rc = moving_ready(ctx)) return rc;
-    MvTracks trk;
-    const ClrTables t = moving_tables(ctx, &trk);
+    const ClrTables t = clearance_tables(ctx);
+    const MvTracks trk = moving_tracks(ctx);
     const MvPlans p = {d_sx, d_sT, d_prof, d_t_start, n_grid};
     HIPCHK(ctx, clearance_timed_launch(t, trk, p, B, n_pts, margin, self_gap, d_out, (hipStream_t)hip_stream));
     return MPCMP_OK;
@@ -1189,8 +1187,8 @@ extern "C" int mpcmp_start_delay_batch_device(mpcmp_ctx *ctx, int B, const doubl
     if (K < 1 || K > MV_MAX_DELAYS || !d_delays) { ctx->err = "mpcmp_start_delay_batch: 1 <= K <= 256 delays required"; return MPCMP_EINVAL; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (int rc = moving_ready(ctx)) return rc;
-    MvTracks trk;
-    const ClrTables t = moving_tables(ctx, &trk);
+    const ClrTables t = clearance_tables(ctx);
+    const MvTracks trk = moving_tracks(ctx);
     const MvPlans p = {d_sx, d_sT, d_prof, nullptr, n_grid};
     HIPCHK(ctx, start_delay_launch(t, trk, p, B, K, d_delays, check_wait, n_pts, margin, self_gap, d_min_all, d_out, (hipStream_t)hip_stream));
     return MPCMP_OK;
@@ -1232,8 +1230,7 @@ extern "C" int mpcmp_sphere_tracks_batch_device(mpcmp_ctx *ctx, int B, const dou
     if (int rc = sphere_tracks_check(ctx, B, d_sx, d_sT, n_grid, d_prof, t0, dt, n_key, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (int rc = moving_ready(ctx)) return rc;
-    MvTracks trk;
-    const ClrTables t = moving_tables(ctx, &trk);
+    const ClrTables t = clearance_tables(ctx);
     const MvPlans p = {d_sx, d_sT, d_prof, d_t_start, n_grid};
     HIPCHK(ctx, sphere_tracks_launch(t, p, B, t0, dt, n_key, d_out, (hipStream_t)hip_stream));
     return MPCMP_OK;
@@ -1254,7 +1251,7 @@ extern "C" int mpcmp_sphere_tracks_batch(mpcmp_ctx *ctx, int B, const double *sx
     return sg.finish();
 }
 
-// ---- certified clearance in a moving world (include/mpcmp_moving_cert.h; the kernel is in moving_cert.hip, the rule in moving_cert_rule.hpp) ----
+// ---- certified clearance in a moving world (include/mpcmp_moving_cert.h; the kernel is k_clearance_cert with a timeline, the rule moving_cert_rule.hpp) ----
 static int clearance_cert_timed_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int self_gap, int n_start, int n_rest,
                                       int max_depth, const mpcmp_clearance *out) {
     if (!ctx) { g_err = "mpcmp_clearance_certified_timed_batch: no context"; return MPCMP_EINVAL; }
@@ -1264,11 +1261,7 @@ static int clearance_cert_timed_check(mpcmp_ctx *ctx, int B, const double *sx, c
                    "[0, 16], a finite margin, self_gap >= 0 and all pointers (but t_start, wait_before, hold_after, cert) required";
         return MPCMP_EINVAL;
     }
-    if (ctx->clr_sets > 1 && B > ctx->clr_sets) {
-        ctx->err = "more problems (" + std::to_string(B) + ") than obstacle sets (" + std::to_string(ctx->clr_sets) + "): see mpcmp_set_obstacles";
-        return MPCMP_EINVAL;
-    }
-    return MPCMP_OK;
+    return obstacle_sets_check(ctx, B);
 }
 
 extern "C" int mpcmp_clearance_certified_timed_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, const double *d_t_start,
@@ -1277,11 +1270,11 @@ extern "C" int mpcmp_clearance_certified_timed_batch_device(mpcmp_ctx *ctx, int 
                                                             void *hip_stream) {
     if (int rc = clearance_cert_timed_check(ctx, B, d_sx, d_sT, margin, self_gap, n_start, n_rest, max_depth, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!ctx->mvc_ready) { HIPCHK(ctx, moving_cert_prepare()); ctx->mvc_ready = true; }
-    MvTracks trk;
-    const ClrTables t = moving_tables(ctx, &trk);
-    const MvcPlans p = {d_sx, d_sT, d_t_start, d_wait, d_hold};
-    HIPCHK(ctx, moving_cert_launch(t, trk, p, B, margin, self_gap, n_start, n_rest, max_depth, d_out, d_cert, (hipStream_t)hip_stream));
+    if (!ctx->clr_cert_ready) { HIPCHK(ctx, clearance_cert_prepare()); ctx->clr_cert_ready = true; }
+    const ClrTables t = clearance_tables(ctx);
+    const MvTracks trk = moving_tracks(ctx);
+    const CertPlans p = {d_sx, d_sT, d_t_start, d_wait, d_hold};
+    HIPCHK(ctx, clearance_cert_launch(t, &trk, p, B, margin, self_gap, n_start, n_rest, max_depth, d_out, d_cert, (hipStream_t)hip_stream));
     return MPCMP_OK;
 }
 
@@ -1436,10 +1429,7 @@ extern "C" int mpcmp_clearance_field_batch_device(mpcmp_ctx *ctx, int B, const d
                                                   mpcmp_clearance *d_out, void *hip_stream) {
     if (int rc = clearance_field_check(ctx, B, d_sx, d_sT, n_pts, margin, d_out)) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    ClrTables t;
-    t.d_model = ctx->d_model; t.narm = ctx->narm; t.nseg = ctx->nseg;
-    t.d_sph = ctx->d_clr_sph; t.n_sph[0] = ctx->clr_nsph[0]; t.n_sph[1] = ctx->narm > 1 ? ctx->clr_nsph[1] : 0;
-    t.d_obs = nullptr; t.n_obs = 0; t.obs_stride = 0;
+    const ClrTables t = clearance_tables(ctx);      // (the obstacle sets are not read)
     if (!ctx->fld_ready) { HIPCHK(ctx, field_prepare()); ctx->fld_ready = true; }
     HIPCHK(ctx, clearance_field_launch(t, field_arrays(ctx, ctx->fld_desc), B, d_sx, d_sT, n_pts, margin, d_out, (hipStream_t)hip_stream));
     return MPCMP_OK;

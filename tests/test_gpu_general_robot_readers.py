@@ -2,8 +2,8 @@
 
 tests/test_gpu_general_robot.py took the rigid-body leaf kernels, k_clearance, the pose targets and the QP paths off the Panda.  The kernels that
 read a finished plan came later, each with its own chain code or its own way of indexing the per-arm and per-problem model array, and saw only
-Panda constants: k_limits, k_retime, k_sample_retimed, k_limits_retimed, k_sample_route, k_clearance_cert, the kernels of moving.hip and
-k_clearance_cert_timed.  Here they run on general_11, tilted_14 (gravity with three components), dual_21 (two DIFFERENT chains) and general_12 /
+Panda constants: k_limits, k_retime, k_sample_retimed, k_limits_retimed, k_sample_route, k_clearance_cert without and with a timeline, and the kernels
+of moving.hip.  Here they run on general_11, tilted_14 (gravity with three components), dual_21 (two DIFFERENT chains) and general_12 /
 dual_21 under per-problem payload rows, on the cases tests/test_general_robot_readers_host.py chooses and qualifies on the CPU (its docstring states
 the shapes, the bounds and the fairness conditions, which are asserted here again on the same cached references), against the same references and
 with the same check functions as the Panda modules.  A kernel that stages arm 0's placements for arm 1, indexes b * mstride + a wrongly, drops a
