@@ -29,8 +29,8 @@
  *     is at most h (sqrt(d2[v]) + |e|) from x, and |e| <= sqrt(3)/2).
  *   - Inside an occupied voxel sd_field is negative (d2 = 0).  That signals a hit; it is NOT a penetration depth.
  *   - sd_field(x) <= max(sd_true(x), 0).
- *   - The true distance is 1-Lipschitz and sd_field lies below it, so a certified check may use sd_field at interval midpoints unchanged.  (No
- *     such check is part of this interface.)
+ *   - The true distance is 1-Lipschitz and sd_field lies below it, so a certified check may use sd_field at interval midpoints unchanged:
+ *     mpcmp_clearance_certified_field_batch (mpcmp_field_cert.h) is that check, and states what its certificate means.
  * CLEARANCE of robot sphere s: sd_field(c_s) - r_s, the world centres c_s from the chain of mpcmp.h.  The record is mpcmp_clearance: `other` is
  *   the linear index of the voxel read at d_min; ties of d_min go to the lowest sample, then the lowest sphere; n_hit, t_first, status and
  *   MPCMP_CLR_NAN are as in mpcmp_clearance_batch.  With no spheres, or on an empty field, the "no pair" record of that function.

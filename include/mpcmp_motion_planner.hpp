@@ -371,6 +371,25 @@ class MotionPlanner {
         }
         return r;
     }
+    // certified clearance record of the last solution against the voxel world (include/mpcmp_field_cert.h): status 0 means clear of the occupied
+    // cubes by `margin` at EVERY time of the plan; `other` is the linear index of a voxel.  *cert (may be null): the certificate.  merge: both
+    // records joined with those of check_clearance_certified(margin, self_gap, n_start, max_depth) by mpcmp_clearance_merge_batch and
+    // mpcmp_clearance_cert_merge_batch; *source (may be null) is then 1 where d_min is the field's
+    mpcmp_clearance check_clearance_certified_field(double margin = 0.0, int n_start = 4, int max_depth = 10, mpcmp_clearance_cert *cert = nullptr,
+                                                    bool merge = false, int self_gap = 0, int *source = nullptr) {
+        mpcmp_clearance r;
+        mpcmp_clearance_cert c;
+        chk(mpcmp_clearance_certified_field_batch(ctx_, 1, sol_x_.data(), &sol_T_, margin, n_start, max_depth, &r, &c));
+        if (source) *source = 1;
+        if (merge) {
+            mpcmp_clearance_cert ca;
+            const mpcmp_clearance a = check_clearance_certified(margin, self_gap, n_start, max_depth, &ca);
+            chk(mpcmp_clearance_merge_batch(ctx_, 1, &a, &r, &r, source));
+            chk(mpcmp_clearance_cert_merge_batch(ctx_, 1, &ca, &c, &c));
+        }
+        if (cert) *cert = c;
+        return r;
+    }
     // The obstacles of set_obstacles that move (include/mpcmp_moving.h): track_of [n_obs] (-1: stands still), offsets [n_tracks][n_key][3] on the
     // world clock t0 + k dt.  n_tracks == 0: the world stands still again, as it does after the next set_obstacles
     void set_moving_obstacles(int n_obs, const int *track_of, int n_tracks, int n_key, double t0, double dt, const double *offsets) {

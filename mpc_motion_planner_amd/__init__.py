@@ -16,6 +16,7 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    CLR_UNDECIDED, CLEARANCE_CERT_DTYPE, clearance_certified_one, clearance_certified_timed_one,
                    START_DELAY_DTYPE, MAX_TRACKS, MAX_TRACK_KEYS, MAX_DELAYS, track_offset, clearance_timed_one, start_delay_one,
                    FIELD_DESC_DTYPE, FIELD_EMPTY, FIELD_MAX_DIM, FIELD_MAX_VOXELS, field_desc, field_edt, field_sd, clearance_field_config,
+                   clearance_certified_field_one,
                    spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
                    ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
                    LIMITS_SPEC_DTYPE, LIMITS_DTYPE, LIM_GROUPS, LIM_Q, LIM_QD, LIM_QDD, LIM_TAU, LIM_HEIGHT, LIM_TOOL_LIN, LIM_TOOL_ANG, LIM_NAN, limits_spec, limits_config,
@@ -38,6 +39,7 @@ __all__ = ["TOOL_LINE_SPEC_DTYPE", "TOOL_LINE_DTYPE", "TOOL_DEV_DTYPE", "TL_STOP
            "START_DELAY_DTYPE", "MAX_TRACKS", "MAX_TRACK_KEYS", "MAX_DELAYS", "track_offset", "clearance_timed_one", "start_delay_one",
            "spheres", "obstacle", "link_spheres", "clearance_config",
            "FIELD_DESC_DTYPE", "FIELD_EMPTY", "FIELD_MAX_DIM", "FIELD_MAX_VOXELS", "field_desc", "field_edt", "field_sd", "clearance_field_config",
+           "clearance_certified_field_one",
            "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",
            "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate",
            "LIMITS_SPEC_DTYPE", "LIMITS_DTYPE", "LIM_GROUPS", "LIM_Q", "LIM_QD", "LIM_QDD", "LIM_TAU", "LIM_HEIGHT", "LIM_TOOL_LIN", "LIM_TOOL_ANG", "LIM_NAN", "limits_spec", "limits_config",

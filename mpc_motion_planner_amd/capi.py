@@ -208,6 +208,12 @@ ABI_FIELD = {
     "mpcmp_get_field": "ppp", "mpcmp_clearance_field_batch": "pippidp", "mpcmp_clearance_field_batch_device": "pippidpp",
     "mpcmp_clearance_merge_batch": "pipppp", "mpcmp_clearance_merge_batch_device": "pippppp",
 }
+# ... and every function include/mpcmp_field_cert.h declares (certified clearance against a voxel world, the certificate merge), in its order
+ABI_FIELD_CERT = {
+    "mpcmp_clearance_certified_field_batch": "pippdiipp", "mpcmp_clearance_certified_field_batch_device": "pippdiippp",
+    "mpcmp_clearance_certified_field_one": "piipppppddiipp",
+    "mpcmp_clearance_cert_merge_batch": "pippp", "mpcmp_clearance_cert_merge_batch_device": "pipppp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -264,7 +270,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()) + list(ABI_FIELD.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()) + list(ABI_FIELD.items()) + list(ABI_FIELD_CERT.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -532,6 +538,27 @@ def clearance_field_config(models, spheres_per_arm, desc, d2, q):
     check(lib().mpcmp_clearance_field_config(arr, narm, host(cnt), host(tab), desc.ctypes.data, host(d2), host(q), C.byref(d), C.byref(sp),
                                              C.byref(vx)))
     return d.value, sp.value, vx.value
+
+
+def clearance_certified_field_one(models, num_seg, spheres_per_arm, desc, d2, x, T, margin=0.0, n_start=4, max_depth=10):
+    """mpcmp_clearance_certified_field_one: the certified check of ONE plan x [N][14 narm] of duration T against the field d2 of the grid desc on the
+    host (no context, no GPU).  models and spheres_per_arm as for clearance_config, desc and d2 as for field_sd.  Returns (the CLEARANCE_DTYPE
+    record, the CLEARANCE_CERT_DTYPE record)."""
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models); N = 3 * int(num_seg) + 1
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    desc = _field_desc_arg(desc); d2 = _field_array(desc, d2, np.uint32, "d2")
+    x = f64(x).reshape(N, 14 * narm)
+    rec, cert = np.zeros(1, dtype=CLEARANCE_DTYPE), np.zeros(1, dtype=CLEARANCE_CERT_DTYPE)
+    check(lib().mpcmp_clearance_certified_field_one(arr, narm, int(num_seg), host(cnt), host(tab), desc.ctypes.data, host(d2), host(x), float(T),
+                                                    float(margin), int(n_start), int(max_depth), host(rec), host(cert)))
+    return rec[0], cert[0]
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

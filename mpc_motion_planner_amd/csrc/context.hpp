@@ -72,6 +72,7 @@ struct mpcmp_ctx {
     size_t fld_cap = 0;
     bool fld_set = false;
     bool fld_ready = false;          // the dynamic-LDS ceiling of k_clearance_field, by the first field check
+    bool fld_cert_ready = false;     // ... and of k_clearance_cert_field, by the first certified field check (include/mpcmp_field_cert.h)
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
     // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;

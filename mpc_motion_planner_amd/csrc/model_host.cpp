@@ -27,6 +27,7 @@
 #include "moving_rule.hpp"
 #include "moving_cert_rule.hpp"
 #include "field_rule.hpp"
+#include "field_cert_rule.hpp"
 
 using namespace mpcmp;
 
@@ -898,5 +899,76 @@ extern "C" int mpcmp_clearance_field_config(const mpcmp_model *models, int narm,
     *d_min = best;
     if (sphere) *sphere = bs;
     if (voxel) *voxel = bv;
+    return MPCMP_OK;
+}
+
+// ---- certified clearance against a voxel world on the host (include/mpcmp_field_cert.h): one plan through the source the kernel runs
+// (field_cert_rule.hpp on top of clearance_cert.hpp and field_rule.hpp) ----
+extern "C" int mpcmp_clearance_certified_field_one(const mpcmp_model *models, int narm, int num_seg, const int *n_spheres, const mpcmp_sphere *spheres,
+                                                   const mpcmp_field_desc *desc, const unsigned *d2, const double *x, double T, double margin, int n_start,
+                                                   int max_depth, mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (!models || narm < 1 || narm > 2 || num_seg < 1 || !n_spheres || !x || !out || !desc || !d2 || !fld_desc_ok(*desc) || !std::isfinite(margin) ||
+        n_start < 1 || n_start > CERT_CAP || (long)num_seg * n_start > CERT_CAP || max_depth < 0 || max_depth > CERT_MAX_DEPTH) {
+        g_err = "mpcmp_clearance_certified_field_one: one or two arms, num_seg >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a "
+                "finite margin, a valid grid and all pointers (but cert) required";
+        return MPCMP_EINVAL;
+    }
+    MvHost H;          // (no obstacles, no tracks, and T is not tested)
+    if (int rc = host_tables(models, narm, num_seg, n_spheres, spheres, 0, nullptr, x, &H)) return rc;
+    if (H.nan) {
+        *out = clr_nan_record();
+        if (cert) *cert = cert_nan_record();
+        return MPCMP_OK;
+    }
+    const int nq = 7 * narm, nsph = H.nsph, n0 = num_seg * n_start;
+    std::vector<double> reach(7 * (nsph > 0 ? nsph : 1));
+    for (int s = 0; s < nsph; s++) cert_reach(H.mk.data() + 84 * H.arm[s] + 9, 12, H.jnt[s], spheres[s].c, reach.data() + 7 * s);
+    CertBest B;
+    int best_v = 0;
+    std::vector<int> cur(n0), nxt;
+    for (int i = 0; i < n0; i++) cur[i] = i;
+    for (int l = 0; !cur.empty(); l++) {
+        B.depth = l;
+        nxt.clear();
+        int n_split = 0;
+        for (int i : cur) {
+            const CertInterval v = cert_interval(n0, n_start, l, i);
+            const unsigned tk = cert_tkey(l, i);
+            double dev[14], sc[28], fr[2 * 84];
+            for (int j = 0; j < nq; j++) {
+                double qm;
+                dev[j] = cert_deviation(H.nodes.data() + j, nq, num_seg, v, &qm);
+                sc[2 * j] = std::sin(qm); sc[2 * j + 1] = std::cos(qm);
+            }
+            for (int a = 0; a < narm; a++) cert_frames(H.mk.data() + 84 * a, sc + 14 * a, fr + 84 * a);
+            double d_mid = INFINITY, L = INFINITY;
+            for (int s = 0; s < nsph; s++) {
+                double c[3];
+                int vox;
+                cert_centre(fr + 84 * H.arm[s] + 12 * H.jnt[s], spheres[s].c, c);
+                const double d = fcert_distance(*desc, d2, c, spheres[s].r, &vox);
+                const double D = cert_motion(reach.data() + 7 * s, dev + 7 * H.arm[s]);
+                const unsigned long long key = fcert_key(tk, s);
+                if (d < INFINITY && cert_better(d, key, B.d, B.k)) { B.d = d; B.k = key; best_v = vox; }
+                d_mid = std::fmin(d_mid, d); L = std::fmin(L, d - D);
+            }
+            B.n_eval++;
+            int what = cert_decide(d_mid, L, margin, l, max_depth);
+            if (what == CERT_SPLIT_IT) {
+                if (n_split < CERT_SPLIT) { n_split++; nxt.push_back(2 * i); nxt.push_back(2 * i + 1); continue; }
+                what = CERT_UNDECIDED;          // (the capacity rule)
+            }
+            if (what == CERT_HIT) { B.n_hit++; if (tk < B.first) B.first = tk; }
+            else if (what == CERT_CLEAR) B.n_clear++;
+            else B.n_und++;
+            const unsigned long long lk = cert_key(tk, 0, 0, 0);
+            if (cert_better(L, lk, B.L, B.Lk)) { B.L = L; B.Lk = lk; }
+        }
+        cur.swap(nxt);
+    }
+    mpcmp_clearance_cert c;
+    cert_records(B, [&](unsigned tkey) { return cert_time(n0, tkey) * T; }, out, &c);
+    if (B.k != CERT_NO_PAIR) out->other = best_v;
+    if (cert) *cert = c;
     return MPCMP_OK;
 }

@@ -24,6 +24,7 @@
 #include "clearance.hpp"
 #include "moving.hpp"
 #include "field.hpp"
+#include "field_cert.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
 #include "retimed_check.hpp"
@@ -1468,6 +1469,68 @@ extern "C" int mpcmp_clearance_merge_batch(mpcmp_ctx *ctx, int B, const mpcmp_cl
     if (source) sg.out(&dsrc, source, B);
     if (int rc = sg.upload()) return rc;
     HIPCHK(ctx, clearance_merge_launch(B, da, db, dout, dsrc, ctx->stream));
+    return sg.finish();
+}
+
+// ---- certified clearance against the voxel world (include/mpcmp_field_cert.h; the kernels are in field_cert.hip, the rule in field_cert_rule.hpp) ----
+static int clearance_cert_field_check(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int n_start, int max_depth,
+                                      const mpcmp_clearance *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_certified_field_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !sx || !sT || !out || !std::isfinite(margin) || n_start < 1 || n_start > MPCMP_CLR_CERT_CAPACITY ||
+        ctx->nseg * n_start > MPCMP_CLR_CERT_CAPACITY || max_depth < 0 || max_depth > 16) {
+        ctx->err = "mpcmp_clearance_certified_field_batch: B >= 1, n_start >= 1 with num_seg n_start <= 4096, max_depth in [0, 16], a finite margin "
+                   "and all pointers (but cert) required";
+        return MPCMP_EINVAL;
+    }
+    if (!ctx->fld_set) { ctx->err = "mpcmp_clearance_certified_field_batch: no field is set: see mpcmp_set_field"; return MPCMP_EINVAL; }
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_field_batch_device(mpcmp_ctx *ctx, int B, const double *d_sx, const double *d_sT, double margin, int n_start,
+                                                            int max_depth, mpcmp_clearance *d_out, mpcmp_clearance_cert *d_cert, void *hip_stream) {
+    if (int rc = clearance_cert_field_check(ctx, B, d_sx, d_sT, margin, n_start, max_depth, d_out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const ClrTables t = clearance_tables(ctx);      // (the obstacle sets are not read)
+    if (!ctx->fld_cert_ready) { HIPCHK(ctx, field_cert_prepare()); ctx->fld_cert_ready = true; }
+    HIPCHK(ctx, clearance_cert_field_launch(t, field_arrays(ctx, ctx->fld_desc), B, d_sx, d_sT, margin, n_start, max_depth, d_out, d_cert,
+                                            (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_certified_field_batch(mpcmp_ctx *ctx, int B, const double *sx, const double *sT, double margin, int n_start,
+                                                     int max_depth, mpcmp_clearance *out, mpcmp_clearance_cert *cert) {
+    if (int rc = clearance_cert_field_check(ctx, B, sx, sT, margin, n_start, max_depth, out)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    double *dx, *dT;
+    mpcmp_clearance *dout;
+    mpcmp_clearance_cert *dcert = nullptr;
+    sg.in(&dx, sx, (size_t)ctx->nx * ctx->N * B); sg.in(&dT, sT, B); sg.out(&dout, out, B);
+    if (cert) sg.out(&dcert, cert, B);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = mpcmp_clearance_certified_field_batch_device(ctx, B, dx, dT, margin, n_start, max_depth, dout, dcert, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+extern "C" int mpcmp_clearance_cert_merge_batch_device(mpcmp_ctx *ctx, int B, const mpcmp_clearance_cert *d_a, const mpcmp_clearance_cert *d_b,
+                                                       mpcmp_clearance_cert *d_out, void *hip_stream) {
+    if (!ctx) { g_err = "mpcmp_clearance_cert_merge_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !d_a || !d_b || !d_out) { ctx->err = "mpcmp_clearance_cert_merge_batch: B >= 1 and a, b and out required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, clearance_cert_merge_launch(B, d_a, d_b, d_out, (hipStream_t)hip_stream));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_clearance_cert_merge_batch(mpcmp_ctx *ctx, int B, const mpcmp_clearance_cert *a, const mpcmp_clearance_cert *b,
+                                                mpcmp_clearance_cert *out) {
+    if (!ctx) { g_err = "mpcmp_clearance_cert_merge_batch: no context"; return MPCMP_EINVAL; }
+    if (B < 1 || !a || !b || !out) { ctx->err = "mpcmp_clearance_cert_merge_batch: B >= 1 and a, b and out required"; return MPCMP_EINVAL; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    Stage sg(ctx);
+    mpcmp_clearance_cert *da, *db, *dout;
+    sg.in(&da, a, B); sg.in(&db, b, B); sg.out(&dout, out, B);
+    if (int rc = sg.upload()) return rc;
+    HIPCHK(ctx, clearance_cert_merge_launch(B, da, db, dout, ctx->stream));
     return sg.finish();
 }
 

@@ -316,6 +316,39 @@ class Solver:
     def clearance_merge_device(self, B, a, b, out, source=0, stream=0):
         check(lib().mpcmp_clearance_merge_batch_device(self._ctx, int(B), a or None, b or None, out or None, source or None, stream or None), self._ctx)
 
+    # -- certified clearance against the voxel world, and the merge of two certificates (include/mpcmp_field_cert.h)
+    def clearance_certified_field(self, sx, sT, margin=0.0, n_start=4, max_depth=10):
+        """mpcmp_clearance_certified_field_batch: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE [B]) of the trajectories sx [B][N][nx], sT [B]
+        against the field: status 0 means clear of the occupied cubes by `margin` at EVERY time of the plan; `other` is a voxel"""
+        sx, sT = f64(sx), f64(sT).reshape(-1); B = sT.shape[0]
+        if sx.shape != (B, self.N, self.nx):
+            raise ValueError("sx must be [B][%d][%d] with sT [B], got %s and %s" % (self.N, self.nx, sx.shape, sT.shape))
+        out, cert = np.zeros(B, dtype=capi.CLEARANCE_DTYPE), np.zeros(B, dtype=capi.CLEARANCE_CERT_DTYPE)
+        check(lib().mpcmp_clearance_certified_field_batch(self._ctx, B, host(sx), host(sT), float(margin), int(n_start), int(max_depth), host(out),
+                                                          host(cert)), self._ctx)
+        return out, cert
+
+    def clearance_certified_field_device(self, B, sol_x, sol_T, margin, n_start, max_depth, out, cert=0, stream=0):
+        check(lib().mpcmp_clearance_certified_field_batch_device(self._ctx, int(B), sol_x or None, sol_T or None, float(margin), int(n_start),
+                                                                 int(max_depth), out or None, cert or None, stream or None), self._ctx)
+
+    def clearance_cert_merge(self, a, b, out=None):
+        """mpcmp_clearance_cert_merge_batch: one CLEARANCE_CERT_DTYPE record per plan from the certificates a [B] and b [B]; out: an array to write
+        into (it may be a or b), a new one by default"""
+        a = capi._records(a, capi.CLEARANCE_CERT_DTYPE, "clearance_cert").reshape(-1)
+        b = capi._records(b, capi.CLEARANCE_CERT_DTYPE, "clearance_cert").reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError("a and b must hold one record per plan each, got %s and %s" % (a.shape, b.shape))
+        if out is None:
+            out = np.zeros(a.shape[0], dtype=capi.CLEARANCE_CERT_DTYPE)
+        elif out.dtype != capi.CLEARANCE_CERT_DTYPE or out.shape != a.shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous CLEARANCE_CERT_DTYPE array of the shape of a")
+        check(lib().mpcmp_clearance_cert_merge_batch(self._ctx, a.shape[0], host(a), host(b), host(out)), self._ctx)
+        return out
+
+    def clearance_cert_merge_device(self, B, a, b, out, stream=0):
+        check(lib().mpcmp_clearance_cert_merge_batch_device(self._ctx, int(B), a or None, b or None, out or None, stream or None), self._ctx)
+
     # -- clearance in a moving world: tracked obstacles, timed checks, start delays, a plan as another robot's world (include/mpcmp_moving.h)
     def set_obstacle_tracks(self, track_of, offsets, t0, dt):
         """the track table of the obstacle sets in force: track_of [n_obs] or [n_sets][n_obs] (-1: the obstacle stands still), offsets
@@ -1216,6 +1249,28 @@ class BatchMotionPlanner:
                                                          max_depth)
             return self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3], cert.reshape(r["sol_T"].shape)
         return self._solver.clearance_certified(self._sol[0], self._sol[2], margin, self_gap, n_start, max_depth)
+
+    def check_clearance_certified_field(self, margin=0.0, n_start=4, max_depth=10, merge=True, self_gap=0):
+        """certified clearance of the last solve_trajectory's solutions against the voxel world (include/mpcmp_field_cert.h): (capi.CLEARANCE_DTYPE
+        [B], capi.CLEARANCE_CERT_DTYPE); status 0 holds at every time of the plan.  Of routes: the legs' records joined per route [B] and the
+        certificates per leg [B][M + 1], as check_clearance_certified.  merge: when obstacles are set (set_obstacles) or self_gap > 0, both records
+        are merged with those of check_clearance_certified(margin, self_gap, n_start, max_depth), and (records, certificates, source [B]) is returned:
+        source 1 where d_min is the field's and `other` a voxel"""
+        if self._route is not None:
+            r = self._route
+            L = r["sol_T"].size
+            clr, cert = self._solver.clearance_certified_field(r["sol_x"].reshape(L, self._solver.N, 14), r["sol_T"].reshape(L), margin, n_start,
+                                                               max_depth)
+            clr = self._solver.route_join(r["sol_x"], r["sol_u"], r["sol_T"], r["info"], clr.reshape(r["sol_T"].shape))[3]
+            cert = cert.reshape(r["sol_T"].shape)
+        else:
+            clr, cert = self._solver.clearance_certified_field(self._sol[0], self._sol[2], margin, n_start, max_depth)
+        if not merge or not (getattr(self, "_has_obstacles", False) or self_gap > 0):
+            return clr, cert
+        pclr, pcert = self.check_clearance_certified(margin, self_gap, n_start, max_depth)
+        mclr, src = self._solver.clearance_merge(pclr, clr)
+        mcert = self._solver.clearance_cert_merge(np.ascontiguousarray(pcert).reshape(-1), np.ascontiguousarray(cert).reshape(-1)).reshape(cert.shape)
+        return mclr, mcert, src
 
     def check_limits(self, n_pts=200, tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):
         """limit records (capi.LIMITS_DTYPE) of the last solve_trajectory's solutions between their nodes, [B]; of routes: one record per leg,
