@@ -480,6 +480,7 @@ int mpcmp_select_clear_batch_device(mpcmp_ctx *ctx, int B, const double *d_sol_T
 #include "mpcmp_moving_cert.h"
 #include "mpcmp_field.h"
 #include "mpcmp_field_cert.h"
+#include "mpcmp_frame.h"
 
 /* ---- via-point routes: plan, join, sample and check multi-leg moves ----
  * A route is x0 -> via_0 -> .. -> via_{M-1} -> xf, passed without stopping.  With the joint state (q, qd) fixed at a via, the legs on either side are

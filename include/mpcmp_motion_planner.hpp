@@ -357,6 +357,24 @@ class MotionPlanner {
         field_spheres(sphere_radius, sphere_spacing);
         chk(mpcmp_set_field_points(ctx_, &desc, n_points, points));
     }
+    // Camera frames (include/mpcmp_frame.h): the same worlds with the robot itself, seen by the camera at the posture robot_q [7] (null: no
+    // filter), removed: points, pixels or occupied voxel centres within r_s + robot_pad of a skeleton sphere.  keep: added to the world in force.
+    // The counts of the last of the three calls are kept in frame_stats
+    mpcmp_frame_stats frame_stats = {};
+    void set_point_cloud_filtered(const mpcmp_field_desc &desc, int n_points, const double *points, const double *robot_q, double robot_pad,
+                                  bool keep = false, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        field_spheres(sphere_radius, sphere_spacing);
+        chk(mpcmp_set_field_points_filtered(ctx_, &desc, n_points, points, robot_q, robot_pad, keep ? MPCMP_FRAME_KEEP : 0, &frame_stats));
+    }
+    void set_depth_image(const mpcmp_field_desc &desc, const mpcmp_camera &camera, const void *depth, int depth_type, const double *robot_q = nullptr,
+                         double robot_pad = 0.0, bool keep = false, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        field_spheres(sphere_radius, sphere_spacing);
+        chk(mpcmp_set_field_depth(ctx_, &desc, &camera, depth, depth_type, robot_q, robot_pad, keep ? MPCMP_FRAME_KEEP : 0, &frame_stats));
+    }
+    void carve_robot(const double *robot_q, double robot_pad, double sphere_radius = 0.06, double sphere_spacing = 0.08) {
+        field_spheres(sphere_radius, sphere_spacing);
+        chk(mpcmp_field_carve(ctx_, robot_q, robot_pad, &frame_stats));
+    }
     // the grid in force and (d2 may be null) its squared distance field d2 [n[2]][n[1]][n[0]] as the GPU built it
     void voxel_field(mpcmp_field_desc *desc, unsigned *d2 = nullptr) { chk(mpcmp_get_field(ctx_, desc, d2)); }
     // clearance record of the last solution against the voxel world (`other` is the linear index of a voxel).  merge: joined with the record of

@@ -16,6 +16,8 @@ from .capi import (STATUS_NAN, STATUS_NOT_PD, STATUS_XCH_DEAD, STATUS_QP_CAPPED,
                    CLR_UNDECIDED, CLEARANCE_CERT_DTYPE, clearance_certified_one, clearance_certified_timed_one,
                    START_DELAY_DTYPE, MAX_TRACKS, MAX_TRACK_KEYS, MAX_DELAYS, track_offset, clearance_timed_one, start_delay_one,
                    FIELD_DESC_DTYPE, FIELD_EMPTY, FIELD_MAX_DIM, FIELD_MAX_VOXELS, field_desc, field_edt, field_sd, clearance_field_config,
+                   CAMERA_DTYPE, FRAME_STATS_DTYPE, DEPTH_U16, DEPTH_F32, FRAME_KEEP, FRAME_MAX_PIXELS, camera, frame_spheres, frame_points_one,
+                   frame_depth_one, frame_carve_one,
                    clearance_certified_field_one,
                    spheres, obstacle, link_spheres, clearance_config, BOUNDS_DTYPE, bounds_from_config, bounds_from_margins,
                    ROUTE_SEAM_DTYPE, route_via_velocity, route_locate,
@@ -39,6 +41,8 @@ __all__ = ["TOOL_LINE_SPEC_DTYPE", "TOOL_LINE_DTYPE", "TOOL_DEV_DTYPE", "TL_STOP
            "START_DELAY_DTYPE", "MAX_TRACKS", "MAX_TRACK_KEYS", "MAX_DELAYS", "track_offset", "clearance_timed_one", "start_delay_one",
            "spheres", "obstacle", "link_spheres", "clearance_config",
            "FIELD_DESC_DTYPE", "FIELD_EMPTY", "FIELD_MAX_DIM", "FIELD_MAX_VOXELS", "field_desc", "field_edt", "field_sd", "clearance_field_config",
+           "CAMERA_DTYPE", "FRAME_STATS_DTYPE", "DEPTH_U16", "DEPTH_F32", "FRAME_KEEP", "FRAME_MAX_PIXELS", "camera", "frame_spheres", "frame_points_one",
+           "frame_depth_one", "frame_carve_one",
            "clearance_certified_field_one",
            "BOUNDS_DTYPE", "bounds_from_config", "bounds_from_margins",
            "ROUTE_SEAM_DTYPE", "route_via_velocity", "route_locate",

@@ -73,6 +73,12 @@ MAX_SPHERES, MAX_OBSTACLES = 64, 256
 # the grid of a voxel world (mpcmp_field_desc, include/mpcmp_field.h): 48 bytes; the field entry of an empty world and the limits of a grid
 FIELD_DESC_DTYPE = np.dtype([("origin", "f8", 3), ("h", "f8"), ("n", "i4", 3), ("pad", "i4")])
 FIELD_EMPTY, FIELD_MAX_DIM, FIELD_MAX_VOXELS = 0xFFFFFFFF, 1024, 1 << 24
+# camera frames (mpcmp_camera, mpcmp_frame_stats, include/mpcmp_frame.h): 160 and 32 bytes; the depth types, the flag and the largest image
+CAMERA_DTYPE = np.dtype([("R", "f8", 9), ("t", "f8", 3), ("fx", "f8"), ("fy", "f8"), ("cx", "f8"), ("cy", "f8"), ("depth_scale", "f8"), ("z_min", "f8"),
+                         ("z_max", "f8"), ("width", "i4"), ("height", "i4")])
+FRAME_STATS_DTYPE = np.dtype([("n_in", "i4"), ("n_invalid", "i4"), ("n_outside", "i4"), ("n_robot", "i4"), ("n_marked", "i4"), ("n_cleared", "i4"),
+                              ("pad", "i4", 2)])
+DEPTH_U16, DEPTH_F32, FRAME_KEEP, FRAME_MAX_PIXELS = 0, 1, 1, 1 << 22
 
 # records of the between-node limit checks (mpcmp_limits_spec, mpcmp_limits; include/mpcmp.h): 72 and 168 bytes
 LIMITS_SPEC_DTYPE = np.dtype([("tol", "f8", 7), ("tool_lin_max", "f8"), ("tool_ang_max", "f8")])
@@ -214,6 +220,15 @@ ABI_FIELD_CERT = {
     "mpcmp_clearance_certified_field_one": "piipppppddiipp",
     "mpcmp_clearance_cert_merge_batch": "pippp", "mpcmp_clearance_cert_merge_batch_device": "pipppp",
 }
+# ... and every function include/mpcmp_frame.h declares (camera frames as voxel worlds: the robot removed from clouds, depth images and grids), in
+# its order
+ABI_FRAME = {
+    "mpcmp_frame_spheres": "pipppdp", "mpcmp_frame_points_one": "pipppipp" + "dipp", "mpcmp_frame_depth_one": "pippppp" + "ipdipp",
+    "mpcmp_frame_carve_one": "pippppdpp",
+    "mpcmp_set_field_points_filtered": "ppippdip", "mpcmp_set_field_points_filtered_device": "ppippdipp",
+    "mpcmp_set_field_depth": "ppppipdip", "mpcmp_set_field_depth_device": "ppppipdipp",
+    "mpcmp_field_carve": "ppdp", "mpcmp_field_carve_device": "ppdpp",
+}
 _KINDS = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "l": C.c_long}
 _RETURNS_TEXT = ("mpcmp_version", "mpcmp_last_error")         # const char *; every other function returns int
 SYMBOLS = list(ABI)
@@ -270,7 +285,7 @@ def lib():
                                  "there is no CPU fallback" % _SO)
         _torch_runtime_first()
         L = C.CDLL(_SO)
-        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()) + list(ABI_FIELD.items()) + list(ABI_FIELD_CERT.items()):
+        for name, kinds in list(ABI.items()) + list(ABI_LIMITS.items()) + list(ABI_RETIME.items()) + list(ABI_ROUTE_RETIME.items()) + list(ABI_RETIMED_CHECK.items()) + list(ABI_TOOLPATH.items()) + list(ABI_CLEARANCE_CERT.items()) + list(ABI_MOVING.items()) + list(ABI_MOVING_CERT.items()) + list(ABI_FIELD.items()) + list(ABI_FIELD_CERT.items()) + list(ABI_FRAME.items()):
             f = getattr(L, name)
             f.argtypes = [_KINDS[k] for k in kinds]
             f.restype = C.c_char_p if name in _RETURNS_TEXT else C.c_int
@@ -559,6 +574,102 @@ def clearance_certified_field_one(models, num_seg, spheres_per_arm, desc, d2, x,
     check(lib().mpcmp_clearance_certified_field_one(arr, narm, int(num_seg), host(cnt), host(tab), desc.ctypes.data, host(d2), host(x), float(T),
                                                     float(margin), int(n_start), int(max_depth), host(rec), host(cert)))
     return rec[0], cert[0]
+
+
+def camera(R, t, fx, fy, cx, cy, width, height, depth_scale=1.0, z_min=0.0, z_max=np.inf):
+    """one CAMERA_DTYPE record (mpcmp_camera): R [3][3] and t [3] map the camera frame to the world frame, pixel (row v, column u) of depth d lies at
+    z = d depth_scale, p = (z (u - cx) / fx, z (v - cy) / fy, z); pixels with z outside [z_min, z_max] are invalid.  z_max must be finite for the
+    library (the default here is for the reader's convenience: pass the sensor's range)"""
+    c = np.zeros((), dtype=CAMERA_DTYPE)
+    c["R"] = f64(R).reshape(9); c["t"] = f64(t).reshape(3)
+    c["fx"], c["fy"], c["cx"], c["cy"] = float(fx), float(fy), float(cx), float(cy)
+    c["depth_scale"], c["z_min"], c["z_max"] = float(depth_scale), float(z_min), float(z_max)
+    c["width"], c["height"] = int(width), int(height)
+    return c
+
+
+def _camera_arg(cam):
+    cam = np.ascontiguousarray(cam).reshape(())
+    if cam.dtype != CAMERA_DTYPE:
+        raise ValueError("camera must be one CAMERA_DTYPE record (capi.camera)")
+    return cam
+
+
+def _depth_arg(cam, depth):
+    """(the image as a contiguous uint16 or float32 array of the camera's size, its depth type)"""
+    depth = np.asarray(depth)
+    if depth.dtype != np.uint16:
+        depth = depth.astype(np.float32, copy=False)
+    depth = np.ascontiguousarray(depth)
+    if depth.size != int(cam["width"]) * int(cam["height"]):
+        raise ValueError("depth must hold height x width = %d x %d entries, got %s" % (cam["height"], cam["width"], depth.shape))
+    return depth, (DEPTH_U16 if depth.dtype == np.uint16 else DEPTH_F32)
+
+
+def _frame_robot(models, spheres_per_arm, q):
+    """(the Model array, narm, the counts, the table, q or None) of the host statements of include/mpcmp_frame.h; with q None no robot is read"""
+    if q is None:
+        return None, 1, None, None, None
+    if isinstance(models, Model):
+        models = [models]; spheres_per_arm = [spheres_per_arm] if isinstance(spheres_per_arm, np.ndarray) else spheres_per_arm
+    narm = len(models)
+    arr = (Model * narm)(*[Model.from_buffer_copy(m) for m in models])
+    per = [_records(sp, SPHERE_DTYPE, "sphere").reshape(-1) for sp in spheres_per_arm]
+    if len(per) != narm:
+        raise ValueError("one sphere table per arm")
+    cnt = np.array([p.shape[0] for p in per], dtype=np.int32)
+    tab = np.ascontiguousarray(np.concatenate(per)) if per else np.zeros(0, dtype=SPHERE_DTYPE)
+    return arr, narm, cnt, tab, f64(q).reshape(7 * narm)
+
+
+def _frame_occ(desc, occ, keep):
+    n = [int(v) for v in desc["n"]]
+    if occ is None:
+        if keep:
+            raise ValueError("keep needs the occupancy to add to")
+        return np.zeros((n[2], n[1], n[0]), dtype=np.uint8)
+    return _field_array(desc, (np.asarray(occ) != 0).astype(np.uint8), np.uint8, "occ").copy()
+
+
+def frame_spheres(models, spheres_per_arm, q, pad):
+    """mpcmp_frame_spheres: the filter spheres [ns][4] = world centre, r + pad of the posture q [7 narm] on the host"""
+    arr, narm, cnt, tab, q = _frame_robot(models, spheres_per_arm, f64(q))
+    out = np.zeros((tab.shape[0], 4))
+    check(lib().mpcmp_frame_spheres(arr, narm, host(cnt), host(tab), host(q), float(pad), host(out) if out.size else out.ctypes.data))
+    return out
+
+
+def frame_points_one(models, spheres_per_arm, desc, points, q, pad, keep=False, occ=None):
+    """mpcmp_frame_points_one: (occ [n2][n1][n0] uint8, the FRAME_STATS_DTYPE record) of the cloud points [n][3] with the robot at q [7 narm] (None:
+    no filter) removed, on the host; keep: marked into a copy of `occ`"""
+    arr, narm, cnt, tab, q = _frame_robot(models, spheres_per_arm, q)
+    desc = _field_desc_arg(desc); pts = f64(points).reshape(-1, 3); occ = _frame_occ(desc, occ, keep)
+    st = np.zeros((), dtype=FRAME_STATS_DTYPE)
+    check(lib().mpcmp_frame_points_one(arr, narm, host(cnt) if cnt is not None else None, host(tab) if tab is not None else None, desc.ctypes.data,
+                                       pts.shape[0], host(pts), host(q) if q is not None else None, float(pad), FRAME_KEEP if keep else 0,
+                                       occ.ctypes.data, st.ctypes.data))
+    return occ, st
+
+
+def frame_depth_one(models, spheres_per_arm, desc, cam, depth, q, pad, keep=False, occ=None):
+    """mpcmp_frame_depth_one: the same for a depth image depth [height][width] (uint16, or anything else as float32) of the camera cam"""
+    arr, narm, cnt, tab, q = _frame_robot(models, spheres_per_arm, q)
+    desc = _field_desc_arg(desc); cam = _camera_arg(cam); depth, kind = _depth_arg(cam, depth); occ = _frame_occ(desc, occ, keep)
+    st = np.zeros((), dtype=FRAME_STATS_DTYPE)
+    check(lib().mpcmp_frame_depth_one(arr, narm, host(cnt) if cnt is not None else None, host(tab) if tab is not None else None, desc.ctypes.data,
+                                      cam.ctypes.data, depth.ctypes.data, kind, host(q) if q is not None else None, float(pad),
+                                      FRAME_KEEP if keep else 0, occ.ctypes.data, st.ctypes.data))
+    return occ, st
+
+
+def frame_carve_one(models, spheres_per_arm, desc, occ, q, pad):
+    """mpcmp_frame_carve_one: (a copy of occ with the robot at q carved out, the FRAME_STATS_DTYPE record) on the host"""
+    arr, narm, cnt, tab, q = _frame_robot(models, spheres_per_arm, q)
+    desc = _field_desc_arg(desc); occ = _frame_occ(desc, occ, True)
+    st = np.zeros((), dtype=FRAME_STATS_DTYPE)
+    check(lib().mpcmp_frame_carve_one(arr, narm, host(cnt) if cnt is not None else None, host(tab) if tab is not None else None, desc.ctypes.data,
+                                      host(q) if q is not None else None, float(pad), occ.ctypes.data, st.ctypes.data))
+    return occ, st
 
 
 def limits_spec(tol=None, tool_lin_max=np.inf, tool_ang_max=np.inf):

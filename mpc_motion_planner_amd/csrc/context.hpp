@@ -73,6 +73,10 @@ struct mpcmp_ctx {
     bool fld_set = false;
     bool fld_ready = false;          // the dynamic-LDS ceiling of k_clearance_field, by the first field check
     bool fld_cert_ready = false;     // ... and of k_clearance_cert_field, by the first certified field check (include/mpcmp_field_cert.h)
+    // camera frames (include/mpcmp_frame.h): the filter table [128][4] = c_s, R_s^2 of the last frame's posture and one counts record, one
+    // allocation made by the family's first use.  Read by mpcmp_set_field_points_filtered*, mpcmp_set_field_depth* and mpcmp_field_carve* only
+    double *d_frm_tab = nullptr;
+    mpcmp_frame_stats *d_frm_stats = nullptr;
     // via-point routes (mpcmp_solve_route_batch*): [max_batch] rows each, allocated by its first call and never afterwards: the leg states and their
     // start guess, and the legs' records when the caller wants none
     double *d_rt_x0 = nullptr, *d_rt_xf = nullptr, *d_rt_wx = nullptr, *d_rt_wu = nullptr, *d_rt_wT = nullptr;

@@ -1,7 +1,7 @@
 // model_host.cpp — the host-only part of the C ABI (include/mpcmp.h): the default model, limits and configuration, the URDF reader, the rules a
 // configuration, a bound row and a payload must satisfy, the single-problem kinematics of the reference's robot wrapper and the single-problem
 // statements of the tool-line moves (toolpath.hpp), of the certified clearance check (clearance_cert.hpp), of the checks in a moving world
-// (moving_rule.hpp), of the certified check in a moving world (moving_cert_rule.hpp) and of the voxel worlds (field_rule.hpp).  Plain C++: no HIP
+// (moving_rule.hpp), of the certified check in a moving world (moving_cert_rule.hpp) and of the voxel worlds (field_rule.hpp, frame_rule.hpp).  Plain C++: no HIP
 // header is read and nothing here runs on or talks to a device, so this file can also be compiled on its own and checked with the host sanitizers
 // (examples/urdf_selftest.cpp).
 #include <array>
@@ -28,6 +28,7 @@
 #include "moving_cert_rule.hpp"
 #include "field_rule.hpp"
 #include "field_cert_rule.hpp"
+#include "frame_rule.hpp"
 
 using namespace mpcmp;
 
@@ -899,6 +900,106 @@ extern "C" int mpcmp_clearance_field_config(const mpcmp_model *models, int narm,
     *d_min = best;
     if (sphere) *sphere = bs;
     if (voxel) *voxel = bv;
+    return MPCMP_OK;
+}
+
+// ---- camera frames on the host (include/mpcmp_frame.h): the filter table, the marker over its three sources and the carver through the source the
+// kernels run (frame_rule.hpp) ----
+// tab [ns][4] = c_s, R_s^2 of the posture q; false: an argument the rule refuses
+static bool frame_table_host(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, const double *q, double pad,
+                             std::vector<double> *tab) {
+    if (!models || narm < 1 || narm > 2 || !n_spheres || !q || !frm_pad_ok(pad)) return false;
+    int nsph = 0;
+    for (int a = 0; a < narm; a++) { if (n_spheres[a] < 0 || n_spheres[a] > CLR_MAX_SPH) return false; nsph += n_spheres[a]; }
+    if (nsph > 0 && !spheres) return false;
+    for (int s = 0; s < nsph; s++) if (spheres[s].joint < 0 || spheres[s].joint > 6) return false;
+    for (int j = 0; j < 7 * narm; j++) if (!std::isfinite(q[j])) return false;
+    tab->assign(4 * (size_t)nsph, 0.0);
+    for (int a = 0, s = 0; a < narm; a++) {
+        double mk[84], sc[14], fr[84];
+        for (int i = 0; i < 7; i++) {
+            for (int c = 0; c < 9; c++) mk[12 * i + c] = models[a].R0[i][c];
+            for (int c = 0; c < 3; c++) mk[12 * i + 9 + c] = models[a].p[i][c];
+            sc[2 * i] = std::sin(q[7 * a + i]); sc[2 * i + 1] = std::cos(q[7 * a + i]);
+        }
+        cert_frames(mk, sc, fr);
+        for (int k = 0; k < n_spheres[a]; k++, s++) frm_entry(fr + 12 * spheres[s].joint, spheres[s].c, spheres[s].r, pad, tab->data() + 4 * s);
+    }
+    return true;
+}
+static const char *const FRAME_HOST_ERR = ": one or two arms with their sphere tables and a finite q (or q == NULL), a finite pad >= 0, a valid grid, the "
+                                          "data, occ and no flag but MPCMP_FRAME_KEEP required";
+
+extern "C" int mpcmp_frame_spheres(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, const double *q, double pad,
+                                   double *out) {
+    std::vector<double> tab;
+    if (!out || !frame_table_host(models, narm, n_spheres, spheres, q, pad, &tab)) {
+        g_err = "mpcmp_frame_spheres: one or two arms with their sphere tables, a finite q, a finite pad >= 0 and out required"; return MPCMP_EINVAL;
+    }
+    for (size_t s = 0; s < tab.size() / 4; s++) {
+        for (int c = 0; c < 3; c++) out[4 * s + c] = tab[4 * s + c];
+        out[4 * s + 3] = spheres[s].r + pad;
+    }
+    return MPCMP_OK;
+}
+
+// `source`: n items, item i gives its world point (false: INVALID)
+template <class Source>
+static int frame_mark_host(const char *who, const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres,
+                           const mpcmp_field_desc *desc, bool given, int n, Source source, const double *q, double pad, int flags, unsigned char *occ,
+                           mpcmp_frame_stats *stats) {
+    std::vector<double> tab;
+    if (!desc || !fld_desc_ok(*desc) || !given || !occ || !frm_pad_ok(pad) || (flags & ~MPCMP_FRAME_KEEP) ||
+        (q && !frame_table_host(models, narm, n_spheres, spheres, q, pad, &tab))) {
+        g_err = std::string(who) + FRAME_HOST_ERR; return MPCMP_EINVAL;
+    }
+    const int ns = (int)(tab.size() / 4);
+    if (!(flags & MPCMP_FRAME_KEEP)) std::memset(occ, 0, (size_t)fld_voxels(*desc));
+    int count[4] = {0, 0, 0, 0};
+    for (int i = 0; i < n; i++) {
+        double x[3];
+        int code = -1 - FRM_INVALID;
+        if (source(i, x)) code = frm_classify(*desc, tab.data(), ns, x);
+        if (code >= 0) occ[code] = 1;
+        count[frm_class_of(code)]++;
+    }
+    if (stats) *stats = mpcmp_frame_stats{n, count[FRM_INVALID], count[FRM_OUTSIDE], count[FRM_ROBOT], count[FRM_MARKED], 0, {0, 0}};
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_frame_points_one(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, const mpcmp_field_desc *desc,
+                                      int n_points, const double *points, const double *q, double pad, int flags, unsigned char *occ,
+                                      mpcmp_frame_stats *stats) {
+    return frame_mark_host("mpcmp_frame_points_one", models, narm, n_spheres, spheres, desc, n_points >= 0 && (n_points == 0 || points), n_points,
+                           [&](int i, double *x) { for (int c = 0; c < 3; c++) x[c] = points[3 * (size_t)i + c]; return true; }, q, pad, flags, occ, stats);
+}
+
+extern "C" int mpcmp_frame_depth_one(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, const mpcmp_field_desc *desc,
+                                     const mpcmp_camera *cam, const void *depth, int depth_type, const double *q, double pad, int flags,
+                                     unsigned char *occ, mpcmp_frame_stats *stats) {
+    const bool given = cam && depth && frm_camera_ok(*cam) && (depth_type == MPCMP_DEPTH_U16 || depth_type == MPCMP_DEPTH_F32);
+    return frame_mark_host("mpcmp_frame_depth_one", models, narm, n_spheres, spheres, desc, given, given ? cam->width * cam->height : 0,
+                           [&](int i, double *x) {
+                               if (depth_type == MPCMP_DEPTH_U16) {
+                                   const unsigned short d = static_cast<const unsigned short *>(depth)[i];
+                                   return frm_pixel(*cam, i % cam->width, i / cam->width, (double)d, frm_raw_ok_u16(d), x);
+                               }
+                               const float d = static_cast<const float *>(depth)[i];
+                               return frm_pixel(*cam, i % cam->width, i / cam->width, (double)d, frm_raw_ok_f32(d), x);
+                           }, q, pad, flags, occ, stats);
+}
+
+extern "C" int mpcmp_frame_carve_one(const mpcmp_model *models, int narm, const int *n_spheres, const mpcmp_sphere *spheres, const mpcmp_field_desc *desc,
+                                     const double *q, double pad, unsigned char *occ, mpcmp_frame_stats *stats) {
+    std::vector<double> tab;
+    if (!desc || !fld_desc_ok(*desc) || !occ || !frm_pad_ok(pad) || (q && !frame_table_host(models, narm, n_spheres, spheres, q, pad, &tab))) {
+        g_err = std::string("mpcmp_frame_carve_one") + FRAME_HOST_ERR; return MPCMP_EINVAL;
+    }
+    const int ns = (int)(tab.size() / 4), nv = fld_voxels(*desc);
+    int cleared = 0;
+    for (int v = 0; v < nv; v++)
+        if (occ[v] && frm_carved(*desc, tab.data(), ns, v)) { occ[v] = 0; cleared++; }
+    if (stats) *stats = mpcmp_frame_stats{0, 0, 0, 0, 0, cleared, {0, 0}};
     return MPCMP_OK;
 }
 

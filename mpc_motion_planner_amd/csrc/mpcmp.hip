@@ -25,6 +25,7 @@
 #include "moving.hpp"
 #include "field.hpp"
 #include "field_cert.hpp"
+#include "frame.hpp"
 #include "limits.hpp"
 #include "retime.hpp"
 #include "retimed_check.hpp"
@@ -1470,6 +1471,157 @@ extern "C" int mpcmp_clearance_merge_batch(mpcmp_ctx *ctx, int B, const mpcmp_cl
     if (int rc = sg.upload()) return rc;
     HIPCHK(ctx, clearance_merge_launch(B, da, db, dout, dsrc, ctx->stream));
     return sg.finish();
+}
+
+// ---- camera frames as voxel worlds (include/mpcmp_frame.h; the kernels are in frame.hip, the rule in frame_rule.hpp) ----
+// the checks the setters of the family share; `given`: the data of the call are there.  Nothing is changed before they have passed
+static int frame_check(mpcmp_ctx *ctx, const char *who, const mpcmp_field_desc *desc, bool given, const double *q, double pad, int flags) {
+    if (!ctx) { g_err = std::string(who) + ": no context"; return MPCMP_EINVAL; }
+    bool q_ok = true;
+    if (q) for (int j = 0; j < 7 * ctx->narm; j++) q_ok = q_ok && std::isfinite(q[j]);
+    if (!desc || !fld_desc_ok(*desc) || !given || !q_ok || !frm_pad_ok(pad) || (flags & ~MPCMP_FRAME_KEEP)) {
+        ctx->err = std::string(who) + ": a grid of 1 <= n[d] <= 1024 with at most 2^24 voxels, a finite origin and a finite h > 0, the data, a finite q, "
+                   "a finite pad >= 0 and no flag but MPCMP_FRAME_KEEP required";
+        return MPCMP_EINVAL;
+    }
+    if ((flags & MPCMP_FRAME_KEEP) && !(ctx->fld_set && frm_same_grid(ctx->fld_desc, *desc))) {
+        ctx->err = std::string(who) + ": MPCMP_FRAME_KEEP needs a field in force with an identical desc"; return MPCMP_EINVAL;
+    }
+    return MPCMP_OK;
+}
+// the filter table and the counts record (the family's own allocation, made by its first use)
+static int frame_reserve(mpcmp_ctx *ctx) {
+    if (ctx->d_frm_tab) return MPCMP_OK;
+    void *p = nullptr;
+    const size_t tab_bytes = sizeof(double) * 4 * FRM_MAX_SPH;
+    if (hipMalloc(&p, tab_bytes + sizeof(mpcmp_frame_stats)) != hipSuccess) {
+        ctx->err = "mpcmp_frame: device allocation of the filter table failed"; return MPCMP_ERUNTIME;
+    }
+    ctx->allocs.push_back(p);
+    ctx->d_frm_tab = (double *)p;
+    ctx->d_frm_stats = (mpcmp_frame_stats *)((char *)p + tab_bytes);
+    return MPCMP_OK;
+}
+// the filter of one call, enqueued on st: the table of the sphere tables in force at q; none for q == NULL or empty tables
+static int frame_filter(mpcmp_ctx *ctx, const double *q, double pad, hipStream_t st, FrmFilter *flt) {
+    const ClrTables t = clearance_tables(ctx);
+    flt->d_tab = ctx->d_frm_tab; flt->ns = 0;
+    if (!q || t.n_sph[0] + t.n_sph[1] < 1) return MPCMP_OK;
+    FrmPosture P = {};
+    for (int j = 0; j < 7 * ctx->narm; j++) P.q[j] = q[j];
+    HIPCHK(ctx, frame_spheres_launch(t, P, pad, ctx->d_frm_tab, st));
+    flt->ns = t.n_sph[0] + t.n_sph[1];
+    return MPCMP_OK;
+}
+// filter, mark, build: the device half of the four marking setters.  d_stats == NULL: the context's record
+static int frame_mark_enqueue(mpcmp_ctx *ctx, const FldArrays &f, int src, int n, const void *d_src, const mpcmp_camera *cam, const double *q, double pad,
+                              int flags, mpcmp_frame_stats *d_stats, hipStream_t st) {
+    FrmFilter flt;
+    if (int rc = frame_filter(ctx, q, pad, st, &flt)) return rc;
+    HIPCHK(ctx, frame_mark_launch(f, src, n, d_src, cam, flt, (flags & MPCMP_FRAME_KEEP) != 0, d_stats ? d_stats : ctx->d_frm_stats, st));
+    HIPCHK(ctx, field_build_launch(f, st));
+    return MPCMP_OK;
+}
+// host variant: everything is waited for, the data go through the staging scratch
+static int frame_mark_host(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int src, int n, const void *data, size_t bytes, const mpcmp_camera *cam,
+                           const double *q, double pad, int flags, mpcmp_frame_stats *stats) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (int rc = frame_reserve(ctx)) return rc;
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    Stage sg(ctx);
+    unsigned char *dd = nullptr;
+    mpcmp_frame_stats *ds = nullptr;
+    if (n > 0) sg.in(&dd, static_cast<const unsigned char *>(data), bytes);
+    if (stats) sg.out(&ds, stats, 1);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = frame_mark_enqueue(ctx, f, src, n, dd, cam, q, pad, flags, ds, ctx->stream)) return rc;
+    if (int rc = sg.finish()) return rc;
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+static int frame_mark_device(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int src, int n, const void *d_data, const mpcmp_camera *cam, const double *q,
+                             double pad, int flags, mpcmp_frame_stats *d_stats, void *hip_stream) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = frame_reserve(ctx)) return rc;
+    if (int rc = field_reserve(ctx, *desc)) return rc;
+    const FldArrays f = field_arrays(ctx, *desc);
+    ctx->fld_set = false;
+    if (int rc = with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int {
+            return frame_mark_enqueue(ctx, f, src, n, d_data, cam, q, pad, flags, d_stats, st);
+        })) return rc;
+    ctx->fld_desc = *desc; ctx->fld_set = true;
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_set_field_points_filtered(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int n_points, const double *points, const double *q,
+                                               double pad, int flags, mpcmp_frame_stats *stats) {
+    if (int rc = frame_check(ctx, "mpcmp_set_field_points_filtered", desc, n_points >= 0 && (n_points == 0 || points), q, pad, flags)) return rc;
+    return frame_mark_host(ctx, desc, FRM_SRC_POINTS, n_points, points, sizeof(double) * 3 * (size_t)n_points, nullptr, q, pad, flags, stats);
+}
+
+extern "C" int mpcmp_set_field_points_filtered_device(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, int n_points, const double *d_points,
+                                                      const double *q, double pad, int flags, mpcmp_frame_stats *d_stats, void *hip_stream) {
+    if (int rc = frame_check(ctx, "mpcmp_set_field_points_filtered_device", desc, n_points >= 0 && (n_points == 0 || d_points), q, pad, flags)) return rc;
+    return frame_mark_device(ctx, desc, FRM_SRC_POINTS, n_points, d_points, nullptr, q, pad, flags, d_stats, hip_stream);
+}
+
+static bool depth_args_ok(const mpcmp_camera *cam, const void *depth, int depth_type) {
+    return cam && depth && frm_camera_ok(*cam) && (depth_type == MPCMP_DEPTH_U16 || depth_type == MPCMP_DEPTH_F32);
+}
+
+extern "C" int mpcmp_set_field_depth(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, const mpcmp_camera *cam, const void *depth, int depth_type,
+                                     const double *q, double pad, int flags, mpcmp_frame_stats *stats) {
+    if (int rc = frame_check(ctx, "mpcmp_set_field_depth (a valid camera, an image and a known depth_type are data)", desc,
+                             depth_args_ok(cam, depth, depth_type), q, pad, flags)) return rc;
+    const int n = cam->width * cam->height;
+    return frame_mark_host(ctx, desc, depth_type == MPCMP_DEPTH_U16 ? FRM_SRC_U16 : FRM_SRC_F32, n, depth,
+                           (size_t)n * (depth_type == MPCMP_DEPTH_U16 ? 2 : 4), cam, q, pad, flags, stats);
+}
+
+extern "C" int mpcmp_set_field_depth_device(mpcmp_ctx *ctx, const mpcmp_field_desc *desc, const mpcmp_camera *cam, const void *d_depth, int depth_type,
+                                            const double *q, double pad, int flags, mpcmp_frame_stats *d_stats, void *hip_stream) {
+    if (int rc = frame_check(ctx, "mpcmp_set_field_depth_device (a valid camera, an image and a known depth_type are data)", desc,
+                             depth_args_ok(cam, d_depth, depth_type), q, pad, flags)) return rc;
+    return frame_mark_device(ctx, desc, depth_type == MPCMP_DEPTH_U16 ? FRM_SRC_U16 : FRM_SRC_F32, cam->width * cam->height, d_depth, cam, q, pad, flags,
+                             d_stats, hip_stream);
+}
+
+static int frame_carve_check(mpcmp_ctx *ctx, const double *q, double pad) {
+    if (!ctx) { g_err = "mpcmp_field_carve: no context"; return MPCMP_EINVAL; }
+    if (!ctx->fld_set) { ctx->err = "mpcmp_field_carve: no field is set: see mpcmp_set_field"; return MPCMP_EINVAL; }
+    return frame_check(ctx, "mpcmp_field_carve", &ctx->fld_desc, true, q, pad, 0);
+}
+static int frame_carve_enqueue(mpcmp_ctx *ctx, const FldArrays &f, const double *q, double pad, mpcmp_frame_stats *d_stats, hipStream_t st) {
+    FrmFilter flt;
+    if (int rc = frame_filter(ctx, q, pad, st, &flt)) return rc;
+    HIPCHK(ctx, frame_carve_launch(f, flt, d_stats ? d_stats : ctx->d_frm_stats, st));
+    HIPCHK(ctx, field_build_launch(f, st));
+    return MPCMP_OK;
+}
+
+extern "C" int mpcmp_field_carve(mpcmp_ctx *ctx, const double *q, double pad, mpcmp_frame_stats *stats) {
+    if (int rc = frame_carve_check(ctx, q, pad)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (int rc = frame_reserve(ctx)) return rc;
+    const FldArrays f = field_arrays(ctx, ctx->fld_desc);
+    Stage sg(ctx);
+    mpcmp_frame_stats *ds = nullptr;
+    if (stats) sg.out(&ds, stats, 1);
+    if (int rc = sg.upload()) return rc;
+    if (int rc = frame_carve_enqueue(ctx, f, q, pad, ds, ctx->stream)) return rc;
+    return sg.finish();
+}
+
+extern "C" int mpcmp_field_carve_device(mpcmp_ctx *ctx, const double *q, double pad, mpcmp_frame_stats *d_stats, void *hip_stream) {
+    if (int rc = frame_carve_check(ctx, q, pad)) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = frame_reserve(ctx)) return rc;
+    const FldArrays f = field_arrays(ctx, ctx->fld_desc);
+    return with_caller_stream(ctx, hip_stream, [&](hipStream_t st) -> int { return frame_carve_enqueue(ctx, f, q, pad, d_stats, st); });
 }
 
 // ---- certified clearance against the voxel world (include/mpcmp_field_cert.h; the kernels are in field_cert.hip, the rule in field_cert_rule.hpp) ----

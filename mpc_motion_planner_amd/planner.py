@@ -316,6 +316,56 @@ class Solver:
     def clearance_merge_device(self, B, a, b, out, source=0, stream=0):
         check(lib().mpcmp_clearance_merge_batch_device(self._ctx, int(B), a or None, b or None, out or None, source or None, stream or None), self._ctx)
 
+    # -- camera frames as voxel worlds: clouds, depth images and grids with the robot removed (include/mpcmp_frame.h)
+    def _frame_q(self, q):
+        return None if q is None else f64(q).reshape(7 * self.narm)
+
+    @staticmethod
+    def _frame_stats(st):
+        return {k: int(st[k]) for k in ("n_in", "n_invalid", "n_outside", "n_robot", "n_marked", "n_cleared")}
+
+    def set_field_points_filtered(self, desc, points, q=None, pad=0.0, keep=False):
+        """mpcmp_set_field_points_filtered: set_field_points without the points within r_s + pad of a robot sphere at the posture q [7 narm] (None:
+        no filter); keep: marked into the occupancy in force.  Returns the counts as a dict"""
+        desc = capi._field_desc_arg(desc); pts = f64(points).reshape(-1, 3); q = self._frame_q(q)
+        st = np.zeros((), dtype=capi.FRAME_STATS_DTYPE)
+        check(lib().mpcmp_set_field_points_filtered(self._ctx, desc.ctypes.data, pts.shape[0], host(pts), None if q is None else q.ctypes.data,
+                                                    float(pad), capi.FRAME_KEEP if keep else 0, st.ctypes.data), self._ctx)
+        return self._frame_stats(st)
+
+    def set_field_points_filtered_device(self, desc, n_points, points, q=None, pad=0.0, keep=False, stats=0, stream=0):
+        """the cloud at the device pointer `points`, the counts (32 bytes) written to the device pointer `stats` (0: none), ordered on `stream`"""
+        desc = capi._field_desc_arg(desc); q = self._frame_q(q)
+        check(lib().mpcmp_set_field_points_filtered_device(self._ctx, desc.ctypes.data, int(n_points), points or None, None if q is None else q.ctypes.data,
+                                                           float(pad), capi.FRAME_KEEP if keep else 0, stats or None, stream or None), self._ctx)
+
+    def set_field_depth(self, desc, camera, depth, q=None, pad=0.0, keep=False):
+        """mpcmp_set_field_depth: the depth image depth [height][width] (uint16, or anything else as float32) of capi.camera(...) unprojected, filtered
+        and marked on the GPU.  Returns the counts as a dict"""
+        desc = capi._field_desc_arg(desc); cam = capi._camera_arg(camera); depth, kind = capi._depth_arg(cam, depth); q = self._frame_q(q)
+        st = np.zeros((), dtype=capi.FRAME_STATS_DTYPE)
+        check(lib().mpcmp_set_field_depth(self._ctx, desc.ctypes.data, cam.ctypes.data, depth.ctypes.data, kind, None if q is None else q.ctypes.data,
+                                          float(pad), capi.FRAME_KEEP if keep else 0, st.ctypes.data), self._ctx)
+        return self._frame_stats(st)
+
+    def set_field_depth_device(self, desc, camera, depth, depth_type, q=None, pad=0.0, keep=False, stats=0, stream=0):
+        desc = capi._field_desc_arg(desc); cam = capi._camera_arg(camera); q = self._frame_q(q)
+        check(lib().mpcmp_set_field_depth_device(self._ctx, desc.ctypes.data, cam.ctypes.data, depth or None, int(depth_type),
+                                                 None if q is None else q.ctypes.data, float(pad), capi.FRAME_KEEP if keep else 0, stats or None,
+                                                 stream or None), self._ctx)
+
+    def field_carve(self, q, pad=0.0):
+        """mpcmp_field_carve: the occupied voxels whose centre lies within r_s + pad of a robot sphere at q are cleared from the occupancy in force,
+        the field is rebuilt.  Returns the counts as a dict (n_cleared)"""
+        q = self._frame_q(q)
+        st = np.zeros((), dtype=capi.FRAME_STATS_DTYPE)
+        check(lib().mpcmp_field_carve(self._ctx, None if q is None else q.ctypes.data, float(pad), st.ctypes.data), self._ctx)
+        return self._frame_stats(st)
+
+    def field_carve_device(self, q, pad=0.0, stats=0, stream=0):
+        q = self._frame_q(q)
+        check(lib().mpcmp_field_carve_device(self._ctx, None if q is None else q.ctypes.data, float(pad), stats or None, stream or None), self._ctx)
+
     # -- certified clearance against the voxel world, and the merge of two certificates (include/mpcmp_field_cert.h)
     def clearance_certified_field(self, sx, sT, margin=0.0, n_start=4, max_depth=10):
         """mpcmp_clearance_certified_field_batch: (capi.CLEARANCE_DTYPE [B], capi.CLEARANCE_CERT_DTYPE [B]) of the trajectories sx [B][N][nx], sT [B]
@@ -1132,6 +1182,31 @@ class BatchMotionPlanner:
         point are solid; points outside the grid and non-finite points are skipped"""
         self._field_spheres(sphere_radius, sphere_spacing, spheres)
         self._solver.set_field_points(capi.field_desc(origin, h, n), points)
+
+    # -- camera frames (include/mpcmp_frame.h): the same worlds with the robot itself, seen by the camera at the posture robot_q, removed.
+    # robot_pad above 4.34 h + margin (clouds, images) or 3.47 h + margin (grids) makes that posture clear of the frame by construction
+    frame_stats = None      # the counts of the last of the three calls below, a dict
+
+    def set_point_cloud_filtered(self, origin, h, n, points, robot_q, robot_pad, keep=False, sphere_radius=0.06, sphere_spacing=0.08, spheres=None):
+        """set_point_cloud without the points within r_s + robot_pad of a robot sphere at robot_q [7] (None: no filter); keep: the cloud is added
+        to the world in force (a second camera, or a camera on top of set_voxel_world).  The counts are kept in frame_stats and returned"""
+        self._field_spheres(sphere_radius, sphere_spacing, spheres)
+        self.frame_stats = self._solver.set_field_points_filtered(capi.field_desc(origin, h, n), points, robot_q, robot_pad, keep)
+        return self.frame_stats
+
+    def set_depth_image(self, origin, h, n, camera, depth, robot_q=None, robot_pad=0.0, keep=False, sphere_radius=0.06, sphere_spacing=0.08,
+                        spheres=None):
+        """a depth image depth [height][width] (uint16 or float) of capi.camera(...) as the world: unprojected, filtered and marked on the GPU"""
+        self._field_spheres(sphere_radius, sphere_spacing, spheres)
+        self.frame_stats = self._solver.set_field_depth(capi.field_desc(origin, h, n), camera, depth, robot_q, robot_pad, keep)
+        return self.frame_stats
+
+    def carve_robot(self, robot_q, robot_pad, sphere_radius=0.06, sphere_spacing=0.08, spheres=None):
+        """the robot at robot_q removed from the voxel world in force (set_voxel_world, a map): occupied voxels whose centre lies within
+        r_s + robot_pad of a sphere are cleared"""
+        self._field_spheres(sphere_radius, sphere_spacing, spheres)
+        self.frame_stats = self._solver.field_carve(robot_q, robot_pad)
+        return self.frame_stats
 
     def check_clearance_field(self, n_pts=200, margin=0.0, merge=True, self_gap=0):
         """clearance records (capi.CLEARANCE_DTYPE [B]) of the last solve_trajectory's solutions against the voxel world; of routes: the legs'
